@@ -2,6 +2,8 @@
 """Benchmark of the facet-graph-convolution hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (plain shell: N > 1 starts its own torchrun child)
+    python bench.py ... --full                             (also every untimed extra listed below)
+    python bench.py ... --dump-outputs DIR                 (what the last timed step computed, as DIR/<name>.npy)
 
 One "step" = one full training iteration of the reference's loop body (train.py:558-575,619) on one
 synthetic mesh: random rotation of inputs and ground truth, full 3-level graph U-Net + MLP forward,
@@ -25,10 +27,14 @@ gradient is all-reduced once per step.  With c2 the mesh has N x 100 000 facets:
 grows ("weak" scaling).  --mode replicas: each rank trains on its own mesh, gradient all-reduce only.
 FGC_BENCH_BACKEND=gloo rehearses N > 1 with N processes on ONE GPU (host-staged exchange).
 
-Rank 0 prints ONE JSON line.  Besides the contract fields it carries
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints it: `value` and `ms_per_step`
+come from those K steps alone.  With --full the line also carries what takes runs of its own, all measured outside the
+timed region:
   roofline      the dominant kernel FAMILY (summed time per step) through its launch with the most algorithmic work:
                 achieved TFLOP/s from hipEvent timings taken live in this process; `families` has the top three
   cpu_baseline  the oracle (reference-shaped torch CPU restatement) timed on this host on a bounded sample
+  extras        repeat blocks of K steps, the eager / hipGraph comparison, the forward-only rate, the bf16 runs (`also`),
+                a sharded run's blocking exchange costs (`exchange`) and its strong-scaling reading (`strong`)
 """
 import argparse
 import json
@@ -78,12 +84,18 @@ def parse_args(argv=None):
                          "collectives next to replays have not run on a real node).  Needs DEBUG_CLR_GRAPH_PACKET_CAPTURE=0, which the package sets at import: with "
                          "the runtime's pre-built graph packets a replay after a stream synchronise computes garbage on "
                          "this ROCm stack (DESIGN.md section 6)")
-    ap.add_argument("--repeats", type=int, default=5, help="untimed-extra repeats of the K-step block (min / median)")
+    ap.add_argument("--repeats", type=int, default=5, help="--full: untimed-extra repeats of the K-step block (min / median)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--dump-kernels", type=str, default="", help="write the full per-kernel table to this file")
     ap.add_argument("--mode", choices=["shard", "replicas"], default="shard", help="multi-GPU decomposition")
     ap.add_argument("--scaling", choices=["weak", "strong"], default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every untimed extra (per-kernel roofline, repeat blocks, eager / hipGraph comparison, "
+                         "forward-only rate, bf16 extras, CPU baseline, sharded exchange costs and strong scaling)")
+    ap.add_argument("--dump-outputs", type=str, default="",
+                    help="after the timed steps, write what the last of them computed as DIR/<name>.npy (rank 0; float32 "
+                         "or float64, at most 64 MB in all)")
     args = ap.parse_args(argv)
     nu, nv, ms, scaling, what = CONFIGS[args.config]
     args.nu = args.nu or nu
@@ -460,6 +472,29 @@ def family_of(kern):
     return kern.split("<")[0]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every array as out_dir/<name>.npy, float64 kept, anything else as float32.  If they hold more than
+    `limit` bytes in all, an array larger than its equal share of the limit keeps a seeded sample of its rows (sorted; the
+    same rows for the same shape on every run), so that two builds stay comparable output for output.  Returns the names."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrs = {}
+    for name, a in arrays.items():
+        a = np.atleast_1d(np.asarray(a))
+        arrs[name] = a if a.dtype == np.float64 else a.astype(np.float32)
+    if sum(a.nbytes for a in arrs.values()) > limit:
+        share = limit // len(arrs)
+        for name, a in arrs.items():
+            if a.nbytes > share:
+                keep = max(1, share // (a.nbytes // a.shape[0]))
+                arrs[name] = a[np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))]
+    for name, a in arrs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrs)
+
+
 def main(argv=None):
     argv = list(sys.argv[1:] if argv is None else argv)
     if os.environ.get("FGC_BENCH_ARGV") and "WORLD_SIZE" in os.environ:
@@ -682,34 +717,48 @@ def main(argv=None):
             torch.cuda.synchronize()
             step()
         w_done = 1
-    # Per-kernel durations (hipEvents recorded by the library around every launch, same stream) over `steps` eager steps of the
-    # same work as the timed region, taken BEFORE the timed region since round 6 (behind the capture step, in
-    # front of the other warm-up steps, so that no host-only stretch separates it from the timed block): the pass doubles as the
-    # clock warm-up the contract's W steps are too short for (a GPU that idled through the mesh preprocessing runs its first
-    # ~15 steps 3 - 15 % slow: profiles/r5_first_steps_probe.txt; the driver's --warmup 5 --steps 20 sat inside that ramp).
-    # The timed region itself is unchanged: W untimed steps, then exactly K steps between barriers.  Facet-sharded: every
-    # rank runs the steps (they hold collectives), rank 0's table is the one reported; a layer that runs as interior |
-    # exchange | boundary launches counts with the SUM of its launches.
+    # Clock warm-up: min(K, 50) eager steps of the same work as the timed region, behind the capture step and in front of the
+    # other warm-up steps, so that no host-only stretch separates them from the timed block.  The contract's W steps are too
+    # short for it: a GPU that idled through the mesh preprocessing runs its first ~15 steps 3 - 15 % slow
+    # (profiles/r5_first_steps_probe.txt; the driver's --warmup 5 --steps 20 sat inside that ramp).  With --full the same steps
+    # carry the per-kernel durations (hipEvents recorded by the library around every launch, same stream); a plain run takes
+    # them without, so both walk the same steps and compute the same outputs.  The timed region itself is unchanged: W untimed
+    # steps, then exactly K steps between barriers.  Facet-sharded: every rank runs the steps (they hold collectives), rank
+    # 0's table is the one reported; a layer that runs as interior | exchange | boundary launches counts with the SUM of its
+    # launches.
     prof = None
-    if not args.no_roofline and train and (shard or world == 1):
-        net.profile_start()
-        for k in range(args.steps):
+    ramp = min(args.steps, 50) if train and (shard or world == 1) else 0
+    if ramp:
+        profile = args.full and not args.no_roofline
+        if profile:
+            net.profile_start()
+        for k in range(ramp):
             kk = k % nsteps_total
             net.set_step_inputs_packed(SR_all[kk], S_loc[kk] if S_loc else None, in_place=True)
             net.forward_backward(rotate=True, capture=False)
             net.adam_step()
-        prof = net.profile_stop()
+        if profile:
+            prof = net.profile_stop()
     for _ in range(args.warmup - w_done):
         step()
     dt = timed_block()                       # THE timed region: exactly K steps, max over ranks
     loss = net.buffers["loss"][0].item() if train else None
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed its caller (a sharded run: rank 0's rows), before any extra touches the network
+        B = net.buffers
+        outs = ({"loss": B["loss"], "normals": B["nconv"], "grad": net.params.grad, "weights": net.params.theta} if train else
+                {"normals": B["nconv"]})
+        if args.multi_scale:
+            outs.update(normals_level1=B["nconv1"], normals_level2=B["nconv2"])
+        write_outputs(args.dump_outputs, {k: (t.detach() if t.dtype == torch.float64 else t.detach().float()).cpu().numpy()
+                                          for k, t in outs.items()})
     # the same K-step block again (extras: spread of the measurement)
-    rep_ms = [dt / args.steps * 1e3] + [timed_block() / args.steps * 1e3 for _ in range(nrep - 1)]
+    rep_ms = [dt / args.steps * 1e3] + ([timed_block() / args.steps * 1e3 for _ in range(nrep - 1)] if args.full else [])
 
     # the same steps as hipGraph replays (one graph per step holds the whole forward+backward enqueue), untimed extra:
     # a second network from the same seed walks the same inputs, so its final loss must equal the eager one bit for bit
     hipgraph = None
-    if world == 1 and train and (not args.graph or auto_graph):
+    if args.full and world == 1 and train and (not args.graph or auto_graph):
         net_g = FacetDenoiser(dev, **mk).bind_mesh(ds.in_list[0], ds.adj_list[0], gt=ds.gt_list[0])
         net_e = FacetDenoiser(dev, **mk).bind_mesh(ds.in_list[0], ds.adj_list[0], gt=ds.gt_list[0])
 
@@ -736,7 +785,7 @@ def main(argv=None):
             hipgraph = {"error": "%s: %s" % (type(e).__name__, str(e)[:200]), "timed_region": "hipgraph" if args.graph else "eager"}
             print("bench: the eager / replay comparison failed (%s)" % hipgraph["error"], file=sys.stderr)
         del net_g, net_e
-    elif shard and train and graph_mode[0]:
+    elif args.full and shard and train and graph_mode[0]:
         # sharded: the timed region replayed one hipGraph per stretch of launches between two exchanges (the exchanges
         # eager in between); the same K steps with eager launches beside it
         graph_mode[0] = False
@@ -747,20 +796,22 @@ def main(argv=None):
                     "timed_region": "hipgraph"}
 
     # forward-only rate (BASELINE config 2 wording), untimed extra
-    torch.cuda.synchronize()
-    nf = max(3, args.steps // 2)
-    t1 = time.perf_counter()
-    for _ in range(nf):
-        net.forward(rotate=False)
-    torch.cuda.synchronize()
-    fwd_ms = (time.perf_counter() - t1) / nf * 1e3
-    if world > 1:
-        dist.barrier()
+    fwd_ms = None
+    if args.full:
+        torch.cuda.synchronize()
+        nf = max(3, args.steps // 2)
+        t1 = time.perf_counter()
+        for _ in range(nf):
+            net.forward(rotate=False)
+        torch.cuda.synchronize()
+        fwd_ms = (time.perf_counter() - t1) / nf * 1e3
+        if world > 1:
+            dist.barrier()
 
     # sharded runs: what the exchanges cost when nothing overlaps them (blocking, timed on the host around device
     # synchronises), and how many collectives a step issues
     exchange = None
-    if shard:
+    if args.full and shard:
         exchange = net.measure_exchanges(lambda: step(), steps=max(2, min(5, args.steps)))
         dist.barrier()
 
@@ -939,7 +990,7 @@ def main(argv=None):
         # `steps` eager steps of the same work as the timed region.  Facet-sharded: every rank runs the steps (they hold
         # collectives), rank 0's table is the one reported; a layer that runs as interior | exchange | boundary launches
         # counts with the SUM of its launches
-        roofline, families, pair_form, kernels = analyse(net, prof, args.steps, args.dtype, args.nu, args.nv, args.dump_kernels)
+        roofline, families, pair_form, kernels = analyse(net, prof, ramp, args.dtype, args.nu, args.nv, args.dump_kernels)
 
     fwd_b, fb_b = algorithmic_bytes_fwd_bwd(net, elem=2 if args.dtype == "bf16" else 4)
     n0_line = n0
@@ -1015,19 +1066,21 @@ def main(argv=None):
                            ", hipGraph replay" if (args.graph and not shard) else ""),
                        "parallelism": ("single GPU" if world == 1 else
                                        ("one %d-facet mesh facet-sharded over %d GPUs (%s world size %d), halo all-to-all per "
-                                        "conv + flat-gradient all-reduce; halo/owned rows per level on rank 0: %s; %d "
-                                        "collectives per step, %.3f ms per step when exchanged blocking; %s" %
+                                        "conv + flat-gradient all-reduce; halo/owned rows per level on rank 0: %s; %s%s" %
                                         (F_total, world, "RCCL" if backend == "nccl" else backend, dist.get_world_size(),
-                                         ", ".join("%.3f" % h for h in halo_frac), exchange["collectives_per_step"],
-                                         exchange["blocking_ms_per_step"], launch_mode)) if shard else
+                                         ", ".join("%.3f" % h for h in halo_frac),
+                                         "%d collectives per step, %.3f ms per step when exchanged blocking; " % (
+                                             exchange["collectives_per_step"], exchange["blocking_ms_per_step"])
+                                         if exchange else "", launch_mode)) if shard else
                                        "1 mesh per GPU, flat-gradient all-reduce (%s world size %d)" % (
                                            "RCCL" if backend == "nccl" else backend, dist.get_world_size()))},
             "loss_deg": loss,
             # what the process ran, in order (round 6: the hipEvent pass moved in front; the timed region is W + K steps as ever)
-            "timeline": ("%s%sW = %d untimed warm-up steps -> K = %d timed steps between barriers -> untimed extras" % (
+            "timeline": ("%s%sW = %d untimed warm-up steps -> K = %d timed steps between barriers%s" % (
                 "schedule tuning (`split_tune`) -> " if split_tune is not None else "",
-                "per-kernel hipEvent pass (%d eager steps; also warms the clocks) -> " % args.steps if prof is not None else "",
-                args.warmup, args.steps)),
+                ("per-kernel hipEvent pass (%d eager steps; also warms the clocks) -> " % ramp if prof is not None else
+                 "clock warm-up (%d eager steps) -> " % ramp if ramp else ""),
+                args.warmup, args.steps, " -> untimed extras" if args.full else "")),
             "startup_s": {k: round(v, 2) for k, v in startup.items()},
             "world_check": world_check,
             "repeats_ms_per_step": [round(v, 4) for v in rep_ms],
@@ -1037,7 +1090,7 @@ def main(argv=None):
             "retry_note": os.environ.get("FGC_BENCH_RETRY_NOTE") or graph_note,
             "split_tune": split_tune,
             "forward_only_ms": fwd_ms,
-            "forward_only_facets_per_s": F_total / (fwd_ms * 1e-3),
+            "forward_only_facets_per_s": F_total / (fwd_ms * 1e-3) if fwd_ms else None,
             "hbm_roofline_frac_whole_step": step_bytes / (ms_step * 1e-3) / (PEAK_HBM_GBS * 1e9),
             "algorithmic_bytes_per_step": step_bytes,
             "exchange": exchange,
@@ -1079,9 +1132,9 @@ def main(argv=None):
                 pass
 
     also = None
-    if world == 1:
+    if args.full and world == 1:
         emit_early(make_record(None, None, None), "before the bf16 extras and the CPU baseline")
-    if world == 1 and train and args.config == "c2" and args.dtype == "f32" and (args.nu, args.nv) == (250, 200) \
+    if args.full and world == 1 and train and args.config == "c2" and args.dtype == "f32" and (args.nu, args.nv) == (250, 200) \
             and not args.multi_scale and not os.environ.get("FGC_BENCH_NO_ALSO"):
         # BASELINE config 3 (train step, bf16 storage / fp32 accumulate) at its own 50k facets and at the headline's 100k: a
         # few seconds, so that the driver's record carries them.  A build extension (the reference is fp32 only): accepted at
@@ -1109,6 +1162,8 @@ def main(argv=None):
     # region, with the same barriers and the max over ranks
     strong = None
     line_out = False
+    strong_extra = args.full and shard and train and args.scaling == "weak" and args.config == "c2" and \
+        not os.environ.get("FGC_BENCH_NO_STRONG")
     if world > 1:
         # N > 1: the ONE JSON line is printed HERE, before the strong-scaling extra, which re-shards, binds a new network and
         # issues collectives: a rank that raises or aborts in there would leave its peers waiting in a collective and the
@@ -1116,9 +1171,9 @@ def main(argv=None):
         # gpurun_out/bench_strong.json; a watchdog ends the process (exit 0: the line is out) if it does not return.
         if rank == 0:
             print(json.dumps(make_record(None, {"note": "measured after this line was printed: see `bench: strong-scaling "
-                                                        "extra` on stderr"}, None)), flush=True)
+                                                        "extra` on stderr"} if strong_extra else None, None)), flush=True)
         line_out = True
-    if shard and train and args.scaling == "weak" and args.config == "c2" and not os.environ.get("FGC_BENCH_NO_STRONG"):
+    if strong_extra:
         import threading
         limit = float(os.environ.get("FGC_BENCH_STRONG_LIMIT_S", "180"))
 
@@ -1172,7 +1227,7 @@ def main(argv=None):
         watchdog.cancel()
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline()
 
     if rank == 0 and not line_out:

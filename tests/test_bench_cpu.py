@@ -40,11 +40,18 @@ def test_family_names_group_by_kernel_function():
     assert f("mlp_bwd_kernel") == "mlp" and f("gemm_tn_stream_kernel") == "gemm_tn"
 
 
-def test_self_launch_without_a_gpu_fails_loudly():
-    """No GPU here: both ranks of the child die in FacetDenoiser ("no CPU fallback").  The parent must come back with a
-    non-zero exit code and no JSON line - not hang, not print a number."""
-    env = dict(os.environ, FGC_BENCH_BACKEND="gloo")
+def _env_without_a_gpu():
+    """Two gloo ranks that see no GPU on any machine (an invalid device ordinal hides every device), so that their child
+    group fails the same way with or without a GPU in the box, before any GPU work."""
+    env = dict(os.environ, FGC_BENCH_BACKEND="gloo", HIP_VISIBLE_DEVICES="-1", CUDA_VISIBLE_DEVICES="-1")
     env.pop("WORLD_SIZE", None)
+    return env
+
+
+def test_self_launch_without_a_gpu_fails_loudly():
+    """The child sees no GPU (_env_without_a_gpu): both of its ranks die in FacetDenoiser ("no CPU fallback").  The parent
+    must come back with a non-zero exit code and no JSON line - not hang, not print a number."""
+    env = _env_without_a_gpu()
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
                         "--nu", "12", "--nv", "10", "--no-cpu-baseline"], env=env, capture_output=True, text=True,
                        timeout=300, cwd=REPO)
@@ -55,9 +62,8 @@ def test_self_launch_without_a_gpu_fails_loudly():
 
 def test_self_launch_retries_once_with_eager_launches_when_a_graph_run_dies_without_a_line():
     """--graph 1 (hipGraph segments between the exchanges): a rank group that ends without a result line is followed by ONE
-    fresh child group with --graph 0.  Here both groups die (no GPU): the parent says what it did and fails."""
-    env = dict(os.environ, FGC_BENCH_BACKEND="gloo")
-    env.pop("WORLD_SIZE", None)
+    fresh child group with --graph 0.  Here both groups die (no GPU visible): the parent says what it did and fails."""
+    env = _env_without_a_gpu()
     r = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0",
                         "--nu", "12", "--nv", "10", "--no-cpu-baseline", "--graph", "1"], env=env, capture_output=True,
                        text=True, timeout=600, cwd=REPO)
@@ -80,3 +86,32 @@ def test_algorithmic_bytes_match_the_survey_formula():
     assert abs(fwd / 123472 - 1584) < 12 and abs(fb / fwd - 3879 / 1584) < 1e-9
     fwd16, _ = bench.algorithmic_bytes_fwd_bwd(Net(), elem=2)
     assert 0.5 * fwd < fwd16 < 0.62 * fwd      # activations halve, the CSR and the 6 / 3-channel ends do not
+
+
+def test_a_plain_run_is_the_default_and_full_adds_the_extras():
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "3"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 3, False, "")
+    a = bench.parse_args(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_writer_keeps_floats_and_samples_rows_within_the_limit(tmp_path):
+    import numpy as np
+    import bench
+    rs = np.random.RandomState(1)
+    arrays = {"a": rs.rand(100, 3), "b": rs.rand(10).astype(np.float16), "c": np.arange(5, dtype=np.int32)}
+    assert bench.write_outputs(str(tmp_path / "x"), arrays) == ["a", "b", "c"]
+    a, b, c = (np.load(tmp_path / "x" / (n + ".npy")) for n in "abc")
+    assert a.dtype == np.float64 and np.array_equal(a, arrays["a"])
+    assert b.dtype == c.dtype == np.float32 and np.array_equal(b, arrays["b"].astype(np.float32))
+    assert np.array_equal(c, np.arange(5, dtype=np.float32))
+    # over the limit: an array larger than its share keeps a seeded sample of its rows, in order, the same on every call
+    big = {"big": rs.rand(4000, 3).astype(np.float32), "small": rs.rand(8).astype(np.float32)}
+    for d in ("y", "z"):
+        bench.write_outputs(str(tmp_path / d), big, limit=4096)
+    y, z = np.load(tmp_path / "y" / "big.npy"), np.load(tmp_path / "z" / "big.npy")
+    assert np.array_equal(y, z) and y.shape[1] == 3 and 0 < y.nbytes <= 2048
+    assert np.array_equal(np.load(tmp_path / "y" / "small.npy"), big["small"])
+    rows = [int(np.flatnonzero((big["big"] == r).all(1))[0]) for r in y]
+    assert rows == sorted(set(rows))

@@ -5,11 +5,13 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
 REPO = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
-SMALL = ["--steps", "2", "--warmup", "1", "--nu", "48", "--nv", "40", "--no-cpu-baseline", "--repeats", "2"]
+# (--full: these tests read the extras a plain run leaves out)
+SMALL = ["--steps", "2", "--warmup", "1", "--nu", "48", "--nv", "40", "--no-cpu-baseline", "--repeats", "2", "--full"]
 
 
 def _bench(args, env=None, timeout=900):
@@ -59,6 +61,28 @@ def test_single_gpu_line_has_the_contract_fields_and_family_rooflines():
     assert j["roofline"]["launches_per_step"] > 20 and j["startup_s"]["preprocess_s"] > 0 and j["world_check"] is None
 
 
+def test_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """Without --full: set-up, warm-up, exactly K timed steps and the line, no extra measured.  --dump-outputs writes what
+    the last timed step handed its caller, and a --full run of the same arguments (its extras come after the dump) walks
+    the same steps to the same outputs."""
+    plain = ["--steps", "3", "--warmup", "2", "--nu", "48", "--nv", "40"]
+    a = _bench(plain + ["--dump-outputs", str(tmp_path / "plain")])
+    assert (a["n_gpus"], a["steps"], a["warmup"], a["dtype"], a["unit"], a["higher_is_better"]) == (1, 3, 2, "f32", "facets/s", True)
+    assert abs(a["value"] - 48 * 40 * 2 * 3 / (a["ms_per_step"] * 3e-3)) < 1e-6 * a["value"]
+    for k in ("roofline", "families", "kernels", "hipgraph_replay", "forward_only_ms", "also", "cpu_baseline"):
+        assert not a[k], k
+    assert len(a["repeats_ms_per_step"]) == 1 and "_early_record" not in a
+    assert "clock warm-up (3 eager steps)" in a["timeline"] and "extras" not in a["timeline"]
+    outs = {p.stem: np.load(p) for p in (tmp_path / "plain").glob("*.npy")}
+    assert set(outs) == {"loss", "normals", "grad", "weights"}
+    assert all(o.dtype == np.float32 and np.isfinite(o).all() for o in outs.values())
+    assert outs["loss"][0] == np.float32(a["loss_deg"]) and outs["normals"].shape[1] == 3
+    b = _bench(plain + ["--full", "--no-cpu-baseline", "--repeats", "2", "--dump-outputs", str(tmp_path / "full")])
+    assert b["roofline"] is not None and len(b["repeats_ms_per_step"]) == 2 and b["hipgraph_replay"]["matches_eager"] is True
+    for name, o in outs.items():
+        np.testing.assert_allclose(np.load(tmp_path / "full" / (name + ".npy")), o, rtol=1e-5, atol=1e-6, err_msg=name)
+
+
 def test_two_ranks_from_a_plain_shell_over_gloo():
     """`python bench.py --gpus 2` with no torchrun environment: the parent starts the ranks itself."""
     j = _bench(["--gpus", "2"] + SMALL, env={"FGC_BENCH_BACKEND": "gloo"})
@@ -101,6 +125,17 @@ def test_two_ranks_from_a_plain_shell_over_gloo():
     assert st["scaling"] == "strong" and st["facets"] == 48 * 40 * 2 and st["steps"] == 2 and 0 < st["loss_deg"] < 180
     assert abs(st["value"] - st["facets"] / (st["ms_per_step"] * 1e-3)) < 1e-6 * st["value"]
     assert j["also"] is None
+
+
+def test_two_ranks_plain_run_over_gloo(tmp_path):
+    """Without --full a sharded run measures neither the blocking exchanges nor the strong-scaling reading; rank 0 dumps its
+    rows of the last timed step."""
+    j = _bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--nu", "48", "--nv", "40", "--dump-outputs", str(tmp_path)],
+               env={"FGC_BENCH_BACKEND": "gloo"})
+    assert j["n_gpus"] == 2 and j["exchange"] is None and j["strong"] is None and "_strong_after_line" not in j
+    assert "facet-sharded over 2 GPUs" in j["config"]["parallelism"] and "eager launches" in j["config"]["parallelism"]
+    assert "split_tune" in j["timeline"] and "extras" not in j["timeline"] and 0 < j["loss_deg"] < 180
+    assert np.load(tmp_path / "loss.npy")[0] == np.float32(j["loss_deg"])
 
 
 def test_multi_scale_denoising_mode_sharded_and_single():

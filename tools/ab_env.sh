@@ -6,7 +6,7 @@ pat=$1; rounds=$2; sw=$3; shift 3
 for i in $(seq 1 $rounds); do
   for mode in off on; do
     if [ $mode = on ]; then export "$sw"; else unset "${sw%%=*}"; fi
-    FGC_BENCH_NO_ALSO=1 python bench.py --no-cpu-baseline --dump-kernels /tmp/k.txt "$@" > /tmp/b.json 2>/tmp/b.err || { echo "$mode FAILED"; tail -3 /tmp/b.err; continue; }
+    FGC_BENCH_NO_ALSO=1 python bench.py --full --no-cpu-baseline --dump-kernels /tmp/k.txt "$@" > /tmp/b.json 2>/tmp/b.err || { echo "$mode FAILED"; tail -3 /tmp/b.err; continue; }
     python - "$mode $sw" "$pat" <<'PY'
 import json, sys
 j = json.load(open("/tmp/b.json"))

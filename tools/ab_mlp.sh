@@ -4,7 +4,7 @@
 pat=$1; rounds=$2; shift 2
 for i in $(seq 1 $rounds); do
   for lib in "$@"; do
-    FGC_BENCH_NO_ALSO=1 FGC_LIB=$lib python bench.py --no-cpu-baseline --dump-kernels /tmp/k.txt > /tmp/b.json 2>/tmp/b.err || { echo "$lib FAILED"; tail -3 /tmp/b.err; continue; }
+    FGC_BENCH_NO_ALSO=1 FGC_LIB=$lib python bench.py --full --no-cpu-baseline --dump-kernels /tmp/k.txt > /tmp/b.json 2>/tmp/b.err || { echo "$lib FAILED"; tail -3 /tmp/b.err; continue; }
     python - "$lib" "$pat" <<'PY'
 import json, sys
 j = json.load(open("/tmp/b.json"))

@@ -32,7 +32,7 @@ def main():
     lines.append("Launch bench.py's `roofline` reports (%s): %s; best launch of its family: %s" % (
         roof.get("selected_by", "largest summed time per step of its family"), roof["kernel"],
         (roof.get("family_best") or {}).get("kernel")))
-    lines.append("command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --steps %d --warmup %d --repeats 5   "
+    lines.append("command: rocprofv3 --kernel-trace --stats --output-format csv -- python3 bench.py --full --steps %d --warmup %d --repeats 5   "
                  "(profiles/%s_rocprofv3_kernel_stats.csv, profiles/%s_bench_under_rocprofv3.json)"
                  % (prof["steps"], prof["warmup"], tag, tag))
     # the trace rows of the reported launch: the kernel's instantiation(s) by name, on the largest grid they run on (= the

@@ -3,7 +3,7 @@
 # usage: tools/bench_variants.sh <kernel-substring> lib1.so lib2.so ...
 pat=$1; shift
 for lib in "$@"; do
-  FGC_LIB=$lib python bench.py --no-cpu-baseline --dump-kernels /tmp/k.txt > /tmp/b.json 2>/tmp/b.err || { echo "$lib FAILED"; tail -3 /tmp/b.err; continue; }
+  FGC_LIB=$lib python bench.py --full --no-cpu-baseline --dump-kernels /tmp/k.txt > /tmp/b.json 2>/tmp/b.err || { echo "$lib FAILED"; tail -3 /tmp/b.err; continue; }
   python - "$lib" "$pat" <<'PY'
 import json, sys
 j = json.load(open("/tmp/b.json"))

@@ -4,7 +4,7 @@
 pats=$1; shift
 for envs in "$@"; do
   if [ "$envs" = "-" ]; then e=""; else e="$envs"; fi
-  env $e timeout -k 10 200 python bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --dump-kernels /tmp/k.txt > /tmp/b.json 2>/tmp/b.err || { echo "$envs FAILED"; tail -3 /tmp/b.err; continue; }
+  env $e timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --dump-kernels /tmp/k.txt > /tmp/b.json 2>/tmp/b.err || { echo "$envs FAILED"; tail -3 /tmp/b.err; continue; }
   python - "$envs" $pats <<'PY'
 import json, sys
 j = json.load(open("/tmp/b.json"))

@@ -5,7 +5,7 @@ extra=$1; shift
 pats=$1; shift
 for lib in "$@"; do
   if [ "$lib" = "-" ]; then unset FGC_LIB; else export FGC_LIB=$lib; fi
-  timeout -k 10 200 python bench.py --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --dump-kernels /tmp/k.txt $extra > /tmp/b.json 2>/tmp/b.err || { echo "$lib FAILED"; tail -3 /tmp/b.err; continue; }
+  timeout -k 10 200 python bench.py --full --steps 10 --warmup 3 --repeats 1 --no-cpu-baseline --dump-kernels /tmp/k.txt $extra > /tmp/b.json 2>/tmp/b.err || { echo "$lib FAILED"; tail -3 /tmp/b.err; continue; }
   python - "$lib" $pats <<'PY'
 import json, sys
 j = json.load(open("/tmp/b.json"))

@@ -17,25 +17,25 @@ cp profiles/${rnd}_traffic_*.json profiles/${rnd}_traffic_summary*.txt $o/
 echo "traffic done"
 fi
 if [ $first -le 2 ]; then
-timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -o p -- python3 bench.py --steps 20 --warmup 5 --repeats 5 \
+timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof -o p -- python3 bench.py --full --steps 20 --warmup 5 --repeats 5 \
     > $o/${tag}_bench_under_rocprofv3.json 2> $o/prof.err
 cp $(find $o/prof -name "*kernel_stats.csv" | head -1) $o/${tag}_rocprofv3_kernel_stats.csv
 echo "rocprof done"
-timeout -k 10 400 python3 bench.py > $o/${tag}_bench.json 2> $o/bench.err
+timeout -k 10 400 python3 bench.py --full > $o/${tag}_bench.json 2> $o/bench.err
 python3 tools/agreement.py $(find $o/prof -name "*kernel_trace.csv" | head -1) $o/${tag}_bench_under_rocprofv3.json $o/${tag}_bench.json \
     $o/${tag}_dominant_kernel_agreement.txt $tag > /dev/null
 echo "default bench done"
 fi
 if [ $first -le 3 ]; then
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_bf -o p -- python3 bench.py --dtype bf16 --steps 20 --warmup 5 --repeats 5 \
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $o/prof_bf -o p -- python3 bench.py --full --dtype bf16 --steps 20 --warmup 5 --repeats 5 \
     --no-cpu-baseline > $o/bf16_bench_under_rocprofv3.json 2> $o/prof_bf.err
 cp $(find $o/prof_bf -name "*kernel_stats.csv" | head -1) $o/bf16_rocprofv3_kernel_stats.csv
-timeout -k 10 300 python3 bench.py --dtype bf16 --no-cpu-baseline > $o/bf16_bench.json 2> $o/bf16.err
+timeout -k 10 300 python3 bench.py --full --dtype bf16 --no-cpu-baseline > $o/bf16_bench.json 2> $o/bf16.err
 echo "bf16 done"
 fi
-timeout -k 10 300 python3 bench.py --config c3 --no-cpu-baseline > $o/c3_bench.json 2> $o/c3.err
-timeout -k 10 400 python3 bench.py --config c4 --steps 20 --warmup 5 --repeats 3 --no-cpu-baseline > $o/c4_bench.json 2> $o/c4.err
-timeout -k 10 400 python3 bench.py --config c5 --no-cpu-baseline > $o/c5_bench.json 2> $o/c5.err
+timeout -k 10 300 python3 bench.py --full --config c3 --no-cpu-baseline > $o/c3_bench.json 2> $o/c3.err
+timeout -k 10 400 python3 bench.py --full --config c4 --steps 20 --warmup 5 --repeats 3 --no-cpu-baseline > $o/c4_bench.json 2> $o/c4.err
+timeout -k 10 400 python3 bench.py --full --config c5 --no-cpu-baseline > $o/c5_bench.json 2> $o/c5.err
 rm -rf $o/prof $o/prof_bf
 python3 - <<'PY'
 import json, glob
