@@ -433,3 +433,36 @@ def vertex_update_ms(x, normals, faces, v_faces, iters=(80, 20, 20)):
                                           ptr(n1), ptr(n2), it, ptr(dx), ptr(scr), nscr, stream_ptr()),
           "fgc_vertex_update_ms")
     return out, dx
+
+
+def pack_cells(ijk):
+    """int [n,3] cell coordinates (0 <= c < 512; a row with any negative entry = in no cell) -> the packed int32 cells of
+    fgc_nn_query, (i << 20) | (j << 10) | k, or -1."""
+    ijk = np.asarray(ijk, dtype=np.int64).reshape(-1, 3)
+    if (ijk >= 512).any():
+        raise ValueError("cell coordinates must be < 512")
+    packed = (ijk[:, 0] << 20) | (ijk[:, 1] << 10) | ijk[:, 2]
+    return np.where((ijk < 0).any(1), -1, packed).astype(np.int32)
+
+
+def nn_query(q, p, q_cell=None, p_cell=None):
+    """Nearest point of p [np,3] for every query q [nq,3] (fp32 GPU tensors; include/fgc.h: fgc_nn_query): (dist [nq]
+    float32, idx [nq] int32), ties to the lowest index.  With q_cell / p_cell (int32 [nq] / [np], packed by pack_cells)
+    only the 2x2x2 candidate cells of a query's cell count; no candidate: (+inf, -1)."""
+    _req_cuda(q, p, q_cell, p_cell)
+    q, p = _f32c(q.reshape(-1, 3)), _f32c(p.reshape(-1, 3))
+    if (q_cell is None) != (p_cell is None):
+        raise ValueError("q_cell and p_cell go together")
+    if q_cell is not None:
+        q_cell = q_cell.to(torch.int32).contiguous()
+        p_cell = p_cell.to(torch.int32).contiguous()
+        if q_cell.numel() != q.shape[0] or p_cell.numel() != p.shape[0]:
+            raise ValueError("one cell per point")
+    nq, n_p = q.shape[0], p.shape[0]
+    dist = torch.empty(nq, dtype=torch.float32, device=q.device)
+    idx = torch.empty(nq, dtype=torch.int32, device=q.device)
+    nbytes = _lib.lib().fgc_nn_workspace_bytes(nq, n_p)
+    ws = _workspace(nbytes, q.device, "nn")
+    check(_lib.lib().fgc_nn_query(ptr(q), nq, ptr(p), n_p, ptr(q_cell), ptr(p_cell), ptr(dist), ptr(idx), ptr(ws),
+                                  ws.numel(), stream_ptr()), "fgc_nn_query")
+    return dist, idx

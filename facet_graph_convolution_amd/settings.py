@@ -7,6 +7,7 @@ MIN_PATCH_SIZE = 2000       # settings.py:22
 SAVEITER = 5000             # settings.py:30
 NUM_ITERATIONS = 300000     # settings.py:33
 MAX_EDGES = 20              # dataClasses.py:40 (getEdgeMap(faces0, maxEdges = 20)); train.py:44 reads it off v_e_map
+HEATMAP_MAX_ANGLE = 30.0    # settings.py:39: the angular error (degrees) that computeMetrics' heat maps show in red
 
 
 def getGTFilename(filename):

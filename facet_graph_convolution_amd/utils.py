@@ -1,4 +1,6 @@
 """Host-side helpers that keep the names of the reference's ``utils.py`` where a counterpart exists."""
+import math
+
 import numpy as np
 
 
@@ -305,3 +307,190 @@ def write_mesh(vl, fl, strFileName):
             if row[0] == 0 and row[1] == 0:
                 continue
             fh.write("f " + " ".join(str(int(t)) for t in row) + " \n")
+
+
+# ---------------------------------------------------------------------------------------------------
+# evaluation metrics (what computeMetrics.py calls, utils.py:227-240, 816-1006, 1168-1239, 1973-2031, 2322-2342)
+# ---------------------------------------------------------------------------------------------------
+def _nn_gpu(q, p, q_cell=None, p_cell=None):
+    """fgc_nn_query on host arrays: (dist float32 [nq], idx int64 [nq]) of the nearest point of p for every row of q."""
+    import torch
+    from . import ops
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def put(a, dt):
+        return None if a is None else torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    dist, idx = ops.nn_query(put(q, np.float32), put(p, np.float32), put(q_cell, np.int32), put(p_cell, np.int32))
+    return dist.cpu().numpy(), idx.cpu().numpy().astype(np.int64)
+
+
+def _slice_cells(pts, bounds, slices):
+    """Cell coordinates of every point in the reference's partition (utils.py:876-930): along each axis slice i holds
+    the points with i*max/slices < c < (i+1)*max/slices, the same numpy expressions as the reference; -1 on an axis
+    where a point lies on a bound or outside [0, max]."""
+    cell = np.full((pts.shape[0], 3), -1, dtype=np.int64)
+    for axis, m in enumerate(bounds):
+        c = pts[:, axis]
+        for i in range(slices):
+            cm = i * m / slices
+            cM = (i + 1) * m / slices
+            cell[(c > cm) & (c < cM), axis] = i
+    return cell
+
+
+def _one_side_over_cells(Q, S, bounds):
+    """Distances of the query points Q that lie in a cell of the 5^3 partition to their nearest point of S among the
+    2x2x2 cells of the 6^3 partition that the reference concatenates for that query cell (utils.py:951-965), in the
+    reference's order: query cells (i, j, k) in lexicographic order, points in row order inside a cell."""
+    from .ops import pack_cells
+    qc = _slice_cells(Q, bounds, 5)
+    sc = _slice_cells(S, bounds, 6)
+    inside = np.flatnonzero((qc >= 0).all(1))
+    if inside.size == 0:
+        raise ValueError("zero-size array to reduction operation minimum which has no identity (no point in any cell)")
+    flat = (qc[inside] * np.array([25, 5, 1])).sum(1)
+    order = inside[np.argsort(flat, kind="stable")]
+    dist, idx = _nn_gpu(Q, S, pack_cells(qc), pack_cells(sc))
+    if (idx[order] < 0).any():
+        raise ValueError("zero-size array to reduction operation minimum which has no identity "
+                         "(a query cell with points has no candidate point in its 2x2x2 cells)")
+    return dist[order]
+
+
+def hausdorffOverSampled(V0, V1, sV0, sV1, accuracyOnly=False):
+    """utils.py:816-1006: (min_acc, min_comp, avg_acc, avg_comp) over the reference's spatial partition.
+
+    Normalisation as the reference: every set is translated by the float32 corner of V0 u V1 and divided by the
+    bounding-box diagonal of V0 u V1; the partition's upper bounds are the maxima of the normalised V0 u V1.  Accuracy:
+    every point of V0 that lies in one of the 5^3 query cells, to its nearest point of sV1 among the 2x2x2 cells of the
+    6^3 candidate partition above that query cell; completeness: V1 against sV0 the same way (skipped with accuracyOnly,
+    which returns 0 for both completeness values, as the reference).  The distance scan is fgc_nn_query (libfgc) with
+    the cells as masks; distances are float32 in the reference's arithmetic, so the values match the reference's.
+
+    Quirks of the reference, kept:
+      * the first two values are the MINIMUM of the per-point distances (np.amin, utils.py:997), although
+        computeMetrics stores the first as its Hausdorff distance;
+      * a query whose true nearest point lies outside its 2x2x2 candidate cells gets the larger, approximate distance;
+      * points in no cell (on a slice bound, or outside [0, max] on an axis) are left out, of the minimum and the mean;
+      * no point in any query cell, or an empty candidate set for a query cell that holds points, raises ValueError
+        where the reference's np.amin over a zero-size axis raises.
+    Queries and candidates are float32 on the device whatever the input dtype."""
+    V0, V1, sV0, sV1 = (np.asarray(a) for a in (V0, V1, sV0, sV1))
+    xmin = min(np.amin(V0[:, 0]), np.amin(V1[:, 0]))
+    ymin = min(np.amin(V0[:, 1]), np.amin(V1[:, 1]))
+    zmin = min(np.amin(V0[:, 2]), np.amin(V1[:, 2]))
+    xmax = max(np.amax(V0[:, 0]), np.amax(V1[:, 0]))
+    ymax = max(np.amax(V0[:, 1]), np.amax(V1[:, 1]))
+    zmax = max(np.amax(V0[:, 2]), np.amax(V1[:, 2]))
+    diag = math.sqrt(math.pow(xmax - xmin, 2) + math.pow(ymax - ymin, 2) + math.pow(zmax - zmin, 2))
+    transVec = np.array(([[xmin, ymin, zmin]]), dtype=np.float32)
+    V0 = (V0 - transVec) / diag
+    V1 = (V1 - transVec) / diag
+    sV0 = (sV0 - transVec) / diag
+    sV1 = (sV1 - transVec) / diag
+    bounds = (max(np.amax(V0[:, 0]), np.amax(V1[:, 0])), max(np.amax(V0[:, 1]), np.amax(V1[:, 1])),
+              max(np.amax(V0[:, 2]), np.amax(V1[:, 2])))
+    total_acc = _one_side_over_cells(V0, sV1, bounds)
+    min_acc, avg_acc = np.amin(total_acc), np.mean(total_acc)
+    if accuracyOnly:
+        return min_acc, 0, avg_acc, 0
+    total_comp = _one_side_over_cells(V1, sV0, bounds)
+    return min_acc, np.amin(total_comp), avg_acc, np.mean(total_comp)
+
+
+def mesh_distances(V0, V1):
+    """Exact point-set distances between V0 (e.g. a denoised mesh) and V1 (its ground truth).  NOT a reference function:
+    the reference's 'Hausdorff' column is a minimum of approximate distances (hausdorffOverSampled); this is what a user
+    comparing methods wants.  Both sets are normalised as in hausdorffOverSampled (float32 corner translation, division
+    by the bounding-box diagonal of V0 u V1); two unmasked fgc_nn_query scans give, over ALL points,
+      acc_max, acc_mean    max / mean over V0 of the distance to the nearest point of V1,
+      comp_max, comp_mean  max / mean over V1 of the distance to the nearest point of V0,
+      hausdorff            max(acc_max, comp_max), the two-sided Hausdorff distance of the vertex sets.
+    Returns a dict with these five float32 values."""
+    V0, V1 = np.asarray(V0), np.asarray(V1)
+    lo = np.minimum(V0.min(0), V1.min(0))
+    hi = np.maximum(V0.max(0), V1.max(0))
+    diag = math.sqrt(sum(math.pow(float(h) - float(l), 2) for l, h in zip(lo, hi)))
+    transVec = lo.astype(np.float32)[None]
+    A = (V0 - transVec) / diag
+    B = (V1 - transVec) / diag
+    acc, _ = _nn_gpu(A, B)
+    comp, _ = _nn_gpu(B, A)
+    out = {"acc_max": np.amax(acc), "acc_mean": np.mean(acc), "comp_max": np.amax(comp), "comp_mean": np.mean(comp)}
+    out["hausdorff"] = max(out["acc_max"], out["comp_max"])
+    return out
+
+
+def angularDiffVec(n0, n1):
+    """utils.py:1218-1239: per-row angle in degrees between n0 and n1, arccos(0.999999 * <normalize(n0), normalize(n1)>)
+    with the reference's double normalisation (1e-8 in the norm); fake nodes (rows of n1 with every |entry| <= 1e-3)
+    are NOT excluded here."""
+    n0 = normalize(np.asarray(n0))
+    n1 = normalize(np.asarray(n1))
+    dotP = np.sum(np.multiply(n0, n1), axis=1)
+    angDiff = np.arccos(0.999999 * dotP)
+    return angDiff * 180 / math.pi
+
+
+def fakeNodes(n1):
+    """The fake-node mask of angularDiff (utils.py:1171-1172): every |entry| of the row <= 1e-3."""
+    return np.all(np.less_equal(np.absolute(np.asarray(n1)), 10e-4), axis=-1)
+
+
+def angularDiff(n0, n1):
+    """utils.py:1168-1213: (mean, std) of angularDiffVec over the rows that are not fake nodes of n1."""
+    fake = fakeNodes(n1)
+    angDiff = np.extract(fake == False, angularDiffVec(n0, n1))  # noqa: E712  (the reference's expression)
+    return np.mean(angDiff), np.std(angDiff)
+
+
+def getBorderFaces(faces):
+    """utils.py:227-240: int8 [F], 1 for a face with an edge that has no second face (getEdgeMap, maxEdges = 50)."""
+    faces = np.asarray(faces)
+    fborder = np.zeros([faces.shape[0]], dtype=np.int8)
+    e_map, _ = getEdgeMap(faces)
+    fborder[e_map[e_map[:, 3] < 0, 2]] = 1
+    return fborder
+
+
+def getDensePC(V, F, res=4):
+    """utils.py:2322-2342: V followed by the barycentric samples (b0 V1 + b1 V2 + (res-b0-b1) V3) / res of every face,
+    0 < b0 + b1, b0 < res, b1 < res; with res = 1 there are none and the result is V."""
+    V, F = np.asarray(V), np.asarray(F)
+    V1, V2, V3 = V[F[:, 0]], V[F[:, 1]], V[F[:, 2]]
+    listV = [V]
+    for b0 in range(res):
+        for b1 in range(res - b0 + 1):
+            if b0 < res and b1 < res and b1 + b0 > 0:
+                listV.append((b0 * V1 + b1 * V2 + (res - b0 - b1) * V3) / res)
+    return np.concatenate(listV, axis=0)
+
+
+def getHeatMapColor(myVec):
+    """utils.py:2002-2031, vectorised: float64 [n,3] colours on the ramp blue - cyan - green - yellow - red, four linear
+    pieces on [0, 0.25), [0.25, 0.5), [0.5, 0.75) and the rest (NaN included).  The coefficient 4*e - k is formed in the
+    input's dtype and the blend in float64, as the reference's per-element code does."""
+    myVec = np.asarray(myVec)
+    ramp = np.array([[0.0, 0.0, 1.0], [0.0, 1.0, 1.0], [0.0, 1.0, 0.0], [1.0, 1.0, 0.0], [1.0, 0.0, 0.0]])
+    piece = np.full(myVec.shape[0], 3, dtype=np.int64)
+    for k, lim in reversed(list(enumerate((0.25, 0.5, 0.75)))):
+        piece[myVec < lim] = k
+    heatmap = np.empty((myVec.shape[0], 3))
+    for k in range(4):
+        sel = piece == k
+        coef = 4 * myVec[sel] - k if k else 4 * myVec[sel]
+        heatmap[sel] = coef[:, None] * ramp[k + 1] + (1 - coef)[:, None] * ramp[k]
+    return heatmap
+
+
+def getColoredMesh(V, F, faceColors):
+    """utils.py:1973-2000: a mesh with three vertices of its own per face, rows [x, y, z, r, g, b] (a face index -1
+    reads the zero vertex), faces [F,3] = 0 .. 3F-1."""
+    F = np.asarray(F) + 1
+    V = np.concatenate((np.array([[0, 0, 0]], dtype=np.float32), np.asarray(V)), axis=0)
+    Vl = V[F]
+    faceColors = np.tile(np.expand_dims(np.asarray(faceColors), axis=1), (1, 3, 1))
+    facesNum = F.shape[0]
+    newV = np.reshape(np.concatenate((Vl, faceColors), axis=-1), (3 * facesNum, 6))
+    newF = np.reshape(np.arange(3 * facesNum), (facesNum, 3))
+    return newV, newF

@@ -45,8 +45,9 @@ extern "C" {
  * flags of fgc_mlp_fwd / fgc_mlp_bwd and their _bf16 forms, larger fgc_conv_desc / fgc_conv_bwd_io (all since 101).
  * 103: fgc_conv_pairs_allowed; options NO_BFM, K1_QS14; fgc_conv_desc.options / n_options (per-descriptor option overrides).
  * 104: fgc_conv_bwd_io.r_ld (the stride of r stated with the buffer); fgc_conv_desc.packed_layout + fgc_conv_layout_id,
- * fgc_mlp_layout_id / FGC_MLP_LAYOUT (packed operands carry the identity of their layout). */
-#define FGC_ABI_VERSION 104
+ * fgc_mlp_layout_id / FGC_MLP_LAYOUT (packed operands carry the identity of their layout).
+ * 105: fgc_nn_query / fgc_nn_workspace_bytes (nearest neighbour over point sets, for the evaluation metrics). */
+#define FGC_ABI_VERSION 105
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -640,6 +641,21 @@ int fgc_vertex_update_ms(const float* x, float* x_out, int32_t nv, const int32_t
                          const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
                          const float* normals2, const int32_t* iters, float* dx_out, float* scratch,
                          size_t scratch_floats, void* stream);
+
+/* Nearest neighbour over point sets: the distance scan of hausdorffOverSampled (utils.py:816-1006) and of exact
+ * point-set distances.  For every query point q[i] (float32 [nq,3]) the nearest point of p (float32 [np,3]) by squared
+ * Euclidean distance, computed in fp32 in the reference's order (dx*dx + dy*dy) + dz*dz with every operation rounded
+ * (no fused multiply-add): dist[i] = its distance (the correctly rounded fp32 sqrt of that value), idx[i] = its row.
+ * Exact (brute force) and deterministic: equal squared distances resolve to the LOWEST index, and the result does not
+ * depend on how the launch splits the work.  Candidates whose squared distance is NaN or +inf are never chosen.
+ * Optional masks (both NULL, or both given), int32 [nq] / [np]: packed cell coordinates (i << 20) | (j << 10) | k with
+ * 0 <= i, j, k < 512, or -1 for "in no cell".  Then candidate j counts for query i only if p_cell[j] lies in one of the
+ * 2x2x2 cells (i..i+1, j..j+1, k..k+1) of q_cell[i] (the reference's partition: 5^3 query cells, 6^3 candidate cells).
+ * A query with no candidate gets dist = +inf and idx = -1, and so does a query whose own cell is -1.
+ * workspace (device, 8-byte aligned) >= fgc_nn_workspace_bytes(nq, np); two launches and a memset on `stream`. */
+size_t fgc_nn_workspace_bytes(int32_t nq, int32_t np);
+int fgc_nn_query(const float* q, int32_t nq, const float* p, int32_t np, const int32_t* q_cell, const int32_t* p_cell,
+                 float* dist, int32_t* idx, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Checkpoint files (CPU; HOST pointers)
