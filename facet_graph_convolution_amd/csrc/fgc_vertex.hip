@@ -140,6 +140,139 @@ __global__ __launch_bounds__(256) void vertex_update_ms_kernel(const float* __re
     xo[3 * (size_t)v + 2] = x2 + lm * a2;
 }
 
+// ---------------------------------------------------------------------------------------------
+// adjoint of the multi-scale vertex update (trainAccuracyNet back-propagates through update_position_MS, train.py:767-776)
+// ---------------------------------------------------------------------------------------------
+// One forward iteration at level s (shift = 2s): x'_v = x_v + lam_v sum_k n_j (n_j . (c_j - x_v)), j = v_faces[v,k] >> shift,
+// c = P_s(C(x)).  With gbar = dL/dx' and a_v = lam_v gbar_v, summed over the slot pairs (v,k) that point to node j:
+// A_j = sum a_v, S_j = sum (a_v x_v^T + x_v a_v^T).  Then
+//   dL/dx_v = gbar_v - sum_k n_j (n_j . a_v) + [C^T P_s^T dL/dc]_v,  dL/dc_j = n_j (n_j . A_j),
+//   dL/dn_j += (A_j . n_j) c_j + (n_j . c_j) A_j - S_j n_j.
+// Every sum runs over a fixed list in a fixed order (the inverse tables below, built once per mesh), one thread per
+// output row: no atomics, the result is the same bits from run to run and under hipGraph replay.
+
+// lam_v = 1 / #valid slots, exactly as vertex_update_ms_kernel computes it (0 for a vertex without faces)
+__global__ __launch_bounds__(256) void vertex_lambda_kernel(const int* __restrict__ vfaces, int k_v, int nv,
+                                                            float* __restrict__ lam) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    int numf = 0;
+    for (int k = 0; k < k_v; ++k) numf += vfaces[(size_t)v * k_v + k] >= 0;
+    lam[v] = numf > 0 ? 1.0f / (float)numf : 0.f;
+}
+
+// one thread per node j of level s: A_j and S_j over the slot entries of the fine faces [j 4^s, (j+1) 4^s) (a contiguous
+// segment of the slot inverse), then dL/dc_j (written) and dL/dn_j (accumulated over the iterations of the level)
+__global__ __launch_bounds__(256) void vertex_ms_bwd_node_kernel(const float* __restrict__ g, const float* __restrict__ x,
+                                                                 const float* __restrict__ lam,
+                                                                 const int* __restrict__ slot_ptr,
+                                                                 const int* __restrict__ slot_vert, int shift, int nnodes,
+                                                                 const float* __restrict__ nrm,
+                                                                 const float* __restrict__ c, float* __restrict__ gc,
+                                                                 float* __restrict__ gn) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= nnodes) return;
+    const int lo = slot_ptr[(size_t)j << shift], hi = slot_ptr[(size_t)(j + 1) << shift];
+    float A0 = 0.f, A1 = 0.f, A2 = 0.f;
+    float S00 = 0.f, S11 = 0.f, S22 = 0.f, S01 = 0.f, S02 = 0.f, S12 = 0.f;
+    for (int e = lo; e < hi; ++e) {
+        const int v = slot_vert[e];
+        const float l = lam[v];
+        const float a0 = l * g[3 * (size_t)v], a1 = l * g[3 * (size_t)v + 1], a2 = l * g[3 * (size_t)v + 2];
+        const float x0 = x[3 * (size_t)v], x1 = x[3 * (size_t)v + 1], x2 = x[3 * (size_t)v + 2];
+        A0 += a0;
+        A1 += a1;
+        A2 += a2;
+        S00 += 2.f * a0 * x0;
+        S11 += 2.f * a1 * x1;
+        S22 += 2.f * a2 * x2;
+        S01 += a0 * x1 + a1 * x0;
+        S02 += a0 * x2 + a2 * x0;
+        S12 += a1 * x2 + a2 * x1;
+    }
+    const float n0 = nrm[3 * (size_t)j], n1 = nrm[3 * (size_t)j + 1], n2 = nrm[3 * (size_t)j + 2];
+    const float c0 = c[3 * (size_t)j], c1 = c[3 * (size_t)j + 1], c2 = c[3 * (size_t)j + 2];
+    const float an = (A0 * n0 + A1 * n1) + A2 * n2;
+    const float cn = (c0 * n0 + c1 * n1) + c2 * n2;
+    gc[3 * (size_t)j] = an * n0;
+    gc[3 * (size_t)j + 1] = an * n1;
+    gc[3 * (size_t)j + 2] = an * n2;
+    gn[3 * (size_t)j] += an * c0 + cn * A0 - ((S00 * n0 + S01 * n1) + S02 * n2);
+    gn[3 * (size_t)j + 1] += an * c1 + cn * A1 - ((S01 * n0 + S11 * n1) + S12 * n2);
+    gn[3 * (size_t)j + 2] += an * c2 + cn * A2 - ((S02 * n0 + S12 * n1) + S22 * n2);
+}
+
+// adjoint of pool4_avg_iz_kernel (c = 3): one thread per output row re-derives the forward's zero-row choices from the
+// same input values (x [4n,3]) and routes dy to the four input rows it read; every input row has one reader: plain writes
+__global__ __launch_bounds__(256) void pool4_avg_iz_bwd_kernel(const float* __restrict__ x, int nout,
+                                                               const float* __restrict__ dy, float* __restrict__ dx) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= nout) return;
+    const float* base = x + (size_t)r * 12;
+    bool z[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) z[q] = base[3 * q] == 0.f && base[3 * q + 1] == 0.f && base[3 * q + 2] == 0.f;
+    bool zm0 = true, zm1 = true;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float p0 = z[0] ? base[3 + k] : base[k], p1 = z[1] ? base[k] : base[3 + k];
+        const float q0 = z[2] ? base[9 + k] : base[6 + k], q1 = z[3] ? base[6 + k] : base[9 + k];
+        zm0 = zm0 && ((p0 + p1) / 2.0f == 0.f);
+        zm1 = zm1 && ((q0 + q1) / 2.0f == 0.f);
+    }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float gcc = dy[3 * (size_t)r + k] * 0.5f;                       // y = (c0 + c1) / 2
+        const float gm0 = (zm0 ? 0.f : gcc) + (zm1 ? gcc : 0.f);               // c0 = zm0 ? m1 : m0, c1 = zm1 ? m0 : m1
+        const float gm1 = (zm0 ? gcc : 0.f) + (zm1 ? 0.f : gcc);
+        const float ga = gm0 * 0.5f, gb = gm1 * 0.5f;                          // m = (a0 + a1) / 2
+        // a0 = z0 ? v1 : v0, a1 = z1 ? v0 : v1 (and b likewise over rows 2, 3)
+        dx[(size_t)r * 12 + k] = (z[0] ? 0.f : ga) + (z[1] ? ga : 0.f);
+        dx[(size_t)r * 12 + 3 + k] = (z[0] ? ga : 0.f) + (z[1] ? 0.f : ga);
+        dx[(size_t)r * 12 + 6 + k] = (z[2] ? 0.f : gb) + (z[3] ? gb : 0.f);
+        dx[(size_t)r * 12 + 9 + k] = (z[2] ? gb : 0.f) + (z[3] ? 0.f : gb);
+    }
+}
+
+// one thread per vertex: the direct term over the vertex' own slots, then the barycentre adjoint over its face incidence
+__global__ __launch_bounds__(256) void vertex_ms_bwd_vertex_kernel(const float* __restrict__ g, int nv,
+                                                                   const float* __restrict__ lam,
+                                                                   const int* __restrict__ vfaces, int k_v, int shift,
+                                                                   const float* __restrict__ nrm, int nnodes,
+                                                                   const int* __restrict__ inc_ptr,
+                                                                   const int* __restrict__ inc_face,
+                                                                   const float* __restrict__ gfp0,
+                                                                   float* __restrict__ go) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const float l = lam[v];
+    const float g0 = g[3 * (size_t)v], g1 = g[3 * (size_t)v + 1], g2 = g[3 * (size_t)v + 2];
+    const float a0 = l * g0, a1 = l * g1, a2 = l * g2;
+    float d0 = 0.f, d1 = 0.f, d2 = 0.f;
+    for (int k = 0; k < k_v; ++k) {
+        const int f = vfaces[(size_t)v * k_v + k];
+        if (f < 0) continue;
+        const int node = f >> shift;
+        if (node >= nnodes) continue;
+        const float n0 = nrm[3 * (size_t)node], n1 = nrm[3 * (size_t)node + 1], n2 = nrm[3 * (size_t)node + 2];
+        const float w = (n0 * a0 + n1 * a1) + n2 * a2;
+        d0 += w * n0;
+        d1 += w * n1;
+        d2 += w * n2;
+    }
+    float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+    const int lo = inc_ptr[v], hi = inc_ptr[v + 1];
+    for (int e = lo; e < hi; ++e) {
+        const int f = inc_face[e];
+        b0 += gfp0[3 * (size_t)f];
+        b1 += gfp0[3 * (size_t)f + 1];
+        b2 += gfp0[3 * (size_t)f + 2];
+    }
+    go[3 * (size_t)v] = (g0 - d0) + b0 / 3.0f;
+    go[3 * (size_t)v + 1] = (g1 - d1) + b1 / 3.0f;
+    go[3 * (size_t)v + 2] = (g2 - d2) + b2 / 3.0f;
+}
+
 __global__ void sub3_kernel(const float* a, const float* b, int n, float* o) {   // o may alias b
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) o[i] = a[i] - b[i];
@@ -251,5 +384,142 @@ extern "C" int fgc_vertex_update(const float* x, float* x_out, float* tmp, int32
         src = dst;
     }
     FGC_CHECK_LAUNCH("fgc_vertex_update");
+    return FGC_OK;
+}
+
+// the trajectory form of fgc_vertex_update_ms: the same launches with the same arguments, every iteration writing its own
+// slot of traj (slot 0 = x, slot t + 1 = the output of iteration t) instead of a ping-pong buffer
+extern "C" int fgc_vertex_update_ms_traj(const float* x, int32_t nv, const int32_t* faces, int32_t n0,
+                                         const int32_t* v_faces, int32_t k_v, const float* normals0,
+                                         const float* normals1, const float* normals2, const int32_t* iters,
+                                         float* traj, size_t traj_floats, float* scratch, size_t scratch_floats,
+                                         void* stream) {
+    FGC_CHECK_ARG(x && faces && v_faces && normals0 && normals1 && normals2 && iters && traj && scratch,
+                  "fgc_vertex_update_ms_traj: null pointer");
+    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0,
+                  "fgc_vertex_update_ms_traj: nv=%d n0=%d (multiple of 16) k_v=%d", nv, n0, k_v);
+    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0, "fgc_vertex_update_ms_traj: negative iteration count");
+    const int n1 = n0 / 4, n2 = n0 / 16;
+    const size_t T = (size_t)iters[0] + iters[1] + iters[2];
+    const size_t need_traj = (T + 1) * 3 * (size_t)nv;
+    FGC_CHECK_ARG(traj_floats >= need_traj, "fgc_vertex_update_ms_traj: traj too small (%zu < %zu floats)", traj_floats,
+                  need_traj);
+    const size_t need = 3 * ((size_t)n0 + n1 + n2);
+    FGC_CHECK_ARG(scratch_floats >= need, "fgc_vertex_update_ms_traj: scratch too small (%zu < %zu floats)", scratch_floats,
+                  need);
+    FGC_CHECK_ARG(x < traj || x >= traj + need_traj, "fgc_vertex_update_ms_traj: x must not lie in traj");
+    hipStream_t st = (hipStream_t)stream;
+    float* fp0 = scratch;
+    float* fp1 = fp0 + 3 * (size_t)n0;
+    float* fp2 = fp1 + 3 * (size_t)n1;
+    const float* nrm[3] = {normals0, normals1, normals2};
+    float* fps[3] = {fp0, fp1, fp2};
+    const int nn[3] = {n0, n1, n2};
+    if (hipMemcpyAsync(traj, x, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        fgc::set_error("fgc_vertex_update_ms_traj: copy failed");
+        return FGC_EHIP;
+    }
+    size_t t = 0;
+    for (int stage = 0; stage < 3; ++stage) {
+        const int scale = 2 - stage;
+        for (int it = 0; it < iters[stage]; ++it, ++t) {
+            const float* cur = traj + t * 3 * (size_t)nv;
+            float* nxt = traj + (t + 1) * 3 * (size_t)nv;
+            FGC_LAUNCH("face_centers_kernel", st, face_centers_kernel, dim3(cdiv(n0, 256)), dim3(256), 0, cur, nv, faces, n0, fp0);
+            if (scale >= 1)
+                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n1 * 3, 256)), dim3(256), 0, fp0, n1, 3, fp1);
+            if (scale >= 2)
+                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n2 * 3, 256)), dim3(256), 0, fp1, n2, 3, fp2);
+            FGC_LAUNCH("vertex_update_ms_kernel", st, vertex_update_ms_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, cur, nxt, nv,
+                       v_faces, k_v, 2 * scale, nrm[scale], fps[scale], nn[scale]);
+        }
+    }
+    FGC_CHECK_LAUNCH("fgc_vertex_update_ms_traj");
+    return FGC_OK;
+}
+
+extern "C" size_t fgc_vertex_update_ms_bwd_workspace_floats(int32_t nv, int32_t n0) {
+    if (nv <= 0 || n0 <= 0) return 0;
+    const size_t nodes = (size_t)n0 + n0 / 4 + n0 / 16;
+    return (size_t)nv * 7 + 6 * nodes;      // lam, two gradient buffers; centres and their gradients of the three levels
+}
+
+extern "C" int fgc_vertex_update_ms_bwd(const float* traj, size_t traj_floats, int32_t nv, const int32_t* faces, int32_t n0,
+                                        const int32_t* v_faces, int32_t k_v, const float* normals0,
+                                        const float* normals1, const float* normals2, const int32_t* iters,
+                                        const int32_t* slot_ptr, const int32_t* slot_vert, const int32_t* inc_ptr,
+                                        const int32_t* inc_face, const float* g_out, float* g_x, float* g_n0,
+                                        float* g_n1, float* g_n2, float* workspace, size_t workspace_floats,
+                                        void* stream) {
+    FGC_CHECK_ARG(traj && faces && v_faces && normals0 && normals1 && normals2 && iters && slot_ptr && slot_vert &&
+                      inc_ptr && inc_face && g_out && g_x && g_n0 && g_n1 && g_n2 && workspace,
+                  "fgc_vertex_update_ms_bwd: null pointer");
+    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0,
+                  "fgc_vertex_update_ms_bwd: nv=%d n0=%d (multiple of 16) k_v=%d", nv, n0, k_v);
+    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0, "fgc_vertex_update_ms_bwd: negative iteration count");
+    const size_t need = fgc_vertex_update_ms_bwd_workspace_floats(nv, n0);
+    FGC_CHECK_ARG(workspace_floats >= need, "fgc_vertex_update_ms_bwd: workspace too small (%zu < %zu floats)",
+                  workspace_floats, need);
+    const size_t need_traj = ((size_t)iters[0] + iters[1] + iters[2] + 1) * 3 * (size_t)nv;
+    FGC_CHECK_ARG(traj_floats >= need_traj, "fgc_vertex_update_ms_bwd: traj too small (%zu < %zu floats)", traj_floats,
+                  need_traj);
+    FGC_CHECK_ARG(g_out != g_x, "fgc_vertex_update_ms_bwd: g_out and g_x must be distinct");
+    const int n1 = n0 / 4, n2 = n0 / 16;
+    hipStream_t st = (hipStream_t)stream;
+    float* lam = workspace;
+    float* ga = lam + nv;
+    float* gb = ga + 3 * (size_t)nv;
+    float* fp0 = gb + 3 * (size_t)nv;
+    float* fp1 = fp0 + 3 * (size_t)n0;
+    float* fp2 = fp1 + 3 * (size_t)n1;
+    float* gc0 = fp2 + 3 * (size_t)n2;
+    float* gc1 = gc0 + 3 * (size_t)n0;
+    float* gc2 = gc1 + 3 * (size_t)n1;
+    const float* nrm[3] = {normals0, normals1, normals2};
+    float* gns[3] = {g_n0, g_n1, g_n2};
+    float* fps[3] = {fp0, fp1, fp2};
+    float* gcs[3] = {gc0, gc1, gc2};
+    const int nn[3] = {n0, n1, n2};
+    for (int s = 0; s < 3; ++s)
+        if (hipMemsetAsync(gns[s], 0, (size_t)nn[s] * 12, st) != hipSuccess) {
+            fgc::set_error("fgc_vertex_update_ms_bwd: memset failed");
+            return FGC_EHIP;
+        }
+    if (hipMemcpyAsync(ga, g_out, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        fgc::set_error("fgc_vertex_update_ms_bwd: copy failed");
+        return FGC_EHIP;
+    }
+    FGC_LAUNCH("vertex_lambda_kernel", st, vertex_lambda_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, v_faces, k_v, nv, lam);
+    size_t t = (size_t)iters[0] + iters[1] + iters[2];
+    float* cur = ga;     // dL/d x_{t+1}
+    float* nxt = gb;
+    for (int stage = 2; stage >= 0; --stage) {
+        const int scale = 2 - stage;
+        for (int it = 0; it < iters[stage]; ++it) {
+            --t;
+            const float* xt = traj + t * 3 * (size_t)nv;
+            // the centres the forward iteration read, recomputed by the forward's own kernels from x_t
+            FGC_LAUNCH("face_centers_kernel", st, face_centers_kernel, dim3(cdiv(n0, 256)), dim3(256), 0, xt, nv, faces, n0, fp0);
+            if (scale >= 1)
+                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n1 * 3, 256)), dim3(256), 0, fp0, n1, 3, fp1);
+            if (scale >= 2)
+                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n2 * 3, 256)), dim3(256), 0, fp1, n2, 3, fp2);
+            FGC_LAUNCH("vertex_ms_bwd_node_kernel", st, vertex_ms_bwd_node_kernel, dim3(cdiv(nn[scale], 256)), dim3(256), 0,
+                       cur, xt, lam, slot_ptr, slot_vert, 2 * scale, nn[scale], nrm[scale], fps[scale], gcs[scale], gns[scale]);
+            for (int l = scale; l >= 1; --l)
+                FGC_LAUNCH("pool4_avg_iz_bwd_kernel", st, pool4_avg_iz_bwd_kernel, dim3(cdiv(nn[l], 256)), dim3(256), 0,
+                           fps[l - 1], nn[l], gcs[l], gcs[l - 1]);
+            FGC_LAUNCH("vertex_ms_bwd_vertex_kernel", st, vertex_ms_bwd_vertex_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, cur,
+                       nv, lam, v_faces, k_v, 2 * scale, nrm[scale], nn[scale], inc_ptr, inc_face, gc0, nxt);
+            float* tmp = cur;
+            cur = nxt;
+            nxt = tmp;
+        }
+    }
+    if (hipMemcpyAsync(g_x, cur, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        fgc::set_error("fgc_vertex_update_ms_bwd: copy failed");
+        return FGC_EHIP;
+    }
+    FGC_CHECK_LAUNCH("fgc_vertex_update_ms_bwd");
     return FGC_OK;
 }

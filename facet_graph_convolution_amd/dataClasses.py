@@ -210,6 +210,23 @@ class TrainingSet(PreprocessedData):
         self.addMesh_TimeEfficient(V_noisy, faces, GTV=V_gt, seed=seed, parents=parents)
 
 
+    def addMeshWithVerticesAndGT(self, V_noisy, faces, V_gt, gtfilename=None, seed=None, parents=None):
+        """dataClasses.py:497-506: addMeshWithVertices with the ground-truth vertices (gtv_list), for trainAccuracyNet.
+        Either the reference's call addMeshWithVerticesAndGT(inputFilePath, filename, gtFilePath, gtfilename) (both
+        OBJs read with utils.load_mesh; the noisy file's faces are used) or arrays addMeshWithVerticesAndGT(V_noisy,
+        faces, V_gt)."""
+        if isinstance(V_noisy, str):
+            in_path, in_name, gt_path = V_noisy, faces, V_gt
+            V_noisy, _, _, faces, _ = utils.load_mesh(in_path, in_name, 0, False)
+            V_gt = utils.load_mesh(gt_path, gtfilename, 0, False)[0]
+        V_noisy = np.asarray(V_noisy, dtype=np.float32)
+        self.fNum, self.vNum = np.asarray(faces).shape[0], V_noisy.shape[0]
+        PreprocessedData.addMeshWithVertices(self, V_noisy, faces, GTV=V_gt, seed=seed, parents=parents)
+        self.vertices = V_noisy[np.newaxis]
+        self.faces = np.asarray(faces)
+        self.normals = utils.computeFacesNormals(V_noisy, self.faces)
+
+
 class InferenceMesh(PreprocessedData):
     """dataClasses.py:510-531."""
 

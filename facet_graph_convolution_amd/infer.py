@@ -6,6 +6,10 @@ For each `name.obj`: preprocess (native adjacency + coarsening), predict the fac
 iterations of update_position2, write `name_denoised.obj` (same faces) and, like the reference,
 `name_inferred_normals.obj` is replaced by a plain `name_normals.txt` (one predicted unit normal per face).
 Existing results are skipped unless --overwrite (B_OVERWRITE_RESULT, settings.py).
+
+With --with-vertices (the reference's withVerts branch) the network is the multi-scale one (trainAccuracyNet's): inferNet
+moves the vertices with update_position_MS and writes `name_denoised.obj`, `name_d_mid.obj` and `name_d_coarse.obj`
+(the positions after the fine, the middle and the coarse stage).
 """
 import argparse
 import os
@@ -35,22 +39,47 @@ def denoise_file(net, noisy_dir, filename, results_dir, overwrite=False, log=pri
     return out_path
 
 
+def denoise_file_with_vertices(net, noisy_dir, filename, results_dir, overwrite=False, log=print):
+    """infer.py:82-101 withVerts: the three vertex sets of inferNet as OBJ files with the input's faces."""
+    from .dataClasses import InferenceMesh
+    from .train import inferNet
+    from .utils import write_mesh
+    out_path = os.path.join(results_dir, filename[:-4] + "_denoised.obj")
+    if os.path.isfile(out_path) and not overwrite:
+        log("Skipping %s. File already exists." % os.path.basename(out_path))
+        return None
+    t0 = time.time()
+    mesh = InferenceMesh()
+    mesh.addMeshWithVertices(noisy_dir, filename)
+    log("mesh added (%.0f ms): %d faces" % (1000 * (time.time() - t0), mesh.faces.shape[0]))
+    t0 = time.time()
+    res = inferNet(mesh, net)
+    log("Inference complete (%.0f ms)" % (1000 * (time.time() - t0)))
+    write_mesh(res[0], mesh.faces, out_path)
+    write_mesh(res[1], mesh.faces, os.path.join(results_dir, filename[:-4] + "_d_mid.obj"))
+    write_mesh(res[2], mesh.faces, os.path.join(results_dir, filename[:-4] + "_d_coarse.obj"))
+    return out_path
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("noisy_dir")
     ap.add_argument("results_dir")
     ap.add_argument("network", help="TensorFlow checkpoint directory / prefix (as the reference writes them) or a .pt file")
     ap.add_argument("--overwrite", action="store_true")
+    ap.add_argument("--with-vertices", action="store_true",
+                    help="multi-scale network + update_position_MS (a network trained by trainAccuracyNet)")
     args = ap.parse_args(argv)
     from .net import FacetDenoiser
     from .train import load_checkpoint
-    net = FacetDenoiser("cuda:0")
+    net = FacetDenoiser("cuda:0", multi_scale=args.with_vertices)
     load_checkpoint(args.network, net)
+    run = denoise_file_with_vertices if args.with_vertices else denoise_file
     os.makedirs(args.results_dir, exist_ok=True)
     for f in sorted(os.listdir(args.noisy_dir)):
         if f.endswith(".obj"):
             print("processing noisy file: " + f)
-            denoise_file(net, args.noisy_dir, f, args.results_dir, args.overwrite)
+            run(net, args.noisy_dir, f, args.results_dir, args.overwrite)
 
 
 if __name__ == "__main__":

@@ -28,7 +28,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, ops
 from ._lib import ConvDesc, ConvBwdIO, AG_LD, DL_LD, FGC_M
 from .graph import FacetGraph, as_graph
 
@@ -36,6 +36,9 @@ LRELU_ALPHA = 0.1      # model.py:846
 STD_W, STD_B = 0.05, 0.01  # model.py:17-18
 HIDDEN = 1024          # model.py:936
 COST_SAMPLES = 4000    # train.py:411
+POINT_SAMPLES = 500    # SAMP_NUM of trainAccuracyNet (train.py:653)
+POINT_LOSS_THRESHOLD = 5000.0   # accuracyThreshold / compThreshold of fullLoss (train.py:1375-1376)
+VERTEX_ITERS = (80, 20, 20)     # update_position_MS in trainAccuracyNet (train.py:776)
 
 
 def param_spec(multi_scale=False, in_channels=6):
@@ -865,8 +868,8 @@ class FacetDenoiser:
             if self.sharded or self.dtype != "f32":
                 raise NotImplementedError("training the multi-scale heads: unsharded fp32 network only")
             # Build extension: the reference trains the coarse heads through a point-set loss on the vertex update
-            # (train.py:1075-1105; SURVEY.md section 2: out of scope).  Here every head gets the angular loss of the fine
-            # head (train.py:1272-1294) against the pooled ground truth, on the same sampled rows modulo the level's size.
+            # (trainAccuracyNet: pointset_step below).  Here every head gets the angular loss of the fine head
+            # (train.py:1272-1294) against the pooled ground truth, on the same sampled rows modulo the level's size.
             for k, name, head in (("2", "dconv3", "head2"), ("1", "dconv2", "head1")):
                 lvl = int(k)
                 nk = ns[lvl]
@@ -884,13 +887,33 @@ class FacetDenoiser:
                                                   _p(B["g_nconv" + k]), st), "loss bwd")
                 _lib.check(L.fgc_normalize_bwd(_p(y), _p(B["g_nconv" + k]), nk, _p(B["g_y" + k]), _p(sc), st),
                            "normalize bwd")
-                lay = next(l for l in self.layers if l.name == name)
-                xin = B[lay.y]
-                hs = self.slot[head]
-                _lib.check(L.fgc_mlp_bwd(_p(xin), _p(B["g_y" + k]), nk, xin.shape[1], HIDDEN, 3, _p(vals[hs]),
-                                         _p(vals[hs + 1]), _p(vals[hs + 2]), LRELU_ALPHA, _p(B["g_" + lay.y]),
-                                         _p(grads[hs]), _p(grads[hs + 1]), _p(grads[hs + 2]), _p(grads[hs + 3]), 0, _p(ws),
-                                         ws.numel(), st), head + " bwd")
+                self._coarse_head_bwd(k)
+        yield from self._params_backward_gen(fused)
+
+    def _coarse_head_bwd(self, k):
+        """g_y<k> (the gradient of coarse head k's raw output) -> the head's parameter gradients and g_d3 / g_d2 (written:
+        the up-convolution adds its own later)."""
+        M, L, st = self._mesh, self.L, self._st()
+        B, ws = M["B"], M["B"]["ws"]
+        vals, grads = self.params.values, self.params.grads
+        name, head = {"2": ("dconv3", "head2"), "1": ("dconv2", "head1")}[k]
+        nk = M["ns"][int(k)]
+        lay = next(l for l in self.layers if l.name == name)
+        xin = B[lay.y]
+        hs = self.slot[head]
+        _lib.check(L.fgc_mlp_bwd(_p(xin), _p(B["g_y" + k]), nk, xin.shape[1], HIDDEN, 3, _p(vals[hs]),
+                                 _p(vals[hs + 1]), _p(vals[hs + 2]), LRELU_ALPHA, _p(B["g_" + lay.y]),
+                                 _p(grads[hs]), _p(grads[hs + 1]), _p(grads[hs + 2]), _p(grads[hs + 3]), 0, _p(ws),
+                                 ws.numel(), st), head + " bwd")
+
+    def _params_backward_gen(self, fused):
+        """g_y0 (and, multi-scale, the coarse heads' contributions to g_d3 / g_d2, already written) -> every parameter
+        gradient: the fine head's backward, the trunk's backward, the batched reduction (sharded: the flat all-reduce).
+        Shared by the angular-loss step and the point-set step."""
+        M, L, st = self._mesh, self.L, self._st()
+        B, ws, ns = M["B"], M["B"]["ws"], M["ns"]
+        n0 = ns[0]
+        vals, grads = self.params.values, self.params.grads
         s = self.slot["head0"]
         self._tag("bwd:mlp")
         _lib.check(self._mlp_bwd(_p(B["d1"]), _p(B["g_y0"]), n0, 32, HIDDEN, 3, _p(vals[s]), _p(vals[s + 1]),
@@ -1389,6 +1412,156 @@ class FacetDenoiser:
         samp = B["sample_ind"]
         _lib.check(L.fgc_angular_loss_fwd(_p(B["nconv"]), _p(gt), _p(samp), samp.numel(), _p(B["loss"]), st), "loss")
         return B["loss"]
+
+    # ------------------------------------------------------------------------------------------
+    # point-set training (trainAccuracyNet, train.py:636-916): network -> update_position_MS -> fullLoss
+    # ------------------------------------------------------------------------------------------
+    def bind_vertices(self, key, x, adjs, verts, faces, v_faces, gt_verts, iters=VERTEX_ITERS):
+        """Bind a mesh for the point-set step: its graph (bind_cached under `key`) together with its vertex data - the
+        normalised vertices [V,3], the faces in node order [N0,3] (-1 rows = fake nodes), v_faces [V,K], the
+        ground-truth vertices [Vgt,3] and the two inverse tables of the vertex-update adjoint (ops.vertex_ms_tables) -
+        all cached with the graph, like bind_cached."""
+        if not self.multi_scale or self.dtype != "f32":      # (bind_cached binds unsharded)
+            raise NotImplementedError("point-set training: unsharded fp32 multi-scale network only")
+        cache = self.__dict__.setdefault("_mesh_cache", {})
+        if key in cache and "verts" in cache[key]:      # (a training loop rebinds its meshes every iteration)
+            self._mesh = cache[key]
+            self._graph_fb = None
+            return self
+        fresh = key not in cache
+        n0 = np.asarray(x).reshape(-1, np.asarray(x).shape[-1]).shape[0]
+        # the backward buffers of the heads come with a ground truth; the point-set step never reads its values
+        self.bind_cached(key, x, adjs, gt=np.zeros((1, n0, 3), dtype=np.float32))
+        M = self._mesh
+        if "verts" in M and not fresh:
+            return self
+        dev = self.device
+        vx = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+        fc = np.asarray(faces).reshape(-1, 3).astype(np.int32)
+        vf = np.asarray(v_faces).reshape(vx.shape[0], -1).astype(np.int32)
+        gv = np.asarray(gt_verts, dtype=np.float32).reshape(-1, 3)
+        if fc.shape[0] != M["ns"][0]:
+            raise ValueError("faces has %d rows, the graph %d nodes" % (fc.shape[0], M["ns"][0]))
+        if gv.shape[0] == 0:
+            raise ValueError("no ground-truth vertices")
+        tabs = ops.vertex_ms_tables(fc, vf, vx.shape[0])
+        it = [int(i) for i in iters]
+        nv, T = vx.shape[0], sum(it)
+        f = dict(dtype=torch.float32, device=dev)
+        V = dict(x=torch.as_tensor(vx, device=dev), gt=torch.as_tensor(gv, device=dev),
+                 faces=torch.as_tensor(fc, device=dev), v_faces=torch.as_tensor(vf, device=dev),
+                 tables=[torch.as_tensor(t, device=dev) for t in tabs], iters=it)
+        V["xr"], V["gtr"] = torch.empty_like(V["x"]), torch.empty_like(V["gt"])
+        V["traj"] = torch.empty((T + 1) * nv * 3, **f)
+        V["centres"] = torch.empty(3 * (n0 + n0 // 4 + n0 // 16), **f)
+        V["g_p"], V["g_x"] = torch.zeros(nv, 3, **f), torch.zeros(nv, 3, **f)
+        V["bwd_ws"] = torch.empty(self.L.fgc_vertex_update_ms_bwd_workspace_floats(nv, n0), **f)
+        V["i0"] = torch.zeros(POINT_SAMPLES, dtype=torch.int32, device=dev)
+        V["i1"] = torch.zeros(POINT_SAMPLES, dtype=torch.int32, device=dev)
+        V["loss"] = torch.zeros(1, **f)
+        V["loss_ws"] = torch.empty(self.L.fgc_point_loss_workspace_bytes(nv, gv.shape[0], POINT_SAMPLES, POINT_SAMPLES) + 256,
+                                   dtype=torch.uint8, device=dev)
+        V["threshold"] = POINT_LOSS_THRESHOLD
+        M["verts"] = V
+        self._graph_fb = None
+        return self
+
+    def set_point_samples(self, sample_ind0, sample_ind1):
+        """The 500 + 500 sampled rows of fullLoss (train.py:810-811): rows of the vertices and of the ground truth."""
+        V = self._mesh["verts"]
+        for dst, src in ((V["i0"], sample_ind0), (V["i1"], sample_ind1)):
+            a = np.asarray(src).astype(np.int32).reshape(-1)
+            if a.shape[0] != dst.numel():
+                raise ValueError("the point-set step samples %d rows per side" % dst.numel())
+            self._upload(dst, a)
+
+    def _pointset_forward(self, rotate, want_grad):
+        """Network (normalizeTensor on head 0 only, train.py:767-773), the rotated vertices moved by update_position_MS
+        with its trajectory, fullLoss (and its gradient on the moved vertices)."""
+        M, L, st = self._mesh, self.L, self._st()
+        B, V = M["B"], M["verts"]
+        n0, nv = M["ns"][0], V["x"].shape[0]
+        self._drain(self._forward_gen(rotate))
+        self._tag("pts:rotate")
+        x, gt = V["x"], V["gt"]
+        if rotate:
+            _lib.check(L.fgc_rotate_rows(_p(x), _p(V["xr"]), nv, 1, _p(B["R"]), st), "rotate vertices")
+            _lib.check(L.fgc_rotate_rows(_p(gt), _p(V["gtr"]), gt.shape[0], 1, _p(B["R"]), st), "rotate gt vertices")
+            x, gt = V["xr"], V["gtr"]
+        self._tag("pts:vertex_fwd")
+        it = (C.c_int32 * 3)(*V["iters"])
+        _lib.check(L.fgc_vertex_update_ms_traj(_p(x), nv, _p(V["faces"]), n0, _p(V["v_faces"]), V["v_faces"].shape[1],
+                                               _p(B["nconv"]), _p(B["y1"]), _p(B["y2"]), it, _p(V["traj"]),
+                                               V["traj"].numel(), _p(V["centres"]), V["centres"].numel(), st),
+                   "vertex update")
+        self._tag("pts:loss")
+        T = sum(V["iters"])
+        refined = C.c_void_p(V["traj"].data_ptr() + T * nv * 12)
+        ws = V["loss_ws"]
+        _lib.check(L.fgc_point_loss(refined, nv, _p(gt), gt.shape[0], _p(V["i0"]), V["i0"].numel(), _p(V["i1"]),
+                                    V["i1"].numel(), V["threshold"], _p(V["loss"]), _p(V["g_p"]) if want_grad else None,
+                                    _p(ws), ws.numel(), st), "point loss")
+
+    def _pointset_gen(self, rotate):
+        self._pointset_forward(rotate, True)
+        M, L, st = self._mesh, self.L, self._st()
+        B, V = M["B"], M["verts"]
+        n0, nv = M["ns"][0], V["x"].shape[0]
+        self._tag("pts:vertex_bwd")
+        it = (C.c_int32 * 3)(*V["iters"])
+        sp, sv, ip, fi = V["tables"]
+        wsv = V["bwd_ws"]
+        # dL/d normals: head 0 into g_nconv (then through normalizeTensor), the raw coarse heads straight into g_y1 / g_y2
+        _lib.check(L.fgc_vertex_update_ms_bwd(_p(V["traj"]), V["traj"].numel(), nv, _p(V["faces"]), n0, _p(V["v_faces"]),
+                                              V["v_faces"].shape[1], _p(B["nconv"]), _p(B["y1"]), _p(B["y2"]), it,
+                                              _p(sp), _p(sv), _p(ip), _p(fi), _p(V["g_p"]), _p(V["g_x"]),
+                                              _p(B["g_nconv"]), _p(B["g_y1"]), _p(B["g_y2"]), _p(wsv), wsv.numel(), st),
+                   "vertex update bwd")
+        self._tag("bwd:normalize")
+        _lib.check(L.fgc_normalize_bwd(_p(B["y0"]), _p(B["g_nconv"]), n0, _p(B["g_y0"]), _p(B["norm_scratch"]), st),
+                   "normalize bwd")
+        for k in ("2", "1"):
+            self._tag("bwd:head" + k)
+            self._coarse_head_bwd(k)
+        yield from self._params_backward_gen(False)
+
+    def pointset_forward_backward(self, rotate=True, capture=False):
+        """One point-set step without the optimiser: loss in the returned device tensor [1], every parameter gradient
+        in params.grads.  capture=True: the whole step as ONE hipGraph (recorded on the first call, replayed after)."""
+        if "verts" not in (self._mesh or {}):
+            raise RuntimeError("bind_vertices(...) is required for the point-set step")
+        V = self._mesh["verts"]
+        if capture:
+            from . import require_graph_replay_safe
+            require_graph_replay_safe()
+            g = V.get("graph")
+            if g is None or g[1] != rotate:
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    self._drain(self._pointset_gen(rotate))
+                torch.cuda.current_stream().wait_stream(s)
+                graph = torch.cuda.CUDAGraph()
+                with _no_gc_while_capturing(), torch.cuda.graph(graph):
+                    self._drain(self._pointset_gen(rotate))
+                V["graph"] = g = (graph, rotate)
+            g[0].replay()
+        else:
+            self._drain(self._pointset_gen(rotate))
+        return V["loss"]
+
+    def pointset_loss(self, rotate=True):
+        """The point-set loss alone (the validation pass of trainAccuracyNet, keep_prob 1): device tensor [1]."""
+        self._pointset_forward(rotate, False)
+        return self._mesh["verts"]["loss"]
+
+    def pointset_step(self, sample_ind0, sample_ind1, R, capture=False):
+        """One iteration of trainAccuracyNet's loop body (train.py:800-840): samples, rotation, forward, backward, Adam."""
+        self.set_point_samples(sample_ind0, sample_ind1)
+        self.set_rotation(R)
+        loss = self.pointset_forward_backward(rotate=True, capture=capture)
+        self.adam_step()
+        return loss
 
     def adam_step(self, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):
         P = self.params

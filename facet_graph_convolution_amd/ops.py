@@ -466,3 +466,99 @@ def nn_query(q, p, q_cell=None, p_cell=None):
     check(_lib.lib().fgc_nn_query(ptr(q), nq, ptr(p), n_p, ptr(q_cell), ptr(p_cell), ptr(dist), ptr(idx), ptr(ws),
                                   ws.numel(), stream_ptr()), "fgc_nn_query")
     return dist, idx
+
+
+def vertex_ms_tables(faces, v_faces, nv):
+    """The two inverse tables of fgc_vertex_update_ms_bwd, built once per mesh on the host (int32 numpy):
+    (slot_ptr [N0+1], slot_vert) - for every fine node f the vertices whose slots name f, in (vertex, slot) order - and
+    (inc_ptr [nv+1], inc_face) - for every vertex the faces that name it as a corner, in (face, corner) order."""
+    faces = np.asarray(faces).reshape(-1, 3).astype(np.int64)
+    v_faces = np.asarray(v_faces).reshape(nv, -1).astype(np.int64)
+    n0 = faces.shape[0]
+    flat = v_faces.reshape(-1)
+    ok = (flat >= 0) & (flat < n0)
+    f = flat[ok]
+    v = np.repeat(np.arange(nv), v_faces.shape[1])[ok]
+    order = np.argsort(f, kind="stable")
+    slot_vert = v[order].astype(np.int32)
+    slot_ptr = np.concatenate([[0], np.cumsum(np.bincount(f, minlength=n0))]).astype(np.int32)
+    corners = faces.reshape(-1)
+    ok = (corners >= 0) & (corners < nv)
+    vv = corners[ok]
+    ff = np.repeat(np.arange(n0), 3)[ok]
+    order = np.argsort(vv, kind="stable")
+    inc_face = ff[order].astype(np.int32)
+    inc_ptr = np.concatenate([[0], np.cumsum(np.bincount(vv, minlength=nv))]).astype(np.int32)
+    return slot_ptr, slot_vert, inc_ptr, inc_face
+
+
+def _ms_args(x, normals, faces, v_faces):
+    _req_cuda(x, faces, v_faces, *normals)
+    x = _f32c(x.reshape(-1, 3))
+    n0, n1, n2 = (_f32c(t.reshape(-1, 3)) for t in normals)
+    faces = faces.to(torch.int32).contiguous()
+    v_faces = v_faces.to(torch.int32).reshape(x.shape[0], -1).contiguous()
+    N0 = faces.shape[0]
+    if n0.shape[0] != N0 or n1.shape[0] * 4 != N0 or n2.shape[0] * 16 != N0:
+        raise ValueError("normals must have N0, N0/4 and N0/16 rows (N0 = %d)" % N0)
+    return x, (n0, n1, n2), faces, v_faces
+
+
+def vertex_update_ms_traj(x, normals, faces, v_faces, iters=(80, 20, 20)):
+    """vertex_update_ms keeping every iterate: traj [T+1, V, 3] (traj[0] = x, traj[-1] = vertex_update_ms's x_out, bit
+    for bit; include/fgc.h: fgc_vertex_update_ms_traj)."""
+    x, (n0, n1, n2), faces, v_faces = _ms_args(x, normals, faces, v_faces)
+    nv, N0 = x.shape[0], faces.shape[0]
+    T = sum(int(i) for i in iters)
+    traj = torch.empty(T + 1, nv, 3, dtype=torch.float32, device=x.device)
+    nscr = 3 * (N0 + N0 // 4 + N0 // 16)
+    scr = torch.empty(nscr, dtype=torch.float32, device=x.device)
+    it = (C.c_int32 * 3)(*[int(i) for i in iters])
+    check(_lib.lib().fgc_vertex_update_ms_traj(ptr(x), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0),
+                                               ptr(n1), ptr(n2), it, ptr(traj), traj.numel(), ptr(scr), nscr,
+                                               stream_ptr()), "fgc_vertex_update_ms_traj")
+    return traj
+
+
+def vertex_update_ms_bwd(traj, normals, faces, v_faces, g_out, iters=(80, 20, 20), tables=None):
+    """Adjoint of vertex_update_ms (include/fgc.h: fgc_vertex_update_ms_bwd): given the trajectory of
+    vertex_update_ms_traj and g_out = dL/dx_out [V,3], returns (dL/dx [V,3], [dL/dn0, dL/dn1, dL/dn2]).  tables: the
+    device tensors of vertex_ms_tables (built here when None)."""
+    nv = traj.shape[1]
+    if traj.dtype != torch.float32 or not traj.is_contiguous():
+        raise ValueError("traj must be the contiguous float32 [T+1, V, 3] of vertex_update_ms_traj")
+    _, (n0, n1, n2), faces, v_faces = _ms_args(traj[0], normals, faces, v_faces)
+    _req_cuda(g_out)
+    g_out = _f32c(g_out.reshape(nv, 3))
+    N0 = faces.shape[0]
+    if tables is None:
+        tables = [torch.as_tensor(t, device=traj.device)
+                  for t in vertex_ms_tables(faces.cpu().numpy(), v_faces.cpu().numpy(), nv)]
+    sp, sv, ip, fi = tables
+    g_x = torch.empty(nv, 3, dtype=torch.float32, device=traj.device)
+    g_n = [torch.empty_like(t) for t in (n0, n1, n2)]
+    nws = _lib.lib().fgc_vertex_update_ms_bwd_workspace_floats(nv, N0)
+    ws = _workspace(nws * 4, traj.device, "vms_bwd")
+    it = (C.c_int32 * 3)(*[int(i) for i in iters])
+    check(_lib.lib().fgc_vertex_update_ms_bwd(ptr(traj), traj.numel(), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0),
+                                              ptr(n1), ptr(n2), it, ptr(sp), ptr(sv), ptr(ip), ptr(fi), ptr(g_out),
+                                              ptr(g_x), ptr(g_n[0]), ptr(g_n[1]), ptr(g_n[2]), ptr(ws), ws.numel() // 4,
+                                              stream_ptr()), "fgc_vertex_update_ms_bwd")
+    return g_x, g_n
+
+
+def point_loss(p0, p1, sample_ind0, sample_ind1, threshold=5000.0, want_grad=True):
+    """fullLoss (train.py:1373-1424; include/fgc.h: fgc_point_loss) of the points p0 [n0,3] against p1 [n1,3] on the
+    sampled rows: (loss [1], dloss/dp0 [n0,3] or None)."""
+    _req_cuda(p0, p1, sample_ind0, sample_ind1)
+    p0, p1 = _f32c(p0.reshape(-1, 3)), _f32c(p1.reshape(-1, 3))
+    i0 = sample_ind0.to(torch.int32).reshape(-1).contiguous()
+    i1 = sample_ind1.to(torch.int32).reshape(-1).contiguous()
+    loss = torch.empty(1, dtype=torch.float32, device=p0.device)
+    g = torch.empty_like(p0) if want_grad else None
+    nbytes = _lib.lib().fgc_point_loss_workspace_bytes(p0.shape[0], p1.shape[0], i0.numel(), i1.numel())
+    ws = _workspace(nbytes, p0.device, "point_loss")
+    check(_lib.lib().fgc_point_loss(ptr(p0), p0.shape[0], ptr(p1), p1.shape[0], ptr(i0), i0.numel(), ptr(i1), i1.numel(),
+                                    float(threshold), ptr(loss), ptr(g), ptr(ws), ws.numel(), stream_ptr()),
+          "fgc_point_loss")
+    return loss, g

@@ -5,7 +5,10 @@
 Every `name.obj` of TRAINING_DIR is paired with its ground truth through `gt_name` (default: the reference's
 `getGTFilename`, settings.py:44-47, `<model>_n<k>.obj` -> `<model>.obj`; `gt_filename` below is a laxer variant), preprocessed
 natively (adjacency, coarsening, padding) `redundancy` times (each pass draws a different coarsening: the reference
-uses this as data augmentation, settings.py:24) and pickled as `trainingSet.pkl` / `validSet.pkl`.
+uses this as data augmentation, settings.py:24) and pickled as `trainingSet.pkl` / `validSet.pkl`.  With --with-vertices
+(the reference's INCLUDE_VERTICES) every mesh also keeps its vertices, faces in node order, vertex-face slots and
+ground-truth vertices (addMeshWithVerticesAndGT) for trainAccuracyNet, pickled as `trainingSetWithVertices.pkl` /
+`validSetWithVertices.pkl`.
 """
 import argparse
 import os
@@ -23,10 +26,12 @@ def gt_filename(noisy_name):
     return stem + ".obj"
 
 
-def pickleData(training_dir, gt_dir, dump_dir, valid_dir=None, redundancy=1, gt_name=getGTFilename, log=print):
+def pickleData(training_dir, gt_dir, dump_dir, valid_dir=None, redundancy=1, gt_name=getGTFilename, log=print,
+               withVerts=False):
     os.makedirs(dump_dir, exist_ok=True)
     out = {}
-    for tag, folder, rep in (("trainingSet.pkl", training_dir, redundancy), ("validSet.pkl", valid_dir, 1)):
+    names = ("trainingSetWithVertices.pkl", "validSetWithVertices.pkl") if withVerts else ("trainingSet.pkl", "validSet.pkl")
+    for tag, folder, rep in ((names[0], training_dir, redundancy), (names[1], valid_dir, 1)):
         if not folder or not os.path.isdir(folder):
             continue
         ds = TrainingSet()
@@ -35,7 +40,10 @@ def pickleData(training_dir, gt_dir, dump_dir, valid_dir=None, redundancy=1, gt_
                 continue
             log("Adding %s (%i)" % (f, ds.mesh_count))
             for _ in range(rep):
-                ds.addMeshWithGT(folder, f, gt_dir, gt_name(f))
+                if withVerts:
+                    ds.addMeshWithVerticesAndGT(folder, f, gt_dir, gt_name(f))
+                else:
+                    ds.addMeshWithGT(folder, f, gt_dir, gt_name(f))
         if ds.mesh_count:
             with open(os.path.join(dump_dir, tag), "wb") as fp:
                 pickle.dump(ds, fp)
@@ -50,8 +58,9 @@ def main(argv=None):
     ap.add_argument("dump_dir")
     ap.add_argument("--valid", default=None)
     ap.add_argument("--redundancy", type=int, default=1)
+    ap.add_argument("--with-vertices", action="store_true", help="keep the vertex data trainAccuracyNet needs")
     args = ap.parse_args(argv)
-    pickleData(args.training_dir, args.gt_dir, args.dump_dir, args.valid, args.redundancy)
+    pickleData(args.training_dir, args.gt_dir, args.dump_dir, args.valid, args.redundancy, withVerts=args.with_vertices)
     print("Preprocessing complete. Dump files saved to " + args.dump_dir)
 
 

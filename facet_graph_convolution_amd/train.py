@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import ops, tfckpt
-from .net import FacetDenoiser, COST_SAMPLES
+from .net import FacetDenoiser, COST_SAMPLES, POINT_SAMPLES, POINT_LOSS_THRESHOLD
 from .settings import SAVEITER
 from .utils import rand_rotation_matrix
 
@@ -36,6 +36,32 @@ class _LossFn(torch.autograd.Function):
 def faceNormalsLoss(fn, gt_fn):
     """train.py:1272-1294: mean angle in degrees over the rows whose ground truth is not a fake (all-zero) row."""
     return _LossFn.apply(fn.reshape(-1, 3).contiguous(), gt_fn.reshape(-1, 3).contiguous().float())
+
+
+class _FullLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p0, p1, i0, i1, threshold):
+        loss, g = ops.point_loss(p0, p1, i0, i1, threshold, want_grad=True)
+        ctx.save_for_backward(g)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        g, = ctx.saved_tensors
+        return g * dloss, None, None, None, None
+
+
+def fullLoss(P0, P1, sample_ind0, sample_ind1, threshold=POINT_LOSS_THRESHOLD):
+    """train.py:1373-1424: 1000 (mean distance of the sampled rows of P0 to P1 + mean distance of the sampled rows of P1
+    to P0), distances above `threshold` counted as 0.  P0 [1,n0,3] / [n0,3] (differentiable), P1 the ground-truth
+    points; sample_ind0 / sample_ind1 rows of P0 / P1 (int tensors on the GPU or arrays).  Gradient departures from
+    TensorFlow: 0 at distance 0, and an exact tie sends the gradient to the lowest index (include/fgc.h)."""
+    dev = P0.device
+    i0 = torch.as_tensor(np.asarray(sample_ind0.cpu() if isinstance(sample_ind0, torch.Tensor) else sample_ind0),
+                         dtype=torch.int32).to(dev)
+    i1 = torch.as_tensor(np.asarray(sample_ind1.cpu() if isinstance(sample_ind1, torch.Tensor) else sample_ind1),
+                         dtype=torch.int32).to(dev)
+    return _FullLossFn.apply(P0.reshape(-1, 3), P1.reshape(-1, 3).detach(), i0, i1, float(threshold))
 
 
 def save_checkpoint(path, net, iteration):
@@ -146,6 +172,115 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
     return net, lossArray
 
 
+def _resume(net, network_path, net_name):
+    """Restore the directory's latest checkpoint if it belongs to this network (train.py:525-533); the iteration."""
+    st = tfckpt.get_checkpoint_state(network_path)
+    if st and st.model_checkpoint_path:
+        split = os.path.basename(st.model_checkpoint_path).split('-')
+        if split[0] == net_name:
+            load_checkpoint(st.model_checkpoint_path, net)
+            return int(split[1]) if len(split) > 1 and split[1].isdigit() else 0
+    elif os.path.exists(os.path.join(network_path, net_name) + ".pt"):
+        return load_checkpoint(os.path.join(network_path, net_name) + ".pt", net)
+    return 0
+
+
+def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
+                     capture=False, validSet=None):
+    """train.py:636-916: the multi-scale network trained through update_position_MS on the point-set loss fullLoss.
+    trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT.  One iteration = a random mesh
+    (meshes without ground-truth vertices are skipped), SAMP_NUM = 500 random rows of the vertices and of the
+    ground-truth vertices, a fresh random rotation of the input rows, the vertices and the ground truth, ONE network
+    forward (normalizeTensor on head 0 only) + vertex update (80, 20, 20) + fullLoss + backward + TF1-Adam update
+    (FacetDenoiser.pointset_step).  The smoothed training loss is logged every 10 iterations, the validation loss
+    (every validation mesh, keep_prob 1 - this network has no dropout -, the iteration's rotation, fresh rows) every 20
+    iterations before the training step; checkpoint and loss CSV every 500 iterations and at the end; resumes from the
+    directory's latest checkpoint of `net_name`.
+
+    Departure from the reference's CSV bookkeeping (train.py:846-913): the reference writes the smoothed training loss
+    of iteration i to row lossArrayIter/10 - 1 (row -1, the last row, at the start of every 500-iteration block) and
+    re-zeroes a 50-row array after each save.  Here iteration i writes row (i mod 500) / 10 of a 50-row block (training
+    loss in column 0, validation loss in column 1, the previous row's validation entry set to the mean of its two
+    neighbours as the reference does), and the block is appended to `<net_name>.csv` at every save.
+
+    Returns (net, lossArray of the last block, per-iteration training losses [num_iterations])."""
+    meshes = []
+    gtv = getattr(trainSet, "gtv_list", [])
+    for i in range(len(trainSet.in_list)):
+        if i >= len(gtv) or np.asarray(gtv[i]).reshape(-1, 3).shape[0] == 0:
+            continue        # train.py:792-796 draws again when a mesh has no ground-truth vertices
+        meshes.append((trainSet.in_list[i], trainSet.adj_list[i], trainSet.v_list[i], trainSet.faces_list[i],
+                       trainSet.v_faces_list[i], gtv[i]))
+    if not meshes:
+        raise ValueError("no training mesh has ground-truth vertices (addMeshWithVerticesAndGT)")
+    valid = []
+    if validSet is not None:
+        vgt = getattr(validSet, "gtv_list", [])
+        valid = [(validSet.in_list[i], validSet.adj_list[i], validSet.v_list[i], validSet.faces_list[i],
+                  validSet.v_faces_list[i], vgt[i]) for i in range(len(validSet.in_list))
+                 if i < len(vgt) and np.asarray(vgt[i]).reshape(-1, 3).shape[0] > 0]
+    net = FacetDenoiser(device, multi_scale=True, seed=seed)
+    ckpt = os.path.join(network_path, net_name) if network_path else None
+    start = _resume(net, network_path, net_name) if ckpt else 0
+    rs = np.random.RandomState(seed + 1)
+    evalStepNum, validStepNum, block = 10, 20, 500
+    lossArray = np.zeros([block // evalStepNum, 2])
+    hist = torch.zeros(max(num_iterations, 1), dtype=torch.float32, device=net.device)
+    acc = torch.zeros(1, dtype=torch.float32, device=net.device)
+    acc_n, last_loss = 0, 0.0
+
+    def bind(key, m):
+        net.bind_vertices(key, *m)      # (a cached mesh returns at once; bind_vertices reshapes the [1, ...] arrays)
+
+    def save(iteration):
+        save_checkpoint(ckpt, net, iteration)
+        with open(os.path.join(network_path, net_name + ".csv"), "ab") as fh:
+            np.savetxt(fh, lossArray, delimiter=",")
+
+    for it in range(num_iterations):
+        b = rs.randint(len(meshes))
+        num_v = np.asarray(meshes[b][2]).reshape(-1, 3).shape[0]
+        num_vgt = np.asarray(meshes[b][5]).reshape(-1, 3).shape[0]
+        i0 = rs.randint(num_v, size=POINT_SAMPLES)
+        i1 = rs.randint(num_vgt, size=POINT_SAMPLES)
+        R_it = rand_rotation_matrix(randnums=rs.uniform(size=3))
+        row = (it % block) // evalStepNum
+        if valid and it % validStepNum == 0 and it > 0:
+            valid_loss = 0.0
+            for vbm, m in enumerate(valid):
+                bind(("valid", vbm), m)
+                nvv = np.asarray(m[2]).reshape(-1, 3).shape[0]
+                nvg = np.asarray(m[5]).reshape(-1, 3).shape[0]
+                net.set_point_samples(rs.randint(nvv, size=POINT_SAMPLES), rs.randint(nvg, size=POINT_SAMPLES))
+                net.set_rotation(R_it)
+                valid_loss += net.pointset_loss(rotate=True)[0].item()
+            valid_loss /= len(valid)
+            log("Iteration %d, validation loss %g" % (it, valid_loss))
+            lossArray[row, 1] = valid_loss
+            if row > 0:
+                lossArray[row - 1, 1] = (valid_loss + last_loss) / 2
+            last_loss = valid_loss
+        bind(b, meshes[b])
+        loss = net.pointset_step(i0, i1, R_it, capture=capture)
+        hist[it:it + 1].copy_(loss)
+        acc += loss
+        acc_n += 1
+        if it % evalStepNum == 0:
+            lv = acc.item() / acc_n           # the only host sync of a training iteration, every 10 iterations
+            if not np.isfinite(lv):
+                log("WARNING! NAN FOUND AFTER TRAINING!!!! training example %d/%d" % (b, len(meshes)))
+            log("Iteration %d, training loss %g" % (it, lv))
+            lossArray[row, 0] = lv
+            acc.zero_()
+            acc_n = 0
+        if ckpt and it % block == 0 and it > 0:
+            save(start + it)
+            lossArray = np.zeros_like(lossArray)
+    if ckpt:
+        save(start + num_iterations)
+    return net, lossArray, hist[:num_iterations].cpu().numpy()
+
+
 def update_position2(x, face_normals, edge_map, v_edges, iter_num=20, max_edges=20):
     """train.py:1467-1557, same argument layout on torch GPU tensors: x [1,V,3], face_normals [1,F,3], edge_map
     int [1,E,4], v_edges int [1,V,max_edges] (-1 = unused slot); returns the updated positions [1,V,3].
@@ -169,13 +304,46 @@ def updateFacesCenter(vertices, faces, coarsening_steps):
     return [f0.unsqueeze(0), f1.unsqueeze(0), f2.unsqueeze(0)]
 
 
-def update_position_MS(x, face_normals_list, faces, v_faces0, coarsening_steps, iter_num_list=[80, 20, 20]):
+class _UpdatePositionMSFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, n0, n1, n2, faces, v_faces, iters, tables):
+        traj = ops.vertex_update_ms_traj(x, [n0, n1, n2], faces, v_faces, iters)
+        ctx.save_for_backward(traj, n0, n1, n2, faces, v_faces)
+        ctx.iters, ctx.tables = iters, tables
+        ctx.set_materialize_grads(False)      # (unused outputs: None, not zero tensors)
+        T0, T1 = iters[0], iters[0] + iters[1]
+        out = traj[-1].clone()
+        # dx of each stage = end - start, the same fp32 subtraction as fgc_vertex_update_ms's dx_out
+        return out, traj[T0] - traj[0], traj[T1] - traj[T0], traj[-1] - traj[T1]
+
+    @staticmethod
+    def backward(ctx, g_out, g_dx0, g_dx1, g_dx2):
+        traj, n0, n1, n2, faces, v_faces = ctx.saved_tensors
+        it = ctx.iters
+        if g_out is None or any(g is not None for g in (g_dx0, g_dx1, g_dx2)):
+            raise NotImplementedError("update_position_MS differentiates its positions, not the stage displacements")
+        g_x, g_n = ops.vertex_update_ms_bwd(traj, [n0, n1, n2], faces, v_faces, g_out, it, tables=ctx.tables)
+        return g_x, g_n[0], g_n[1], g_n[2], None, None, None, None
+
+
+def update_position_MS(x, face_normals_list, faces, v_faces0, coarsening_steps, iter_num_list=[80, 20, 20], tables=None):
     """train.py:1668-1764, same arguments on torch GPU tensors: x [1,V,3], face_normals_list = [n0 [1,N0,3],
     n1 [1,N0/4,3], n2 [1,N0/16,3]], faces int [1,N0,3] (fake nodes = -1 rows), v_faces0 int [1,V,K].  Returns
-    (x [1,V,3], [dx of the coarse, the middle and the fine stage, each [V,3]])."""
+    (x [1,V,3], [dx of the coarse, the middle and the fine stage, each [V,3]]).  Differentiable with respect to x and
+    the three normal fields when one of them requires grad (the adjoint kernels of fgc_vertex_update_ms_bwd; the
+    forward keeps its trajectory, 12 bytes per vertex and iteration); the values are the same bits either way.
+    tables: the mesh's inverse tables (ops.vertex_ms_tables, as device tensors) for the backward; without them every
+    backward copies faces and v_faces to the host and rebuilds them there (a host synchronisation per call) - pass them
+    when the same mesh is differentiated repeatedly.  (FacetDenoiser.pointset_step keeps them per bound mesh.)"""
     from . import ops, tfckpt
     if coarsening_steps != 2 or len(face_normals_list) != 3:
         raise NotImplementedError("three levels pooled 4:1, as the network has them (settings.py:31-32)")
+    if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in face_normals_list)):
+        nv = x.reshape(-1, 3).shape[0]
+        out, d0, d1, d2 = _UpdatePositionMSFn.apply(x.reshape(-1, 3), *[t.reshape(-1, 3) for t in face_normals_list],
+                                                     faces.reshape(-1, 3), v_faces0.reshape(nv, -1),
+                                                     tuple(int(i) for i in iter_num_list), tables)
+        return out.unsqueeze(0), [d0, d1, d2]
     out, dx = ops.vertex_update_ms(x.reshape(-1, 3), [t.reshape(-1, 3) for t in face_normals_list], faces.reshape(-1, 3),
                                    v_faces0.reshape(x.reshape(-1, 3).shape[0], -1), iter_num_list)
     return out.unsqueeze(0), [dx[0], dx[1], dx[2]]

@@ -46,8 +46,10 @@ extern "C" {
  * 103: fgc_conv_pairs_allowed; options NO_BFM, K1_QS14; fgc_conv_desc.options / n_options (per-descriptor option overrides).
  * 104: fgc_conv_bwd_io.r_ld (the stride of r stated with the buffer); fgc_conv_desc.packed_layout + fgc_conv_layout_id,
  * fgc_mlp_layout_id / FGC_MLP_LAYOUT (packed operands carry the identity of their layout).
- * 105: fgc_nn_query / fgc_nn_workspace_bytes (nearest neighbour over point sets, for the evaluation metrics). */
-#define FGC_ABI_VERSION 105
+ * 105: fgc_nn_query / fgc_nn_workspace_bytes (nearest neighbour over point sets, for the evaluation metrics).
+ * 106: fgc_vertex_update_ms_traj / fgc_vertex_update_ms_bwd (+ _workspace_floats), fgc_point_loss (+ _workspace_bytes):
+ * training through the multi-scale vertex update on the point-set loss. */
+#define FGC_ABI_VERSION 106
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -641,6 +643,56 @@ int fgc_vertex_update_ms(const float* x, float* x_out, int32_t nv, const int32_t
                          const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
                          const float* normals2, const int32_t* iters, float* dx_out, float* scratch,
                          size_t scratch_floats, void* stream);
+
+/* Trajectory form of fgc_vertex_update_ms, for training through it: the same launches with the same arithmetic (the
+ * result is bit-identical), every iteration writing a slot of its own.  traj [T+1][nv,3], T = iters[0] + iters[1] +
+ * iters[2]: slot 0 receives x, slot t + 1 the positions after iteration t (slot T is fgc_vertex_update_ms's x_out; a
+ * stage's dx is the difference of the slots at its ends).  scratch: at least 3*(n0 + n0/4 + n0/16) floats (the node
+ * centres).  x may not lie in traj. */
+int fgc_vertex_update_ms_traj(const float* x, int32_t nv, const int32_t* faces, int32_t n0, const int32_t* v_faces,
+                              int32_t k_v, const float* normals0, const float* normals1, const float* normals2,
+                              const int32_t* iters, float* traj, size_t traj_floats, float* scratch,
+                              size_t scratch_floats, void* stream);
+
+/* Adjoint of fgc_vertex_update_ms: given g_out = dL/d x_out [nv,3] and the trajectory fgc_vertex_update_ms_traj wrote,
+ * g_x [nv,3] = dL/dx and g_n<s> [n0/4^s,3] = dL/d normals<s> (overwritten).  Per forward iteration at level s, with
+ * a_v = g_v / #faces(v) and A_j, S_j the sums of a_v and of a_v x_v^T + x_v a_v^T over the slots (v,k) whose node is j:
+ *   dL/dx_v = g_v - sum_k n_j (n_j . a_v) + (barycentre and pooling adjoints of dL/dc),  dL/dc_j = n_j (n_j . A_j),
+ *   dL/dn_j += (A_j . n_j) c_j + (n_j . c_j) A_j - S_j n_j.
+ * The centres are recomputed from the trajectory by the forward's kernels; the pooling adjoint makes the forward's
+ * zero-row choices.  Two inverse tables, built once per mesh (int32, CSR):
+ *   slot_ptr [n0+1], slot_vert: for every fine node f, the vertices v of the slots v_faces[v,k] == f, in (v, k) order
+ *     (a slot table truncated to k_v slots keeps only the slots it has);
+ *   inc_ptr [nv+1], inc_face: for every vertex, the faces that name it as a corner, once per corner, in (face, corner)
+ *     order.
+ * Every entry must lie in range (vertices < nv, nodes < n0).  traj_floats: the size of traj, at least (T+1)*3*nv.
+ * workspace: at least
+ * fgc_vertex_update_ms_bwd_workspace_floats(nv, n0) floats.  No atomics: the same bits from run to run.  A vertex
+ * without faces passes its gradient straight through (it does not move).  g_out may not alias g_x. */
+size_t fgc_vertex_update_ms_bwd_workspace_floats(int32_t nv, int32_t n0);
+int fgc_vertex_update_ms_bwd(const float* traj, size_t traj_floats, int32_t nv, const int32_t* faces, int32_t n0, const int32_t* v_faces,
+                             int32_t k_v, const float* normals0, const float* normals1, const float* normals2,
+                             const int32_t* iters, const int32_t* slot_ptr, const int32_t* slot_vert,
+                             const int32_t* inc_ptr, const int32_t* inc_face, const float* g_out, float* g_x,
+                             float* g_n0, float* g_n1, float* g_n2, float* workspace, size_t workspace_floats,
+                             void* stream);
+
+/* Point-set loss fullLoss (train.py:1373-1424) and its gradient.  p0 [np0,3] refined vertices, p1 [np1,3] ground-truth
+ * vertices, i0 [ns0] rows of p0 and i1 [ns1] rows of p1 (repeats allowed):
+ *   precision_i = min_j |p0[i0_i] - p1_j|,  completeness_i = min_j |p0_j - p1[i1_i]|,
+ *   loss[0] = 1000 (mean(precision <= threshold ? precision : 0) + mean(completeness <= threshold ? completeness : 0)).
+ * The nearest points come from fgc_nn_query.  g_p0 (may be NULL) [np0,3] receives dL/dp0 (dL/dloss = 1): a kept term
+ * adds 1000/ns (p0_row - p1_nn) / d to its p0 row; terms sharing a row are summed in a fixed order (no atomics).
+ * Two departures from TensorFlow's gradient: at d = 0 the term's gradient is 0 (TensorFlow: NaN), and an exact tie between
+ * nearest points sends the whole gradient to the lowest index (tf.reduce_min splits it).  A sample index out of range
+ * makes the loss NaN.  workspace (device, 256-byte aligned) >= fgc_point_loss_workspace_bytes(np0, np1, ns0, ns1).
+ * ns0 + ns1 <= FGC_POINT_LOSS_MAX_SAMPLES: the row reduction runs in one workgroup and costs O((ns0 + ns1)^2) compares
+ * (the reference samples 500 + 500). */
+#define FGC_POINT_LOSS_MAX_SAMPLES 16384
+size_t fgc_point_loss_workspace_bytes(int32_t np0, int32_t np1, int32_t ns0, int32_t ns1);
+int fgc_point_loss(const float* p0, int32_t np0, const float* p1, int32_t np1, const int32_t* i0, int32_t ns0,
+                   const int32_t* i1, int32_t ns1, float threshold, float* loss, float* g_p0, void* workspace,
+                   size_t workspace_bytes, void* stream);
 
 /* Nearest neighbour over point sets: the distance scan of hausdorffOverSampled (utils.py:816-1006) and of exact
  * point-set distances.  For every query point q[i] (float32 [nq,3]) the nearest point of p (float32 [np,3]) by squared

@@ -1,0 +1,110 @@
+"""Cost of the point-set training step (trainAccuracyNet) on the MI355X.
+
+    python tools/points_probe.py [--faces 20000 100000] [--steps 20] [--out FILE] [--only all|network|vertex_fwd|vertex_bwd|loss]
+
+Per mesh size (a noisy torus): ms per point-set step eager and replayed from its hipGraph, the graph's node count
+(launches per step), the multi-scale angular-loss step on the same mesh for comparison, and the parts of the step timed
+alone with device events: network forward + backward, vertex update forward with trajectory, its adjoint, fullLoss.
+--only runs one part in a loop (for a `rocprofv3 --kernel-trace --stats` run of its own)."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import facet_graph_convolution_amd  # noqa: E402,F401  (before torch.cuda: hipGraph replay switch)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def timed(fn, steps, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--faces", type=int, nargs="+", default=[20000, 100000])
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--out", default="")
+    ap.add_argument("--only", default="all")
+    args = ap.parse_args()
+    from facet_graph_convolution_amd import ops
+    from facet_graph_convolution_amd.net import FacetDenoiser, _graph_node_count
+    from facet_graph_convolution_amd.dataClasses import TrainingSet
+    from facet_graph_convolution_amd.meshgen import torus, add_noise
+    from facet_graph_convolution_amd.utils import rand_rotation_matrix
+    res = []
+    for nf in args.faces:
+        n = int(round((nf / 2) ** 0.5))
+        V, F = torus(n, n)
+        ds = TrainingSet()
+        ds.addMeshWithVerticesAndGT(add_noise(V, F, seed=1), F, V, seed=0)
+        x, adjs = ds.in_list[0], ds.adj_list[0]
+        v, faces, vf, gtv = ds.v_list[0][0], ds.faces_list[0][0], ds.v_faces_list[0][0], ds.gtv_list[0][0]
+        rs = np.random.RandomState(0)
+        Rm = rand_rotation_matrix(randnums=rs.uniform(size=3))
+        net = FacetDenoiser("cuda:0", multi_scale=True, seed=0)
+        net.bind_vertices(0, x, adjs, v, faces, vf, gtv)
+        net.set_point_samples(rs.randint(len(v), size=500), rs.randint(len(gtv), size=500))
+        net.set_rotation(Rm)
+        row = dict(faces=int(F.shape[0]), nodes=int(x.shape[1]), vertices=int(len(v)))
+        B, Vb = net._mesh["B"], net._mesh["verts"]
+        nrm = [B["nconv"], B["y1"], B["y2"]]
+        dev = net.device
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)  # noqa: E731
+        xv, fc, vft = t(v.astype(np.float32)), t(faces.astype(np.int32)), t(vf.astype(np.int32))
+        parts = {
+            "vertex_fwd": lambda: ops.vertex_update_ms_traj(xv, nrm, fc, vft),
+            "loss": lambda: ops.point_loss(xv, Vb["gt"], Vb["i0"], Vb["i1"]),
+        }
+        net.pointset_forward_backward(rotate=True)
+        traj = ops.vertex_update_ms_traj(xv, nrm, fc, vft)
+        g = torch.randn_like(xv)
+        parts["vertex_bwd"] = lambda: ops.vertex_update_ms_bwd(traj, nrm, fc, vft, g, tables=Vb["tables"])
+        def network():      # forward, the coarse heads' and the trunk's backward (the normals' gradients as they stand)
+            net._drain(net._forward_gen(True))
+            net._coarse_head_bwd("2")
+            net._coarse_head_bwd("1")
+            net._drain(net._params_backward_gen(False))
+        parts["network"] = network
+        if args.only != "all":
+            for _ in range(args.steps):
+                parts[args.only]()
+            torch.cuda.synchronize()
+            res.append(dict(row, only=args.only))
+            continue
+        row["pointset_eager_ms"] = timed(lambda: net.pointset_forward_backward(rotate=True), args.steps)
+        row["pointset_replay_ms"] = timed(lambda: net.pointset_forward_backward(rotate=True, capture=True), args.steps)
+        try:
+            row["pointset_graph_nodes"] = _graph_node_count(Vb["graph"][0])
+        except Exception as e:       # (the graph was instantiated without keep_graph)
+            row["pointset_graph_nodes"] = repr(e)[:80]
+        for k, fn in parts.items():
+            row[k + "_ms"] = timed(fn, args.steps)
+        ang = FacetDenoiser("cuda:0", multi_scale=True, seed=0)
+        ang.bind_mesh(x, adjs, gt=ds.gt_list[0])
+        ang.set_samples(rs.randint(x.shape[1], size=4000))
+        ang.set_rotation(Rm)
+        row["angular_ms_eager_ms"] = timed(lambda: ang.forward_backward(rotate=True), args.steps)
+        row["angular_ms_replay_ms"] = timed(lambda: ang.forward_backward(rotate=True, capture=True), args.steps)
+        print(json.dumps(row), flush=True)
+        res.append(row)
+        del net, ang
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
