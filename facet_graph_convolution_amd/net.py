@@ -1416,17 +1416,20 @@ class FacetDenoiser:
     # ------------------------------------------------------------------------------------------
     # point-set training (trainAccuracyNet, train.py:636-916): network -> update_position_MS -> fullLoss
     # ------------------------------------------------------------------------------------------
-    def bind_vertices(self, key, x, adjs, verts, faces, v_faces, gt_verts, iters=VERTEX_ITERS):
+    def bind_vertices(self, key, x, adjs, verts, faces, v_faces, gt_verts, iters=VERTEX_ITERS, gt_normals=None):
         """Bind a mesh for the point-set step: its graph (bind_cached under `key`) together with its vertex data - the
         normalised vertices [V,3], the faces in node order [N0,3] (-1 rows = fake nodes), v_faces [V,K], the
         ground-truth vertices [Vgt,3] and the two inverse tables of the vertex-update adjoint (ops.vertex_ms_tables) -
-        all cached with the graph, like bind_cached."""
+        all cached with the graph, like bind_cached.  gt_normals: the ground-truth face normals [N0,3] in node order
+        (gt_list), for the double-loss step; uploaded into the cached vertex state (the first time they are given)."""
         if not self.multi_scale or self.dtype != "f32":      # (bind_cached binds unsharded)
             raise NotImplementedError("point-set training: unsharded fp32 multi-scale network only")
         cache = self.__dict__.setdefault("_mesh_cache", {})
         if key in cache and "verts" in cache[key]:      # (a training loop rebinds its meshes every iteration)
             self._mesh = cache[key]
             self._graph_fb = None
+            if gt_normals is not None and "gtn" not in self._mesh["verts"]:
+                self._bind_gt_normals(gt_normals)
             return self
         fresh = key not in cache
         n0 = np.asarray(x).reshape(-1, np.asarray(x).shape[-1]).shape[0]
@@ -1464,7 +1467,23 @@ class FacetDenoiser:
         V["threshold"] = POINT_LOSS_THRESHOLD
         M["verts"] = V
         self._graph_fb = None
+        if gt_normals is not None:
+            self._bind_gt_normals(gt_normals)
         return self
+
+    def _bind_gt_normals(self, gt_normals):
+        """The bound mesh's ground-truth face normals [N0,3] and the buffers of the double-loss step."""
+        M = self._mesh
+        V, n0 = M["verts"], M["ns"][0]
+        g = np.asarray(gt_normals.cpu() if isinstance(gt_normals, torch.Tensor) else gt_normals, dtype=np.float32)
+        g = g.reshape(-1, 3)
+        if g.shape[0] != n0:
+            raise ValueError("gt_normals has %d rows, the graph %d nodes" % (g.shape[0], n0))
+        f = dict(dtype=torch.float32, device=self.device)
+        V["gtn"] = torch.as_tensor(g, device=self.device)
+        V["dl_out"] = torch.zeros(4, **f)      # {total, points, normals, real rows}
+        nsc = self.L.fgc_dense_normals_loss_scratch_floats(n0)
+        V["dl_scratch"] = torch.zeros(nsc, **f)
 
     def set_point_samples(self, sample_ind0, sample_ind1):
         """The 500 + 500 sampled rows of fullLoss (train.py:810-811): rows of the vertices and of the ground truth."""
@@ -1475,13 +1494,23 @@ class FacetDenoiser:
                 raise ValueError("the point-set step samples %d rows per side" % dst.numel())
             self._upload(dst, a)
 
-    def _pointset_forward(self, rotate, want_grad):
+    def _pointset_forward(self, rotate, want_grad, double=False):
         """Network (normalizeTensor on head 0 only, train.py:767-773), the rotated vertices moved by update_position_MS
-        with its trajectory, fullLoss (and its gradient on the moved vertices)."""
+        with its trajectory, fullLoss (and its gradient on the moved vertices).  double: trainDoubleLossNet's form
+        (train.py:1075-1102) - normalizeTensor on all three heads, which feed the vertex update, fullLoss into
+        dl_out[1] and the dense face-normal loss of head 0 into dl_out[2], their sum into dl_out[0]."""
         M, L, st = self._mesh, self.L, self._st()
         B, V = M["B"], M["verts"]
         n0, nv = M["ns"][0], V["x"].shape[0]
         self._drain(self._forward_gen(rotate))
+        heads = (B["nconv"], B["y1"], B["y2"])
+        if double:
+            self._tag("dl:normalize")
+            for k in ("1", "2"):
+                y, part, sc = B["y" + k], B["abs_part" + k], B["norm_scratch" + k]
+                _lib.check(L.fgc_normalize_fwd(_p(y), M["ns"][int(k)], _p(part), part.numel(), _p(B["nconv" + k]),
+                                               _p(sc), st), "normalize head" + k)
+            heads = (B["nconv"], B["nconv1"], B["nconv2"])
         self._tag("pts:rotate")
         x, gt = V["x"], V["gt"]
         if rotate:
@@ -1491,19 +1520,27 @@ class FacetDenoiser:
         self._tag("pts:vertex_fwd")
         it = (C.c_int32 * 3)(*V["iters"])
         _lib.check(L.fgc_vertex_update_ms_traj(_p(x), nv, _p(V["faces"]), n0, _p(V["v_faces"]), V["v_faces"].shape[1],
-                                               _p(B["nconv"]), _p(B["y1"]), _p(B["y2"]), it, _p(V["traj"]),
+                                               _p(heads[0]), _p(heads[1]), _p(heads[2]), it, _p(V["traj"]),
                                                V["traj"].numel(), _p(V["centres"]), V["centres"].numel(), st),
                    "vertex update")
         self._tag("pts:loss")
         T = sum(V["iters"])
         refined = C.c_void_p(V["traj"].data_ptr() + T * nv * 12)
         ws = V["loss_ws"]
+        out = V["dl_out"] if double else None
+        loss = C.c_void_p(out.data_ptr() + 4) if double else _p(V["loss"])
         _lib.check(L.fgc_point_loss(refined, nv, _p(gt), gt.shape[0], _p(V["i0"]), V["i0"].numel(), _p(V["i1"]),
-                                    V["i1"].numel(), V["threshold"], _p(V["loss"]), _p(V["g_p"]) if want_grad else None,
+                                    V["i1"].numel(), V["threshold"], loss, _p(V["g_p"]) if want_grad else None,
                                     _p(ws), ws.numel(), st), "point loss")
+        if double:
+            self._tag("dl:loss")
+            sc = V["dl_scratch"]
+            _lib.check(L.fgc_dense_normals_loss_fwd(_p(B["nconv"]), _p(V["gtn"]), _p(B["R"]) if rotate else None, n0,
+                                                    C.c_void_p(out.data_ptr() + 8), loss, _p(out), _p(sc), sc.numel(),
+                                                    st), "dense normals loss")
 
-    def _pointset_gen(self, rotate):
-        self._pointset_forward(rotate, True)
+    def _pointset_gen(self, rotate, double=False):
+        self._pointset_forward(rotate, True, double)
         M, L, st = self._mesh, self.L, self._st()
         B, V = M["B"], M["verts"]
         n0, nv = M["ns"][0], V["x"].shape[0]
@@ -1512,43 +1549,60 @@ class FacetDenoiser:
         sp, sv, ip, fi = V["tables"]
         wsv = V["bwd_ws"]
         # dL/d normals: head 0 into g_nconv (then through normalizeTensor), the raw coarse heads straight into g_y1 / g_y2
+        # (double: the normalised coarse heads into g_nconv1 / g_nconv2, then through their own normalizeTensor)
+        heads = (B["nconv"], B["nconv1"], B["nconv2"]) if double else (B["nconv"], B["y1"], B["y2"])
+        g_heads = (B["g_nconv"], B["g_nconv1"], B["g_nconv2"]) if double else (B["g_nconv"], B["g_y1"], B["g_y2"])
         _lib.check(L.fgc_vertex_update_ms_bwd(_p(V["traj"]), V["traj"].numel(), nv, _p(V["faces"]), n0, _p(V["v_faces"]),
-                                              V["v_faces"].shape[1], _p(B["nconv"]), _p(B["y1"]), _p(B["y2"]), it,
+                                              V["v_faces"].shape[1], _p(heads[0]), _p(heads[1]), _p(heads[2]), it,
                                               _p(sp), _p(sv), _p(ip), _p(fi), _p(V["g_p"]), _p(V["g_x"]),
-                                              _p(B["g_nconv"]), _p(B["g_y1"]), _p(B["g_y2"]), _p(wsv), wsv.numel(), st),
+                                              _p(g_heads[0]), _p(g_heads[1]), _p(g_heads[2]), _p(wsv), wsv.numel(), st),
                    "vertex update bwd")
+        if double:
+            self._tag("dl:bwd")      # (added to what the vertex adjoint has just written)
+            sc = V["dl_scratch"]
+            _lib.check(L.fgc_dense_normals_loss_bwd(_p(B["nconv"]), _p(V["gtn"]), _p(B["R"]) if rotate else None, n0,
+                                                    _p(sc), sc.numel(), 1.0, _p(B["g_nconv"]), st), "dense normals bwd")
         self._tag("bwd:normalize")
         _lib.check(L.fgc_normalize_bwd(_p(B["y0"]), _p(B["g_nconv"]), n0, _p(B["g_y0"]), _p(B["norm_scratch"]), st),
                    "normalize bwd")
         for k in ("2", "1"):
             self._tag("bwd:head" + k)
+            if double:
+                _lib.check(L.fgc_normalize_bwd(_p(B["y" + k]), _p(B["g_nconv" + k]), M["ns"][int(k)], _p(B["g_y" + k]),
+                                               _p(B["norm_scratch" + k]), st), "normalize bwd head" + k)
             self._coarse_head_bwd(k)
         yield from self._params_backward_gen(False)
+
+    def _run_pointset(self, rotate, capture, double):
+        """The point-set (double=False) or double-loss step, eager or as ONE hipGraph per mesh and form (recorded on the
+        first call, replayed after)."""
+        V = self._mesh["verts"]
+        if capture:
+            from . import require_graph_replay_safe
+            require_graph_replay_safe()
+            slot = "graph_dl" if double else "graph"
+            g = V.get(slot)
+            if g is None or g[1] != rotate:
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    self._drain(self._pointset_gen(rotate, double))
+                torch.cuda.current_stream().wait_stream(s)
+                graph = torch.cuda.CUDAGraph()
+                with _no_gc_while_capturing(), torch.cuda.graph(graph):
+                    self._drain(self._pointset_gen(rotate, double))
+                V[slot] = g = (graph, rotate)
+            g[0].replay()
+        else:
+            self._drain(self._pointset_gen(rotate, double))
 
     def pointset_forward_backward(self, rotate=True, capture=False):
         """One point-set step without the optimiser: loss in the returned device tensor [1], every parameter gradient
         in params.grads.  capture=True: the whole step as ONE hipGraph (recorded on the first call, replayed after)."""
         if "verts" not in (self._mesh or {}):
             raise RuntimeError("bind_vertices(...) is required for the point-set step")
-        V = self._mesh["verts"]
-        if capture:
-            from . import require_graph_replay_safe
-            require_graph_replay_safe()
-            g = V.get("graph")
-            if g is None or g[1] != rotate:
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self._drain(self._pointset_gen(rotate))
-                torch.cuda.current_stream().wait_stream(s)
-                graph = torch.cuda.CUDAGraph()
-                with _no_gc_while_capturing(), torch.cuda.graph(graph):
-                    self._drain(self._pointset_gen(rotate))
-                V["graph"] = g = (graph, rotate)
-            g[0].replay()
-        else:
-            self._drain(self._pointset_gen(rotate))
-        return V["loss"]
+        self._run_pointset(rotate, capture, False)
+        return self._mesh["verts"]["loss"]
 
     def pointset_loss(self, rotate=True):
         """The point-set loss alone (the validation pass of trainAccuracyNet, keep_prob 1): device tensor [1]."""
@@ -1562,6 +1616,38 @@ class FacetDenoiser:
         loss = self.pointset_forward_backward(rotate=True, capture=capture)
         self.adam_step()
         return loss
+
+    # ------------------------------------------------------------------------------------------
+    # double-loss training (trainDoubleLossNet, train.py:919-1268): the point-set loss + the dense face-normal loss
+    # ------------------------------------------------------------------------------------------
+    def _require_double(self):
+        if "verts" not in (self._mesh or {}):
+            raise RuntimeError("bind_vertices(...) is required for the double-loss step")
+        if "gtn" not in self._mesh["verts"]:
+            raise RuntimeError("the double-loss step needs the ground-truth face normals: bind_vertices(..., gt_normals=...)")
+
+    def double_loss_forward_backward(self, rotate=True, capture=False):
+        """One double-loss step without the optimiser (train.py:1079-1102): all three heads normalised, update_position_MS
+        on them, fullLoss + faceNormalsLoss(head 0, the rotated ground-truth normals); the returned device tensor [3] =
+        {total, points, normals}, every parameter gradient in params.grads.  capture=True: ONE hipGraph per mesh."""
+        self._require_double()
+        self._run_pointset(rotate, capture, True)
+        return self._mesh["verts"]["dl_out"][:3]
+
+    def double_loss(self, rotate=True):
+        """The double loss alone (the validation pass of trainDoubleLossNet, keep_prob 1): device tensor [3] = {total,
+        points, normals}."""
+        self._require_double()
+        self._pointset_forward(rotate, False, True)
+        return self._mesh["verts"]["dl_out"][:3]
+
+    def double_loss_step(self, sample_ind0, sample_ind1, R, capture=False):
+        """One iteration of trainDoubleLossNet's loop body (train.py:1160-1243): samples, rotation, step, Adam."""
+        self.set_point_samples(sample_ind0, sample_ind1)
+        self.set_rotation(R)
+        out = self.double_loss_forward_backward(rotate=True, capture=capture)
+        self.adam_step()
+        return out
 
     def adam_step(self, lr=1e-3, b1=0.9, b2=0.999, eps=1e-8):
         P = self.params

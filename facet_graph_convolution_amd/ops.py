@@ -562,3 +562,34 @@ def point_loss(p0, p1, sample_ind0, sample_ind1, threshold=5000.0, want_grad=Tru
                                     float(threshold), ptr(loss), ptr(g), ptr(ws), ws.numel(), stream_ptr()),
           "fgc_point_loss")
     return loss, g
+
+
+def dense_normals_loss(fn, gt, R=None, g=None, dloss=1.0, want_grad=True):
+    """faceNormalsLoss (train.py:1272-1294) over ALL rows of fn [n,3] against the ground truth gt [n,3] rotated by R
+    (3x3 array-like or device tensor; None = identity) on the fly (include/fgc.h: fgc_dense_normals_loss_fwd / _bwd).
+    Returns (loss [2] = {loss in degrees, real rows}, g): the gradient dloss * dL/dfn is ADDED to g [n,3] (a zero tensor
+    when g is None); g is None when want_grad is False."""
+    _req_cuda(fn, gt)
+    fn, gt = _f32c(fn.reshape(-1, 3)), _f32c(gt.reshape(-1, 3))
+    n = fn.shape[0]
+    if gt.shape[0] != n:
+        raise ValueError("fn has %d rows, gt %d" % (n, gt.shape[0]))
+    if R is not None:
+        if not isinstance(R, torch.Tensor) or not R.is_cuda:
+            R = torch.as_tensor(np.asarray(R, dtype=np.float32).reshape(9)).to(fn.device)
+        R = R.reshape(9).float().contiguous()
+    L = _lib.lib()
+    nsc = L.fgc_dense_normals_loss_scratch_floats(n)
+    scr = torch.empty(max(nsc, 1), dtype=torch.float32, device=fn.device)
+    loss = torch.empty(2, dtype=torch.float32, device=fn.device)
+    check(L.fgc_dense_normals_loss_fwd(ptr(fn), ptr(gt), ptr(R), n, ptr(loss), None, None, ptr(scr), nsc, stream_ptr()),
+          "fgc_dense_normals_loss_fwd")
+    if not want_grad:
+        return loss, None
+    if g is None:
+        g = torch.zeros_like(fn)
+    elif g.dtype != torch.float32 or not g.is_contiguous() or g.numel() != 3 * n or g.device != fn.device:
+        raise ValueError("g must be a contiguous float32 [n,3] tensor on the device of fn (it is accumulated into)")
+    check(L.fgc_dense_normals_loss_bwd(ptr(fn), ptr(gt), ptr(R), n, ptr(scr), nsc, float(dloss), ptr(g), stream_ptr()),
+          "fgc_dense_normals_loss_bwd")
+    return loss, g

@@ -7,15 +7,25 @@
   * the NaN watchdog (train.py:505-506,620-623), the smoothed loss every 50 iterations and the CSV of losses
     (train.py:580-586,629-632), checkpoints every SAVEITER iterations (train.py:551-552) with resume;
   * inference: forward without rotation, un-permute, drop fake rows, normalise twice (train.py:115-121,136).
+
+Training command (the reference's ``train(withVerts)``, train.py:1894-1921):
+
+    python -m facet_graph_convolution_amd.train DUMP_DIR NETWORK_DIR [--num-iterations N] [--net-name NAME]
+        [--with-vertices] [--double-loss] [--capture] [--seed S]
+
+loads the pickles `preprocess` wrote and runs trainNet, trainAccuracyNet (--with-vertices) or trainDoubleLossNet
+(--with-vertices --double-loss).
 """
+import argparse
 import os
+import pickle
 
 import numpy as np
 import torch
 
 from . import ops, tfckpt
 from .net import FacetDenoiser, COST_SAMPLES, POINT_SAMPLES, POINT_LOSS_THRESHOLD
-from .settings import SAVEITER
+from .settings import SAVEITER, NUM_ITERATIONS
 from .utils import rand_rotation_matrix
 
 
@@ -204,33 +214,74 @@ def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net"
     neighbours as the reference does), and the block is appended to `<net_name>.csv` at every save.
 
     Returns (net, lossArray of the last block, per-iteration training losses [num_iterations])."""
-    meshes = []
-    gtv = getattr(trainSet, "gtv_list", [])
-    for i in range(len(trainSet.in_list)):
+    return _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
+                                double=False)
+
+
+def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
+                       capture=False, validSet=None):
+    """train.py:919-1268: the multi-scale network trained on the point-set loss fullLoss PLUS the dense face-normal loss
+    faceNormalsLoss of head 0 against the rotated ground-truth face normals (customLoss = pointsLoss + normalsLoss,
+    unweighted, train.py:1100-1102).  trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT
+    (both gtv_list and gt_list).  One iteration is trainAccuracyNet's, except that all three heads go through
+    normalizeTensor before the vertex update (train.py:1079-1081) and the normal loss joins the loss
+    (FacetDenoiser.double_loss_step).  Same mesh selection, cadence (training loss every 10 iterations, validation every
+    20 - logged with its points / normals split, train.py:1237 -, checkpoint and CSV every 500 and at the end), resume
+    and NaN warning as trainAccuracyNet.  A mesh with ground-truth vertices but no ground-truth normals is an error.
+
+    Departure from the reference's CSV bookkeeping (train.py:1199-1257), the same as trainAccuracyNet's: iteration i
+    writes row (i mod 500) / 10 of a 50-row block (training loss - the total - in column 0, validation total in column
+    1, the previous row's validation entry set to the mean of its two neighbours), and the block is appended to
+    `<net_name>.csv` at every save.
+
+    Returns (net, lossArray of the last block, per-iteration {total, points, normals} [num_iterations, 3])."""
+    return _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
+                                double=True)
+
+
+def _vertex_meshes(ds, double, strict):
+    """The meshes of a TrainingSet that have ground-truth vertices: (features, adjacency, vertices, faces, v_faces,
+    gt vertices[, gt normals])."""
+    gtv = getattr(ds, "gtv_list", [])
+    gtn = getattr(ds, "gt_list", [])
+    out = []
+    for i in range(len(ds.in_list)):
         if i >= len(gtv) or np.asarray(gtv[i]).reshape(-1, 3).shape[0] == 0:
             continue        # train.py:792-796 draws again when a mesh has no ground-truth vertices
-        meshes.append((trainSet.in_list[i], trainSet.adj_list[i], trainSet.v_list[i], trainSet.faces_list[i],
-                       trainSet.v_faces_list[i], gtv[i]))
+        m = (ds.in_list[i], ds.adj_list[i], ds.v_list[i], ds.faces_list[i], ds.v_faces_list[i], gtv[i])
+        if double:
+            if i >= len(gtn) or np.asarray(gtn[i]).reshape(-1, 3).shape[0] == 0:
+                if strict:
+                    raise ValueError("mesh %d has no ground-truth face normals (gt_list) for the double loss" % i)
+                continue
+            m = m + (gtn[i],)
+        out.append(m)
+    return out
+
+
+def _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet, double):
+    """The loop of trainAccuracyNet (double=False) and trainDoubleLossNet (double=True)."""
+    meshes = _vertex_meshes(trainSet, double, True)
     if not meshes:
         raise ValueError("no training mesh has ground-truth vertices (addMeshWithVerticesAndGT)")
-    valid = []
-    if validSet is not None:
-        vgt = getattr(validSet, "gtv_list", [])
-        valid = [(validSet.in_list[i], validSet.adj_list[i], validSet.v_list[i], validSet.faces_list[i],
-                  validSet.v_faces_list[i], vgt[i]) for i in range(len(validSet.in_list))
-                 if i < len(vgt) and np.asarray(vgt[i]).reshape(-1, 3).shape[0] > 0]
+    valid = _vertex_meshes(validSet, double, True) if validSet is not None else []
     net = FacetDenoiser(device, multi_scale=True, seed=seed)
     ckpt = os.path.join(network_path, net_name) if network_path else None
     start = _resume(net, network_path, net_name) if ckpt else 0
     rs = np.random.RandomState(seed + 1)
     evalStepNum, validStepNum, block = 10, 20, 500
     lossArray = np.zeros([block // evalStepNum, 2])
-    hist = torch.zeros(max(num_iterations, 1), dtype=torch.float32, device=net.device)
+    hist = torch.zeros((max(num_iterations, 1), 3) if double else max(num_iterations, 1), dtype=torch.float32,
+                       device=net.device)
     acc = torch.zeros(1, dtype=torch.float32, device=net.device)
     acc_n, last_loss = 0, 0.0
 
     def bind(key, m):
-        net.bind_vertices(key, *m)      # (a cached mesh returns at once; bind_vertices reshapes the [1, ...] arrays)
+        # (a cached mesh returns at once; bind_vertices reshapes the [1, ...] arrays)
+        if double:
+            net.bind_vertices(key, *m[:6], gt_normals=m[6])
+        else:
+            net.bind_vertices(key, *m)
 
     def save(iteration):
         save_checkpoint(ckpt, net, iteration)
@@ -246,23 +297,35 @@ def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net"
         R_it = rand_rotation_matrix(randnums=rs.uniform(size=3))
         row = (it % block) // evalStepNum
         if valid and it % validStepNum == 0 and it > 0:
-            valid_loss = 0.0
+            vsum = np.zeros(3)
             for vbm, m in enumerate(valid):
                 bind(("valid", vbm), m)
                 nvv = np.asarray(m[2]).reshape(-1, 3).shape[0]
                 nvg = np.asarray(m[5]).reshape(-1, 3).shape[0]
                 net.set_point_samples(rs.randint(nvv, size=POINT_SAMPLES), rs.randint(nvg, size=POINT_SAMPLES))
                 net.set_rotation(R_it)
-                valid_loss += net.pointset_loss(rotate=True)[0].item()
-            valid_loss /= len(valid)
-            log("Iteration %d, validation loss %g" % (it, valid_loss))
+                if double:
+                    vsum += net.double_loss(rotate=True).cpu().numpy()
+                else:
+                    vsum[0] += net.pointset_loss(rotate=True)[0].item()
+            vsum /= len(valid)
+            valid_loss = vsum[0]
+            if double:
+                log("Iteration %d, validation loss = %g (points %g, normals %g)" % (it, vsum[0], vsum[1], vsum[2]))
+            else:
+                log("Iteration %d, validation loss %g" % (it, valid_loss))
             lossArray[row, 1] = valid_loss
             if row > 0:
                 lossArray[row - 1, 1] = (valid_loss + last_loss) / 2
             last_loss = valid_loss
         bind(b, meshes[b])
-        loss = net.pointset_step(i0, i1, R_it, capture=capture)
-        hist[it:it + 1].copy_(loss)
+        if double:
+            out = net.double_loss_step(i0, i1, R_it, capture=capture)
+            hist[it].copy_(out)
+            loss = out[0:1]
+        else:
+            loss = net.pointset_step(i0, i1, R_it, capture=capture)
+            hist[it:it + 1].copy_(loss)
         acc += loss
         acc_n += 1
         if it % evalStepNum == 0:
@@ -464,3 +527,43 @@ def inferNetOld(inputMesh, net_or_checkpoint, device="cuda", update_vertices=Fal
         return pts[0].cpu().numpy(), out.cpu().numpy()
     torch.cuda.synchronize()
     return out.cpu().numpy()
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description="Train the network on the pickles of `preprocess` (the reference's train()).")
+    ap.add_argument("dump_dir", help="folder of trainingSet.pkl / validSet.pkl (or the ...WithVertices.pkl pair)")
+    ap.add_argument("network_dir", help="checkpoint folder (created; a checkpoint of --net-name there is resumed)")
+    ap.add_argument("--num-iterations", type=int, default=NUM_ITERATIONS)
+    ap.add_argument("--net-name", default="net")
+    ap.add_argument("--with-vertices", action="store_true",
+                    help="the multi-scale network through update_position_MS on the point-set loss (trainAccuracyNet)")
+    ap.add_argument("--double-loss", action="store_true",
+                    help="with --with-vertices: the point-set loss plus the face-normal loss (trainDoubleLossNet)")
+    ap.add_argument("--capture", action="store_true", help="replay every training step from a hipGraph")
+    ap.add_argument("--seed", type=int, default=0)
+    args = ap.parse_args(argv)
+    if args.double_loss and not args.with_vertices:
+        ap.error("--double-loss trains on the vertex data: it needs --with-vertices")
+    if args.num_iterations < 0:
+        ap.error("--num-iterations must be >= 0")
+    names = (("trainingSetWithVertices.pkl", "validSetWithVertices.pkl") if args.with_vertices
+             else ("trainingSet.pkl", "validSet.pkl"))
+    ts_path, vs_path = (os.path.join(args.dump_dir, n) for n in names)
+    if not os.path.isfile(ts_path):
+        ap.error("no training set at %s: run `python -m facet_graph_convolution_amd.preprocess TRAINING_DIR GT_DIR %s%s` "
+                 "first" % (ts_path, args.dump_dir, " --with-vertices" if args.with_vertices else ""))
+    with open(ts_path, "rb") as fp:
+        train_set = pickle.load(fp)
+    valid_set = None
+    if os.path.isfile(vs_path):
+        with open(vs_path, "rb") as fp:
+            valid_set = pickle.load(fp)
+    os.makedirs(args.network_dir, exist_ok=True)
+    trainer = (trainDoubleLossNet if args.double_loss else trainAccuracyNet) if args.with_vertices else trainNet
+    trainer(train_set, args.num_iterations, network_path=args.network_dir, net_name=args.net_name, seed=args.seed,
+            capture=args.capture, validSet=valid_set)
+    return trainer.__name__
+
+
+if __name__ == "__main__":
+    main()

@@ -48,8 +48,10 @@ extern "C" {
  * fgc_mlp_layout_id / FGC_MLP_LAYOUT (packed operands carry the identity of their layout).
  * 105: fgc_nn_query / fgc_nn_workspace_bytes (nearest neighbour over point sets, for the evaluation metrics).
  * 106: fgc_vertex_update_ms_traj / fgc_vertex_update_ms_bwd (+ _workspace_floats), fgc_point_loss (+ _workspace_bytes):
- * training through the multi-scale vertex update on the point-set loss. */
-#define FGC_ABI_VERSION 106
+ * training through the multi-scale vertex update on the point-set loss.
+ * 107: fgc_dense_normals_loss_fwd / _bwd (+ _scratch_floats): the face-normal loss over all rows, for training on the
+ * point-set and face-normal losses together. */
+#define FGC_ABI_VERSION 107
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -693,6 +695,24 @@ size_t fgc_point_loss_workspace_bytes(int32_t np0, int32_t np1, int32_t ns0, int
 int fgc_point_loss(const float* p0, int32_t np0, const float* p1, int32_t np1, const int32_t* i0, int32_t ns0,
                    const int32_t* i1, int32_t ns1, float threshold, float* loss, float* g_p0, void* workspace,
                    size_t workspace_bytes, void* stream);
+
+/* Dense face-normal loss of trainDoubleLossNet: faceNormalsLoss (train.py:1272-1294) over ALL n rows, against the
+ * ground truth rotated on the fly (train.py:1019-1021).  fn [n,3]: head 0, normalised; gt [n,3]: the UNROTATED ground
+ * truth; R: device pointer to 9 floats (row-major, applied as fgc_rotate_rows does) or NULL (identity).  A row whose
+ * rotated ground truth has an L1 norm <= 1e-3 is a fake node and does not count.  Per row the same arithmetic as
+ * fgc_rotate_rows + fgc_angular_loss_fwd / _bwd (they agree row for row; the loss differs only in the order of the sum).
+ *   fwd: one partial {sum of angles, real rows} per 256 rows into scratch, then loss_out [2] = {loss in degrees, real
+ *     rows} (no real row: 0 / 0).  add / total (both NULL or both given, device scalars): total[0] = add[0] + loss[0]
+ *     (the step's sum of the point-set and the normal loss stays on the device).  Two launches.
+ *   bwd: g_fn [n,3] is ADDED TO (not overwritten): every real row strictly inside the clip gets
+ *     dloss k (R gt_r), k = -(180/pi) / sqrt(1 - dt^2) / (real rows); the real-row count comes from the partials the
+ *     forward left in scratch.  One launch, one writer per row, no atomics.
+ * scratch: at least fgc_dense_normals_loss_scratch_floats(n) floats, kept between the forward and the backward. */
+size_t fgc_dense_normals_loss_scratch_floats(int32_t n);
+int fgc_dense_normals_loss_fwd(const float* fn, const float* gt, const float* R, int32_t n, float* loss_out,
+                               const float* add, float* total, float* scratch, size_t scratch_floats, void* stream);
+int fgc_dense_normals_loss_bwd(const float* fn, const float* gt, const float* R, int32_t n, const float* scratch,
+                               size_t scratch_floats, float dloss, float* g_fn, void* stream);
 
 /* Nearest neighbour over point sets: the distance scan of hausdorffOverSampled (utils.py:816-1006) and of exact
  * point-set distances.  For every query point q[i] (float32 [nq,3]) the nearest point of p (float32 [np,3]) by squared

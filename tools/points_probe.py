@@ -1,11 +1,15 @@
 """Cost of the point-set training step (trainAccuracyNet) on the MI355X.
 
     python tools/points_probe.py [--faces 20000 100000] [--steps 20] [--out FILE] [--only all|network|vertex_fwd|vertex_bwd|loss]
+        [--double-loss]
 
 Per mesh size (a noisy torus): ms per point-set step eager and replayed from its hipGraph, the graph's node count
 (launches per step), the multi-scale angular-loss step on the same mesh for comparison, and the parts of the step timed
 alone with device events: network forward + backward, vertex update forward with trajectory, its adjoint, fullLoss.
---only runs one part in a loop (for a `rocprofv3 --kernel-trace --stats` run of its own)."""
+--only runs one part in a loop (for a `rocprofv3 --kernel-trace --stats` run of its own).  --double-loss: the mesh is bound
+with its ground-truth face normals, and the double-loss step (trainDoubleLossNet) is timed next to the point-set step,
+eager and replayed, with the dense face-normal loss alone (forward + accumulating backward) as one more part; --only then
+also takes `double` (the whole double-loss step) and `dense_loss`."""
 import argparse
 import json
 import os
@@ -36,6 +40,7 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--out", default="")
     ap.add_argument("--only", default="all")
+    ap.add_argument("--double-loss", action="store_true")
     args = ap.parse_args()
     from facet_graph_convolution_amd import ops
     from facet_graph_convolution_amd.net import FacetDenoiser, _graph_node_count
@@ -53,7 +58,7 @@ def main():
         rs = np.random.RandomState(0)
         Rm = rand_rotation_matrix(randnums=rs.uniform(size=3))
         net = FacetDenoiser("cuda:0", multi_scale=True, seed=0)
-        net.bind_vertices(0, x, adjs, v, faces, vf, gtv)
+        net.bind_vertices(0, x, adjs, v, faces, vf, gtv, gt_normals=ds.gt_list[0][0] if args.double_loss else None)
         net.set_point_samples(rs.randint(len(v), size=500), rs.randint(len(gtv), size=500))
         net.set_rotation(Rm)
         row = dict(faces=int(F.shape[0]), nodes=int(x.shape[1]), vertices=int(len(v)))
@@ -76,6 +81,10 @@ def main():
             net._coarse_head_bwd("1")
             net._drain(net._params_backward_gen(False))
         parts["network"] = network
+        if args.double_loss:
+            gacc = torch.zeros_like(B["nconv"])
+            parts["dense_loss"] = lambda: ops.dense_normals_loss(B["nconv"], Vb["gtn"], B["R"], g=gacc)
+            parts["double"] = lambda: net.double_loss_forward_backward(rotate=True)
         if args.only != "all":
             for _ in range(args.steps):
                 parts[args.only]()
@@ -88,8 +97,17 @@ def main():
             row["pointset_graph_nodes"] = _graph_node_count(Vb["graph"][0])
         except Exception as e:       # (the graph was instantiated without keep_graph)
             row["pointset_graph_nodes"] = repr(e)[:80]
+        if args.double_loss:
+            row["double_eager_ms"] = timed(lambda: net.double_loss_forward_backward(rotate=True), args.steps)
+            row["double_replay_ms"] = timed(lambda: net.double_loss_forward_backward(rotate=True, capture=True), args.steps)
+            try:
+                row["double_graph_nodes"] = _graph_node_count(Vb["graph_dl"][0])
+            except Exception as e:
+                row["double_graph_nodes"] = repr(e)[:80]
+            row["double_minus_pointset_replay_ms"] = row["double_replay_ms"] - row["pointset_replay_ms"]
         for k, fn in parts.items():
-            row[k + "_ms"] = timed(fn, args.steps)
+            if k != "double":
+                row[k + "_ms"] = timed(fn, args.steps)
         ang = FacetDenoiser("cuda:0", multi_scale=True, seed=0)
         ang.bind_mesh(x, adjs, gt=ds.gt_list[0])
         ang.set_samples(rs.randint(x.shape[1], size=4000))
