@@ -2118,6 +2118,7 @@ extern "C" int32_t fgc_conv_r_ld(int32_t cout, int32_t padded, int32_t bf16) {
 }
 
 extern "C" int fgc_conv_bwd_needs_exchange(const fgc_conv_desc* d, const fgc_conv_bwd_io* io) {
+    FGC_OPT_SCOPE(d);
     if (!d || !io) return 1;
     return (io->dx0 == nullptr && narrow_supported(d)) ? 0 : 1;
 }

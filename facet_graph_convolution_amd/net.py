@@ -18,6 +18,7 @@ Design (MI355X-first, nothing traced or compiled at run time):
     results are bitwise reproducible;
   * the whole forward+backward enqueue is capturable into a hipGraph (``capture=True``).
 """
+import collections
 import contextlib
 import ctypes as C
 import gc
@@ -28,7 +29,7 @@ import math
 import numpy as np
 import torch
 
-from . import _lib, ops
+from . import _lib, ops, require_graph_replay_safe
 from ._lib import ConvDesc, ConvBwdIO, AG_LD, DL_LD, FGC_M
 from .graph import FacetGraph, as_graph
 
@@ -153,12 +154,44 @@ def _no_gc_while_capturing():
             gc.enable()
 
 
-class _ConvLayer:
-    """Static description of one conv: which buffers it reads/writes and its parameter slots."""
+# One conv of the trunk (in forward order, model.py:858-931): level, inputs, 4x upsampling shift, output, pooled output,
+# activation, width, and (per network) its first parameter slot
+_ConvLayer = collections.namedtuple("_ConvLayer", "name level x0 x1 shift y pool act cout pidx", defaults=(None,))
+TRUNK = (
+    _ConvLayer("conv1", 0, "xr", None, 0, "h1", "p1", 1, 32),
+    _ConvLayer("conv2", 1, "p1", None, 0, "h2", "p2", 1, 64),
+    _ConvLayer("conv3", 2, "p2", None, 0, "h3", None, 1, 128),
+    _ConvLayer("dconv3", 2, "h3", None, 0, "d3", None, 1, 128),
+    _ConvLayer("upconv2", 1, "d3", None, 2, "u2", None, 0, 64),
+    _ConvLayer("dconv2", 1, "u2", "h2", 0, "d2", None, 1, 64),
+    _ConvLayer("upconv1", 0, "d2", None, 2, "u1", None, 0, 32),
+    _ConvLayer("dconv1", 0, "u1", "h1", 0, "d1", None, 1, 32),
+)
 
-    def __init__(self, name, level, x0, x1, shift, pidx, y, pool, act):
-        self.name, self.level, self.x0, self.x1, self.shift = name, level, x0, x1, shift
-        self.pidx, self.y, self.pool, self.act = pidx, y, pool, act
+
+def r_ld(cout, r_pad, bf16):
+    """Elements per row of a layer's backward aggregate r (include/fgc.h: FGC_CONV_R_PAD)."""
+    return _lib.lib().fgc_conv_r_ld(cout, 1 if r_pad else 0, 1 if bf16 else 0)
+
+
+def plan_grouped_dw(ns, dtype, pairs, mode, max_r_bytes, windowed, training, r_pad=True):
+    """The layers (in forward order) whose weight-gradient GEMM waits for the grouped launch at the end of the backward
+    pass (FGC_CONV_DEFER_DW); all but the first keep an `r` of their own until then.  ns: the level sizes [N0, N1, N2];
+    mode "0" / "1": none / all, otherwise the layers whose `r` is at most max_r_bytes; windowed: a facet-sharded mesh with
+    the weight-gradient stages in the next layer's exchange window (FacetDenoiser.dw_in_window).  Allocates nothing."""
+    if mode == "0" or not training:
+        return ()
+    # (the first layer has no r to keep apart: its GEMM reads the saved aggregates and ds.)  Facet-sharded: a layer's GEMM
+    # is what the NEXT layer's backward exchange hides behind, worth a collective's latency per layer - more than the ramp
+    # and tail a grouped launch saves; only the first layer, which has no exchange, still waits for the grouped launch
+    grouped = [TRUNK[0].name]
+    for lay in ([] if windowed else TRUNK[1:]):
+        cnt = ns[lay.level] * r_ld(lay.cout, r_pad, dtype == "bf16")
+        # (a layer over a 4x-upsampled tensor runs on its n / 4 coarse rows - the pair form - unless refused)
+        used = cnt // 4 if (lay.shift == 2 and pairs) else cnt
+        if mode == "1" or used * (2 if dtype == "bf16" else 4) <= max_r_bytes:
+            grouped.append(lay.name)
+    return tuple(grouped)
 
 
 class FacetDenoiser:
@@ -179,8 +212,9 @@ class FacetDenoiser:
         self.in_channels = in_channels
         self.params = FlatParams(param_spec(multi_scale, in_channels), self.device)
         self.params.init_random(seed)
+        # the bound mesh's state - buffers, descriptors, the grouped-dw set, captured steps - and the states bind_cached keeps
         self._mesh = None
-        self._graph_fb = None
+        self._mesh_cache = {}
         self.profile = False   # when True every enqueue is labelled for fgc_profile_collect
         self.comm = None       # exchange back end of a facet-sharded run (shard.DistComm)
         # facet-sharded runs: compute the interior tiles of a layer while its halo rows travel (FGC_NO_OVERLAP=1: the
@@ -199,13 +233,13 @@ class FacetDenoiser:
         # (FGC_CONV_DEFER_DW; a deferring layer keeps an `r` of its own until then).  bf16 storage: all layers - a layer's GEMM is
         # mostly ramp and tail there (100k facets: 1.095 -> 1.070 ms per step, 50k: 0.726 -> 0.705).  fp32: the GEMMs are
         # matrix-bound and grouping ALL of them loses the shared `r` whose lines stay in the Infinity Cache (1.761 -> 1.773 ms
-        # at 100k facets), so a layer defers only if its `r` is small (grouped_dw_max_r_bytes, bind_mesh decides per layer):
-        # on a 100k-facet mesh the level-2 layers and the up-convolutions' coarse rows, on a mesh of 25k facets or a shard of
-        # a strong-scaling run every layer - where a step is its launches, not its FLOPs.  FGC_GROUPED_DW=0 / 1: none / all.
+        # at 100k facets), so a layer defers only if its `r` is small (grouped_dw_max_r_bytes, plan_grouped_dw decides per
+        # mesh and layer): on a 100k-facet mesh the level-2 layers and the up-convolutions' coarse rows, on a mesh of 25k
+        # facets or a shard of a strong-scaling run every layer - where a step is its launches, not its FLOPs.
+        # FGC_GROUPED_DW=0 / 1: none / all (also on a facet-sharded mesh, which otherwise groups the first layer only).
         self.grouped_dw_mode = os.environ.get("FGC_GROUPED_DW", "1" if dtype == "bf16" else "auto") if self.batched else "0"
+        self.grouped_dw_forced = "FGC_GROUPED_DW" in os.environ
         self.grouped_dw_max_r_bytes = int(os.environ.get("FGC_GROUPED_DW_MAX_R_MB", "40")) << 20
-        self.grouped_dw = self.grouped_dw_mode == "1"       # (all layers; bind_mesh fills grouped_dw_layers)
-        self.grouped_dw_layers = frozenset()
         self.save_z = os.environ.get("FGC_NO_SAVE_Z", "0") != "1"
         # rows of the backward aggregate r padded to whole 128-byte lines (include/fgc.h: FGC_CONV_R_PAD); FGC_NO_R_PAD=1: the
         # packed rows of M*cout + 24 elements
@@ -237,16 +271,7 @@ class FacetDenoiser:
             self.slot[name] = k
             k += 5
         self.slot["head0"] = k
-        self.layers = [
-            _ConvLayer("conv1", 0, "xr", None, 0, self.slot["conv1"], "h1", "p1", 1),
-            _ConvLayer("conv2", 1, "p1", None, 0, self.slot["conv2"], "h2", "p2", 1),
-            _ConvLayer("conv3", 2, "p2", None, 0, self.slot["conv3"], "h3", None, 1),
-            _ConvLayer("dconv3", 2, "h3", None, 0, self.slot["dconv3"], "d3", None, 1),
-            _ConvLayer("upconv2", 1, "d3", None, 2, self.slot["upconv2"], "u2", None, 0),
-            _ConvLayer("dconv2", 1, "u2", "h2", 0, self.slot["dconv2"], "d2", None, 1),
-            _ConvLayer("upconv1", 0, "d2", None, 2, self.slot["upconv1"], "u1", None, 0),
-            _ConvLayer("dconv1", 0, "u1", "h1", 0, self.slot["dconv1"], "d1", None, 1),
-        ]
+        self.layers = [lay._replace(pidx=self.slot[lay.name]) for lay in TRUNK]
 
     # ------------------------------------------------------------------------------------------
     # mesh binding: graphs + every buffer, once
@@ -258,24 +283,33 @@ class FacetDenoiser:
 
         plan / comm (facet sharding, shard.py): x, adjs, gt are still the WHOLE mesh; this rank keeps only its
         shard ([owned rows | halo rows] per level) and exchanges halos through `comm` between the layers."""
+        M = self._bind_inputs(x, adjs, plan, gt is not None)
+        B = M["B"]
+        B.update(self._bind_activations(M))
+        scratch, M["grouped_dw_layers"] = self._bind_backward_scratch(M)
+        B.update(scratch)
+        B.update(self._bind_ground_truth(M, gt))
+        layer_bufs, M["descs"], M["ios"], M["layer_flags"] = self._bind_layers(M)
+        B.update(layer_bufs)
+        self._bind_backward_wiring(M)
+        mlp_bufs, M["arrays"] = self._bind_mlp_and_arrays(M)
+        B.update(mlp_bufs)
+        self._mesh = M
+        self.comm = comm
+        return self
+
+    def _bind_inputs(self, x, adjs, plan, training):
+        """A new mesh state: the graphs, the level sizes, the input rows and the per-step inputs."""
         dev = self.device
-        bf16 = self.dtype == "bf16"
         xt = torch.as_tensor(np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.float32))
         xt = xt.reshape(-1, xt.shape[-1]).contiguous()
         if xt.shape[1] != self.in_channels:
             raise ValueError("expected %d input channels" % self.in_channels)
-        gtt = None
-        if gt is not None:
-            gtt = torch.as_tensor(np.asarray(gt.cpu() if isinstance(gt, torch.Tensor) else gt, dtype=np.float32))
-            gtt = gtt.reshape(-1, 3).contiguous()
         if plan is None:
             graphs = [as_graph(a, dev) for a in adjs]
             if len(graphs) != 3:
                 raise ValueError("the network needs exactly 3 adjacency levels (model.py:858-931)")
-            nh = [0, 0, 0]
-            nhp = [0, 0]
-            n_total = [g.n for g in graphs]
-            own_lo = 0
+            nh, nhp, n_total, own_lo = [0, 0, 0], [0, 0], [g.n for g in graphs], 0
         else:
             from .shard import LocalGraph
             graphs = [LocalGraph(P, dev) for P in plan.levels]
@@ -286,20 +320,21 @@ class FacetDenoiser:
             n_total = list(plan.n_total)
             own_lo = plan.levels[0].lo
             xt = xt[torch.from_numpy(plan.local_rows(0))]
-            real_flag = None
-            if gtt is not None:
-                # which rows of the WHOLE mesh count in the loss (train.py:1283-1292): every rank can then count the
-                # real rows among a step's samples without asking the others
-                real_flag = (gtt.abs().sum(1) > 1e-3).to(torch.float32)
-                gtt = gtt[plan.levels[0].lo:plan.levels[0].hi]
-        n0, n1, n2 = (g.n for g in graphs)
+        n0, n1, n2 = ns = [g.n for g in graphs]
         if n0 != 4 * n1 or n1 != 4 * n2 or xt.shape[0] != n0 + nh[0]:
             raise ValueError("level sizes must be N0 = 4 N1 = 16 N2 and match x (got %d, %d, %d, x %d)" %
                              (n0, n1, n2, xt.shape[0]))
-        xt = xt.contiguous().to(dev)
-        f = dict(dtype=torch.float32, device=dev)
-        ns = [n0, n1, n2]
-        B = {"x": xt, "xr": torch.empty_like(xt)}
+        B = {"x": xt.contiguous().to(dev)}
+        B["xr"] = torch.empty_like(B["x"])
+        self._alloc_step_inputs(B, COST_SAMPLES)
+        # (captured: the mesh's captured steps by form - "angular", "points", "double" -, each (graph or segments, rotate))
+        return dict(graphs=graphs, B=B, ns=ns, nh=nh, nhp=nhp, has_gt=training, plan=plan, n_total=n_total,
+                    own_lo=own_lo, captured={})
+
+    def _bind_activations(self, M):
+        """Every activation and its gradient twin, the aggregate tables, and the heads' output and loss buffers."""
+        (n0, n1, n2), nh, nhp = M["ns"], M["nh"], M["nhp"]
+        f = dict(dtype=torch.float32, device=self.device)
         # rows: owned + the halo rows a consumer gathers (d3 / d2 are read 4x-upsampled by the level above, their tail
         # rows hold the parents of THAT level's halo nodes)
         shapes = {"h1": (n0 + nh[0], 32), "p1": (n1 + nh[1], 32), "h2": (n1 + nh[1], 64), "p2": (n2 + nh[2], 64),
@@ -308,78 +343,87 @@ class FacetDenoiser:
         # dtype "bf16": every activation that crosses a layer boundary (and its gradient) is STORED as bf16; the network
         # input, the 3-channel outputs, logit tables, per-edge d-logits and all parameters stay fp32 (include/fgc.h:
         # FGC_CONV_BF16)
-        act = dict(dtype=torch.bfloat16, device=dev) if bf16 else f
+        act = dict(dtype=torch.bfloat16, device=self.device) if self.dtype == "bf16" else f
+        B = {}
         for k, sh in shapes.items():
             kw = f if k in ("y0", "nconv") else act
             B[k] = torch.zeros(*sh, **kw)
             B["g_" + k] = torch.zeros(*sh, **kw)   # gradient twin
+        rows = dict({k: sh[0] for k, sh in shapes.items()}, xr=M["B"]["xr"].shape[0])
         for lay in self.layers:
-            B["ag_" + lay.name] = torch.empty(B[lay.x0].shape[0], AG_LD, **f)
+            B["ag_" + lay.name] = torch.empty(rows[lay.x0], AG_LD, **f)
         if self.multi_scale:
             for k, nk in (("1", n1), ("2", n2)):
                 B["y" + k] = torch.empty(nk, 3, **f)
                 B["nconv" + k] = torch.empty(nk, 3, **f)
                 B["abs_part" + k] = torch.empty(self.L.fgc_mlp_num_partials(nk), **f)
                 B["norm_scratch" + k] = torch.zeros(2 + self.L.fgc_norm_num_partials(nk), **f)
-                if gtt is not None and plan is None:
+                if M["has_gt"] and M["plan"] is None:
                     B["g_y" + k] = torch.zeros(nk, 3, **f)
                     B["g_nconv" + k] = torch.zeros(nk, 3, **f)
                     B["loss" + k] = torch.zeros(2, **f)
-        # shared backward scratch, sized for the largest user
-        max_ds = max((ns[l.level] + nh[l.level]) * self._cout(l) for l in self.layers)
-        rld = lambda l: self.L.fgc_conv_r_ld(self._cout(l), 1 if self.r_pad else 0, 1 if bf16 else 0)   # elements per row of r
-        max_r = max(ns[l.level] * rld(l) for l in self.layers)
-        if bf16:
-            max_r = (max_r + 1) // 2           # (B["r"] is allocated in fp32 words)
-        max_dl = max(max(g.nnz + getattr(g, "n_cross_in", 0) for g in graphs),
-                     max((g.pair.n_pairs + g.pair.n_cross_in for g in graphs[:2] if getattr(g, "pair", None) is not None), default=0))
-        B["ds"] = torch.zeros(max_ds, **f)
-        B["dl"] = torch.zeros(max(max_dl, 1) * DL_LD, **f)
-        B["dag"] = torch.empty(max(ns) * AG_LD, **f)
-        B["r"] = torch.empty(max_r, **f)
-        grouped = []
-        if self.grouped_dw_mode != "0" and gt is not None:
-            grouped.append(self.layers[0].name)   # (no r to keep apart: its GEMM can always wait for the grouped launch)
-            # Facet-sharded: a layer's weight-gradient GEMM is what the NEXT layer's backward exchange hides behind
-            # (_loss_backward_gen: dw_in_window), worth a collective's latency per layer - more than the ramp and tail a grouped
-            # launch saves; only the first layer, which has no exchange, still waits for the grouped launch.  (An explicit
-            # FGC_GROUPED_DW decides otherwise.)
-            windowed = plan is not None and self.dw_in_window and "FGC_GROUPED_DW" not in os.environ
-            for lay in ([] if windowed else self.layers[1:]):   # (the first layer has no r: its GEMM reads the saved aggregates and ds)
-                cnt = ns[lay.level] * rld(lay)
-                # (a layer over a 4x-upsampled tensor runs on its n / 4 coarse rows - the pair form - unless refused)
-                used = cnt // 4 if (lay.shift == 2 and self.pairs) else cnt
-                if self.grouped_dw_mode == "1" or used * (2 if bf16 else 4) <= self.grouped_dw_max_r_bytes:
-                    B["r_" + lay.name] = torch.empty((cnt + 1) // 2 if bf16 else cnt, **f)
-                    grouped.append(lay.name)
-        self.grouped_dw_layers = frozenset(grouped)
         B["abs_part"] = torch.empty(self.L.fgc_mlp_num_partials(n0), **f)
         B["norm_scratch"] = torch.zeros(2 + self.L.fgc_norm_num_partials(n0), **f)
         B["loss"] = torch.zeros(2, **f)
         B["loss_gacc"] = torch.zeros(n0, 3, **f)     # scatter accumulator of the fused loss end (zero between steps)
-        self._alloc_step_inputs(B, COST_SAMPLES)
-        if gtt is not None:
-            B["gt"] = gtt.contiguous().to(dev)
-            B["gtr"] = torch.empty_like(B["gt"])
-            if plan is not None:
-                B["real_flag"] = real_flag.to(dev)
-            elif self.multi_scale:
-                # ground truth of the coarse heads (build extension, see train_step): the fine normals pooled with
-                # "average ignoring zero rows" (model.py:792-814) and renormalised; rows of fake nodes only stay zero
-                from . import ops
-                g = B["gt"]
-                for k in ("1", "2"):
-                    g = ops.pool4_avg_iz(g)
-                    nrm = g.norm(dim=1, keepdim=True)
-                    g = torch.where(nrm > 0, g / nrm.clamp_min(1e-20), torch.zeros_like(g)).contiguous()
-                    B["gt" + k] = g
-                    B["gtr" + k] = torch.empty_like(g)
-        # descriptors + workspace
+        return B
+
+    def _bind_backward_scratch(self, M):
+        """The shared backward scratch and the own `r` of each deferring layer (plan_grouped_dw): (buffers, grouped set)."""
+        ns, nh, graphs = M["ns"], M["nh"], M["graphs"]
+        bf16, f = self.dtype == "bf16", dict(dtype=torch.float32, device=self.device)
+        max_ds = max((ns[l.level] + nh[l.level]) * l.cout for l in self.layers)
+        max_r = max(ns[l.level] * r_ld(l.cout, self.r_pad, bf16) for l in self.layers)
+        if bf16:
+            max_r = (max_r + 1) // 2           # (B["r"] is allocated in fp32 words)
+        max_dl = max(max(g.nnz + getattr(g, "n_cross_in", 0) for g in graphs),
+                     max((g.pair.n_pairs + g.pair.n_cross_in for g in graphs[:2] if getattr(g, "pair", None) is not None), default=0))
+        B = {"ds": torch.zeros(max_ds, **f), "dl": torch.zeros(max(max_dl, 1) * DL_LD, **f),
+             "dag": torch.empty(max(ns) * AG_LD, **f), "r": torch.empty(max_r, **f)}
+        windowed = M["plan"] is not None and self.dw_in_window and not self.grouped_dw_forced
+        grouped = plan_grouped_dw(ns, self.dtype, self.pairs, self.grouped_dw_mode, self.grouped_dw_max_r_bytes, windowed,
+                                  M["has_gt"], self.r_pad)
+        for lay in self.layers[1:]:
+            if lay.name in grouped:
+                cnt = ns[lay.level] * r_ld(lay.cout, self.r_pad, bf16)
+                B["r_" + lay.name] = torch.empty((cnt + 1) // 2 if bf16 else cnt, **f)
+        return B, frozenset(grouped)
+
+    def _bind_ground_truth(self, M, gt):
+        """A training mesh's ground-truth normals (facet-sharded: this rank's rows), the flags of the real rows of the whole
+        mesh (facet-sharded) or the pooled ground truth of the coarse heads (multi-scale)."""
+        if gt is None:
+            return {}
+        dev, plan = self.device, M["plan"]
+        gtt = torch.as_tensor(np.asarray(gt.cpu() if isinstance(gt, torch.Tensor) else gt, dtype=np.float32))
+        gtt = gtt.reshape(-1, 3).contiguous()
+        B = {"gt": gtt.to(dev) if plan is None else gtt[plan.levels[0].lo:plan.levels[0].hi].contiguous().to(dev)}
+        B["gtr"] = torch.empty_like(B["gt"])
+        if plan is not None:
+            # which rows of the WHOLE mesh count in the loss (train.py:1283-1292): every rank can then count the
+            # real rows among a step's samples without asking the others
+            B["real_flag"] = (gtt.abs().sum(1) > 1e-3).to(torch.float32).to(dev)
+        elif self.multi_scale:
+            # ground truth of the coarse heads (build extension, see train_step): the fine normals pooled with
+            # "average ignoring zero rows" (model.py:792-814) and renormalised; rows of fake nodes only stay zero
+            g = B["gt"]
+            for k in ("1", "2"):
+                g = ops.pool4_avg_iz(g)
+                nrm = g.norm(dim=1, keepdim=True)
+                g = torch.where(nrm > 0, g / nrm.clamp_min(1e-20), torch.zeros_like(g)).contiguous()
+                B["gt" + k] = g
+                B["gtr" + k] = torch.empty_like(g)
+        return B
+
+    def _bind_layers(self, M):
+        """Per layer: descriptor, backward io, workspaces and pair-form tables.  Returns (buffers, descs, ios, layer_flags)."""
+        dev, plan, graphs, training = self.device, M["plan"], M["graphs"], M["has_gt"]
+        bf16 = self.dtype == "bf16"
+        act = dict(dtype=torch.bfloat16 if bf16 else torch.float32, device=dev)
+        A = M["B"]          # (the buffers bound so far)
         vals, grads = self.params.values, self.params.grads
-        descs, ios, ws_f, ws_b = {}, {}, 0, 0
+        descs, ios, layer_flags, B = {}, {}, {}, {}
         pair_ios = []
-        layer_flags = {}
-        wsf, wsb = {}, {}    # a workspace of its own per layer: packed operands and partial sums stay put for the step
         for lay in self.layers:
             g = graphs[lay.level]
             W0, b, u, c, v = vals[lay.pidx:lay.pidx + 5]
@@ -387,17 +431,18 @@ class FacetDenoiser:
             d.n, d.nnz = g.n, g.nnz
             col = g.col_up if (plan is not None and lay.shift) else g.col
             d.rowptr, d.col = g.rowptr.data_ptr(), col.data_ptr()
-            d.x0 = B[lay.x0].data_ptr()
-            d.x1 = B[lay.x1].data_ptr() if lay.x1 else None
-            d.c0 = B[lay.x0].shape[1]
-            d.c1 = B[lay.x1].shape[1] if lay.x1 else 0
+            d.x0 = A[lay.x0].data_ptr()
+            d.x1 = A[lay.x1].data_ptr() if lay.x1 else None
+            d.c0 = A[lay.x0].shape[1]
+            d.c1 = A[lay.x1].shape[1] if lay.x1 else 0
             d.shift, d.cout = lay.shift, W0.shape[1]
             d.W0, d.b, d.u, d.c, d.v = (t.data_ptr() for t in (W0, b, u, c, v))
             d.bias_mask, d.act, d.alpha = 1, lay.act, LRELU_ALPHA
-            d.src_rows = B[lay.x0].shape[0]
+            d.src_rows = A[lay.x0].shape[0]
             d.max_deg = g.max_deg
-            # a narrow first layer leaves its aggregates in the forward workspace for the backward pass (training only)
-            d.flags = _lib.CONV_SAVE_Z if (gt is not None and lay.name == "conv1" and self.save_z) else 0
+            # a narrow first layer leaves its aggregates in the forward workspace for the backward pass (training only;
+            # _bind_backward_wiring drops the flag where the library does not take that path)
+            d.flags = _lib.CONV_SAVE_Z if (training and lay.name == "conv1" and self.save_z) else 0
             if bf16:
                 d.flags |= _lib.CONV_BF16
             layer_flags[lay.name] = d.flags
@@ -417,7 +462,7 @@ class FacetDenoiser:
             if use_pairs:
                 # (facet-sharded: the level's LOCAL pair graph, whose columns address [owned coarse rows | unique halo parents])
                 pg = g.pairs() if plan is None else g.pair
-                hc = torch.empty(B[lay.x0].shape[0], FGC_M * d.cout, **act)      # (bf16 storage: a bf16 table)
+                hc = torch.empty(A[lay.x0].shape[0], FGC_M * d.cout, **act)      # (bf16 storage: a bf16 table)
                 d.pair_rowptr, d.pair_col, d.pair_mul = pg.prow.data_ptr(), pg.pcol.data_ptr(), pg.pmul.data_ptr()
                 d.n_pairs, d.max_pair_deg, d.max_pair_in_deg = pg.n_pairs, pg.max_deg, pg.max_in_deg
                 d.hc = hc.data_ptr()
@@ -432,26 +477,27 @@ class FacetDenoiser:
                     d.pair_rowptr = d.pair_col = d.pair_mul = d.hc = None
                     d.n_pairs = d.max_pair_deg = d.max_pair_in_deg = 0
                     pg = None
-            wsf[lay.name] = torch.empty(self.L.fgc_conv_workspace_bytes(C.byref(d)) + 256, dtype=torch.uint8, device=dev)
-            if gt is not None:
-                wsb[lay.name] = torch.empty(self.L.fgc_conv_bwd_workspace_bytes(C.byref(d)) + 256, dtype=torch.uint8,
-                                            device=dev)
+            # a workspace of its own per layer: packed operands and partial sums stay put for the step
+            B["wsf_" + lay.name] = torch.empty(self.L.fgc_conv_workspace_bytes(C.byref(d)) + 256, dtype=torch.uint8,
+                                               device=dev)
+            if training:
+                B["wsb_" + lay.name] = torch.empty(self.L.fgc_conv_bwd_workspace_bytes(C.byref(d)) + 256,
+                                                   dtype=torch.uint8, device=dev)
             trow, tcol, tedge = g.transposed()
             io = ConvBwdIO()
             io.trowptr, io.tcol, io.tedge = trow.data_ptr(), tcol.data_ptr(), tedge.data_ptr()
             io.max_in_deg = g.max_in_deg
             io.stages = 0
-            io.ag, io.y, io.dy = B["ag_" + lay.name].data_ptr(), B[lay.y].data_ptr(), B["g_" + lay.y].data_ptr()
-            io.ds, io.dl, io.dag, io.r = (B[k].data_ptr() for k in ("ds", "dl", "dag", "r"))
-            if ("r_" + lay.name) in B:
-                io.r = B["r_" + lay.name].data_ptr()
+            io.ag, io.y, io.dy = A["ag_" + lay.name].data_ptr(), A[lay.y].data_ptr(), A["g_" + lay.y].data_ptr()
+            io.ds, io.dl, io.dag = (A[k].data_ptr() for k in ("ds", "dl", "dag"))
+            io.r = A.get("r_" + lay.name, A["r"]).data_ptr()
             # the stride of r belongs to the buffer: stated once here, not re-derived from every staged call's flags
-            io.r_ld = rld(lay)
+            io.r_ld = r_ld(lay.cout, self.r_pad, bf16)
             gW0, gb, gu, gc, gv = grads[lay.pidx:lay.pidx + 5]
             io.dW0, io.db, io.du, io.dc, io.dv = (t.data_ptr() for t in (gW0, gb, gu, gc, gv))
             if pg is not None:
                 io.tpair_rowptr, io.tpair_col, io.tpair_edge = pg.trow.data_ptr(), pg.tcol.data_ptr(), pg.tedge.data_ptr()
-                if gt is not None:
+                if training:
                     # (one row per owned pair, then the incoming cross-shard pairs of a facet-sharded rank)
                     need = max(pg.n_pairs + getattr(pg, "n_cross_in", 0), 1) * d.cout
                     if "dt" not in B or B["dt"].numel() < need:
@@ -460,57 +506,58 @@ class FacetDenoiser:
             ios[lay.name] = io
         for io in pair_ios:
             io.dt = B["dt"].data_ptr() if "dt" in B else None
+        return B, descs, ios, layer_flags
+
+    def _bind_backward_wiring(self, M):
+        """Where each layer's backward pass writes (dx, accumulate, pool fusion) and whether conv1 keeps its aggregates."""
+        B, descs, ios, layer_flags, training = M["B"], M["descs"], M["ios"], M["layer_flags"], M["has_gt"]
         # who writes each activation gradient first (write) / second (accumulate): fixed backward order
         #   g_h1: dconv1 (x1, write) then pool1 backward (accumulate);  g_h2: dconv2 (x1) then pool2 backward
-        for name in ["dconv1", "upconv1", "dconv2", "upconv2", "dconv3", "conv3", "conv2"]:
-            lay = next(l for l in self.layers if l.name == name)
-            io = ios[name]
+        for lay in self.layers[1:]:
+            io = ios[lay.name]
             io.dx0 = B["g_" + lay.x0].data_ptr()
             io.dx1 = B["g_" + lay.x1].data_ptr() if lay.x1 else None
             io.accumulate0, io.accumulate1 = 0, 0
-        ios["conv1"].dx0 = None
-        ios["conv1"].dx1 = None
-        if self.fused_pool and gt is not None:
+        ios["conv1"].dx0 = ios["conv1"].dx1 = None       # (the network input has no gradient)
+        if self.fused_pool and training:
             ios["conv1"].pool_y, ios["conv1"].pool_dy = B["p1"].data_ptr(), B["g_p1"].data_ptr()
             ios["conv2"].pool_y, ios["conv2"].pool_dy = B["p2"].data_ptr(), B["g_p2"].data_ptr()
-        if self.multi_scale and gt is not None and plan is None:
+        if self.multi_scale and training and M["plan"] is None:
             # training the three heads: the coarse heads write their input gradients into g_d3 / g_d2 first, the
             # up-convolutions then add theirs
             ios["upconv2"].accumulate0 = 1
             ios["upconv1"].accumulate0 = 1
         if (layer_flags["conv1"] & _lib.CONV_SAVE_Z) and not self.L.fgc_conv_bwd_needs_exchange(
                 C.byref(descs["conv1"]), C.byref(ios["conv1"])):
-            ios["conv1"].z_saved = wsf["conv1"].data_ptr()      # (the library took the narrow path: see FGC_CONV_SAVE_Z)
+            ios["conv1"].z_saved = B["wsf_conv1"].data_ptr()      # (the library took the narrow path: see FGC_CONV_SAVE_Z)
         else:
             layer_flags["conv1"] = descs["conv1"].flags = layer_flags["conv1"] & ~_lib.CONV_SAVE_Z
-        ws_f = max(ws_f, self.L.fgc_mlp_workspace_bytes(128, HIDDEN, 3))
-        ws_b = max(ws_b, self.L.fgc_mlp_bwd_workspace_bytes(n0, 32, HIDDEN, 3))
+        # a deferring layer's r must outlive the layers behind it: one of its own (the first layer has none)
+        if any(ios[n].r == B["r"].data_ptr() for n in M["grouped_dw_layers"] if n != "conv1"):
+            raise RuntimeError("a layer that defers its weight-gradient GEMM shares the backward scratch r")
+
+    def _bind_mlp_and_arrays(self, M):
+        """The MLP heads' workspaces and the layer arrays of fgc_conv_pack / fgc_conv_bwd_reduce: (buffers, arrays)."""
+        L, B, (n0, n1, n2) = self.L, M["B"], M["ns"]
+        u8 = dict(dtype=torch.uint8, device=self.device)
+        ws_b = L.fgc_mlp_bwd_workspace_bytes(n0, 32, HIDDEN, 3)
         if self.multi_scale:
-            ws_b = max(ws_b, self.L.fgc_mlp_bwd_workspace_bytes(n1, 64, HIDDEN, 3),
-                       self.L.fgc_mlp_bwd_workspace_bytes(n2, 128, HIDDEN, 3))
-        if bf16:
-            ws_b = max(ws_b, self.L.fgc_mlp_bwd_bf16_workspace_bytes(n0, 32, HIDDEN, 3))
-        B["ws"] = torch.empty(max(ws_f, ws_b) + 256, dtype=torch.uint8, device=dev)     # the MLP heads
+            ws_b = max(ws_b, L.fgc_mlp_bwd_workspace_bytes(n1, 64, HIDDEN, 3), L.fgc_mlp_bwd_workspace_bytes(n2, 128, HIDDEN, 3))
+        if self.dtype == "bf16":
+            ws_b = max(ws_b, L.fgc_mlp_bwd_bf16_workspace_bytes(n0, 32, HIDDEN, 3))
+        bufs = {"ws": torch.empty(max(L.fgc_mlp_workspace_bytes(128, HIDDEN, 3), ws_b) + 256, **u8)}     # the MLP heads
         # the last head's forward operands have a workspace of their own: the step's first launch (fgc_conv_pack with an
         # fgc_pack_extra) packs them and the backward operands (at the start of B["ws"]) beside the conv operands
-        B["ws_mlp_f"] = torch.empty(max(self.L.fgc_mlp_workspace_bytes(32, HIDDEN, 3),
-                                        self.L.fgc_mlp_bf16_workspace_bytes(32, HIDDEN, 3)) + 256, dtype=torch.uint8, device=dev)
-        for k, t in wsf.items():
-            B["wsf_" + k] = t
-        for k, t in wsb.items():
-            B["wsb_" + k] = t
+        bufs["ws_mlp_f"] = torch.empty(max(L.fgc_mlp_workspace_bytes(32, HIDDEN, 3),
+                                           L.fgc_mlp_bf16_workspace_bytes(32, HIDDEN, 3)) + 256, **u8)
         names = [lay.name for lay in self.layers]
         nl = len(names)
         arrays = dict(
-            descs=(C.POINTER(ConvDesc) * nl)(*[C.pointer(descs[k]) for k in names]),
-            ios=(C.POINTER(ConvBwdIO) * nl)(*[C.pointer(ios[k]) for k in names]),
-            wsf=(C.c_void_p * nl)(*[wsf[k].data_ptr() for k in names]),
-            wsb=(C.c_void_p * nl)(*[wsb[k].data_ptr() for k in names]) if wsb else None, count=nl)
-        self._mesh = dict(graphs=graphs, B=B, descs=descs, ios=ios, ns=ns, nh=nh, has_gt=gt is not None,
-                          plan=plan, n_total=n_total, own_lo=own_lo, arrays=arrays, layer_flags=layer_flags)
-        self.comm = comm
-        self._graph_fb = None
-        return self
+            descs=(C.POINTER(ConvDesc) * nl)(*[C.pointer(M["descs"][k]) for k in names]),
+            ios=(C.POINTER(ConvBwdIO) * nl)(*[C.pointer(M["ios"][k]) for k in names]),
+            wsf=(C.c_void_p * nl)(*[B["wsf_" + k].data_ptr() for k in names]),
+            wsb=(C.c_void_p * nl)(*[B["wsb_" + k].data_ptr() for k in names]) if M["has_gt"] else None, count=nl)
+        return bufs, arrays
 
     def _alloc_step_inputs(self, B, ns):
         """The per-step inputs - sample indices (train.py:561) and the rotation (train.py:563-565) - live in ONE device
@@ -539,24 +586,25 @@ class FacetDenoiser:
             own.copy_(B["step_in"])
             self._bind_step_inputs(B, own)
 
-    def bind_cached(self, key, x, adjs, gt=None, max_bytes=64 << 30):
-        """bind_mesh with the bound state (graphs, activations, descriptors: ~7 KB per facet) kept in HBM under `key`,
-        so that a training loop that alternates between meshes (train.py:556 draws one per iteration) switches
-        between them without re-uploading or re-allocating anything.  States are kept while they fit in max_bytes."""
-        cache = self.__dict__.setdefault("_mesh_cache", {})
+    def _cached(self, key, bind, max_bytes=64 << 30):
+        """Bind the mesh state kept under `key`, or bind() a new one and keep it while all fit in max_bytes."""
+        cache = self._mesh_cache
         if key in cache:
             self._mesh = cache[key]
-            self._graph_fb = None
-            return self
-        self.bind_mesh(x, adjs, gt=gt)
+            return self._mesh
+        bind()
         used = sum(sum(t.numel() * t.element_size() for t in m["B"].values()) for m in cache.values())
         mine = sum(t.numel() * t.element_size() for t in self._mesh["B"].values())
         if used + mine <= max_bytes:
             cache[key] = self._mesh
-        return self
+        return self._mesh
 
-    def _cout(self, lay):
-        return self.params.spec[lay.pidx][1][1]
+    def bind_cached(self, key, x, adjs, gt=None, max_bytes=64 << 30):
+        """bind_mesh with the bound state (graphs, buffers, descriptors, captured steps: ~7 KB per facet) kept in HBM under
+        `key`: a training loop that alternates between meshes (train.py:556 draws one per iteration) switches between them
+        without re-uploading, re-allocating or re-capturing anything.  States are kept while they fit in max_bytes."""
+        self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt), max_bytes)
+        return self
 
     # ------------------------------------------------------------------------------------------
     # enqueue helpers (no allocation, no sync).  The schedules are GENERATORS: they yield an exchange request
@@ -609,6 +657,23 @@ class FacetDenoiser:
     def _tag(self, name):
         if self.profile:
             self.L.fgc_profile_tag(name.encode())
+
+    @property
+    def grouped_dw_layers(self):
+        """The bound mesh's layers whose weight-gradient GEMM waits for the grouped launch (plan_grouped_dw)."""
+        return self._mesh["grouped_dw_layers"] if self._mesh is not None else frozenset()
+
+    @property
+    def _graph_fb(self):
+        """The bound mesh's captured angular-loss step: (hipGraph, rotate), or on a facet-sharded rank ((forward segments,
+        backward segments), rotate) (_capture_segments); None until forward_backward(capture=True) has recorded it."""
+        return self._mesh["captured"].get("angular") if self._mesh is not None else None
+
+    @_graph_fb.setter
+    def _graph_fb(self, step):
+        self._mesh["captured"].pop("angular", None)
+        if step is not None:
+            self._mesh["captured"]["angular"] = step
 
     @property
     def sharded(self):
@@ -959,7 +1024,7 @@ class FacetDenoiser:
             d, io = M["descs"][name], M["ios"][name]
             lws = B["wsb_" + name]
             base = (_lib.CONV_PACKED | _lib.CONV_DEFER_REDUCE) if self.batched else 0
-            if self.batched and name in self.grouped_dw_layers:
+            if self.batched and name in M["grouped_dw_layers"]:
                 base |= _lib.CONV_DEFER_DW
             if not self.sharded:
                 io.stages, io.flags = 0, base
@@ -980,32 +1045,40 @@ class FacetDenoiser:
                 io.stages = 1 | 2 | 8
                 call("params")
                 continue
-            if L.fgc_conv_uses_pairs(C.byref(d)):
+            pair = L.fgc_conv_uses_pairs(C.byref(d))
+            io.stages = 1 | 2
+            call("pair logits" if pair else "logits")
+            if pair:
                 # pair form: dt and the d-logits of the owned pairs; the rows of the pairs whose parent a peer owns travel to it
                 # (ONE grouped exchange, no rows of s), then the data kernel over the owned coarse rows and the weight gradients
                 pg = g.pair
                 npl = pg.n_pairs + pg.n_cross_in
-                io.stages = 1 | 2
-                call("pair logits")
-                dtb = B["dt"][:npl * cout].view(npl, cout)
-                dlb = B["dl"][:npl * DL_LD].view(npl, DL_LD)
-                items = [("pedges", lay.level, dtb), ("pedges", lay.level, dlb)]
-                if self.overlap and pg.tiles["ttiles_int"][1] >= self.pair_split_min_tiles:
-                    # ... it travels under the data kernel of the coarse-row tiles whose in-pairs all have owned parents; the
-                    # tiles with an incoming cross-shard pair and the weight gradients follow (round 6: the pair layers'
-                    # backward exchange used to block - tools/shard_latency_probe.py)
-                    yield ("xchg", items, "bwd")
-                    flush_dw()
-                    self._tag("bwd:" + name)
-                    io.stages, io.flags = 4, base | _lib.CONV_PACKED
-                    io.data_tile_list, io.n_data_tiles = pg.tiles["ttiles_int"][0].data_ptr(), pg.tiles["ttiles_int"][1]
-                    call("pair data/interior")
-                    yield ("wait", "bwd")
-                    io.data_tile_list, io.n_data_tiles = pg.tiles["ttiles_bnd"][0].data_ptr(), pg.tiles["ttiles_bnd"][1]
-                    call("pair data/boundary")
-                    io.data_tile_list, io.n_data_tiles, io.flags = None, 0, 0
-                    defer_dw(name, d, io, lws, base | _lib.CONV_PACKED)
-                    continue
+                items = [("pedges", lay.level, B["dt"][:npl * cout].view(npl, cout)),
+                         ("pedges", lay.level, B["dl"][:npl * DL_LD].view(npl, DL_LD))]
+                tiles, min_tiles, what = pg.tiles, self.pair_split_min_tiles, "pair data"
+            else:
+                # s = dy * lrelu'(y) / deg on owned rows and the d-logits of owned edges came in one call (the deep d-logits
+                # kernel computes s in its prologue; packs the operands of stages 2 and 4 when the network did not).  ONE
+                # grouped exchange per layer: the halo rows of s (their owners') and the d-logits of incoming cross-shard
+                # edges, both first read by the data kernel
+                ds_rows = (B["ds"].view(torch.bfloat16) if self.dtype == "bf16" else B["ds"])[:nloc * cout].view(nloc, cout)
+                items = [("rows", lay.level, ds_rows, False), ("edges", lay.level)]
+                tiles, min_tiles, what = g.tiles, self.split_min_tiles, "data"
+            if self.overlap and tiles["ttiles_int"][1] >= min_tiles:
+                # ... it travels under the data kernel of the interior tiles (all in-edges from owned rows; pair form: all
+                # in-pairs with owned parents); the boundary tiles and the weight gradients follow (round 6: the pair layers'
+                # backward exchange used to block - tools/shard_latency_probe.py)
+                yield ("xchg", items, "bwd")
+                flush_dw()
+                self._tag("bwd:" + name)
+                io.stages, io.flags = 4, base | _lib.CONV_PACKED
+                io.data_tile_list, io.n_data_tiles = tiles["ttiles_int"][0].data_ptr(), tiles["ttiles_int"][1]
+                call(what + "/interior")
+                yield ("wait", "bwd")
+                io.data_tile_list, io.n_data_tiles = tiles["ttiles_bnd"][0].data_ptr(), tiles["ttiles_bnd"][1]
+                call(what + "/boundary")
+                io.data_tile_list, io.n_data_tiles, io.flags = None, 0, 0
+            else:
                 # (nothing to put under it - no weight-gradient stage pending -: ONE blocking call, a synchronous collective on
                 #  the compute stream, without the cross-stream dependencies of an asynchronous one)
                 key = "bwd" if pending_dw[0] is not None else None
@@ -1015,46 +1088,13 @@ class FacetDenoiser:
                     yield ("wait", key)
                 self._tag("bwd:" + name)
                 io.stages, io.flags = 4, base | _lib.CONV_PACKED
-                call("pair data")
-                io.flags = 0
-                defer_dw(name, d, io, lws, base | _lib.CONV_PACKED)
-                continue
-            # s = dy * lrelu'(y) / deg on owned rows and the d-logits of owned edges, in one call (the deep d-logits kernel
-            # computes s in its prologue; packs the operands of stages 2 and 4 when the network did not)
-            io.stages = 1 | 2
-            call("logits")
-            # ONE grouped exchange per layer: the halo rows of s (their owners') and the d-logits of incoming cross-shard
-            # edges, both first read by the data kernel
-            ds_rows = (B["ds"].view(torch.bfloat16) if self.dtype == "bf16" else B["ds"])[:nloc * cout].view(nloc, cout)
-            items = [("rows", lay.level, ds_rows, False), ("edges", lay.level)]
-            if self.overlap and g.tiles["ttiles_int"][1] >= self.split_min_tiles:
-                # ... it travels under the data kernel of the interior tiles (all in-edges from owned rows); boundary
-                # tiles and the weight gradients follow
-                yield ("xchg", items, "bwd")
-                flush_dw()
-                self._tag("bwd:" + name)
-                io.stages, io.flags = 4, base | _lib.CONV_PACKED
-                io.data_tile_list, io.n_data_tiles = g.tiles["ttiles_int"][0].data_ptr(), g.tiles["ttiles_int"][1]
-                call("data/interior")
-                yield ("wait", "bwd")
-                io.data_tile_list, io.n_data_tiles = g.tiles["ttiles_bnd"][0].data_ptr(), g.tiles["ttiles_bnd"][1]
-                call("data/boundary")
-                io.data_tile_list, io.n_data_tiles, io.flags = None, 0, 0
-            else:
-                key = "bwd" if pending_dw[0] is not None else None
-                yield ("xchg", items, key)
-                flush_dw()
-                if key:
-                    yield ("wait", key)
-                self._tag("bwd:" + name)
-                io.stages, io.flags = 4, base | _lib.CONV_PACKED
-                call("data")
+                call(what)
                 io.flags = 0
             defer_dw(name, d, io, lws, base | _lib.CONV_PACKED)
         flush_dw()
         if self.batched:
             A = M["arrays"]
-            for lname in self.grouped_dw_layers:      # (the staged calls of a sharded step leave other flags behind)
+            for lname in M["grouped_dw_layers"]:      # (the staged calls of a sharded step leave other flags behind)
                 M["ios"][lname].flags = _lib.CONV_PACKED | _lib.CONV_DEFER_REDUCE | _lib.CONV_DEFER_DW
             self._tag("bwd:reduce")
             _lib.check(L.fgc_conv_bwd_reduce(A["descs"], A["ios"], A["wsb"], A["count"], st), "reduce")
@@ -1175,12 +1215,6 @@ class FacetDenoiser:
     def _fused_loss_now(self):
         return self.fused_loss
 
-    def _enqueue_forward(self, rotate, training=False):
-        self._drain(self._forward_gen(rotate, defer_normalize=training and self._fused_loss_now()))
-
-    def _enqueue_loss_backward(self, rotate):
-        self._drain(self._loss_backward_gen(rotate))
-
     # ------------------------------------------------------------------------------------------
     # public API
     # ------------------------------------------------------------------------------------------
@@ -1207,7 +1241,7 @@ class FacetDenoiser:
             R = B["R"].clone()
             self._alloc_step_inputs(B, t.size)
             B["R"].copy_(R)
-            self._graph_fb = None
+            self._mesh["captured"].clear()     # (every captured step of the mesh holds the old buffer's address)
         self._upload(B["sample_ind"], t)
         if self.sharded:
             lo = self._mesh["own_lo"]
@@ -1246,10 +1280,10 @@ class FacetDenoiser:
         """Samples and rotation of the next step(s) = a row of pack_step_inputs, COPIED into the network's own buffer (one
         device-to-device copy; the caller may reuse the row at once).  in_place=True: with eager launches the step reads the
         row where it is - no copy launch, and the caller must keep the row alive and unchanged until every queued step that
-        uses it has run (bench.py, whose rows are a window bound once); a network whose step is held by a hipGraph copies
+        uses it has run (bench.py, whose rows are a window bound once); a mesh whose step is held by a hipGraph copies
         anyway, because the graph holds the address of the own buffer."""
         B = self._mesh["B"]
-        if (in_place and self._graph_fb is None and packed_row.dtype == torch.int32 and packed_row.is_contiguous()
+        if (in_place and not self._mesh["captured"] and packed_row.dtype == torch.int32 and packed_row.is_contiguous()
                 and packed_row.numel() == B["step_in_own"].numel() and packed_row.device == B["step_in_own"].device
                 and packed_row.data_ptr() % 4 == 0):
             self._bind_step_inputs(B, packed_row)
@@ -1273,7 +1307,7 @@ class FacetDenoiser:
 
     def forward(self, rotate=False):
         """Normalised normals of the bound mesh: [N0,3] (padded, permuted order). Un-normalised output in buffers['y0']."""
-        self._enqueue_forward(rotate)
+        self._drain(self._forward_gen(rotate))
         return self._mesh["B"]["nconv"]
 
     def _forward_ms_gen(self, rotate):
@@ -1352,48 +1386,51 @@ class FacetDenoiser:
         return {"collectives_per_step": per, "blocking_ms_per_step": stats["s"] / steps * 1e3,
                 "bytes_sent_per_step": stats["bytes"] // steps, "per_collective": each}
 
+    def _angular_step(self, rotate):
+        self._drain(self._forward_gen(rotate, defer_normalize=self._fused_loss_now()))
+        self._drain(self._loss_backward_gen(rotate))
+
+    def _run_step(self, form, rotate, capture, enqueue):
+        """The bound mesh's step `form` ("angular", "points", "double"): enqueue(), or capture=True: ONE hipGraph kept with
+        the mesh, recorded (after a warm-up on a side stream) by the first call for this `rotate` value and replayed."""
+        if not capture:
+            return enqueue()
+        require_graph_replay_safe()
+        g = self._mesh["captured"].get(form)
+        if g is None or g[1] != rotate:
+            self._own_step_inputs()
+            s = torch.cuda.Stream()
+            s.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(s):
+                enqueue()
+            torch.cuda.current_stream().wait_stream(s)
+            graph = torch.cuda.CUDAGraph()
+            with _no_gc_while_capturing(), torch.cuda.graph(graph):
+                enqueue()
+            self._mesh["captured"][form] = g = (graph, rotate)
+        g[0].replay()
+
     def forward_backward(self, rotate=True, capture=False):
         """One forward + backward (train.py:492-520 without the optimiser); loss in buffers['loss'][0]."""
         if not self._mesh["has_gt"]:
             raise RuntimeError("bind_mesh(..., gt=...) is required for training")
-        if capture:
-            from . import require_graph_replay_safe
-            require_graph_replay_safe()
-            if self.sharded:
-                # one hipGraph per stretch of launches between two exchanges (17 collectives -> ~25 graphs per step
-                # instead of ~110 launches); the first call runs one step eagerly (lazy one-time set-up inside the
-                # library must not happen under capture), every later one replays
-                if self._graph_fb is None:
-                    self._own_step_inputs()
-                    self._enqueue_forward(rotate, training=True)
-                    self._enqueue_loss_backward(rotate)
-                    torch.cuda.synchronize()
-                    self._graph_fb = ((self._capture_segments(lambda: self._forward_gen(rotate, self._fused_loss_now())),
-                                       self._capture_segments(lambda: self._loss_backward_gen(rotate))), rotate)
-                    return self._mesh["B"]["loss"]
-                if self._graph_fb[1] != rotate:
-                    raise RuntimeError("the captured schedule was recorded with rotate=%s" % self._graph_fb[1])
-                for segs in self._graph_fb[0]:
-                    self._replay_segments(segs)
-                return self._mesh["B"]["loss"]
-            if self._graph_fb is None:
-                # warm up on a side stream, then capture the whole enqueue sequence into one hipGraph
-                self._own_step_inputs()
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self._enqueue_forward(rotate, training=True)
-                    self._enqueue_loss_backward(rotate)
-                torch.cuda.current_stream().wait_stream(s)
-                g = torch.cuda.CUDAGraph()
-                with _no_gc_while_capturing(), torch.cuda.graph(g):
-                    self._enqueue_forward(rotate, training=True)
-                    self._enqueue_loss_backward(rotate)
-                self._graph_fb = (g, rotate)
-            self._graph_fb[0].replay()
+        if not (capture and self.sharded):
+            self._run_step("angular", rotate, capture, lambda: self._angular_step(rotate))
         else:
-            self._enqueue_forward(rotate, training=True)
-            self._enqueue_loss_backward(rotate)
+            # one hipGraph per stretch of launches between two exchanges (17 collectives -> ~25 graphs per step instead of
+            # ~110 launches); the recording call runs one step eagerly (lazy one-time set-up inside the library must not
+            # happen under capture), every later one replays
+            require_graph_replay_safe()
+            g = self._graph_fb
+            if g is None or g[1] != rotate:
+                self._own_step_inputs()
+                self._angular_step(rotate)
+                torch.cuda.synchronize()
+                self._graph_fb = ((self._capture_segments(lambda: self._forward_gen(rotate, self._fused_loss_now())),
+                                   self._capture_segments(lambda: self._loss_backward_gen(rotate))), rotate)
+            else:
+                for segs in g[0]:
+                    self._replay_segments(segs)
         return self._mesh["B"]["loss"]
 
     def eval_loss(self, rotate=True):
@@ -1403,7 +1440,7 @@ class FacetDenoiser:
             raise RuntimeError("bind_mesh(..., gt=...) is required for a loss")
         if self.sharded:
             raise NotImplementedError("validation runs on an unsharded network")
-        self._enqueue_forward(rotate)
+        self._drain(self._forward_gen(rotate))
         B, L, st = self._mesh["B"], self.L, self._st()
         gt = B["gt"]
         if rotate:
@@ -1424,66 +1461,52 @@ class FacetDenoiser:
         (gt_list), for the double-loss step; uploaded into the cached vertex state (the first time they are given)."""
         if not self.multi_scale or self.dtype != "f32":      # (bind_cached binds unsharded)
             raise NotImplementedError("point-set training: unsharded fp32 multi-scale network only")
-        cache = self.__dict__.setdefault("_mesh_cache", {})
-        if key in cache and "verts" in cache[key]:      # (a training loop rebinds its meshes every iteration)
-            self._mesh = cache[key]
-            self._graph_fb = None
-            if gt_normals is not None and "gtn" not in self._mesh["verts"]:
-                self._bind_gt_normals(gt_normals)
-            return self
-        fresh = key not in cache
-        n0 = np.asarray(x).reshape(-1, np.asarray(x).shape[-1]).shape[0]
-        # the backward buffers of the heads come with a ground truth; the point-set step never reads its values
-        self.bind_cached(key, x, adjs, gt=np.zeros((1, n0, 3), dtype=np.float32))
-        M = self._mesh
-        if "verts" in M and not fresh:
-            return self
-        dev = self.device
-        vx = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
-        fc = np.asarray(faces).reshape(-1, 3).astype(np.int32)
-        vf = np.asarray(v_faces).reshape(vx.shape[0], -1).astype(np.int32)
-        gv = np.asarray(gt_verts, dtype=np.float32).reshape(-1, 3)
-        if fc.shape[0] != M["ns"][0]:
-            raise ValueError("faces has %d rows, the graph %d nodes" % (fc.shape[0], M["ns"][0]))
-        if gv.shape[0] == 0:
-            raise ValueError("no ground-truth vertices")
-        tabs = ops.vertex_ms_tables(fc, vf, vx.shape[0])
-        it = [int(i) for i in iters]
-        nv, T = vx.shape[0], sum(it)
-        f = dict(dtype=torch.float32, device=dev)
-        V = dict(x=torch.as_tensor(vx, device=dev), gt=torch.as_tensor(gv, device=dev),
-                 faces=torch.as_tensor(fc, device=dev), v_faces=torch.as_tensor(vf, device=dev),
-                 tables=[torch.as_tensor(t, device=dev) for t in tabs], iters=it)
-        V["xr"], V["gtr"] = torch.empty_like(V["x"]), torch.empty_like(V["gt"])
-        V["traj"] = torch.empty((T + 1) * nv * 3, **f)
-        V["centres"] = torch.empty(3 * (n0 + n0 // 4 + n0 // 16), **f)
-        V["g_p"], V["g_x"] = torch.zeros(nv, 3, **f), torch.zeros(nv, 3, **f)
-        V["bwd_ws"] = torch.empty(self.L.fgc_vertex_update_ms_bwd_workspace_floats(nv, n0), **f)
-        V["i0"] = torch.zeros(POINT_SAMPLES, dtype=torch.int32, device=dev)
-        V["i1"] = torch.zeros(POINT_SAMPLES, dtype=torch.int32, device=dev)
-        V["loss"] = torch.zeros(1, **f)
-        V["loss_ws"] = torch.empty(self.L.fgc_point_loss_workspace_bytes(nv, gv.shape[0], POINT_SAMPLES, POINT_SAMPLES) + 256,
-                                   dtype=torch.uint8, device=dev)
-        V["threshold"] = POINT_LOSS_THRESHOLD
-        M["verts"] = V
-        self._graph_fb = None
-        if gt_normals is not None:
-            self._bind_gt_normals(gt_normals)
-        return self
 
-    def _bind_gt_normals(self, gt_normals):
-        """The bound mesh's ground-truth face normals [N0,3] and the buffers of the double-loss step."""
-        M = self._mesh
-        V, n0 = M["verts"], M["ns"][0]
-        g = np.asarray(gt_normals.cpu() if isinstance(gt_normals, torch.Tensor) else gt_normals, dtype=np.float32)
-        g = g.reshape(-1, 3)
-        if g.shape[0] != n0:
-            raise ValueError("gt_normals has %d rows, the graph %d nodes" % (g.shape[0], n0))
-        f = dict(dtype=torch.float32, device=self.device)
-        V["gtn"] = torch.as_tensor(g, device=self.device)
-        V["dl_out"] = torch.zeros(4, **f)      # {total, points, normals, real rows}
-        nsc = self.L.fgc_dense_normals_loss_scratch_floats(n0)
-        V["dl_scratch"] = torch.zeros(nsc, **f)
+        def bind():
+            # the backward buffers of the heads come with a ground truth; the point-set step never reads its values
+            xa = np.asarray(x)
+            self.bind_mesh(x, adjs, gt=np.zeros((1, xa.size // xa.shape[-1], 3), dtype=np.float32))
+        M = self._cached(key, bind)      # (a training loop rebinds its meshes every iteration)
+        if "verts" not in M:
+            dev, n0 = self.device, M["ns"][0]
+            vx = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+            fc = np.asarray(faces).reshape(-1, 3).astype(np.int32)
+            vf = np.asarray(v_faces).reshape(vx.shape[0], -1).astype(np.int32)
+            gv = np.asarray(gt_verts, dtype=np.float32).reshape(-1, 3)
+            if fc.shape[0] != n0:
+                raise ValueError("faces has %d rows, the graph %d nodes" % (fc.shape[0], n0))
+            if gv.shape[0] == 0:
+                raise ValueError("no ground-truth vertices")
+            tabs = ops.vertex_ms_tables(fc, vf, vx.shape[0])
+            it = [int(i) for i in iters]
+            nv, T = vx.shape[0], sum(it)
+            f = dict(dtype=torch.float32, device=dev)
+            V = dict(x=torch.as_tensor(vx, device=dev), gt=torch.as_tensor(gv, device=dev),
+                     faces=torch.as_tensor(fc, device=dev), v_faces=torch.as_tensor(vf, device=dev),
+                     tables=[torch.as_tensor(t, device=dev) for t in tabs], iters=it)
+            V["xr"], V["gtr"] = torch.empty_like(V["x"]), torch.empty_like(V["gt"])
+            V["traj"] = torch.empty((T + 1) * nv * 3, **f)
+            V["centres"] = torch.empty(3 * (n0 + n0 // 4 + n0 // 16), **f)
+            V["g_p"], V["g_x"] = torch.zeros(nv, 3, **f), torch.zeros(nv, 3, **f)
+            V["bwd_ws"] = torch.empty(self.L.fgc_vertex_update_ms_bwd_workspace_floats(nv, n0), **f)
+            V["i0"], V["i1"] = (torch.zeros(POINT_SAMPLES, dtype=torch.int32, device=dev) for _ in range(2))
+            V["loss"] = torch.zeros(1, **f)
+            V["loss_ws"] = torch.empty(self.L.fgc_point_loss_workspace_bytes(nv, gv.shape[0], POINT_SAMPLES, POINT_SAMPLES)
+                                       + 256, dtype=torch.uint8, device=dev)
+            V["threshold"] = POINT_LOSS_THRESHOLD
+            M["verts"] = V
+        if gt_normals is not None and "gtn" not in M["verts"]:
+            # the ground-truth face normals and the buffers of the double-loss step
+            g = np.asarray(gt_normals.cpu() if isinstance(gt_normals, torch.Tensor) else gt_normals, dtype=np.float32)
+            g = g.reshape(-1, 3)
+            if g.shape[0] != M["ns"][0]:
+                raise ValueError("gt_normals has %d rows, the graph %d nodes" % (g.shape[0], M["ns"][0]))
+            V = M["verts"]
+            V["gtn"] = torch.as_tensor(g, device=self.device)
+            V["dl_out"] = torch.zeros(4, dtype=torch.float32, device=self.device)      # {total, points, normals, real rows}
+            V["dl_scratch"] = torch.zeros(self.L.fgc_dense_normals_loss_scratch_floats(M["ns"][0]), dtype=torch.float32,
+                                          device=self.device)
+        return self
 
     def set_point_samples(self, sample_ind0, sample_ind1):
         """The 500 + 500 sampled rows of fullLoss (train.py:810-811): rows of the vertices and of the ground truth."""
@@ -1573,35 +1596,11 @@ class FacetDenoiser:
             self._coarse_head_bwd(k)
         yield from self._params_backward_gen(False)
 
-    def _run_pointset(self, rotate, capture, double):
-        """The point-set (double=False) or double-loss step, eager or as ONE hipGraph per mesh and form (recorded on the
-        first call, replayed after)."""
-        V = self._mesh["verts"]
-        if capture:
-            from . import require_graph_replay_safe
-            require_graph_replay_safe()
-            slot = "graph_dl" if double else "graph"
-            g = V.get(slot)
-            if g is None or g[1] != rotate:
-                s = torch.cuda.Stream()
-                s.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(s):
-                    self._drain(self._pointset_gen(rotate, double))
-                torch.cuda.current_stream().wait_stream(s)
-                graph = torch.cuda.CUDAGraph()
-                with _no_gc_while_capturing(), torch.cuda.graph(graph):
-                    self._drain(self._pointset_gen(rotate, double))
-                V[slot] = g = (graph, rotate)
-            g[0].replay()
-        else:
-            self._drain(self._pointset_gen(rotate, double))
-
     def pointset_forward_backward(self, rotate=True, capture=False):
         """One point-set step without the optimiser: loss in the returned device tensor [1], every parameter gradient
         in params.grads.  capture=True: the whole step as ONE hipGraph (recorded on the first call, replayed after)."""
-        if "verts" not in (self._mesh or {}):
-            raise RuntimeError("bind_vertices(...) is required for the point-set step")
-        self._run_pointset(rotate, capture, False)
+        self._require_verts()
+        self._run_step("points", rotate, capture, lambda: self._drain(self._pointset_gen(rotate)))
         return self._mesh["verts"]["loss"]
 
     def pointset_loss(self, rotate=True):
@@ -1620,24 +1619,24 @@ class FacetDenoiser:
     # ------------------------------------------------------------------------------------------
     # double-loss training (trainDoubleLossNet, train.py:919-1268): the point-set loss + the dense face-normal loss
     # ------------------------------------------------------------------------------------------
-    def _require_double(self):
+    def _require_verts(self, double=False):
         if "verts" not in (self._mesh or {}):
-            raise RuntimeError("bind_vertices(...) is required for the double-loss step")
-        if "gtn" not in self._mesh["verts"]:
+            raise RuntimeError("bind_vertices(...) is required for the %s step" % ("double-loss" if double else "point-set"))
+        if double and "gtn" not in self._mesh["verts"]:
             raise RuntimeError("the double-loss step needs the ground-truth face normals: bind_vertices(..., gt_normals=...)")
 
     def double_loss_forward_backward(self, rotate=True, capture=False):
         """One double-loss step without the optimiser (train.py:1079-1102): all three heads normalised, update_position_MS
         on them, fullLoss + faceNormalsLoss(head 0, the rotated ground-truth normals); the returned device tensor [3] =
         {total, points, normals}, every parameter gradient in params.grads.  capture=True: ONE hipGraph per mesh."""
-        self._require_double()
-        self._run_pointset(rotate, capture, True)
+        self._require_verts(double=True)
+        self._run_step("double", rotate, capture, lambda: self._drain(self._pointset_gen(rotate, True)))
         return self._mesh["verts"]["dl_out"][:3]
 
     def double_loss(self, rotate=True):
         """The double loss alone (the validation pass of trainDoubleLossNet, keep_prob 1): device tensor [3] = {total,
         points, normals}."""
-        self._require_double()
+        self._require_verts(double=True)
         self._pointset_forward(rotate, False, True)
         return self._mesh["verts"]["dl_out"][:3]
 

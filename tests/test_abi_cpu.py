@@ -127,6 +127,25 @@ def test_a_descriptor_can_carry_its_own_option_values():
     assert set(out["plain"]) == {1} and set(out["fine"]) == {0}
     with pytest.raises(ValueError):
         _lib.option_overrides(NO_SUCH_OPTION=1)
+    # fgc_conv_bwd_needs_exchange (asked at bind time) follows them too: a narrow first layer (no dx0) needs no exchange
+    # unless its own descriptor refuses the narrow path
+    def narrow_desc():
+        d = _lib.ConvDesc()
+        fake = 4096
+        d.n, d.nnz, d.rowptr, d.col, d.x0 = 64, 256, fake, fake, fake
+        d.c0, d.c1, d.shift, d.cout, d.max_deg = 6, 0, 0, 32, 13
+        d.W0 = d.b = d.u = d.c = d.v = fake
+        return d
+
+    io = _lib.ConvBwdIO()
+    io.dx0 = None
+    narrow, wide = narrow_desc(), narrow_desc()
+    no_narrow = _lib.option_overrides(NO_NARROW=1)
+    wide.options, wide.n_options = C.addressof(no_narrow), len(no_narrow)
+    assert _lib.get_option("NO_NARROW") == 0
+    assert L.fgc_conv_bwd_needs_exchange(C.byref(narrow), C.byref(io)) == 0
+    assert L.fgc_conv_bwd_needs_exchange(C.byref(wide), C.byref(io)) == 1
+    assert _lib.get_option("NO_NARROW") == 0            # nothing global was written
 
 
 def test_packed_operands_carry_the_identity_of_their_layout():

@@ -324,6 +324,33 @@ def test_trainnet_evaluates_the_validation_set():
     assert vlog[2] < vlog[0] and losses[4, 0] < losses[0, 0]
 
 
+def test_trainnet_capture_records_each_mesh_once(monkeypatch):
+    """trainNet(capture=True) on two meshes: each mesh's step is recorded once and kept with the mesh across the switches
+    (not recorded again at every switch), and the run computes what the eager run computes."""
+    from facet_graph_convolution_amd.dataClasses import TrainingSet
+    from facet_graph_convolution_amd.meshgen import icosphere, torus, add_noise
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    from facet_graph_convolution_amd.train import trainNet
+    V, F = icosphere(2)
+    Vt, Ft = torus(20, 16)
+    ts = TrainingSet()
+    ts.addMeshWithGT(add_noise(V, F), F, V, seed=0)
+    ts.addMeshWithGT(add_noise(Vt, Ft), Ft, Vt, seed=1)
+    steps = []
+    adam = FacetDenoiser.adam_step
+
+    def adam_step(self, *a, **k):     # (right behind each step's forward_backward)
+        steps.append(self._graph_fb[0] if self._graph_fb is not None else None)
+        return adam(self, *a, **k)
+    monkeypatch.setattr(FacetDenoiser, "adam_step", adam_step)
+    net, losses = trainNet(ts, 24, capture=True, log=lambda *_: None)
+    graphs = list(steps)
+    switches = sum(1 for a, b in zip(graphs, graphs[1:]) if a is not b)
+    assert None not in graphs and len({id(g) for g in graphs}) == 2 and switches >= 3
+    net_e, losses_e = trainNet(ts, 24, log=lambda *_: None)
+    assert np.array_equal(losses, losses_e) and torch.equal(net.params.theta, net_e.params.theta)
+
+
 def test_graph_capture_refuses_when_the_runtime_switch_was_not_in_effect():
     """forward_backward(capture=True) must raise - not compute garbage - when DEBUG_CLR_GRAPH_PACKET_CAPTURE was not 0
     at HIP initialisation: the caller exported another value, or touched torch.cuda before importing the package."""

@@ -98,6 +98,14 @@ def test_forward_is_bitwise_reproducible_and_graph_capture_matches(golden_dir):
     net.forward_backward(rotate=True, capture=True)
     torch.cuda.synchronize()
     assert torch.equal(g1, net.params.grad) and torch.equal(n1, net.buffers["nconv"])
+    # a step is recorded for one `rotate` value: the other one records it again (and back), each equal to its eager step
+    net.forward_backward(rotate=False)
+    g2, n2 = net.params.grad.clone(), net.buffers["nconv"].clone()
+    assert not torch.equal(g1, g2)
+    for rotate, g, n in ((False, g2, n2), (False, g2, n2), (True, g1, n1)):
+        net.forward_backward(rotate=rotate, capture=True)
+        torch.cuda.synchronize()
+        assert torch.equal(g, net.params.grad) and torch.equal(n, net.buffers["nconv"]), rotate
 
 
 def test_inference_epilogue_matches_reference(golden_dir):
@@ -196,17 +204,22 @@ def test_rccl_code_path_world_of_one():
 
 
 def test_training_alternates_between_cached_meshes(golden_dir):
-    """bind_cached: two meshes stay bound in HBM; switching back and forth gives the same losses as re-binding."""
+    """bind_cached: two meshes stay bound in HBM; switching back and forth gives the same losses as re-binding.  With a
+    grouped-dw threshold between the two meshes' `r` sizes (N0 = 1616 / 784) the meshes defer different layers: each
+    cached mesh must keep its own set, not the one of the mesh bound last (at 0.5 MB the first mesh would otherwise defer
+    dconv2 on the `r` that conv2 overwrites)."""
     prep_a = np.load(os.path.join(golden_dir, "prep_ico3.npz"))
     prep_b = np.load(os.path.join(golden_dir, "prep_torus640.npz"))
     meshes = [(p["x"], [p["adj%d" % l] for l in range(3)], p["gt"]) for p in (prep_a, prep_b)]
 
     from facet_graph_convolution_amd.net import FacetDenoiser
 
-    def run(cached):
+    def run(cached, max_r_bytes):
         net = FacetDenoiser("cuda:0", seed=4)
+        if max_r_bytes is not None:
+            net.grouped_dw_max_r_bytes = max_r_bytes
         rs = np.random.RandomState(1)
-        out = []
+        out, sets = [], {}
         for it in range(8):
             b = it % 2
             x, adjs, gt = meshes[b]
@@ -214,12 +227,18 @@ def test_training_alternates_between_cached_meshes(golden_dir):
                 net.bind_cached(b, x, adjs, gt=gt)
             else:
                 net.bind_mesh(x, adjs, gt=gt)
+            sets[b] = net.grouped_dw_layers
             loss = net.train_step(sample_ind=rs.randint(x.shape[1], size=4000), R=np.eye(3))
             out.append(loss[0].item())
-        return out, net
-    a, net = run(True)
-    b, _ = run(False)
-    assert a == b and len(net._mesh_cache) == 2
+        return out, net, sets
+    for max_r_bytes, differ in ((None, None), (3 << 19, {"dconv1"}), (1 << 19, {"conv2", "dconv2"})):
+        a, net, sets = run(True, max_r_bytes)
+        b, net_b, sets_b = run(False, max_r_bytes)
+        assert a == b and len(net._mesh_cache) == 2, max_r_bytes
+        assert torch.equal(net.params.grad, net_b.params.grad) and torch.equal(net.params.theta, net_b.params.theta)
+        assert sets == sets_b, max_r_bytes
+        if differ is not None:
+            assert sets[0] != sets[1] and sets[0] ^ sets[1] == differ
 
 
 def _irregular_mesh():
@@ -443,7 +462,7 @@ def test_grouped_weight_gradient_launches_equal_the_per_layer_launches(dtype, mo
     for grouped in ("1", "0"):
         monkeypatch.setenv("FGC_GROUPED_DW", grouped)
         net = FacetDenoiser("cuda:0", seed=0, dtype=dtype).bind_mesh(x, adjs, gt=gt)
-        assert net.grouped_dw == (grouped == "1") and len(net.grouped_dw_layers) == (8 if grouped == "1" else 0)
+        assert (net.grouped_dw_mode == "1") == (grouped == "1") and len(net.grouped_dw_layers) == (8 if grouped == "1" else 0)
         losses = [net.train_step(sample_ind=samp, R=Rm)[0].item() for _ in range(3)]
         out.append((losses, net.params.grad.clone(), net.params.theta.clone()))
     assert out[0][0] == out[1][0]

@@ -171,6 +171,21 @@ def test_pointset_step_is_deterministic_and_replays_bit_exactly():
             runs.append((net._mesh["verts"]["loss"].clone(), net.params.grad.clone()))
         for k in range(1, 4):
             assert torch.equal(runs[0][0], runs[k][0]) and torch.equal(runs[0][1], runs[k][1]), k
+        # a new sample count reallocates the step inputs, whose rotation the recorded step reads: it is recorded again
+        import numpy as np
+        from facet_graph_convolution_amd.utils import rand_rotation_matrix
+        g0 = net._mesh["captured"]["points"][0]
+        net.set_samples(np.arange(1000))
+        assert not net._mesh["captured"]
+        net.set_rotation(rand_rotation_matrix(randnums=np.random.RandomState(9).uniform(size=3)))
+        net.pointset_forward_backward(rotate=True)
+        torch.cuda.synchronize()
+        eager = (net._mesh["verts"]["loss"].clone(), net.params.grad.clone())
+        net.pointset_forward_backward(rotate=True, capture=True)
+        torch.cuda.synchronize()
+        assert net._mesh["captured"]["points"][0] is not g0
+        assert torch.equal(eager[0], net._mesh["verts"]["loss"]) and torch.equal(eager[1], net.params.grad)
+        assert not torch.equal(eager[0], runs[0][0])
         print("deterministic ok", runs[0][0].item())
     """ % (REPO, os.path.join(REPO, "tests")))
     env = dict(os.environ)

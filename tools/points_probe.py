@@ -94,14 +94,14 @@ def main():
         row["pointset_eager_ms"] = timed(lambda: net.pointset_forward_backward(rotate=True), args.steps)
         row["pointset_replay_ms"] = timed(lambda: net.pointset_forward_backward(rotate=True, capture=True), args.steps)
         try:
-            row["pointset_graph_nodes"] = _graph_node_count(Vb["graph"][0])
+            row["pointset_graph_nodes"] = _graph_node_count(net._mesh["captured"]["points"][0])
         except Exception as e:       # (the graph was instantiated without keep_graph)
             row["pointset_graph_nodes"] = repr(e)[:80]
         if args.double_loss:
             row["double_eager_ms"] = timed(lambda: net.double_loss_forward_backward(rotate=True), args.steps)
             row["double_replay_ms"] = timed(lambda: net.double_loss_forward_backward(rotate=True, capture=True), args.steps)
             try:
-                row["double_graph_nodes"] = _graph_node_count(Vb["graph_dl"][0])
+                row["double_graph_nodes"] = _graph_node_count(net._mesh["captured"]["double"][0])
             except Exception as e:
                 row["double_graph_nodes"] = repr(e)[:80]
             row["double_minus_pointset_replay_ms"] = row["double_replay_ms"] - row["pointset_replay_ms"]
