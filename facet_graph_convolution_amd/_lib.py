@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FGC_LIB", os.path.join(_HERE, "csrc", "libfgc.so"))  # FGC_LIB: developer A/B builds
 
-ABI_VERSION = 107  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
+ABI_VERSION = 108  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
 FGC_M = 9
 AG_LD = 24
 DL_LD = 12
@@ -241,6 +241,10 @@ _SIGS = {
     "fgc_nn_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "fgc_nn_query": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgc_bilateral_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "fgc_bilateral_filter": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                       C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 EXPORTS = tuple(_SIGS.keys())

@@ -468,6 +468,37 @@ def nn_query(q, p, q_cell=None, p_cell=None):
     return dist, idx
 
 
+def bilateral_filter(centres, normals, areas, sigma_s, sigma_r, cell_order, cell_ptr, grid):
+    """Bilateral normal filter (include/fgc.h: fgc_bilateral_filter) on fp32 GPU tensors: centres [n,3], normals [n,3],
+    areas [n]; sigma_s and sigma_r a number or a sequence each (sigma_r = -1: no range term); cell_order int32 [n] and
+    cell_ptr int32 [sx sy sz + 1] the faces ordered by cell and the range table (utils.bilateral_order), grid =
+    (sx, sy, sz).  Returns [n, 3 S R]: the filtered unit normal of every (sigma_s, sigma_r) pair, sigma_s-major, all
+    pairs from one pass over the candidates.  A face in no cell gets a zero row."""
+    from .utils import BILATERAL_MAX_SLICES
+    _req_cuda(centres, normals, areas, cell_order, cell_ptr)
+    centres, normals = _f32c(centres.reshape(-1, 3)), _f32c(normals.reshape(-1, 3))
+    areas = _f32c(areas.reshape(-1))
+    n = centres.shape[0]
+    if normals.shape[0] != n or areas.numel() != n:
+        raise ValueError("centres, normals and areas must have one row per face")
+    sx, sy, sz = (int(g) for g in grid)
+    if min(sx, sy, sz) < 1 or max(sx, sy, sz) > BILATERAL_MAX_SLICES:
+        raise ValueError("grid %s: 1 .. %d cells per axis" % ((sx, sy, sz), BILATERAL_MAX_SLICES))
+    cell_order = cell_order.to(torch.int32).contiguous()
+    cell_ptr = cell_ptr.to(torch.int32).contiguous()
+    if cell_order.numel() != n or cell_ptr.numel() != sx * sy * sz + 1:
+        raise ValueError("cell_order must have n entries and cell_ptr sx * sy * sz + 1")
+    ss = np.atleast_1d(np.asarray(sigma_s, dtype=np.float32)).ravel()
+    sr = np.atleast_1d(np.asarray(sigma_r, dtype=np.float32)).ravel()
+    out = torch.empty(n, 3 * ss.size * sr.size, dtype=torch.float32, device=centres.device)
+    nbytes = _lib.lib().fgc_bilateral_workspace_bytes(n, sx, sy, sz)
+    ws = _workspace(nbytes, centres.device, "bilateral")
+    check(_lib.lib().fgc_bilateral_filter(ptr(centres), ptr(normals), ptr(areas), n, ptr(cell_order), ptr(cell_ptr), sx, sy,
+                                          sz, ss.ctypes.data, ss.size, sr.ctypes.data, sr.size, ptr(out), ptr(ws),
+                                          ws.numel(), stream_ptr()), "fgc_bilateral_filter")
+    return out
+
+
 def vertex_ms_tables(faces, v_faces, nv):
     """The two inverse tables of fgc_vertex_update_ms_bwd, built once per mesh on the host (int32 numpy):
     (slot_ptr [N0+1], slot_vert) - for every fine node f the vertices whose slots name f, in (vertex, slot) order - and

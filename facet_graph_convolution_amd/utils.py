@@ -69,9 +69,12 @@ def computeFacesNormals(verts, faces):
 
 
 def getTrianglesBarycenter(vl, fl, normalize=True):
-    """utils.py:1264-1294 (normalize=True only: positions divided by the bbox diagonal, not centred)."""
+    """utils.py:1264-1294.  normalize=True: positions divided by the bbox diagonal, not centred (natively);
+    normalize=False: the plain barycentres (v0 + v1 + v2) / 3 in the vertices' dtype, returned as float64 like the
+    reference's array (what the bilateral filter works on)."""
     if not normalize:
-        raise NotImplementedError("only the default normalize=True path is on the denoising path")
+        vl, fl = np.asarray(vl), np.asarray(fl).astype(np.int64)
+        return ((vl[fl[:, 0]] + vl[fl[:, 1]] + vl[fl[:, 2]]) / 3).astype(np.float64)
     return face_features(vl, fl)[1]
 
 
@@ -494,3 +497,131 @@ def getColoredMesh(V, F, faceColors):
     newV = np.reshape(np.concatenate((Vl, faceColors), axis=-1), (3 * facesNum, 6))
     newF = np.reshape(np.arange(3 * facesNum), (facesNum, 3))
     return newV, newF
+
+
+# ---------------------------------------------------------------------------------------------------
+# bilateral normal filtering, the classical baseline (utils.py:1242-1260, 2344-2526)
+# ---------------------------------------------------------------------------------------------------
+BILATERAL_MAX_SLICES = 64     # cells per axis of the filter's grid (FGC_BILATERAL_MAX_SLICES, include/fgc.h)
+
+
+def getTrianglesArea(vl, fl, normalize=False):
+    """utils.py:1242-1260, vectorised: 0.5 |(v1 - v0) x (v2 - v0)| per face in the vertices' dtype, returned as float64
+    like the reference's array; normalize=True divides the vertices by twice the average edge length first."""
+    vl, fl = np.asarray(vl), np.asarray(fl).astype(np.int64)
+    if normalize:
+        el, _ = getAverageEdgeLength(vl, fl)
+        vl = vl / (2 * el)
+    v0 = vl[fl[:, 0]]
+    cp = np.cross(vl[fl[:, 1]] - v0, vl[fl[:, 2]] - v0)
+    return (0.5 * np.sqrt((cp * cp).sum(-1))).astype(np.float64)
+
+
+def getAverageEdgeLength(vl, fl, normalize=False):
+    """utils.py:2501-2526: (mean edge length, number of edges), every edge counted once per adjacent triangle;
+    normalize=True divides the vertices by the bounding-box diagonal first."""
+    vl, fl = np.asarray(vl), np.asarray(fl).astype(np.int64)
+    if normalize:
+        lo, hi = vl.min(0), vl.max(0)
+        vl = vl / math.sqrt(sum(math.pow(h - l, 2) for l, h in zip(lo, hi)))
+    tri = vl[fl]
+    lt = np.concatenate([np.linalg.norm(tri[:, 1] - tri[:, 0], axis=-1), np.linalg.norm(tri[:, 2] - tri[:, 1], axis=-1),
+                         np.linalg.norm(tri[:, 0] - tri[:, 2], axis=-1)], axis=0)
+    return np.mean(lt), lt.shape[0]
+
+
+def bilateral_grid(slices):
+    """(sx, sy, sz) of a `slices` argument: an int (the same count on every axis; the reference's grid is 10) or a
+    3-tuple.  1 .. BILATERAL_MAX_SLICES per axis, ValueError otherwise."""
+    if isinstance(slices, (int, np.integer)):
+        grid = (int(slices),) * 3
+    else:
+        grid = tuple(int(s) for s in slices)
+        if len(grid) != 3 or any(g != s for g, s in zip(grid, slices)):
+            raise ValueError("slices must be an int or three ints, not %r" % (slices,))
+    if min(grid) < 1 or max(grid) > BILATERAL_MAX_SLICES:
+        raise ValueError("slices %r: 1 .. %d cells per axis are supported" % (slices, BILATERAL_MAX_SLICES))
+    return grid
+
+
+def bilateral_cells(Fc, slices=10, flat_axis_one_cell=False):
+    """Cell coordinates int64 [n,3] of every face centre in the partition of the reference's bilateralFilter
+    (utils.py:2351-2399), with the reference's own numpy expressions: the centres minus their float32 corner, bounds
+    max * 1.01 in the centres' dtype, slice i of an axis holds i * max / slices <= c < (i + 1) * max / slices.  -1 on an
+    axis where no slice takes the centre: on an axis of zero extent that is every face (the reference then filters
+    nothing), unless flat_axis_one_cell, which gives such an axis one slice that holds every face."""
+    grid = bilateral_grid(slices)
+    Fc = np.asarray(Fc)
+    transVec = np.array(([[np.amin(Fc[:, 0]), np.amin(Fc[:, 1]), np.amin(Fc[:, 2])]]), dtype=np.float32)
+    Fc = Fc - transVec
+    cell = np.full((Fc.shape[0], 3), -1, dtype=np.int64)
+    for axis, s in enumerate(grid):
+        c = Fc[:, axis]
+        m = np.amax(c)
+        if flat_axis_one_cell and not m > 0:
+            cell[:, axis] = 0
+            continue
+        m *= 1.01
+        for i in range(s):
+            cm = i * m / s
+            cM = (i + 1) * m / s
+            cell[(c >= cm) & (c < cM), axis] = i
+    return cell
+
+
+def bilateral_order(cell, slices):
+    """The filter's two tables (include/fgc.h: fgc_bilateral_filter) from bilateral_cells' coordinates: (order int32 [n],
+    ptr int32 [sx sy sz + 1]).  order lists the faces that lie in a cell by flattened cell (i * sy + j) * sz + k, in face
+    order inside a cell (a stable counting sort), then the faces in no cell; ptr is the range table over it."""
+    sx, sy, sz = bilateral_grid(slices)
+    cell = np.asarray(cell, dtype=np.int64).reshape(-1, 3)
+    if (cell >= np.array([sx, sy, sz])).any():
+        raise ValueError("cell coordinates outside the %d x %d x %d grid" % (sx, sy, sz))
+    ncell = sx * sy * sz
+    flat = np.where((cell < 0).any(1), ncell, (cell[:, 0] * sy + cell[:, 1]) * sz + cell[:, 2])
+    order = np.argsort(flat, kind="stable").astype(np.int32)
+    ptr = np.concatenate([[0], np.cumsum(np.bincount(flat, minlength=ncell + 1)[:ncell])]).astype(np.int32)
+    return order, ptr
+
+
+def bilateral_device_centres(Fc):
+    """float32 centres for the device.  The filter sees only differences of centres: float32 input goes as it is, wider
+    input is moved to its corner first so that the cast keeps the differences."""
+    Fc = np.asarray(Fc)
+    if Fc.dtype == np.float32:
+        return Fc
+    return (Fc - Fc.min(0)).astype(np.float32)
+
+
+def FND(Fc, Fn, Fa, sigma_s_list, sigma_r_list, K=1, slices=10):
+    """utils.py:2480-2496: the filtered normal descriptors, float32 [n, 3 S R]: bilateralFilter for every sigma_s (outer)
+    and sigma_r (inner), concatenated; all pairs come from ONE pass over the candidates (fgc_bilateral_filter), and each
+    equals the single-pair call bit for bit.  K is unused, as in the reference.  `slices` as in bilateralFilter."""
+    import torch
+    from . import ops
+    grid = bilateral_grid(slices)
+    Fc, Fn, Fa = np.asarray(Fc), np.asarray(Fn), np.asarray(Fa)
+    order, ptr = bilateral_order(bilateral_cells(Fc, grid), grid)
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def put(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    out = ops.bilateral_filter(put(bilateral_device_centres(Fc), np.float32), put(Fn, np.float32),
+                               put(Fa.reshape(-1), np.float32), sigma_s_list, sigma_r_list, put(order, np.int32),
+                               put(ptr, np.int32), grid)
+    return out.cpu().numpy()
+
+
+def bilateralFilter(Fc, Fn, Fa, sigma_s, sigma_r, slices=10):
+    """utils.py:2344-2477 ("bilateral filter on list of triangles, as defined in Wang et al."): float32 [n,3],
+
+        normalize( sum over j in window(i) of Fa_j exp(-|Fc_i - Fc_j|^2 / (2 sigma_s^2))
+                                                    exp(-|Fn_i - Fn_j|^2 / (2 sigma_r^2)) Fn_j ),
+
+    sigma_r = -1: no range term.  window(i) is the 3 x 3 x 3 block of cells around face i's cell in a grid of `slices`
+    cells per axis over the centres' bounding box (bilateral_cells).  With the default slices = 10 this is the
+    reference's partition and the reference's result, including what follows from it: on a coarse mesh the window cuts
+    the Gaussian off early, a face in no cell gets a zero row, and a mesh with an axis of zero extent is all zeros.
+    `slices` may also be a 3-tuple (not in the reference); at most BILATERAL_MAX_SLICES per axis, ValueError above.
+    The sum runs on the GPU in float32 (fgc_bilateral_filter), the binning on the host."""
+    return FND(Fc, Fn, Fa, [sigma_s], [sigma_r], slices=slices)

@@ -50,8 +50,9 @@ extern "C" {
  * 106: fgc_vertex_update_ms_traj / fgc_vertex_update_ms_bwd (+ _workspace_floats), fgc_point_loss (+ _workspace_bytes):
  * training through the multi-scale vertex update on the point-set loss.
  * 107: fgc_dense_normals_loss_fwd / _bwd (+ _scratch_floats): the face-normal loss over all rows, for training on the
- * point-set and face-normal losses together. */
-#define FGC_ABI_VERSION 107
+ * point-set and face-normal losses together.
+ * 108: fgc_bilateral_filter / fgc_bilateral_workspace_bytes (bilateral normal filtering, the classical baseline). */
+#define FGC_ABI_VERSION 108
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -728,6 +729,31 @@ int fgc_dense_normals_loss_bwd(const float* fn, const float* gt, const float* R,
 size_t fgc_nn_workspace_bytes(int32_t nq, int32_t np);
 int fgc_nn_query(const float* q, int32_t nq, const float* p, int32_t np, const int32_t* q_cell, const int32_t* p_cell,
                  float* dist, int32_t* idx, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Bilateral normal filter over a list of triangles (utils.bilateralFilter / utils.FND, utils.py:2344-2496), all
+ * P = S x R parameter pairs in one pass over the candidates.  For n faces with centres c [n,3], normals nrm [n,3], areas
+ * a [n] (float32, device):
+ *   out[i, 3p .. 3p+2] = normalize( sum over j in window(i) of a_j exp(-|c_i - c_j|^2 / (2 sigma_s^2))
+ *                                                                 exp(-|n_i - n_j|^2 / (2 sigma_r^2)) n_j ),
+ * p = s * R + r (sigma_s-major), out [n, 3 S R]; sigma_r = -1 means "no range term" (that factor is 1); normalize is
+ * x * (1 / (|x| + 1e-8)) applied twice (utils.normalize), so a zero sum stays zero.  sigma_s [S], sigma_r [R]: HOST arrays.
+ * The cells are an input: the grid has sx x sy x sz cells (1 .. FGC_BILATERAL_MAX_SLICES per axis), flattened as
+ * (i * sy + j) * sz + k; cell_order [n] (device) is a permutation of the faces, those that lie in a cell first, ordered by
+ * flattened cell, then the faces in no cell; cell_ptr [sx sy sz + 1] (device) is the range table over cell_order
+ * (cell_ptr[cells] = number of faces in a cell).  window(i) = the faces of the cells that differ from face i's cell by at
+ * most 1 on every axis, clipped at the grid's edge, face i included.  A face in no cell is in nobody's window and gets a
+ * zero row.  Results are written in the caller's face order.
+ * fp32 throughout, exp through the hardware exp2 with a pre-scaled argument.  Deterministic: every row's sum has one fixed
+ * order (no floating-point atomics), and a pair's result does not depend on which other pairs the call computes.
+ * Entries of cell_order outside [0, n) and ranges of cell_ptr outside [0, n] are ignored, never dereferenced.
+ * workspace (device, 16-byte aligned) >= fgc_bilateral_workspace_bytes(n, sx, sy, sz) (0 for arguments the filter refuses).
+ * A memset, two small launches, then one launch per 4 x 3 block of (sigma_s, sigma_r) on `stream`. */
+#define FGC_BILATERAL_MAX_SLICES 64
+size_t fgc_bilateral_workspace_bytes(int32_t n, int32_t sx, int32_t sy, int32_t sz);
+int fgc_bilateral_filter(const float* centres, const float* normals, const float* areas, int32_t n,
+                         const int32_t* cell_order, const int32_t* cell_ptr, int32_t sx, int32_t sy, int32_t sz,
+                         const float* sigma_s, int32_t S, const float* sigma_r, int32_t R, float* out, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Checkpoint files (CPU; HOST pointers)
