@@ -1,0 +1,63 @@
+// Per-vertex noise draw of fgc_synth_noise (include/fgc.h): Philox4x32-10, Box-Muller, displacement.  Device code; the
+// published known answers of the generator are checked ON the device through fgc_philox_words (tests/test_gpu_synth.py).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#define FGC_HD __device__ __forceinline__
+
+namespace fgc {
+
+FGC_HD uint32_t mulhi32(uint32_t a, uint32_t b) { return (uint32_t)(((uint64_t)a * (uint64_t)b) >> 32); }
+
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds, the key bumped between rounds.  c: counter in, random words out.
+FGC_HD void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
+    for (int r = 0; r < 10; ++r) {
+        const uint32_t hi0 = mulhi32(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const uint32_t hi1 = mulhi32(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const uint32_t n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0;
+        c[1] = lo1;
+        c[2] = n2;
+        c[3] = lo0;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+}
+
+// Two standard normals of two random words.  u = (n + 0.5) 2^-24 with n = x >> 8 lies strictly between 0 and 1 but needs 25
+// bits: it is exact in fp32 only for n < 2^23.  In the upper half 1 - u = ((2^24 - 1 - n) + 0.5) 2^-24 is exact instead, so
+// ln u is taken as log1p(-(1 - u)) and the angle 2 pi u as -2 pi (1 - u): a u next to 1 (where a rounded u would lose all of
+// r = sqrt(-2 ln u)) keeps fp32 relative accuracy.  The angle is never formed: sin / cos of pi (2 w) come from sinpif /
+// cospif on the exact 2 w, so a cosine next to 0 keeps its RELATIVE accuracy too - with the angle rounded to fp32 (2e-7
+// absolute) a draw whose direction (z0, z1, z2) is short turns by 2e-7 r1 / |z|: 1e-5 and more for |z| < 0.05.
+FGC_HD float philox_half(uint32_t n, bool upper) { return ((float)(upper ? 0xFFFFFFu - n : n) + 0.5f) * 0x1p-24f; }
+
+FGC_HD void box_muller(uint32_t x0, uint32_t x1, float* z0, float* z1) {
+    const uint32_t n0 = x0 >> 8, n1 = x1 >> 8;
+    const bool up0 = n0 >= (1u << 23), up1 = n1 >= (1u << 23);
+    const float w0 = philox_half(n0, up0);
+    const float r = sqrtf(-2.0f * (up0 ? log1pf(-w0) : logf(w0)));
+    const float t = 2.0f * philox_half(n1, up1);
+    const float s = sinpif(t);
+    *z0 = r * cospif(t);
+    *z1 = r * (up1 ? -s : s);
+}
+
+// The displaced vertex i: along nrm[0..2] (along_normal), otherwise along the random unit vector (z0, z1, z2) / |.|;
+// the length is sigma z3.  sigma == 0 returns the vertex itself, bit for bit (also a -0.0 coordinate).
+FGC_HD void synth_displace(uint32_t i, uint32_t step_lo, uint32_t step_hi, uint32_t stream_id, uint32_t seed_lo,
+                           uint32_t seed_hi, float sigma, const float v[3], bool along_normal, const float nrm[3],
+                           float out[3]) {
+    uint32_t c[4] = {i, step_lo, step_hi, stream_id};
+    philox4x32_10(c, seed_lo, seed_hi);
+    float z0, z1, z2, z3;
+    box_muller(c[0], c[1], &z0, &z1);
+    box_muller(c[2], c[3], &z2, &z3);
+    const float inv = 1.0f / sqrtf(z0 * z0 + z1 * z1 + z2 * z2);
+    const float d[3] = {along_normal ? nrm[0] : z0 * inv, along_normal ? nrm[1] : z1 * inv, along_normal ? nrm[2] : z2 * inv};
+    const float len = sigma * z3;
+    for (int t = 0; t < 3; ++t) out[t] = sigma == 0.0f ? v[t] : v[t] + d[t] * len;
+}
+
+}  // namespace fgc

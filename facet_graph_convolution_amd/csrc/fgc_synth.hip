@@ -1,0 +1,242 @@
+// Noise synthesis for training from clean meshes (build extension; include/fgc.h: fgc_synth_noise,
+// fgc_face_features_rows): per step, every vertex of a clean mesh is displaced by a counter-based Gaussian draw and the
+// six input channels of every node row are rebuilt from the displaced vertices, bit for bit as the host routine
+// fgc_face_features computes them.  Plain bandwidth work: one thread per vertex, one thread per node row.
+//
+// The features must carry the host routine's roundings: no fused multiply-add anywhere in this file.
+#include <algorithm>
+
+#include "fgc_common.h"
+#include "fgc_synth.h"
+#pragma clang fp contract(off)      // (and -ffp-contract=off for the file: Makefile)
+
+namespace fgc {
+
+constexpr int SY_THREADS = 256;
+constexpr int SY_MAX_BLOCKS = 1024;      // vertex blocks of a launch = bounding-box partials the feature kernel re-reduces
+
+static inline int synth_blocks(int nv) { return std::min(cdiv(nv, SY_THREADS), SY_MAX_BLOCKS); }
+
+// min over mn[0..2] / max over mx[0..2] of the workgroup's threads; the result in every thread.  min / max are exact:
+// the order of the reduction is free.
+__device__ __forceinline__ void block_minmax(float mn[3], float mx[3], float (*red)[6]) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            mn[t] = fminf(mn[t], __shfl_xor(mn[t], off, 64));
+            mx[t] = fmaxf(mx[t], __shfl_xor(mx[t], off, 64));
+        }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            red[wave][t] = mn[t];
+            red[wave][3 + t] = mx[t];
+        }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        mn[t] = red[0][t];
+        mx[t] = red[0][3 + t];
+#pragma unroll
+        for (int w = 1; w < SY_THREADS / 64; ++w) {
+            mn[t] = fminf(mn[t], red[w][t]);
+            mx[t] = fmaxf(mx[t], red[w][3 + t]);
+        }
+    }
+}
+
+__device__ __forceinline__ void store_box(float* __restrict__ dst, const float mn[3], const float mx[3]) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {      // (constant indices: the arrays stay in registers)
+        dst[t] = mn[t];
+        dst[3 + t] = mx[t];
+    }
+}
+
+// One thread per vertex (grid-stride above SY_MAX_BLOCKS workgroups): v_out = v + direction * sigma z3, and the
+// workgroup's bounding box of v_out into partials[6 * blockIdx.x ..] = {min xyz, max xyz}.
+// ctl (device): {step low, step high, sigma word}; sigma word 0 = off (nothing is read or written), otherwise bit 31 is
+// the on flag and the low 31 bits are the float bits of sigma >= 0.  vn == nullptr: random direction.
+__global__ __launch_bounds__(SY_THREADS) void synth_noise_kernel(const float* __restrict__ v, const float* __restrict__ vn,
+                                                                 int nv, const uint32_t* __restrict__ ctl, uint32_t seed_lo,
+                                                                 uint32_t seed_hi, uint32_t stream_id,
+                                                                 float* __restrict__ v_out, float* __restrict__ partials) {
+    __shared__ float red[SY_THREADS / 64][6];
+    const uint32_t word = ctl[2];
+    if (word == 0) return;      // (uniform over the launch)
+    const float sigma = __uint_as_float(word & 0x7FFFFFFFu);
+    const uint32_t step_lo = ctl[0], step_hi = ctl[1];
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = blockIdx.x * SY_THREADS + threadIdx.x; i < nv; i += gridDim.x * SY_THREADS) {
+        const size_t o = 3 * (size_t)i;
+        const float p[3] = {v[o], v[o + 1], v[o + 2]};
+        float nrm[3] = {0.f, 0.f, 0.f};
+        if (vn) {
+            nrm[0] = vn[o];
+            nrm[1] = vn[o + 1];
+            nrm[2] = vn[o + 2];
+        }
+        float q[3];
+        synth_displace((uint32_t)i, step_lo, step_hi, stream_id, seed_lo, seed_hi, sigma, p, vn != nullptr, nrm, q);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            v_out[o + t] = q[t];
+            mn[t] = fminf(mn[t], q[t]);
+            mx[t] = fmaxf(mx[t], q[t]);
+        }
+    }
+    block_minmax(mn, mx, red);
+    if (threadIdx.x == 0) store_box(partials + 6 * (size_t)blockIdx.x, mn, mx);
+}
+
+// The raw generator, for the known-answer test: out[4 i ..] = Philox4x32-10 of counter (first + i, step, stream_id).
+__global__ __launch_bounds__(SY_THREADS) void philox_words_kernel(uint32_t first, int n, uint32_t step_lo, uint32_t step_hi,
+                                                                  uint32_t seed_lo, uint32_t seed_hi, uint32_t stream_id,
+                                                                  uint32_t* __restrict__ out) {
+    const int i = blockIdx.x * SY_THREADS + threadIdx.x;
+    if (i >= n) return;
+    uint32_t c[4] = {first + (uint32_t)i, step_lo, step_hi, stream_id};
+    philox4x32_10(c, seed_lo, seed_hi);
+    *reinterpret_cast<u32x4*>(out + 4 * (size_t)i) = u32x4{c[0], c[1], c[2], c[3]};
+}
+
+// The same partials of vertices as they are (fgc_face_features_rows on vertices no fgc_synth_noise has produced).
+__global__ __launch_bounds__(SY_THREADS) void synth_bbox_kernel(const float* __restrict__ v, int nv,
+                                                                const uint32_t* __restrict__ ctl,
+                                                                float* __restrict__ partials) {
+    __shared__ float red[SY_THREADS / 64][6];
+    if (ctl && ctl[2] == 0) return;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = blockIdx.x * SY_THREADS + threadIdx.x; i < nv; i += gridDim.x * SY_THREADS)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            const float q = v[3 * (size_t)i + t];
+            mn[t] = fminf(mn[t], q);
+            mx[t] = fmaxf(mx[t], q);
+        }
+    block_minmax(mn, mx, red);
+    if (threadIdx.x == 0) store_box(partials + 6 * (size_t)blockIdx.x, mn, mx);
+}
+
+// One thread per node row: x[i] = [unit normal | barycentre / bounding-box diagonal] of face faces_rows[i] on the
+// vertices v, in fgc_face_features's arithmetic (fgc_prep.hip).  Every workgroup first reduces the n_partials
+// bounding-box partials (at most SY_MAX_BLOCKS x 24 bytes, from the L2) to the diagonal: no launch of its own for that.
+// A row with a negative or out-of-range vertex id is a fake node: six zeros, nothing dereferenced.
+__global__ __launch_bounds__(SY_THREADS) void face_features_rows_kernel(const float* __restrict__ v, int nv,
+                                                                        const int32_t* __restrict__ faces, int n,
+                                                                        const uint32_t* __restrict__ ctl,
+                                                                        const float* __restrict__ partials, int n_partials,
+                                                                        float* __restrict__ x) {
+    __shared__ float red[SY_THREADS / 64][6];
+    if (ctl && ctl[2] == 0) return;
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int j = threadIdx.x; j < n_partials; j += SY_THREADS)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            mn[t] = fminf(mn[t], partials[6 * j + t]);
+            mx[t] = fmaxf(mx[t], partials[6 * j + 3 + t]);
+        }
+    block_minmax(mn, mx, red);
+    // the diagonal in double from the fp32 extents, then rounded to fp32 (utils.py:1271-1280 through numpy)
+    double diag2 = 0.0;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const double e = (double)(mx[t] - mn[t]);
+        diag2 += e * e;
+    }
+    const float diag = (float)sqrt(diag2);
+    const int i = blockIdx.x * SY_THREADS + threadIdx.x;
+    if (i >= n) return;
+    const int a = faces[3 * (size_t)i], b = faces[3 * (size_t)i + 1], c = faces[3 * (size_t)i + 2];
+    float row[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (a >= 0 && b >= 0 && c >= 0 && a < nv && b < nv && c < nv) {
+        const float* p0 = v + 3 * (size_t)a;
+        const float* p1 = v + 3 * (size_t)b;
+        const float* p2 = v + 3 * (size_t)c;
+        float q0[3], q1[3], q2[3], e1[3], e2[3];
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            q0[t] = p0[t];
+            q1[t] = p1[t];
+            q2[t] = p2[t];
+            e1[t] = q1[t] - q0[t];
+            e2[t] = q2[t] - q0[t];
+        }
+        // np.cross on float32: every multiply and subtract rounded on its own (contraction is off for this file)
+        float nr[3];
+        nr[0] = e1[1] * e2[2] - e1[2] * e2[1];
+        nr[1] = e1[2] * e2[0] - e1[0] * e2[2];
+        nr[2] = e1[0] * e2[1] - e1[1] * e2[0];
+#pragma unroll
+        for (int it = 0; it < 2; ++it) {      // utils.normalize = normalizeOnce twice, eps 1e-8 added to the norm
+            const float ss = (nr[0] * nr[0] + nr[1] * nr[1]) + nr[2] * nr[2];
+            const float inv = 1.0f / (sqrtf(ss) + 0.00000001f);
+#pragma unroll
+            for (int t = 0; t < 3; ++t) nr[t] = nr[t] * inv;
+        }
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            row[t] = nr[t];
+            row[3 + t] = ((q0[t] / diag + q1[t] / diag) + q2[t] / diag) / 3.0f;
+        }
+    }
+    f32x2c* dst = reinterpret_cast<f32x2c*>(x + 6 * (size_t)i);      // (24-byte rows: 8-byte aligned)
+    dst[0] = f32x2c{row[0], row[1]};
+    dst[1] = f32x2c{row[2], row[3]};
+    dst[2] = f32x2c{row[4], row[5]};
+}
+
+}  // namespace fgc
+
+using namespace fgc;
+
+extern "C" size_t fgc_synth_scratch_floats(int32_t nv) {
+    if (nv <= 0) return 0;
+    return 6 * (size_t)synth_blocks(nv);
+}
+
+extern "C" int fgc_synth_noise(const float* v, const float* vnormals, int32_t nv, const uint32_t* ctl, uint64_t seed,
+                               uint32_t stream_id, float* v_out, float* scratch, size_t scratch_floats, void* stream) {
+    FGC_CHECK_ARG(v && ctl && v_out && scratch, "fgc_synth_noise: null pointer");
+    FGC_CHECK_ARG(nv > 0, "fgc_synth_noise: nv=%d (> 0)", nv);
+    FGC_CHECK_ARG(v_out != v, "fgc_synth_noise: v_out and v must be distinct (the clean vertices are kept)");
+    const size_t need = fgc_synth_scratch_floats(nv);
+    FGC_CHECK_ARG(scratch_floats >= need, "fgc_synth_noise: scratch too small (%zu < %zu floats)", scratch_floats, need);
+    hipStream_t st = (hipStream_t)stream;
+    FGC_LAUNCH("synth_noise_kernel", st, synth_noise_kernel, dim3(synth_blocks(nv)), dim3(SY_THREADS), 0, v, vnormals, nv,
+               ctl, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), stream_id, v_out, scratch);
+    FGC_CHECK_LAUNCH("fgc_synth_noise");
+    return FGC_OK;
+}
+
+extern "C" int fgc_philox_words(uint32_t first, int32_t n, uint64_t step, uint64_t seed, uint32_t stream_id, uint32_t* out,
+                                void* stream) {
+    FGC_CHECK_ARG(out && n > 0, "fgc_philox_words: out=%p, n=%d", (void*)out, n);
+    FGC_CHECK_ARG(((uintptr_t)out & 15) == 0, "fgc_philox_words: out must be 16-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    FGC_LAUNCH("philox_words_kernel", st, philox_words_kernel, dim3(cdiv(n, SY_THREADS)), dim3(SY_THREADS), 0, first, n,
+               (uint32_t)(step & 0xFFFFFFFFu), (uint32_t)(step >> 32), (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32),
+               stream_id, out);
+    FGC_CHECK_LAUNCH("fgc_philox_words");
+    return FGC_OK;
+}
+
+extern "C" int fgc_face_features_rows(const float* v, int32_t nv, const int32_t* faces_rows, int32_t n, const uint32_t* ctl,
+                                      int32_t have_bbox, float* x, float* scratch, size_t scratch_floats, void* stream) {
+    FGC_CHECK_ARG(v && faces_rows && x && scratch, "fgc_face_features_rows: null pointer");
+    FGC_CHECK_ARG(nv > 0 && n > 0, "fgc_face_features_rows: nv=%d, n=%d (> 0)", nv, n);
+    FGC_CHECK_ARG(((uintptr_t)x & 7) == 0, "fgc_face_features_rows: x must be 8-byte aligned");
+    const size_t need = fgc_synth_scratch_floats(nv);
+    FGC_CHECK_ARG(scratch_floats >= need, "fgc_face_features_rows: scratch too small (%zu < %zu floats)", scratch_floats,
+                  need);
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = synth_blocks(nv);
+    if (!have_bbox)
+        FGC_LAUNCH("synth_bbox_kernel", st, synth_bbox_kernel, dim3(nblk), dim3(SY_THREADS), 0, v, nv, ctl, scratch);
+    FGC_LAUNCH("face_features_rows_kernel", st, face_features_rows_kernel, dim3(cdiv(n, SY_THREADS)), dim3(SY_THREADS), 0,
+               v, nv, faces_rows, n, ctl, (const float*)scratch, nblk, x);
+    FGC_CHECK_LAUNCH("fgc_face_features_rows");
+    return FGC_OK;
+}

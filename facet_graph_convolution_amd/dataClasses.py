@@ -209,6 +209,42 @@ class TrainingSet(PreprocessedData):
             seed = None
         self.addMesh_TimeEfficient(V_noisy, faces, GTV=V_gt, seed=seed, parents=parents)
 
+    def addCleanMesh(self, V, faces, seed=None, parents=None):
+        """Build extension (no counterpart in the reference): a CLEAN mesh for training on noise synthesised per step on the
+        GPU (FacetDenoiser.bind_clean).  Arrays addCleanMesh(V, faces) or the file form addCleanMesh(path, filename).
+        Everything addMeshWithGT(V, faces, V) does - the mesh's own rows in in_list, its normals in gt_list - plus, per
+        mesh, clean_vertices (float32 [1, V, 3]), clean_faces_rows (int32 [1, N0, 3]: the faces padded with -1 rows for
+        the fake nodes and reordered like the nodes, as addMeshWithVertices builds faces_list) and clean_edge_len (the
+        mean edge length, utils.getAverageEdgeLength: a noise level is a multiple of it).
+        The graph levels are built from the CLEAN mesh.  The reference coarsens the noisy one; its edge weights are
+        almost always the floor value, so the pairing is decided by the random visiting order
+        and the clean mesh's levels are another valid draw of the same procedure.
+        A mesh above maxSize faces (patch mode) is refused: patches are not synthesised."""
+        if isinstance(V, str):
+            V, _, _, faces, _ = utils.load_mesh(V, faces, 0, False)
+            seed = parents = None
+        V = np.ascontiguousarray(np.asarray(V, dtype=np.float32))
+        faces = np.asarray(faces)
+        if faces.shape[0] > self.maxSize:
+            raise NotImplementedError("addCleanMesh keeps a mesh whole: %d faces > maxSize %d (patch mode)"
+                                      % (faces.shape[0], self.maxSize))
+        first = len(self.in_list)
+        self.addMesh_TimeEfficient(V, faces, GTV=V, seed=seed, parents=parents)
+        oldToNew = self.permutations[first]
+        new_N = len(oldToNew)
+        newToOld = np.empty(new_N, dtype=np.int64)
+        newToOld[oldToNew] = np.arange(new_N)
+        faces_p = np.concatenate((faces.astype(np.int64), -np.ones((new_N - faces.shape[0], 3), dtype=np.int64)),
+                                 axis=0)[newToOld]
+        for name, value in (("clean_vertices", V[np.newaxis]), ("clean_faces_rows", faces_p.astype(np.int32)[np.newaxis]),
+                            ("clean_edge_len", float(utils.getAverageEdgeLength(V, faces)[0]))):
+            self.__dict__.setdefault(name, []).append(value)
+
+    def is_clean(self):
+        """Every mesh of the set came through addCleanMesh (what trainNet(noise_levels=...) needs)."""
+        n = len(self.in_list)
+        return n > 0 and all(len(self.__dict__.get(k, ())) == n for k in ("clean_vertices", "clean_faces_rows",
+                                                                            "clean_edge_len"))
 
     def addMeshWithVerticesAndGT(self, V_noisy, faces, V_gt, gtfilename=None, seed=None, parents=None):
         """dataClasses.py:497-506: addMeshWithVertices with the ground-truth vertices (gtv_list), for trainAccuracyNet.

@@ -561,8 +561,9 @@ class FacetDenoiser:
 
     def _alloc_step_inputs(self, B, ns):
         """The per-step inputs - sample indices (train.py:561) and the rotation (train.py:563-565) - live in ONE device
-        buffer [ns ints | 9 floats | pad]: a step refreshes them with a single device-to-device copy
-        (set_step_inputs_packed)."""
+        buffer [ns ints | 9 floats | 3 noise words]: a step refreshes them with a single device-to-device copy
+        (set_step_inputs_packed).  The noise words (build extension, bind_clean / set_noise: step low, step high, sigma
+        word of fgc_synth_noise) are zero - synthesis off - unless set_noise or a packed row fills them."""
         B["step_in"] = B["step_in_own"] = torch.zeros(ns + 12, dtype=torch.int32, device=self.device)
         B["loss_scratch"] = torch.zeros(self.L.fgc_loss_step_scratch_floats(ns), dtype=torch.float32, device=self.device)
         # facet-sharded steps: [0] the all-reduced sum of |y|, [4:] the all-reduced per-256-samples partial table
@@ -576,6 +577,7 @@ class FacetDenoiser:
         B["step_in"] = row
         B["sample_ind"] = row[:ns]
         B["R"] = row[ns:ns + 9].view(torch.float32)
+        B["noise"] = row[ns + 9:ns + 12]
 
     def _own_step_inputs(self):
         """The step inputs back in the network's own buffer (set_step_inputs_packed may have let the steps read a caller's
@@ -605,6 +607,73 @@ class FacetDenoiser:
         without re-uploading, re-allocating or re-capturing anything.  States are kept while they fit in max_bytes."""
         self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt), max_bytes)
         return self
+
+    # ------------------------------------------------------------------------------------------
+    # training from clean meshes (BUILD EXTENSION, DESIGN.md section 8d): per-step noise synthesis on the GPU
+    # ------------------------------------------------------------------------------------------
+    def bind_clean(self, key, x, adjs, gt, verts, faces_rows, edge_len, seed=0, stream=0, direction="random"):
+        """Build extension: bind a CLEAN mesh whose input rows every step rebuilds from freshly displaced vertices
+        (include/fgc.h: fgc_synth_noise, fgc_face_features_rows).  bind_cached(key, x, adjs, gt=gt) plus a synthesis
+        state kept with the mesh: the clean vertices verts [V,3], faces_rows int [N0,3] (the faces in node order, -1 rows
+        = fake nodes: TrainingSet.addCleanMesh's clean_faces_rows), the mean edge length edge_len (a noise level is a
+        multiple of it), the Philox key `seed` and `stream` id (training 0, validation mesh i 1 + i) and the
+        direction - "random", or "normal": along the clean mesh's area-weighted vertex normals.  x: the clean mesh's own
+        rows (what the steps read until set_noise switches the synthesis on); gt: the clean normals.  Unsharded only."""
+        if self.comm is not None or (self._mesh is not None and self.sharded):
+            raise NotImplementedError("noise synthesis runs on an unsharded network")
+        M = self._mesh_cache.get(key)
+        if M is not None and "synth" in M:
+            # (a training loop rebinds its meshes every iteration: a cached mesh costs this lookup, as in bind_cached)
+            if (M["synth"]["seed"], M["synth"]["stream"], M["synth"]["direction"]) != (int(seed), int(stream), direction):
+                raise ValueError("mesh %r is bound with another seed / stream / direction" % (key,))
+            self._mesh = M
+            return self
+        if direction not in ("random", "normal"):
+            raise ValueError("direction must be 'random' or 'normal'")
+        vx = np.ascontiguousarray(np.asarray(verts, dtype=np.float32).reshape(-1, 3))
+        fr = np.ascontiguousarray(np.asarray(faces_rows).reshape(-1, 3).astype(np.int32))
+        xa = np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)
+        n0 = xa.size // xa.shape[-1]
+        if fr.shape[0] != n0:
+            raise ValueError("faces_rows has %d rows, the graph %d nodes" % (fr.shape[0], n0))
+        if fr.max() >= vx.shape[0]:
+            raise ValueError("faces_rows names vertex %d of %d" % (fr.max(), vx.shape[0]))
+        if not (np.isfinite(edge_len) and edge_len > 0):
+            raise ValueError("edge_len must be a positive length")
+        M = self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt))
+        dev = self.device
+        S = dict(v=torch.as_tensor(vx, device=dev), faces=torch.as_tensor(fr, device=dev), vn=None,
+                 edge_len=float(edge_len), seed=int(seed), stream=int(stream), direction=direction)
+        if direction == "normal":
+            from .utils import areaWeightedVertexNormals
+            S["vn"] = torch.as_tensor(areaWeightedVertexNormals(vx, fr[fr[:, 0] >= 0]).astype(np.float32), device=dev)
+        S["v_out"] = S["v"].clone()
+        S["scratch"] = torch.zeros(max(self.L.fgc_synth_scratch_floats(vx.shape[0]), 1), dtype=torch.float32, device=dev)
+        M["synth"] = S
+        # (a step captured while the mesh was bound by bind_cached under this key has no synthesis nodes: record it again)
+        M["captured"].clear()
+        return self
+
+    def _require_synth(self):
+        if "synth" not in (self._mesh or {}):
+            raise RuntimeError("bind_clean(...) is required for noise synthesis")
+        return self._mesh["synth"]
+
+    def _enqueue_synth(self):
+        """Two launches: noise (+ per-workgroup bounding boxes), then the input rows (each workgroup reduces the boxes).
+        Both read the step's noise words from device memory and return at once while they are zero."""
+        M, L, st = self._mesh, self.L, self._st()
+        B, S = M["B"], M["synth"]
+        self._tag("fwd:synth")
+        nv, sc = S["v"].shape[0], S["scratch"]
+        _lib.check(L.fgc_synth_noise(_p(S["v"]), _p(S["vn"]), nv, _p(B["noise"]), S["seed"] & 0xFFFFFFFFFFFFFFFF,
+                                     S["stream"] & 0xFFFFFFFF, _p(S["v_out"]), _p(sc), sc.numel(), st), "synth noise")
+        _lib.check(L.fgc_face_features_rows(_p(S["v_out"]), nv, _p(S["faces"]), M["ns"][0], _p(B["noise"]), 1, _p(B["x"]),
+                                            _p(sc), sc.numel(), st), "synth features")
+
+    def noisy_vertices(self):
+        """The displaced vertices [V,3] of the last step that synthesised noise (device tensor, overwritten by the next)."""
+        return self._require_synth()["v_out"]
 
     # ------------------------------------------------------------------------------------------
     # enqueue helpers (no allocation, no sync).  The schedules are GENERATORS: they yield an exchange request
@@ -691,6 +760,10 @@ class FacetDenoiser:
         prologue = self.batched and self.step_prologue
         mlp_packed = _lib.MLP_PACKED if (prologue and not self.multi_scale) else 0
         M["mlp_packed"] = mlp_packed
+        if "synth" in M:
+            # a clean mesh (bind_clean): this step's noisy vertices and input rows, in front of everything that reads x;
+            # inside a captured step these launches are nodes of its graph
+            self._enqueue_synth()
         self._tag("fwd:input")
         if rotate and not prologue:
             _lib.check(L.fgc_rotate_rows(_p(B["x"]), _p(B["xr"]), rows0, self.in_channels // 3, _p(B["R"]), st),
@@ -1232,15 +1305,26 @@ class FacetDenoiser:
         self._own_step_inputs()
         self._upload(self._mesh["B"]["R"], np.asarray(R, dtype=np.float32).reshape(9))
 
+    def set_noise(self, step, level):
+        """Build extension (bind_clean): the next steps draw the noise of counter `step` (64-bit) at `level` x the bound
+        clean mesh's mean edge length; level 0 rebuilds the clean input, level None switches the synthesis off (the
+        steps read x as the last synthesis left it).  Filled the way set_rotation fills R; the kernels read the words
+        from device memory, so a captured step replays with the new values."""
+        S = self._require_synth()
+        self._own_step_inputs()
+        words = ops.noise_words(step, None if level is None else np.float32(level) * np.float32(S["edge_len"]))
+        self._upload(self._mesh["B"]["noise"], words.view(np.int32))
+
     def set_samples(self, sample_ind):
         """Indices of the rows the loss is evaluated on (train.py:561), any of the N0 padded rows."""
         t = np.asarray(sample_ind).astype(np.int32)
         self._own_step_inputs()
         B = self._mesh["B"]
         if t.size != B["sample_ind"].numel():
-            R = B["R"].clone()
+            R, noise = B["R"].clone(), B["noise"].clone()
             self._alloc_step_inputs(B, t.size)
             B["R"].copy_(R)
+            B["noise"].copy_(noise)
             self._mesh["captured"].clear()     # (every captured step of the mesh holds the old buffer's address)
         self._upload(B["sample_ind"], t)
         if self.sharded:
@@ -1255,7 +1339,8 @@ class FacetDenoiser:
         """Per-step inputs that are ALREADY on the device (e.g. a window of steps uploaded in one go): device-to-device
         copies are kernels on the compute queue, ordered with hipGraph replays; host -> device DMAs between replays of a
         captured graph were observed to race on this stack when many steps are queued.  sample_local_dev: a facet-sharded
-        rank's own part of the samples (local_samples_device), used in place as this step's list."""
+        rank's own part of the samples (local_samples_device), used in place as this step's list.  The noise words of a
+        clean mesh (bind_clean) are not part of this call: the last set_noise, or the last packed row, still holds."""
         self._own_step_inputs()
         B = self._mesh["B"]
         B["sample_ind"].copy_(sample_ind_dev)
@@ -1266,14 +1351,22 @@ class FacetDenoiser:
             B["sample_ind_local"] = sample_local_dev
 
     @staticmethod
-    def pack_step_inputs(sample_inds, rotations, device):
+    def pack_step_inputs(sample_inds, rotations, device, noise=None):
         """[steps, ns + 12] int32 on the device: row k = the samples and the rotation (bit pattern of 9 floats) of step k,
-        in the layout of the network's step-input buffer."""
+        in the layout of the network's step-input buffer.  noise (build extension, bind_clean): one (step, sigma) pair per
+        row - the noise counter and the ABSOLUTE standard deviation (level x the mesh's mean edge length) - or None per
+        row / for all rows: the three noise words stay zero, synthesis off."""
         S = np.stack([np.asarray(s).astype(np.int32) for s in sample_inds])
         R = np.stack([np.asarray(r, dtype=np.float32).reshape(9) for r in rotations]).view(np.int32)
         out = np.zeros((S.shape[0], S.shape[1] + 12), dtype=np.int32)
         out[:, :S.shape[1]] = S
         out[:, S.shape[1]:S.shape[1] + 9] = R
+        if noise is not None:
+            if len(noise) != S.shape[0]:
+                raise ValueError("one (step, sigma) pair (or None) per row")
+            for k, pair in enumerate(noise):
+                if pair is not None:
+                    out[k, S.shape[1] + 9:] = ops.noise_words(pair[0], pair[1]).view(np.int32)
         return torch.from_numpy(out).to(device)
 
     def set_step_inputs_packed(self, packed_row, sample_local_dev=None, in_place=False):
@@ -1655,8 +1748,9 @@ class FacetDenoiser:
         _lib.check(self.L.fgc_adam_step(_p(P.theta), _p(P.grad), _p(P.m), _p(P.v), P.total, P.step, lr, b1, b2, eps,
                                         self._st()), "adam")
 
-    def train_step(self, sample_ind=None, R=None, capture=False):
-        """One iteration of trainNet's loop body (train.py:558-575,619): returns the loss tensor (device, [2])."""
+    def train_step(self, sample_ind=None, R=None, capture=False, noise=None):
+        """One iteration of trainNet's loop body (train.py:558-575,619): returns the loss tensor (device, [2]).
+        noise = (step, level) (build extension, a mesh bound by bind_clean): set_noise(step, level) first."""
         n0 = self._mesh["ns"][0]
         if sample_ind is None:
             sample_ind = np.random.randint(n0, size=COST_SAMPLES)
@@ -1665,6 +1759,8 @@ class FacetDenoiser:
             R = rand_rotation_matrix()
         self.set_samples(sample_ind)
         self.set_rotation(R)
+        if noise is not None:
+            self.set_noise(*noise)
         loss = self.forward_backward(rotate=True, capture=capture)
         self.adam_step()
         return loss

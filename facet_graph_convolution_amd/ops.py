@@ -624,3 +624,76 @@ def dense_normals_loss(fn, gt, R=None, g=None, dloss=1.0, want_grad=True):
     check(L.fgc_dense_normals_loss_bwd(ptr(fn), ptr(gt), ptr(R), n, ptr(scr), nsc, float(dloss), ptr(g), stream_ptr()),
           "fgc_dense_normals_loss_bwd")
     return loss, g
+
+
+def noise_words(step, sigma):
+    """The three control words of the noise synthesis (include/fgc.h: fgc_synth_noise) as uint32 numpy: step low, step
+    high, FGC_SYNTH_ON | float bits of sigma.  sigma None: three zeros, synthesis off."""
+    if sigma is None:
+        return np.zeros(3, dtype=np.uint32)
+    sigma = np.float32(sigma)
+    if not np.isfinite(sigma) or sigma < 0:
+        raise ValueError("sigma must be finite and >= 0 (got %r)" % (sigma,))
+    step = int(step)
+    if not 0 <= step < 1 << 64:
+        raise ValueError("step must fit 64 bits")
+    bits = int(np.array([sigma], dtype=np.float32).view(np.uint32)[0]) & 0x7FFFFFFF      # (-0.0 -> 0.0)
+    return np.array([step & 0xFFFFFFFF, step >> 32, bits | _lib.SYNTH_ON], dtype=np.uint32)
+
+
+def synth_noise(verts, sigma, step, seed=0, stream=0, normals=None, out=None, scratch=None, ctl=None):
+    """Build extension (include/fgc.h: fgc_synth_noise): the vertices verts [V,3] displaced by Philox4x32-10 Gaussian noise
+    of standard deviation sigma - along a random direction, or along `normals` [V,3] (unit vertex normals) - for the
+    64-bit counter `step`, the 64-bit `seed` and the 32-bit `stream` id.  Returns the displaced vertices [V,3] (`out`).
+    ctl: the control words already on the device (int32 [3]) instead of (step, sigma); scratch: float32, at least
+    fgc_synth_scratch_floats(V) - it receives the bounding-box partials face_features_rows(have_bbox=True) reads."""
+    _req_cuda(verts, normals, out, scratch, ctl)
+    verts = _f32c(verts.reshape(-1, 3))
+    nv = verts.shape[0]
+    if normals is not None:
+        normals = _f32c(normals.reshape(-1, 3))
+        if normals.shape[0] != nv:
+            raise ValueError("one normal per vertex")
+    if ctl is None:
+        ctl = torch.from_numpy(noise_words(step, sigma).view(np.int32)).to(verts.device)
+    if out is None:
+        out = torch.empty_like(verts)
+    need = _lib.lib().fgc_synth_scratch_floats(nv)
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=verts.device)
+    check(_lib.lib().fgc_synth_noise(ptr(verts), ptr(normals), nv, ptr(ctl), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                     int(stream) & 0xFFFFFFFF, ptr(out), ptr(scratch), scratch.numel(), stream_ptr()),
+          "fgc_synth_noise")
+    return out
+
+
+def philox_words(first, n, step, seed=0, stream=0, device="cuda"):
+    """The raw Philox4x32-10 words of synth_noise (include/fgc.h: fgc_philox_words): int32 [n,4] on the device (view as
+    uint32), row i for the counter (first + i, step low, step high, stream) and the key seed."""
+    out = torch.empty(int(n), 4, dtype=torch.int32, device=device)
+    _req_cuda(out)
+    check(_lib.lib().fgc_philox_words(int(first) & 0xFFFFFFFF, int(n), int(step) & 0xFFFFFFFFFFFFFFFF,
+                                      int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, ptr(out), stream_ptr()),
+          "fgc_philox_words")
+    return out
+
+
+def face_features_rows(verts, faces_rows, out=None, scratch=None, have_bbox=False, ctl=None):
+    """Build extension (include/fgc.h: fgc_face_features_rows): the network's six input channels [N,6] - unit normal |
+    barycentre / bounding-box diagonal - of the faces faces_rows int32 [N,3] (-1 rows = fake nodes: zero rows) on the
+    vertices verts [V,3], bit-identical to utils.face_features.  have_bbox: `scratch` holds the bounding-box partials
+    synth_noise has just left for these vertices."""
+    _req_cuda(verts, faces_rows, out, scratch, ctl)
+    verts = _f32c(verts.reshape(-1, 3))
+    faces_rows = faces_rows.reshape(-1, 3).to(torch.int32).contiguous()
+    nv, n = verts.shape[0], faces_rows.shape[0]
+    if out is None:
+        out = torch.empty(n, 6, dtype=torch.float32, device=verts.device)
+    need = _lib.lib().fgc_synth_scratch_floats(nv)
+    if scratch is None:
+        if have_bbox:
+            raise ValueError("have_bbox needs the scratch synth_noise filled")
+        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=verts.device)
+    check(_lib.lib().fgc_face_features_rows(ptr(verts), nv, ptr(faces_rows), n, ptr(ctl), 1 if have_bbox else 0, ptr(out),
+                                            ptr(scratch), scratch.numel(), stream_ptr()), "fgc_face_features_rows")
+    return out

@@ -9,6 +9,13 @@ uses this as data augmentation, settings.py:24) and pickled as `trainingSet.pkl`
 (the reference's INCLUDE_VERTICES) every mesh also keeps its vertices, faces in node order, vertex-face slots and
 ground-truth vertices (addMeshWithVerticesAndGT) for trainAccuracyNet, pickled as `trainingSetWithVertices.pkl` /
 `validSetWithVertices.pkl`.
+
+Build extension - training from clean meshes, the noise synthesised per step on the GPU (train --synth-noise):
+
+    python -m facet_graph_convolution_amd.preprocess CLEAN_DIR DUMP_DIR --clean [--valid CLEAN_VALID_DIR] [--redundancy R]
+
+takes every OBJ of CLEAN_DIR as its own ground truth (TrainingSet.addCleanMesh) and writes `trainingSetClean.pkl` /
+`validSetClean.pkl`.
 """
 import argparse
 import os
@@ -51,17 +58,53 @@ def pickleData(training_dir, gt_dir, dump_dir, valid_dir=None, redundancy=1, gt_
     return out
 
 
+def pickleCleanData(clean_dir, dump_dir, valid_dir=None, redundancy=1, log=print):
+    """Build extension: `trainingSetClean.pkl` / `validSetClean.pkl` from folders of CLEAN OBJ files
+    (TrainingSet.addCleanMesh), `redundancy` coarsenings per training mesh."""
+    os.makedirs(dump_dir, exist_ok=True)
+    out = {}
+    for tag, folder, rep in (("trainingSetClean.pkl", clean_dir, redundancy), ("validSetClean.pkl", valid_dir, 1)):
+        if not folder or not os.path.isdir(folder):
+            continue
+        ds = TrainingSet()
+        for f in sorted(os.listdir(folder)):
+            if not f.endswith(".obj"):
+                continue
+            log("Adding %s (%i)" % (f, ds.mesh_count))
+            for _ in range(rep):
+                ds.addCleanMesh(folder, f)
+        if ds.mesh_count:
+            with open(os.path.join(dump_dir, tag), "wb") as fp:
+                pickle.dump(ds, fp)
+            out[tag] = ds
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("training_dir")
-    ap.add_argument("gt_dir")
-    ap.add_argument("dump_dir")
+    ap.add_argument("training_dir", help="noisy training meshes (with --clean: the clean meshes)")
+    ap.add_argument("gt_dir", help="their ground truth (with --clean: the dump folder)")
+    ap.add_argument("dump_dir", nargs="?", default=None, help="where the pickles go (not with --clean)")
     ap.add_argument("--valid", default=None)
     ap.add_argument("--redundancy", type=int, default=1)
     ap.add_argument("--with-vertices", action="store_true", help="keep the vertex data trainAccuracyNet needs")
+    ap.add_argument("--clean", action="store_true",
+                    help="build extension: CLEAN_DIR DUMP_DIR - clean meshes for training on synthesised noise")
     args = ap.parse_args(argv)
-    pickleData(args.training_dir, args.gt_dir, args.dump_dir, args.valid, args.redundancy, withVerts=args.with_vertices)
-    print("Preprocessing complete. Dump files saved to " + args.dump_dir)
+    if args.clean:
+        if args.dump_dir is not None:
+            ap.error("--clean takes two folders: CLEAN_DIR DUMP_DIR (a clean mesh is its own ground truth)")
+        if args.with_vertices:
+            ap.error("--clean does not go with --with-vertices: point-set training on synthesised noise is not built")
+        dump = args.gt_dir
+        if not pickleCleanData(args.training_dir, dump, args.valid, args.redundancy):
+            ap.error("no OBJ file in %s" % args.training_dir)
+    else:
+        if args.dump_dir is None:
+            ap.error("three folders are needed: TRAINING_DIR GT_DIR DUMP_DIR (or CLEAN_DIR DUMP_DIR --clean)")
+        dump = args.dump_dir
+        pickleData(args.training_dir, args.gt_dir, dump, args.valid, args.redundancy, withVerts=args.with_vertices)
+    print("Preprocessing complete. Dump files saved to " + dump)
 
 
 if __name__ == "__main__":

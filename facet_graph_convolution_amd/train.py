@@ -12,9 +12,11 @@ Training command (the reference's ``train(withVerts)``, train.py:1894-1921):
 
     python -m facet_graph_convolution_amd.train DUMP_DIR NETWORK_DIR [--num-iterations N] [--net-name NAME]
         [--with-vertices] [--double-loss] [--capture] [--seed S]
+        [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal]
 
 loads the pickles `preprocess` wrote and runs trainNet, trainAccuracyNet (--with-vertices) or trainDoubleLossNet
-(--with-vertices --double-loss).
+(--with-vertices --double-loss).  --synth-noise (build extension) loads the CLEAN pickles of `preprocess --clean` and
+runs trainNet on noise synthesised per step on the GPU.
 """
 import argparse
 import os
@@ -106,14 +108,59 @@ def load_checkpoint(path, net):
     return int(ck["iteration"])
 
 
+DEFAULT_NOISE_LEVELS = (0.1, 0.2, 0.3)      # --synth-noise without a value: a choice of this build (README)
+
+
+def _clean_meshes(ds, what):
+    """The meshes of a clean TrainingSet (addCleanMesh): (x, adjs, gt, vertices, faces_rows, edge_len)."""
+    if not (hasattr(ds, "is_clean") and ds.is_clean()):
+        raise ValueError("noise_levels needs a %s of clean meshes (TrainingSet.addCleanMesh, preprocess --clean)" % what)
+    return [(ds.in_list[i], ds.adj_list[i], ds.gt_list[i], ds.clean_vertices[i], ds.clean_faces_rows[i],
+             ds.clean_edge_len[i]) for i in range(len(ds.in_list))]
+
+
+def synthValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random"):
+    """Build extension: the mean loss over every clean validation mesh (tuples of _clean_meshes) at every noise level,
+    with stream = 1 + mesh index and step = level index - the SAME noisy meshes at every call (they are also what
+    makeNoisy writes for the same seed), so the validation curve is comparable along a run.  R: the rotation; rs: the
+    RandomState the loss rows are drawn from."""
+    total = 0.0
+    for vbm, m in enumerate(valid):
+        net.bind_clean(("valid", vbm), *m, seed=seed, stream=1 + vbm, direction=direction)
+        for k, level in enumerate(noise_levels):
+            net.set_samples(rs.randint(np.asarray(m[0]).shape[1], size=COST_SAMPLES))
+            net.set_rotation(R)
+            net.set_noise(k, level)
+            total += net.eval_loss(rotate=True)[0].item()
+    return total / (len(valid) * len(noise_levels))
+
+
 def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
-             capture=False, validSet=None):
-    """train.py:380-632.  trainSet / validSet: dataClasses.TrainingSet.  Returns (net, lossArray [iters/50, 2])."""
-    meshes = []
-    for i in range(len(trainSet.in_list)):
-        net = None
-        meshes.append((trainSet.in_list[i], trainSet.adj_list[i], trainSet.gt_list[i]))
+             capture=False, validSet=None, noise_levels=None, noise_direction="random"):
+    """train.py:380-632.  trainSet / validSet: dataClasses.TrainingSet.  Returns (net, lossArray [iters/50, 2]).
+
+    noise_levels (build extension; None = the reference's loop, untouched): trainSet / validSet hold CLEAN meshes
+    (TrainingSet.addCleanMesh, otherwise ValueError) and every iteration trains on fresh Gaussian vertex noise made on
+    the GPU (FacetDenoiser.bind_clean): a level drawn from the list x the mesh's mean edge length, along
+    noise_direction ("random" / "normal"), with the global iteration as the noise counter - a resumed run goes on with
+    new noise.  Validation: synthValidationLoss."""
+    synth = noise_levels is not None
+    if synth:
+        noise_levels = tuple(float(l) for l in noise_levels)
+        if not noise_levels or not all(np.isfinite(l) and l >= 0 for l in noise_levels):
+            raise ValueError("noise_levels: a non-empty list of levels >= 0")
+        if noise_direction not in ("random", "normal"):
+            raise ValueError("noise_direction must be 'random' or 'normal'")
+        meshes = _clean_meshes(trainSet, "training set")
+    else:
+        meshes = [(trainSet.in_list[i], trainSet.adj_list[i], trainSet.gt_list[i]) for i in range(len(trainSet.in_list))]
     net = FacetDenoiser(device, seed=seed)
+
+    def bind(b):
+        if synth:
+            net.bind_clean(b, *meshes[b], seed=seed, stream=0, direction=noise_direction)
+        else:
+            net.bind_cached(b, *meshes[b][:2], gt=meshes[b][2])
     start = 0
     ckpt = os.path.join(network_path, net_name) if network_path else None
     if ckpt:
@@ -132,38 +179,44 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
     bound = -1
     train_loss, train_samp, hasNan = 0.0, 0, False
     valid, last_loss = [], 0.0
-    if validSet is not None:
+    if validSet is not None and synth:
+        valid = _clean_meshes(validSet, "validation set")
+    elif validSet is not None:
         valid = [(validSet.in_list[i], validSet.adj_list[i], validSet.gt_list[i]) for i in range(len(validSet.in_list))]
     for it in range(num_iterations):
         if ckpt and it % SAVEITER == 0 and it > 0:
             save_checkpoint(ckpt, net, start + it)
         b = rs.randint(len(meshes))
         if b != bound:       # the reference feeds a new patch through feed_dict; here every mesh stays bound in HBM
-            x, adjs, gt = meshes[b]
-            net.bind_cached(b, x, adjs, gt=gt)
+            bind(b)
             bound = b
         n0 = meshes[b][0].shape[1]
         samp_it = rs.randint(n0, size=COST_SAMPLES)
         R_it = rand_rotation_matrix(randnums=rs.uniform(size=3))
+        # (drawn in this mode only: the random stream of a plain run is what it was)
+        noise_it = (start + it, noise_levels[rs.randint(len(noise_levels))]) if synth else None
         if valid and it % (evalStepNum * 2) == 0:
             # train.py:588-617: every 100 iterations the loss alone on every validation mesh, with this iteration's
             # rotation and fresh random rows, BEFORE the training step; the previous row of the CSV gets the mean of
             # this and the last value
-            valid_loss = 0.0
-            for vbm, (vx, vadj, vgt) in enumerate(valid):
-                net.bind_cached(("valid", vbm), vx, vadj, gt=vgt)
-                net.set_samples(rs.randint(vx.shape[1], size=COST_SAMPLES))
-                net.set_rotation(R_it)
-                valid_loss += net.eval_loss(rotate=True)[0].item()
-            valid_loss /= len(valid)
+            if synth:
+                valid_loss = synthValidationLoss(net, valid, noise_levels, R_it, rs, seed, noise_direction)
+            else:
+                valid_loss = 0.0
+                for vbm, (vx, vadj, vgt) in enumerate(valid):
+                    net.bind_cached(("valid", vbm), vx, vadj, gt=vgt)
+                    net.set_samples(rs.randint(vx.shape[1], size=COST_SAMPLES))
+                    net.set_rotation(R_it)
+                    valid_loss += net.eval_loss(rotate=True)[0].item()
+                valid_loss /= len(valid)
             log("Iteration %d, validation loss %g" % (it, valid_loss))
             row = min(it // evalStepNum, len(lossArray) - 1)
             lossArray[row, 1] = valid_loss
             if it > 0:
                 lossArray[row - 1, 1] = (valid_loss + last_loss) / 2
                 last_loss = valid_loss
-            net.bind_cached(b, *meshes[b][:2], gt=meshes[b][2])
-        loss = net.train_step(sample_ind=samp_it, R=R_it, capture=capture)
+            bind(b)
+        loss = net.train_step(sample_ind=samp_it, R=R_it, capture=capture, noise=noise_it)
         if it % evalStepNum == 0 or it == num_iterations - 1:
             lv = loss[0].item()      # the only host sync of the loop
             if not np.isfinite(lv):  # NaN watchdog (train.py:620-623)
@@ -541,14 +594,34 @@ def main(argv=None):
                     help="with --with-vertices: the point-set loss plus the face-normal loss (trainDoubleLossNet)")
     ap.add_argument("--capture", action="store_true", help="replay every training step from a hipGraph")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--synth-noise", nargs="?", const=",".join(str(l) for l in DEFAULT_NOISE_LEVELS), default=None,
+                    metavar="LEVELS", help="build extension: train on the clean pickles of `preprocess --clean`, Gaussian "
+                    "vertex noise made on the GPU every step; LEVELS = comma-separated multiples of the mean edge length "
+                    "(default %(const)s; the value is optional, so write the option BEHIND the two folders or as --synth-noise=LEVELS)")
+    ap.add_argument("--noise-direction", choices=("random", "normal"), default="random",
+                    help="with --synth-noise: displace along a random direction or along the vertex normal")
     args = ap.parse_args(argv)
     if args.double_loss and not args.with_vertices:
         ap.error("--double-loss trains on the vertex data: it needs --with-vertices")
     if args.num_iterations < 0:
         ap.error("--num-iterations must be >= 0")
+    levels = None
+    if args.synth_noise is not None:
+        if args.with_vertices:
+            ap.error("--synth-noise does not go with --with-vertices: point-set training on synthesised noise is not built")
+        try:
+            levels = tuple(float(t) for t in args.synth_noise.split(","))
+        except ValueError:
+            ap.error("--synth-noise takes comma-separated numbers, e.g. 0.1,0.2,0.3 (got %r)" % args.synth_noise)
+        if not all(np.isfinite(l) and l >= 0 for l in levels):
+            ap.error("--synth-noise levels must be >= 0 (got %r)" % args.synth_noise)
     names = (("trainingSetWithVertices.pkl", "validSetWithVertices.pkl") if args.with_vertices
+             else ("trainingSetClean.pkl", "validSetClean.pkl") if levels is not None
              else ("trainingSet.pkl", "validSet.pkl"))
     ts_path, vs_path = (os.path.join(args.dump_dir, n) for n in names)
+    if not os.path.isfile(ts_path) and levels is not None:
+        ap.error("no clean training set at %s: run `python -m facet_graph_convolution_amd.preprocess CLEAN_DIR %s --clean` "
+                 "first" % (ts_path, args.dump_dir))
     if not os.path.isfile(ts_path):
         ap.error("no training set at %s: run `python -m facet_graph_convolution_amd.preprocess TRAINING_DIR GT_DIR %s%s` "
                  "first" % (ts_path, args.dump_dir, " --with-vertices" if args.with_vertices else ""))
@@ -560,8 +633,9 @@ def main(argv=None):
             valid_set = pickle.load(fp)
     os.makedirs(args.network_dir, exist_ok=True)
     trainer = (trainDoubleLossNet if args.double_loss else trainAccuracyNet) if args.with_vertices else trainNet
+    extra = dict(noise_levels=levels, noise_direction=args.noise_direction) if levels is not None else {}
     trainer(train_set, args.num_iterations, network_path=args.network_dir, net_name=args.net_name, seed=args.seed,
-            capture=args.capture, validSet=valid_set)
+            capture=args.capture, validSet=valid_set, **extra)
     return trainer.__name__
 
 

@@ -296,6 +296,22 @@ def computeNormals(verts, faces):
     return normalize(out)
 
 
+def areaWeightedVertexNormals(verts, faces):
+    """Unit vertex normals as the area-weighted SUM of the incident faces' normals (the cross products (v1 - v0) x
+    (v2 - v0), whose length is twice the area, added over all faces around a vertex), float64 [V,3]; a vertex without a
+    face gets a zero row.  Build extension for the noise synthesis along the normal (ops.synth_noise); not
+    computeNormals, which keeps the reference's last-face-wins quirk."""
+    V = np.asarray(verts, dtype=np.float64)
+    F = np.asarray(faces).astype(np.int64)
+    T = V[F]
+    cp = np.cross(T[:, 1] - T[:, 0], T[:, 2] - T[:, 0])
+    out = np.zeros(V.shape, dtype=np.float64)
+    for k in range(3):
+        np.add.at(out, F[:, k], cp)
+    nrm = np.sqrt((out * out).sum(1, keepdims=True))
+    return np.where(nrm > 0, out / np.where(nrm > 0, nrm, 1.0), 0.0)
+
+
 def write_mesh(vl, fl, strFileName):
     """utils.py:659-697: 'v x y z' (6 decimals, extra per-vertex columns such as colours written as they are), then
     'f a b c' one-indexed; a face (0,0,..) ends the list and a face (-1,-1,..) is skipped, as in the reference."""

@@ -51,8 +51,10 @@ extern "C" {
  * training through the multi-scale vertex update on the point-set loss.
  * 107: fgc_dense_normals_loss_fwd / _bwd (+ _scratch_floats): the face-normal loss over all rows, for training on the
  * point-set and face-normal losses together.
- * 108: fgc_bilateral_filter / fgc_bilateral_workspace_bytes (bilateral normal filtering, the classical baseline). */
-#define FGC_ABI_VERSION 108
+ * 108: fgc_bilateral_filter / fgc_bilateral_workspace_bytes (bilateral normal filtering, the classical baseline).
+ * 109: fgc_synth_noise / fgc_face_features_rows (+ fgc_synth_scratch_floats, fgc_philox_words): per-step noise synthesis on
+ * a clean mesh. */
+#define FGC_ABI_VERSION 109
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -754,6 +756,44 @@ int fgc_bilateral_filter(const float* centres, const float* normals, const float
                          const int32_t* cell_order, const int32_t* cell_ptr, int32_t sx, int32_t sy, int32_t sz,
                          const float* sigma_s, int32_t S, const float* sigma_r, int32_t R, float* out, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Noise synthesis: training from clean meshes (BUILD EXTENSION - the reference trains on noisy files prepared on the host)
+ * ---------------------------------------------------------------------------------- */
+
+/* Per step, the vertices of a clean mesh are displaced by a counter-based Gaussian draw and the six input channels of
+ * every node row are rebuilt from the displaced vertices.  Definitions:
+ *   Random numbers: Philox4x32-10, multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85,
+ *     counter = (vertex index, step & 0xffffffff, step >> 32, stream_id), key = (seed & 0xffffffff, seed >> 32); step and
+ *     seed are 64-bit, stream_id is the caller's 32-bit id (training 0, validation mesh i 1 + i).
+ *   Gaussians: u_k = ((x_k >> 8) + 0.5) 2^-24 (never 0 or 1); r0 = sqrt(-2 ln u0), z0 = r0 cos(2 pi u1),
+ *     z1 = r0 sin(2 pi u1); z2, z3 from (u2, u3) in the same way.  u_k needs 25 bits, so it is exact in fp32 only below
+ *     1/2; above, 1 - u_k is exact and the kernel evaluates ln u as log1pf(-(1 - u)) and sin / cos of the angle
+ *     -2 pi (1 - u); sin / cos come from the accurate sinpif / cospif on the exact 2 u (or 2 (1 - u)), not from sinf / cosf
+ *     on an angle rounded to fp32: every function sees an exact argument (csrc/fgc_synth.h says what is lost otherwise).
+ *   Displacement: vnormals == NULL: v' = v + d sigma z3 with d = (z0, z1, z2) / |(z0, z1, z2)|; otherwise
+ *     v' = v + vnormals[i] sigma z3 (unit vertex normals of the clean mesh, [nv,3]).  sigma = 0 gives v' = v bit for bit.
+ *   Features: x[i] = [n | centre] of face (a, b, c) = faces_rows[i] on the vertices, in fgc_face_features's arithmetic -
+ *     cross product with separately rounded multiplies and subtracts, normalised twice with 1e-8 added to the norm, the
+ *     bounding-box diagonal of the vertices in double from the fp32 extents then rounded to fp32, centre =
+ *     ((q0 + q1) + q2) / 3 with q = p / diag - so bit-identical to that host routine; a row with a negative (or
+ *     out-of-range) vertex id is a fake node and gets six zeros.
+ * Control words ctl (DEVICE, 3 x uint32, read by the kernels - a replayed hipGraph draws new noise without re-capture):
+ *   ctl[0], ctl[1] = step low / high; ctl[2] = 0: OFF, the launches read and write nothing (v_out, x and scratch stay as
+ *   they are); otherwise bit 31 is the on flag and bits 0..30 the float bits of sigma >= 0 (FGC_SYNTH_ON | bits).
+ * scratch (device floats) >= fgc_synth_scratch_floats(nv): fgc_synth_noise leaves the per-workgroup bounding boxes of
+ * v_out there; fgc_face_features_rows(have_bbox = 1) reads them (same nv, same scratch, right behind it on the stream),
+ * have_bbox = 0 computes them from v with one more launch.  ctl may be NULL for fgc_face_features_rows (always on).
+ * Enqueue-only, nothing allocated: fgc_synth_noise is one launch, fgc_face_features_rows one (have_bbox) or two. */
+#define FGC_SYNTH_ON 0x80000000u
+size_t fgc_synth_scratch_floats(int32_t nv);
+int fgc_synth_noise(const float* v, const float* vnormals, int32_t nv, const uint32_t* ctl, uint64_t seed,
+                    uint32_t stream_id, float* v_out, float* scratch, size_t scratch_floats, void* stream);
+int fgc_face_features_rows(const float* v, int32_t nv, const int32_t* faces_rows, int32_t n, const uint32_t* ctl,
+                           int32_t have_bbox, float* x, float* scratch, size_t scratch_floats, void* stream);
+/* The raw generator of fgc_synth_noise, for known-answer tests: out [n,4] uint32 (device, 16-byte aligned),
+ * out[i] = Philox4x32-10 of counter (first + i mod 2^32, step & 0xffffffff, step >> 32, stream_id) and key seed.  One launch. */
+int fgc_philox_words(uint32_t first, int32_t n, uint64_t step, uint64_t seed, uint32_t stream_id, uint32_t* out, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Checkpoint files (CPU; HOST pointers)

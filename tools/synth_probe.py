@@ -1,0 +1,141 @@
+"""Cost of the per-step noise synthesis (training from clean meshes) on the MI355X.
+
+    python tools/synth_probe.py [--faces 20480 100000] [--steps 50] [--rounds 5] [--out FILE]
+
+Per mesh size (a clean mesh: the 20 480-face icosphere, otherwise a torus): the DEVICE time of each of the two synthesis
+kernels (noise + bounding boxes, then the input rows) from the library's hipEvent hooks (fgc_profile_*: events around
+every launch) beside the bytes they move and bytes / 8 TB/s, and what a back-to-back stream of the two calls costs per
+pair (event time over `steps` calls: the enqueue rate of the Python wrappers where that is the larger); and, for the
+largest size, the captured training step with the synthesis (a clean mesh, new noise every step) against the captured
+plain step (the same mesh bound with bind_mesh), alternating `rounds` times in this one process, with the launches
+per step of both and the synthesis kernels' own device time from the library's hipEvent hooks."""
+import argparse
+import json
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import facet_graph_convolution_amd  # noqa: E402,F401  (before torch.cuda: hipGraph replay switch)
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+HBM_BYTES_PER_S = 8e12
+
+
+def timed(fn, steps, warmup=5):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--faces", type=int, nargs="+", default=[20480, 100000])
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--out", default="")
+    args = ap.parse_args()
+    import ctypes as C
+    from facet_graph_convolution_amd import ops, _lib
+    L = _lib.lib()
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    from facet_graph_convolution_amd.dataClasses import TrainingSet
+    from facet_graph_convolution_amd.meshgen import torus, icosphere
+    from facet_graph_convolution_amd.utils import rand_rotation_matrix
+    res = []
+    for nf in args.faces:
+        if nf == 20480:
+            V, F = icosphere(5)
+        else:
+            n = int(round((nf / 2) ** 0.5))
+            V, F = torus(n, n)
+        ds = TrainingSet()
+        ds.addCleanMesh(V, F, seed=0)
+        x, adjs, gt = ds.in_list[0], ds.adj_list[0], ds.gt_list[0]
+        n0, nv = x.shape[1], V.shape[0]
+        dev = "cuda:0"
+        Vd = torch.as_tensor(V, device=dev)
+        rows = torch.as_tensor(ds.clean_faces_rows[0][0], device=dev)
+        ctl = torch.from_numpy(ops.noise_words(3, 0.2 * ds.clean_edge_len[0]).view(np.int32)).to(dev)
+        out_v, out_x = torch.empty_like(Vd), torch.empty(n0, 6, dtype=torch.float32, device=dev)
+        scratch = torch.empty(6 * 1024, dtype=torch.float32, device=dev)
+        noise = lambda: ops.synth_noise(Vd, None, None, seed=1, out=out_v, scratch=scratch, ctl=ctl)  # noqa: E731
+        feats = lambda: ops.face_features_rows(out_v, rows, out=out_x, scratch=scratch, have_bbox=True, ctl=ctl)  # noqa: E731
+
+        def both():
+            noise()
+            feats()
+        # bytes: noise reads and writes the vertices; the rows kernel reads the face ids, gathers three vertices per row
+        # (every vertex is read from HBM once, the other five uses hit the caches) and writes 24 bytes per row
+        b_noise, b_feats = 24 * nv, 12 * n0 + 12 * nv + 24 * n0
+        both()
+        torch.cuda.synchronize()
+        L.fgc_profile_enable(1)
+        for _ in range(args.steps):
+            both()
+        torch.cuda.synchronize()
+        buf = C.create_string_buffer(1 << 16)
+        L.fgc_profile_collect(buf, len(buf))
+        L.fgc_profile_enable(0)
+        dev_us = {}
+        for line in buf.value.decode().splitlines():
+            name, cnt, ms = line.rsplit(" ", 2)
+            dev_us[name.split("/")[-1]] = float(ms) / int(cnt) * 1e3
+        row = dict(faces=int(F.shape[0]), nodes=int(n0), vertices=int(nv), noise_bytes=b_noise, features_bytes=b_feats,
+                   noise_floor_us=b_noise / HBM_BYTES_PER_S * 1e6, features_floor_us=b_feats / HBM_BYTES_PER_S * 1e6,
+                   kernel_device_us=dev_us, pair_enqueued_back_to_back_us=timed(both, args.steps) * 1e3)
+        if nf == max(args.faces):
+            rs = np.random.RandomState(0)
+            samp, Rm = rs.randint(n0, size=4000), rand_rotation_matrix(randnums=rs.uniform(size=3))
+            nets = {}
+            nets["synth"] = FacetDenoiser(dev, seed=0)
+            nets["synth"].bind_clean(0, x, adjs, gt, ds.clean_vertices[0], ds.clean_faces_rows[0], ds.clean_edge_len[0])
+            nets["plain"] = FacetDenoiser(dev, seed=0).bind_mesh(x, adjs, gt=gt)
+            for net in nets.values():
+                net.set_samples(samp)
+                net.set_rotation(Rm)
+            def synth_step():
+                nets["synth"].forward_backward(rotate=True, capture=True)
+
+            def plain_step():
+                nets["plain"].forward_backward(rotate=True, capture=True)
+            nets["synth"].set_noise(0, 0.2)
+            times = {"synth": [], "plain": []}
+            for r in range(args.rounds):
+                nets["synth"].set_noise(r + 1, 0.2)
+                times["synth"].append(timed(synth_step, args.steps))
+                times["plain"].append(timed(plain_step, args.steps))
+            row["captured_synth_ms"] = times["synth"]
+            row["captured_plain_ms"] = times["plain"]
+            row["captured_difference_us"] = (float(np.median(times["synth"])) - float(np.median(times["plain"]))) * 1e3
+            # launches per step and the synthesis kernels' own device time, from the library's hipEvent hooks (eager steps)
+            for k, net in nets.items():
+                net.forward_backward(rotate=True)
+                torch.cuda.synchronize()
+                net.profile_start()
+                for _ in range(10):
+                    net.forward_backward(rotate=True)
+                torch.cuda.synchronize()
+                prof = net.profile_stop()
+                row[k + "_launches_per_step"] = sum(c for c, _ in prof.values()) / 10.0
+                if k == "synth":
+                    row["synth_kernels_us"] = {name: ms / cnt * 1e3 for name, (cnt, ms) in prof.items() if "synth" in name}
+            del nets
+        print(json.dumps(row), flush=True)
+        res.append(row)
+        torch.cuda.empty_cache()
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:
+            json.dump(res, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
