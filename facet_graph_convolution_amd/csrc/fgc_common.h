@@ -50,6 +50,23 @@ struct ProfScope {
         hipLaunchKernelGGL(kernel, grid, block, smem, st, __VA_ARGS__);           \
     } while (0)
 
+// one launch of a kernel given as the template argument: raise its dynamic-LDS limit to what this launch asks for, launch
+// under the profile name, check.  launch_kernel<some_kernel<...>>(cfg, kernel arguments...)
+struct LaunchCfg {
+    const char* name;   // profile name (FGC_LAUNCH)
+    const char* what;   // prefix of the error message (FGC_CHECK_LAUNCH)
+    hipStream_t st;
+    int grid, block;
+    size_t smem;        // dynamic LDS bytes
+};
+template <auto Kernel, typename... Args>
+static inline int launch_kernel(const LaunchCfg& c, const Args&... args) {
+    if (c.smem) hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.smem);
+    FGC_LAUNCH(c.name, c.st, Kernel, dim3(c.grid), dim3(c.block), c.smem, args...);
+    FGC_CHECK_LAUNCH(c.what);
+    return FGC_OK;
+}
+
 // ---- process-level options (fgc_set_option / fgc_get_option, include/fgc.h): which kernel form a launch takes where the
 // ---- library has more than one.  No launch path reads the environment: the table is filled once from FGC_<NAME> variables
 // ---- the first time an option is read (fgc_host.hip), after that only fgc_set_option changes it.
@@ -78,9 +95,7 @@ struct ProfScope {
     X(NO_MLP_SPLIT, 0)        /* 1: the MLP's 1024-wide products on the fp32 MFMA (forward and backward) */                      \
     X(NO_MLP_BWD_SPLIT, 0)    /* 1: ... the backward only */                                                                     \
     X(NO_K1_SPLIT, 0)         /* 1: the dz GEMM of the fp32 d-logits kernel (half tiles, 32 outputs) on the fp32 MFMA */                \
-    X(NO_BFM, 0)              /* 1: bf16 conv kernels aggregate on the vector ALU (conv_w8_kernel<BF>), not the matrix pipe */    \
-    X(K1_QS14, 0)             /* 1: fp32 half-tile d-logits kernel with a 14-slot table where degrees allow (5 workgroups / CU) */  \
-    X(W8_HALF2, 0)            /* 1: fp32 half-tile forward conv with the aggregate tile in two halves (6 workgroups / CU) */
+    X(NO_BFM, 0)              /* 1: bf16 conv kernels aggregate on the vector ALU (conv_w8_kernel<BF>), not the matrix pipe */
 enum Opt {
 #define FGC_OPT_ENUM(name, def) OPT_##name,
     FGC_OPTION_LIST(FGC_OPT_ENUM)
@@ -168,8 +183,7 @@ constexpr int ZSTRIDE_BF = 304;
 
 struct ConvGeom {
     int cin, cout;
-    int lpn;        // lanes per node: 2,4,8
-    int kc;         // channels per pass = 4*lpn
+    int kc;         // channels per pass: 4 per lane, 8 lanes per node
     int passes;     // ceil(cin / kc)
     int kpass;      // M*kc rounded up to a multiple of 16 (MFMA k-group)
     int zstride;    // LDS row stride (floats), == 8 mod 16, >= kpass
@@ -192,9 +206,7 @@ static inline ConvGeom conv_geom(int cin, int cout) {
     g.cout = cout;
     // 8 lanes x 4 channels per node and pass for every width the tiled kernels see (narrow inputs, cin <= 8, take
     // fgc_conv_narrow.hip): keeps all 256 threads, the 32-channel z tile and the matrix-core kernels in play
-    const int lpn = 8;
-    g.lpn = lpn;
-    g.kc = 4 * lpn;
+    g.kc = 4 * 8;
     g.passes = (cin + g.kc - 1) / g.kc;
     g.kpass = (FGC_M * g.kc + 15) / 16 * 16;
     g.zstride = lds_stride_for(g.kpass);

@@ -11,29 +11,22 @@
 //         r_j[m,:] = sum_{i->j} q_ijm s_i         -> r[j, 9*cout]  (also the dW reduction's A operand)
 //         dg_j     = sum_{i->j} dl_(i->j)         -> dag[j, 12..20]
 //         dx_j     = r_j W  (f32 MFMA) + da_j u + dg_j v ; 4:1 row sum when the input was upsampled
-//   K3  reductions over nodes (f32 MFMA, K = nodes):  dW0 = r^T x,  [du; dv] = dag^T x ; db, dc column sums
+//   K3  reductions over nodes (f32 MFMA, K = nodes; fgc_gemm_tn.hip):  dW0 = r^T x,  [du; dv] = dag^T x ; db, dc column sums
+// Which form of each kernel a layer takes is decided once, by plan_bwd (fgc_conv_bwd.h); the operand packs are fgc_conv_pack.hip.
 // No float atomics anywhere: every sum has a fixed order, results are bitwise reproducible.
 #include <stdlib.h>
 
 #include <algorithm>
+#include <type_traits>
 
-#include "fgc_conv_w8.h"
+#include "fgc_conv_bwd.h"
 #include "fgc_conv_narrow.h"
 #include "fgc_conv_pair.h"
+#include "fgc_gemm_tn.h"
 #include "fgc_reduce.h"
-#include "fgc_pack.h"
 #include "fgc_split.h"
 
 namespace fgc {
-
-int validate_conv_desc(const fgc_conv_desc* d, const char* who);
-bool conv_vec4_ok(const fgc_conv_desc* d);
-void fill_core_params(CoreParams& p, const ConvGeom& g, int n, const int* rowptr, const int* col, const int* eid,
-                      const float* s0, const float* s1, int c0, int c1, int shift, int nout, const float* ag,
-                      int ag_shift, int ctr_off, int nbr_off, const float* Wp);
-size_t conv_smem_bytes(const ConvGeom& g, size_t extra);
-__global__ void pack_weight_kernel(const float* __restrict__ W0, float* __restrict__ Wp, int cin, int cout, int kdim,
-                                   int ncols, int npad, int kc, int kpass, int passes, int transposed);
 
 __device__ __forceinline__ float slope_from_y(float y, float alpha) { return y > 0.f ? 1.f : (y < 0.f ? alpha : 0.f); }
 
@@ -165,41 +158,6 @@ __global__ __launch_bounds__(256) void ds_db_vec_kernel(const float* __restrict_
         for (int t = 0; t < nrl; ++t) v += part[t * cout + threadIdx.x];
         db_part[(size_t)blockIdx.x * cout + threadIdx.x] = v;
     }
-}
-
-// ---------------------------------------------------------------------------------------------
-// K1 operand: Wq[pass][o/4][kk][o%4] = W0[m][o][pass*kc+cl], kk = m*kc+cl  (K = cout, N = kpass)
-// ---------------------------------------------------------------------------------------------
-__global__ void pack_logit_weight_kernel(const float* __restrict__ W0, float* __restrict__ Wq, int cin, int cout,
-                                         int opad, int kc, int kpass, int passes) {
-    pack_logit_weight_body(W0, Wq, cin, cout, opad, kc, kpass, passes, blockIdx.x, gridDim.x);
-}
-
-__global__ __launch_bounds__(256) void pack_many_kernel(PackJobs J) {
-    int q = 0;
-#pragma unroll
-    for (int t = 1; t < PACK_MAX_JOBS; ++t)
-        if (t < J.njobs && (int)blockIdx.x >= J.job[t].block0) q = t;
-    const PackJob& j = J.job[q];
-    const int bid = blockIdx.x - j.block0;
-    const int nb = (q + 1 < J.njobs ? J.job[q + 1].block0 : J.nblocks) - j.block0;
-    if (j.kind >= 8) {
-        if (j.kind == 14) rotate_logits_body(j.W0, j.dst, j.kdim, j.cin, j.aux, j.lg_u, j.lg_c, j.lg_v, j.lg_ag, bid, nb);
-        else if (j.kind == 8) rotate_rows_body(j.W0, j.dst, j.kdim, j.aux, bid, nb);
-        else if (j.kind == 9) mlp_pack_body(j.W0, j.dst, j.cin, j.kdim, j.ncols, bid, nb);
-        else if (j.kind == 10) mlp_pack_split_body(j.W0, (unsigned short*)j.dst, j.cin, j.ncols, bid, nb);
-        else if (j.kind == 11) mlp_pack_bf16_body(j.W0, (unsigned short*)j.dst, j.cin, j.ncols, bid, nb);
-        else if (j.kind == 12) mlp_pack_w1dx_bf16_body(j.W0, (unsigned short*)j.dst, j.cin, j.ncols, bid, nb);
-        else if (j.kind == 15) mlp_pack_w1dx_split_body(j.W0, (unsigned short*)j.dst, j.cin, j.ncols, bid, nb);
-        else if (j.kind == 16) mlp_pack_w2_split_body(j.W0, (u32x4*)j.dst, j.ncols, j.cout, bid);
-        else if (j.kind == 17) pack_logit_weight_split_body(j.W0, (unsigned short*)j.dst, j.cin, j.cout, j.passes, bid, nb);
-        else mlp_pack_w2_bf16_body(j.W0, (u32x4*)j.dst, j.ncols, j.cout, bid);
-    } else if (j.kind == 7) pack_plain_bf16_body(j.W0, (unsigned short*)j.dst, j.kdim, bid, nb);
-    else if (j.kind == 6) pack_logit_weight_bf16_body(j.W0, (unsigned short*)j.dst, j.cin, j.cout, j.passes, bid, nb);
-    else if (j.kind >= 4) pack_weight_bf16_body(j.W0, (unsigned short*)j.dst, j.cin, j.cout, j.kdim, j.ncols, j.npad, j.passes,
-                                                j.kind - 4, bid, nb);
-    else if (j.kind == 2) pack_logit_weight_body(j.W0, j.dst, j.cin, j.cout, j.opad, j.kc, j.kpass, j.passes, bid, nb);
-    else pack_weight_body(j.W0, j.dst, j.cin, j.cout, j.kdim, j.ncols, j.npad, j.kc, j.kpass, j.passes, j.kind, bid, nb);
 }
 
 struct LogitParams {
@@ -625,20 +583,15 @@ __global__ __launch_bounds__(NTHREADS) void conv_bwd_logits_mfma_kernel(CorePara
 // same-box alternating runs): dconv1 at 100k facets 122.9 -> 116.6 us.  The 64-wide layers were tried and gained nothing
 // (77.5 -> 76.0 / 77.6 us): a half tile re-reads the whole packed operand from L2 - 446 MB per level-0 launch as fp32, half
 // as much again as three bf16 planes - and that stream, not the matrix pipe, is what those launches wait for.
-// QSR: edge slots per node of the soft-assignment table for the regular (!LONG) forms - 16, or 14 where the host knows that no
-// node has more edges (a closed triangle mesh's facet graph: 13): 1.5 KB less LDS per half tile, 32.6 KB - a FIFTH workgroup
-// per CU if the registers stay under 97 (the launch bound asks for five waves per SIMD then).  Round-5 review, candidate
-// "14-slot d-logits table"; measured in DESIGN.md section 10.
-template <bool LONG, int OKG, int NT_ = 32, int NPW_ = 8, bool SPLIT = false, int QSR = 16>
-__global__ __launch_bounds__((NT_ / NPW_) * 64, NT_ == 32 ? 2 : (QSR == 14 ? 5 : 4)) void conv_bwd_logits_deep_kernel(CoreParams p, LogitParams lp) {
-    static_assert(QSR == 16 || (QSR == 14 && NT_ == 16), "14 slots: the half-tile form");
+template <bool LONG, int OKG, int NT_ = 32, int NPW_ = 8, bool SPLIT = false>
+__global__ __launch_bounds__((NT_ / NPW_) * 64, NT_ == 32 ? 2 : 4) void conv_bwd_logits_deep_kernel(CoreParams p, LogitParams lp) {
     static_assert((NT_ == 32 && NPW_ == 8) || (NT_ == 16 && NPW_ == 4 && !LONG), "tile shapes");
     static_assert(!SPLIT || (NT_ == 16 && OKG == 2), "split dz GEMM: half tiles of the 32-wide layers");
     // (shadow the 32-node constants of the file)
     constexpr int TILE = NT_, NPW = NPW_, NWV = NT_ / NPW_, NTHREADS = NWV * 64, RT = NT_ / 16, LPN = NTHREADS / NT_;
     static_assert(NWV == 4, "four waves either way: the column-tile split and the dc sums below assume it");
     extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-    constexpr int QS = LONG ? KMAX : QSR;       // the host sends graphs with a degree above 16 to the LONG form
+    constexpr int QS = LONG ? KMAX : 16;        // the host sends graphs with a degree above 16 to the LONG form
     const Smem s = carve(smem_raw, ZSTRIDE, QS, NT_);
     const int opad = OKG ? OKG * 16 : lp.opad;
     const int ostride = OKG ? OKG * 16 + 8 : lp.ostride;
@@ -1434,668 +1387,217 @@ __global__ __launch_bounds__(NTHREADS) void conv_bwd_data_kernel(CoreParams p, D
 }
 
 // ---------------------------------------------------------------------------------------------
-// K3: C[P,Q] = sum_rows A[row,P] * X[row >> shift, Q]   (X = [x0 | x1]); f32 MFMA with K = rows.
-// Both operands are row-major with the reduction index as the slow dimension, so a lane's 16-byte load of
-// A[row, p0+4*lr .. +3] holds the SAME k (row) for 4 different output rows: MFMA number e takes element e,
-// i.e. MFMA e owns output rows p0 + 4*i + e (i = MFMA row index).  One dwordx4 of A and one of X per lane feed
-// 16 MFMAs (a 64 x 64 tile per wave, 4 rows of K per step); no LDS staging, no barrier in the loop.
-// grid (P tiles * Q tiles, row splits); the 4 waves of a workgroup interleave the k-steps of their split and are
-// summed through LDS in a fixed order; partials go to slab[split][P][Q], reduced by reduce_jobs.
+// The plan: (descriptor, options in force) -> kernel form, partial-sum slots, packed operands, workspace layout.  A function
+// of the descriptor and the options alone, and the only reader of the d-logits options: the workspace size, the layout id,
+// fgc_conv_pack (which may write the operands long before the launch), the launches and the reductions all read this one
+// answer, so slot counts and kernels agree.  The options are read on every call, inside the descriptor's FGC_OPT_SCOPE.
 // ---------------------------------------------------------------------------------------------
-template <bool VEC4>
-__device__ __forceinline__ void tn_load(const float* __restrict__ A, int lda, int P, const float* __restrict__ x0,
-                                        const float* __restrict__ x1, int c0, int c1, int shift, int row, bool valid,
-                                        int pbase, int qbase, f32x4& a, f32x4& b) {
-    a = f32x4{0.f, 0.f, 0.f, 0.f};
-    b = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (!valid) return;
-    const int Q = c0 + c1;
-    const size_t sr = (size_t)(row >> shift);
-    if (VEC4) {
-        if (pbase < P) a = *reinterpret_cast<const f32x4*>(A + (size_t)row * lda + pbase);
-        if (qbase < c0) b = *reinterpret_cast<const f32x4*>(x0 + sr * c0 + qbase);
-        else if (qbase < Q) b = *reinterpret_cast<const f32x4*>(x1 + sr * c1 + (qbase - c0));
-    } else {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            if (pbase + t < P) a[t] = A[(size_t)row * lda + pbase + t];
-            const int q = qbase + t;
-            if (q < c0) b[t] = x0[sr * c0 + q];
-            else if (q < Q) b[t] = x1[sr * c1 + (q - c0)];
-        }
-    }
-}
-
-// Workgroup -> (output tile, node-range split) of the weight-gradient GEMMs.  Workgroups are dealt round-robin over the
-// 8 XCDs, each with a private L2.  With the plain (tile, split) grid the tiles of one split - which read the SAME rows of r
-// and x - land on different XCDs and every L2 fetches those rows from HBM again (dconv2: x came in ten times).  Here all
-// tiles of a split run on one XCD, next to each other in dispatch order: the rows are fetched once and the other tiles
-// hit in L2.  The grid is padded to 8 * ceil(splits / 8) splits; workgroups of a padding split return at once.
-// Same work per (tile, split), same slabs, same sums: results are unchanged bit for bit.
-__device__ __forceinline__ bool tn_block(int ntiles, int nsplits, int& tile, int& split, int vblock = -1) {
-    // (vblock: the workgroup's index within ITS job of a grouped launch; jobs start at multiples of 8, so vblock & 7 is
-    //  still the XCD the hardware dealt this workgroup to)
-    const int L = vblock >= 0 ? vblock : (int)blockIdx.x, xcd = L & 7, idx = L >> 3;
-    tile = idx % ntiles;
-    split = (idx / ntiles) * 8 + xcd;
-    return split < nsplits;
-}
-static inline dim3 tn_grid(int ntiles, int nsplits) { return dim3((unsigned)(ntiles * 8 * cdiv(nsplits, 8))); }
-
-// The weight-gradient GEMMs of several layers in ONE launch (fgc_conv_bwd_reduce with FGC_CONV_DEFER_DW): every job is what
-// one launch of the kernel would be - same tiles, same slabs, same sums, bit-identical gradients -, its workgroups are the
-// range [block0, block0 + tn_grid) of the grid.  On the bf16 network a layer's GEMM is 5-15 us of ramp and tail around a few
-// microseconds of streaming: eight of them back to back cost four times what their work takes.
-struct TnArgs {
-    const void* A;
-    const void* x0;
-    const void* x1;
-    float* slab;
-    int lda, P, c0, c1, shift, rows, rps;
-    int block0;
-};
-constexpr int TN_MAX_JOBS = 8;
-struct TnJobs {
-    TnArgs job[TN_MAX_JOBS];
-    int njobs;
-};
-__device__ __forceinline__ int tn_job_of(const TnJobs& J) {
-    int q = 0;
-#pragma unroll
-    for (int t = 1; t < TN_MAX_JOBS; ++t)
-        if (t < J.njobs && (int)blockIdx.x >= J.job[t].block0) q = t;
-    return q;
-}
-
-template <bool VEC4>
-__global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ A, int lda, int P,
-                                                      const float* __restrict__ x0, const float* __restrict__ x1,
-                                                      int c0, int c1, int shift, int rows, int rows_per_split,
-                                                      float* __restrict__ slab) {
-    __shared__ float red[4][64][65];
-    const int Q = c0 + c1;
-    const int npt = (P + 63) >> 6;
-    int tile_id, split_id;
-    if (!tn_block(npt * ((Q + 63) >> 6), (rows + rows_per_split - 1) / rows_per_split, tile_id, split_id)) return;
-    const int pt = tile_id % npt, qt = tile_id / npt;
-    const int p0 = pt * 64, q0 = qt * 64;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lq = lane >> 4;
-    const int r_begin = split_id * rows_per_split;
-    const int r_end = min(rows, r_begin + rows_per_split);
-    const int nsteps = (r_end - r_begin + 3) >> 2;
-    const int pbase = p0 + 4 * lr, qbase = q0 + 4 * lr;
-    f32x4 acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // two operand register sets with fixed roles (unrolled by 2, no copies of in-flight loads)
-    f32x4 a0, b0, a1, b1;
-    auto ld = [&](int step, f32x4& a, f32x4& b) {
-        const int row = r_begin + 4 * step + lq;
-        tn_load<VEC4>(A, lda, P, x0, x1, c0, c1, shift, row, step < nsteps && row < r_end, pbase, qbase, a, b);
-    };
-    auto mm = [&](const f32x4& a, const f32x4& b) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    };
-    ld(wave, a0, b0);
-    ld(wave + 4, a1, b1);
-    for (int s = wave; s < nsteps; s += 8) {
-        mm(a0, b0);
-        ld(s + 8, a0, b0);
-        if (s + 4 < nsteps) mm(a1, b1);
-        ld(s + 12, a1, b1);
-    }
-    // C layout of acc[i][j]: column index lr -> q = 4*lr + j ; row index lq*4+reg -> p = 4*(lq*4+reg) + i
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) red[wave][4 * (lq * 4 + t) + i][4 * lr + j] = acc[i][j][t];
-    __syncthreads();
-    float* out = slab + (size_t)split_id * P * Q;
-    for (int t = tid; t < 64 * 64; t += 256) {
-        const int pp = t >> 6, qq = t & 63;
-        if (p0 + pp < P && q0 + qq < Q)
-            out[(size_t)(p0 + pp) * Q + q0 + qq] = (red[0][pp][qq] + red[1][pp][qq]) + (red[2][pp][qq] + red[3][pp][qq]);
-    }
-}
-
-// Streaming form of gemm_tn_kernel for 16-byte aligned operands whose widths are multiples of 4 (every layer but
-// conv1).  Same tiling, same summation order, bit-identical results; what differs is how memory is asked for:
-//   * loads are UNCONDITIONAL (row and column indices clamped into the operands, out-of-range rows zeroed by a
-//     select on the A fragment): no exec-masked branch around a load, so hipcc counts its s_waitcnt instead of
-//     draining everything with vmcnt(0) in front of every MFMA group;
-//   * four operand register sets with fixed roles (loop unrolled by 4): each load has three MFMA groups = 48
-//     matrix instructions to land;
-//   * the 4-wave sum goes through 2 x 16 KB of LDS instead of 4, so four workgroups are resident per CU.
-// NJ = 4: 64 x 64 output tile (lane lr owns columns 4*lr .. 4*lr+3); NJ = 2: 64 x 32 for operands only 32 wide (columns
-// 2*lr, 2*lr+1: half the MFMAs instead of multiplying clamped duplicates)
-// BF: both operands are bf16 tensors (FGC_CONV_BF16); they are widened on load and multiplied on the fp32 MFMA: the
-// products are exact and the sum over the nodes stays an fp32 chain, as in the fp32 network
-template <int NJ, bool BF>
-__device__ __forceinline__ void tn_stream_body(const float* __restrict__ A, int lda, int P, const float* __restrict__ x0,
-                                               const float* __restrict__ x1, int c0, int c1, int shift, int rows,
-                                               int rows_per_split, float* __restrict__ slab, int vblock) {
-    __shared__ float red[2][64][65];
-    const int Q = c0 + c1;
-    const int npt = (P + 63) >> 6;
-    int tile_id, split_id;
-    if (!tn_block(npt * ((Q + 16 * NJ - 1) / (16 * NJ)), (rows + rows_per_split - 1) / rows_per_split, tile_id, split_id, vblock))
-        return;
-    const int pt = tile_id % npt, qt = tile_id / npt;
-    const int p0 = pt * 64, q0 = qt * (16 * NJ);
-    const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, lq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r_begin = split_id * rows_per_split;
-    const int r_end = min(rows, r_begin + rows_per_split);
-    const int nsteps = (r_end - r_begin + 3) >> 2;
-    // column quads of this lane, clamped into the operands (results of clamped columns are never stored)
-    const int pc = min(p0 + 4 * lr, P - 4);
-    const int qc = min(q0 + NJ * lr, Q - NJ);
-    const float* bsrc = BF ? reinterpret_cast<const float*>(reinterpret_cast<const unsigned short*>(qc < c0 ? x0 : x1) +
-                                                            (qc < c0 ? qc : qc - c0))
-                           : (qc < c0 ? x0 + qc : x1 + (qc - c0));
-    const int bld = qc < c0 ? c0 : c1;
-    f32x4 acc[4][NJ];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // A load only requests memory; the zeroing of out-of-range rows happens where the fragment is consumed (a select
-    // right behind the load would make the compiler wait for it on the spot)
-    auto ld = [&](int step, f32x4& a, f32x4& b, int& row) {
-        row = r_begin + 4 * step + lq;
-        const int rc = min(row, r_end - 1);
-        if constexpr (BF) {
-            const unsigned short* A16 = reinterpret_cast<const unsigned short*>(A);
-            const unsigned short* b16 = reinterpret_cast<const unsigned short*>(bsrc);
-            a = bf4_to_f4(*reinterpret_cast<const u32x2*>(A16 + (size_t)rc * lda + pc));
-            if constexpr (NJ == 4) {
-                b = bf4_to_f4(*reinterpret_cast<const u32x2*>(b16 + (size_t)(rc >> shift) * bld));
-            } else {
-                const f32x2c b2 = bf2_to_f2(*reinterpret_cast<const unsigned*>(b16 + (size_t)(rc >> shift) * bld));
-                b = f32x4{b2[0], b2[1], 0.f, 0.f};
-            }
-            return;
-        }
-        a = *reinterpret_cast<const f32x4*>(A + (size_t)rc * lda + pc);
-        if constexpr (NJ == 4) {
-            b = *reinterpret_cast<const f32x4*>(bsrc + (size_t)(rc >> shift) * bld);
-        } else {
-            const f32x2c b2 = *reinterpret_cast<const f32x2c*>(bsrc + (size_t)(rc >> shift) * bld);
-            b = f32x4{b2[0], b2[1], 0.f, 0.f};
-        }
-    };
-    auto mm = [&](f32x4 a, const f32x4& b, int row) {
-        if (row >= r_end) a = f32x4{0.f, 0.f, 0.f, 0.f};   // a select, not a branch
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[i], b[j], acc[i][j], 0, 0, 0);
-    };
-    f32x4 a0, b0, a1, b1, a2, b2, a3, b3;
-    int r0, r1, r2, r3;
-    ld(wave, a0, b0, r0);
-    ld(wave + 4, a1, b1, r1);
-    ld(wave + 8, a2, b2, r2);
-    ld(wave + 12, a3, b3, r3);
-    // sched_barrier: keep the program order "16 MFMAs, then the refill of the set they consumed" (left alone the
-    // scheduler sinks every refill to just in front of its use and the prefetch distance collapses to zero)
-#define FGC_TN_STEP(A_, B_, R_, NEXT_)          \
-    mm(A_, B_, R_);                             \
-    __builtin_amdgcn_sched_barrier(0);          \
-    ld(NEXT_, A_, B_, R_);                      \
-    __builtin_amdgcn_sched_barrier(0);
-    for (int s = wave; s < nsteps; s += 16) {   // steps past the end load a clamped row and multiply by zero
-        FGC_TN_STEP(a0, b0, r0, s + 16)
-        FGC_TN_STEP(a1, b1, r1, s + 20)
-        FGC_TN_STEP(a2, b2, r2, s + 24)
-        FGC_TN_STEP(a3, b3, r3, s + 28)
-    }
-#undef FGC_TN_STEP
-    // (w0 + w1) + (w2 + w3), as gemm_tn_kernel sums them.  C layout of acc[i][j]: column lr -> q = 4*lr + j,
-    // row lq*4+reg -> p = 4*(lq*4+reg) + i
-    auto put = [&](int slot) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) red[slot][4 * (lq * 4 + t) + i][NJ * lr + j] = acc[i][j][t];
-    };
-    auto add = [&](int slot) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-#pragma unroll
-            for (int j = 0; j < NJ; ++j)
-#pragma unroll
-                for (int t = 0; t < 4; ++t) acc[i][j][t] += red[slot][4 * (lq * 4 + t) + i][NJ * lr + j];
-    };
-    if (wave == 1) put(0);
-    if (wave == 3) put(1);
-    __syncthreads();
-    if (wave == 0) add(0);
-    if (wave == 2) add(1);
-    __syncthreads();
-    if (wave == 0) put(0);
-    if (wave == 2) put(1);
-    __syncthreads();
-    float* out = slab + (size_t)split_id * P * Q;
-    for (int t = tid; t < 64 * 16 * NJ; t += 256) {
-        const int pp = t / (16 * NJ), qq = t % (16 * NJ);
-        if (p0 + pp < P && q0 + qq < Q) out[(size_t)(p0 + pp) * Q + q0 + qq] = red[0][pp][qq] + red[1][pp][qq];
-    }
-}
-template <int NJ, bool BF = false>
-__global__ __launch_bounds__(256, 4) void gemm_tn_stream_kernel(const float* __restrict__ A, int lda, int P,
-                                                                const float* __restrict__ x0,
-                                                                const float* __restrict__ x1, int c0, int c1, int shift,
-                                                                int rows, int rows_per_split, float* __restrict__ slab) {
-    tn_stream_body<NJ, BF>(A, lda, P, x0, x1, c0, c1, shift, rows, rows_per_split, slab, -1);
-}
-template <int NJ, bool BF = false>
-__global__ __launch_bounds__(256, 4) void gemm_tn_stream_group_kernel(TnJobs J) {
-    const TnArgs& a = J.job[tn_job_of(J)];
-    tn_stream_body<NJ, BF>((const float*)a.A, a.lda, a.P, (const float*)a.x0, (const float*)a.x1, a.c0, a.c1, a.shift, a.rows,
-                           a.rps, a.slab, (int)blockIdx.x - a.block0);
-}
-
-// ---------------------------------------------------------------------------------------------
-// K3 for bf16-stored operands ON the bf16 matrix cores (FGC_CONV_BF16).  C[P,Q] = sum_rows A[row,P] * X[row >> shift, Q]
-// reduces over the rows, the slow index of both operands, while a v_mfma_f32_16x16x32_bf16 fragment wants 8 consecutive k
-// of ONE output row / column in a lane.  The transposition is done by the LDS read: a chunk of 32 rows of A (up to 320
-// columns) and of X (QT * 16 columns) is staged row-major, as it lies in memory (16-byte pieces, coalesced), and read back
-// with ds_read_b64_tr_b16: per 16-lane group a 4 row x 16 column block comes back column-major, lane i holding column i
-// of the four rows.  Two such reads (rows 4*lq .. +3 and 16 + 4*lq .. +3) are a whole fragment; A and X use the same row
-// order, so the permuted k is consistent.  Row strides == 32 bytes mod 256, an odd multiple of 32: the eight rows a
-// 32-lane half touches land on eight disjoint 32-byte bank spans.  Wave w owns row tiles 5w .. 5w+4 of the product
-// (columns of A) and all column tiles: 18 transposed reads per 20 MFMAs.  The kernel streams: what bounds it is how fast
-// the rows of r arrive, so the next chunk travels through registers under the current one.  fp32 accumulators; slabs and
-// their fixed-order sum as for the fp32 kernels.
-// ---------------------------------------------------------------------------------------------
-constexpr int TNB_THREADS = 256;
-constexpr int TNB_PC = 320;               // columns of A per workgroup
-constexpr int TNB_AS = TNB_PC * 2 + 32;   // LDS row strides in bytes
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ u32x4 tnb_frag(const char* tile, int stride, int col0, int lq, int lr) {
-    // block rows 4*lq + q (then 16 + 4*lq + q), columns col0 + 4*p .. +3 for lane 4*q + p of the group
-    const char* a = tile + (4 * lq + (lr >> 2)) * stride + (col0 + 4 * (lr & 3)) * 2;
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)a);
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(a + 16 * stride));
-    const u32x2 l2 = __builtin_bit_cast(u32x2, lo), h2 = __builtin_bit_cast(u32x2, hi);
-    return u32x4{l2[0], l2[1], h2[0], h2[1]};
-}
-
-template <int QT>
-__device__ __forceinline__ void tn_bf16_body(const unsigned short* __restrict__ A, int lda, int P,
-                                             const unsigned short* __restrict__ x0, const unsigned short* __restrict__ x1, int c0,
-                                             int c1, int shift, int rows, int rows_per_split, float* __restrict__ slab,
-                                             int vblock) {
-    constexpr int QC = QT * 16;
-    constexpr int XS = QC * 2 + 32;
-    constexpr int APC = TNB_PC / 8;                                  // 16-byte pieces per row of the A chunk
-    constexpr int NA = 32 * APC / TNB_THREADS;                       // pieces per thread: 5
-    static_assert(32 * APC % TNB_THREADS == 0 && 32 * (QC / 8) <= TNB_THREADS, "staging shape");
-    __shared__ __attribute__((aligned(16))) char As[2][32 * TNB_AS];
-    __shared__ __attribute__((aligned(16))) char Xs[2][32 * XS];
-    const int Q = c0 + c1;
-    const int npc = (P + TNB_PC - 1) / TNB_PC;
-    int tile_id, split_id;
-    if (!tn_block(npc * (Q / QC), (rows + rows_per_split - 1) / rows_per_split, tile_id, split_id, vblock)) return;
-    const int pc = tile_id % npc, qc = tile_id / npc;
-    const int p0 = pc * TNB_PC, q0 = qc * QC;
-    const int pw = min(P - p0, TNB_PC);                              // valid columns of A here (a multiple of 8)
-    const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, lq = lane >> 4;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r_begin = split_id * rows_per_split;
-    const int r_end = min(rows, r_begin + rows_per_split);
-    const int nchunks = (r_end - r_begin + 31) >> 5;
-
-    u32x4 ra[NA], rx;
-    const int xrow = min(tid, 32 * (QC / 8) - 1) / (QC / 8), xcol = (min(tid, 32 * (QC / 8) - 1) % (QC / 8)) * 8;
-    const int qcol = q0 + xcol;
-    const bool x_first = qcol < c0;
-    const unsigned short* xsrc = x_first ? x0 : x1;
-    const int xld = x_first ? c0 : c1;
-    const int xoff = min(x_first ? qcol : qcol - c0, xld - 8);
-    auto fetch = [&](int ch) {
-        const int rb = r_begin + ch * 32;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int t = tid + i * TNB_THREADS;
-            const int row = min(rb + t / APC, r_end - 1);
-            const int col = p0 + min((t % APC) * 8, pw - 8);
-            ra[i] = *reinterpret_cast<const u32x4*>(A + (size_t)row * lda + col);
-        }
-        rx = *reinterpret_cast<const u32x4*>(xsrc + (size_t)(min(rb + xrow, r_end - 1) >> shift) * xld + xoff);
-    };
-    auto stage = [&](int ch, int buf) {
-        const int rb = r_begin + ch * 32;
-#pragma unroll
-        for (int i = 0; i < NA; ++i) {
-            const int t = tid + i * TNB_THREADS;
-            const int r = t / APC, c = (t % APC) * 8;
-            const bool ok = rb + r < r_end && c < pw;
-            *reinterpret_cast<u32x4*>(&As[buf][r * TNB_AS + c * 2]) = ok ? ra[i] : u32x4{0u, 0u, 0u, 0u};
-        }
-        if (tid < 32 * (QC / 8)) {
-            const bool ok = rb + xrow < r_end && qcol < Q;
-            *reinterpret_cast<u32x4*>(&Xs[buf][xrow * XS + xcol * 2]) = ok ? rx : u32x4{0u, 0u, 0u, 0u};
-        }
-    };
-    f32x4 acc[5][QT];
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-#pragma unroll
-        for (int j = 0; j < QT; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    if (nchunks > 0) {
-        fetch(0);
-        stage(0, 0);
-    }
-    __syncthreads();
-    for (int ch = 0; ch < nchunks; ++ch) {
-        const int buf = ch & 1;
-        if (ch + 1 < nchunks) fetch(ch + 1);
-        u32x4 af[5], bq[QT];
-#pragma unroll
-        for (int i = 0; i < 5; ++i) af[i] = tnb_frag(As[buf], TNB_AS, (wave * 5 + i) * 16, lq, lr);
-#pragma unroll
-        for (int j = 0; j < QT; ++j) bq[j] = tnb_frag(Xs[buf], XS, j * 16, lq, lr);
-#pragma unroll
-        for (int i = 0; i < 5; ++i)
-#pragma unroll
-            for (int j = 0; j < QT; ++j)
-                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, af[i]), __builtin_bit_cast(bf16x8, bq[j]),
-                                                                   acc[i][j], 0, 0, 0);
-        if (ch + 1 < nchunks) stage(ch + 1, buf ^ 1);     // (the other buffer: its readers finished before the last barrier)
-        __syncthreads();
-    }
-    // C layout: column = lr -> q, row = 4*lq + reg -> p
-    float* out = slab + (size_t)split_id * P * Q;
-#pragma unroll
-    for (int i = 0; i < 5; ++i)
-#pragma unroll
-        for (int j = 0; j < QT; ++j)
-#pragma unroll
-            for (int t = 0; t < 4; ++t) {
-                const int pp = p0 + (wave * 5 + i) * 16 + lq * 4 + t, qq = q0 + j * 16 + lr;
-                if (pp < p0 + pw && qq < Q) out[(size_t)pp * Q + qq] = acc[i][j][t];
-            }
-}
-template <int QT>
-__global__ __launch_bounds__(TNB_THREADS, 2) void gemm_tn_bf16_kernel(const unsigned short* __restrict__ A, int lda, int P,
-                                                                      const unsigned short* __restrict__ x0,
-                                                                      const unsigned short* __restrict__ x1, int c0, int c1,
-                                                                      int shift, int rows, int rows_per_split,
-                                                                      float* __restrict__ slab) {
-    tn_bf16_body<QT>(A, lda, P, x0, x1, c0, c1, shift, rows, rows_per_split, slab, -1);
-}
-template <int QT>
-__global__ __launch_bounds__(TNB_THREADS, 2) void gemm_tn_bf16_group_kernel(TnJobs J) {
-    const TnArgs& a = J.job[tn_job_of(J)];
-    tn_bf16_body<QT>((const unsigned short*)a.A, a.lda, a.P, (const unsigned short*)a.x0, (const unsigned short*)a.x1, a.c0, a.c1,
-                     a.shift, a.rows, a.rps, a.slab, (int)blockIdx.x - a.block0);
-}
-
-static bool tn_bf16_ok(int P, int c0, int c1) {
-    if (opt(OPT_NO_TNBF16) == 1) return false;
-    const int Q = c0 + c1;
-    return P % 8 == 0 && c0 % 8 == 0 && c1 % 8 == 0 && Q % 32 == 0 && (c1 == 0 || c0 % 16 == 0) && c0 >= 8 && (c1 == 0 || c1 >= 8);
-}
-
-int launch_gemm_tn_stream(const char* tag, const float* A, int lda, int P, const float* x0, int c0, int rows,
-                          int rows_per_split, int nsplits, float* slab, hipStream_t st) {
-    if (c0 <= 32 && c0 % 2 == 0) {
-        const dim3 grid = tn_grid(cdiv(P, 64), nsplits);
-        FGC_LAUNCH(tag, st, gemm_tn_stream_kernel<2>, grid, dim3(256), 0, A, lda, P, x0, (const float*)nullptr, c0, 0, 0, rows,
-                   rows_per_split, slab);
-    } else {
-        const dim3 grid = tn_grid(cdiv(P, 64) * cdiv(c0, 64), nsplits);
-        FGC_LAUNCH(tag, st, gemm_tn_stream_kernel<4>, grid, dim3(256), 0, A, lda, P, x0, (const float*)nullptr, c0, 0, 0, rows,
-                   rows_per_split, slab);
-    }
-    FGC_CHECK_LAUNCH("gemm_tn_stream_kernel");
-    return FGC_OK;
-}
-
-static int tn_rows_per_slab(int n, int splits) { return cdiv(cdiv(n, splits), 4) * 4; }
-
-// A split count near `desired` (at most `maxs`) whose EFFECTIVE number of slabs is a multiple of 8: tn_block gives every
-// XCD the slabs s = xcd, xcd + 8, ...; with 27 slabs two XCDs would work through four of them and six through three.
-int tn_balanced_splits(int desired, int maxs, int rows) {
-    desired = std::max(1, std::min(desired, maxs));
-    for (int delta = 0; delta < 24; ++delta)
-        for (int sgn = 1; sgn >= -1; sgn -= 2) {
-            const int s = desired + sgn * delta;
-            if (s >= 8 && s <= maxs && cdiv(rows, tn_rows_per_slab(rows, s)) % 8 == 0) return s;
-        }
-    return desired;
-}
-
-// An XCD has 32 CUs x 4 resident workgroups of these kernels = 128 slots and is given tiles x (slabs / 8) workgroups: the
-// slab count fills a whole number of slots per CU exactly once (a count just above a multiple of 32 leaves a few CUs with one
-// workgroup more than the rest, and the launch waits for them).
-static int tn_splits(int P, int Q, int rows) {
-    const int tiles = cdiv(P, 64) * cdiv(Q, 64);
-    // Two workgroups per CU (64 slots per XCD), not the four that fit: the kernel is bound by the matrix pipe and by HBM,
-    // which eight waves per CU keep as busy as sixteen, and every workgroup less is a 16 KB slab less to write and to sum
-    // (measured over 32 ... 256 slots: 64 is the minimum of the step, 2.192 -> 2.179 ms; the GEMMs 1-2 us faster each, the
-    // sums 17 -> 12 us per launch).  Layers with more than 32 output tiles (the 128 -> 128 layer of the coarsest level)
-    // would get one slab per XCD that way and keep 128 slots (32 -> 39 us otherwise).  FGC_TN_SLOTS: developer knob.
-    const int slots = (int)opt(OPT_TN_SLOTS);
-    int per = slots / tiles;
-    if (per < 2) per = std::max(1, 2 * slots / tiles);
-    return tn_balanced_splits(8 * per, cdiv(rows, 128), rows);
-}
-
-// Nodes per workgroup of the deep d-logits kernel: half tiles (16 nodes, four workgroups per CU) for the fp32 network on
-// regular graphs.  A function of the descriptor alone: the partial-sum slots (dc per workgroup, db per tile of the fused
-// prologue and of ds_db_kernel) are counted in these units by the workspace plan, the launches and the reductions.
-// FGC_K1_NT16=0: 32-node tiles everywhere.
-static int k1_nodes(const fgc_conv_desc* d) {
-    // (read on every call, like the launch code reads FGC_NO_K1M / FGC_NO_K1DEEP: a process that changes a switch between
-    //  two calls gets slot counts and kernels that agree)
-    const bool on = !(opt(OPT_K1_NT16) == 0);
-    const bool k1m = !(opt(OPT_NO_K1M) == 1);
-    const bool k1deep = !(opt(OPT_NO_K1DEEP) == 1);
-    if (!on || !k1m || !k1deep) return TILE;
-    const int cin = d->c0 + d->c1;
-    const ConvGeom g1 = conv_geom(cin, d->cout);
-    if ((d->flags & FGC_CONV_BF16) && d->cout % 32 != 0) return TILE;
-    const bool deep = g1.lpn == 8 && d->max_deg > 0 && d->max_deg <= 16 && conv_vec4_ok(d) && cin % 32 == 0 &&
-                      (d->c1 == 0 || d->c0 % 32 == 0) && (size_t)d->n * 4 * 128 < 0xFFFFFFFFull;
-    return deep ? 16 : TILE;
-}
-
-// The dz GEMM of the half-tile d-logits kernel on split bf16 operands (conv_bwd_logits_deep_kernel<.., SPLIT>): the fp32
-// network's 32-wide layers on regular graphs.  A function of the descriptor and the options alone: it decides the
-// layout (and size) of the packed operand Wq, which fgc_conv_pack may write long before the launch.  NO_K1_SPLIT=1: fp32 MFMA.
-static bool k1_split(const fgc_conv_desc* d) {
-    if (opt(OPT_NO_K1_SPLIT) == 1 || (d->flags & FGC_CONV_BF16)) return false;
-    return k1_nodes(d) == 16 && d->cout == 32 && !pairs_ok(d);
-}
-// Everything fgc_conv_pack branches on when it chooses what to write into a layer's workspaces, as one number: a caller keeps
-// it with the packed operands (fgc_conv_desc.packed_layout) and the FGC_CONV_PACKED calls compare.
-uint64_t conv_layout_id(const fgc_conv_desc* d) {
-    const uint64_t bf16 = (d->flags & FGC_CONV_BF16) ? 1 : 0;
-    return 1ull | (uint64_t)narrow_supported(d) << 1 | (uint64_t)pairs_ok(d) << 2 | (uint64_t)k1_split(d) << 3 | bf16 << 4;
-}
-// (room for either layout wherever the shape allows the split one: the workspace a caller sized before changing NO_K1_SPLIT
-//  stays large enough; the operand itself must be packed again after such a change, like every packed operand)
-static size_t k1_wq_floats(const fgc_conv_desc* d) {
-    const ConvGeom g1 = conv_geom(d->c0 + d->c1, d->cout);
-    const int opad = (d->cout + 15) / 16 * 16;
-    const size_t f32 = (size_t)g1.passes * opad * g1.kpass;
-    const bool maybe = !(d->flags & FGC_CONV_BF16) && d->cout == 32;
-    return maybe ? std::max(f32, (size_t)g1.passes * (d->cout >> 5) * 18 * 3 * 256) : f32;
-}
-
-// ---- which kernel computes a layer's weight gradient, and with what arguments: shared by the per-layer launch (stage 8) and
-// ---- the grouped launch of fgc_conv_bwd_reduce (FGC_CONV_DEFER_DW)
-enum TnVariant { TN_STREAM2 = 0, TN_STREAM4, TN_STREAM2_BF, TN_STREAM4_BF, TN_BF16_4, TN_BF16_2, TN_PLAIN_V4, TN_PLAIN, TN_NVARIANTS };
-struct TnPlan {
-    int variant;
-    TnArgs a;
-    int ntiles, nsplits;
-};
-static bool tn_groupable(int v) { return v <= TN_BF16_2; }
-// rows x [PL columns of A] against [c0 + c1 columns of x0 | x1]
-static TnPlan tn_plan_of(bool bf16, bool vec4, bool stream_ok, const void* A, int PL, const void* x0, const void* x1, int c0, int c1,
-                         int shift, int rows, int rps, float* slab, int lda = 0) {
-    TnPlan pl;
-    const int cin = c0 + c1, ns = cdiv(rows, rps);
-    pl.a = TnArgs{A, x0, x1, slab, lda ? lda : PL, PL, c0, c1, shift, rows, rps, 0};   // (lda: row stride of A, >= its PL columns)
-    pl.nsplits = ns;
-    if (bf16 && tn_bf16_ok(PL, c0, c1)) {
-        pl.variant = cin % 64 == 0 ? TN_BF16_4 : TN_BF16_2;
-        pl.ntiles = cdiv(PL, TNB_PC) * (cin % 64 == 0 ? cin / 64 : cin / 32);
-    } else if (bf16 && cin <= 32 && c1 == 0) {
-        pl.variant = TN_STREAM2_BF;
-        pl.ntiles = cdiv(PL, 64);
-    } else if (bf16) {
-        pl.variant = TN_STREAM4_BF;
-        pl.ntiles = cdiv(PL, 64) * cdiv(cin, 64);
-    } else if (stream_ok && cin <= 32 && c1 == 0 && cin % 2 == 0) {
-        pl.variant = TN_STREAM2;
-        pl.ntiles = cdiv(PL, 64);
-    } else if (stream_ok) {
-        pl.variant = TN_STREAM4;
-        pl.ntiles = cdiv(PL, 64) * cdiv(cin, 64);
-    } else {
-        pl.variant = vec4 ? TN_PLAIN_V4 : TN_PLAIN;
-        pl.ntiles = cdiv(PL, 64) * cdiv(cin, 64);
-    }
-    return pl;
-}
-static int tn_launch_one(const TnPlan& pl, const char* tag, hipStream_t st) {
-    const TnArgs& a = pl.a;
-    const dim3 grid = tn_grid(pl.ntiles, pl.nsplits);
-    const float *A = (const float*)a.A, *x0 = (const float*)a.x0, *x1 = (const float*)a.x1;
-    const unsigned short *A16 = (const unsigned short*)a.A, *h0 = (const unsigned short*)a.x0, *h1 = (const unsigned short*)a.x1;
-    switch (pl.variant) {
-        case TN_BF16_4: FGC_LAUNCH(tag, st, (gemm_tn_bf16_kernel<4>), grid, dim3(TNB_THREADS), 0, A16, a.lda, a.P, h0, h1, a.c0, a.c1, a.shift, a.rows, a.rps, a.slab); break;
-        case TN_BF16_2: FGC_LAUNCH(tag, st, (gemm_tn_bf16_kernel<2>), grid, dim3(TNB_THREADS), 0, A16, a.lda, a.P, h0, h1, a.c0, a.c1, a.shift, a.rows, a.rps, a.slab); break;
-        case TN_STREAM2_BF: FGC_LAUNCH(tag, st, (gemm_tn_stream_kernel<2, true>), grid, dim3(256), 0, A, a.lda, a.P, x0, x1, a.c0, a.c1, a.shift, a.rows, a.rps, a.slab); break;
-        case TN_STREAM4_BF: FGC_LAUNCH(tag, st, (gemm_tn_stream_kernel<4, true>), grid, dim3(256), 0, A, a.lda, a.P, x0, x1, a.c0, a.c1, a.shift, a.rows, a.rps, a.slab); break;
-        case TN_STREAM2: FGC_LAUNCH(tag, st, gemm_tn_stream_kernel<2>, grid, dim3(256), 0, A, a.lda, a.P, x0, x1, a.c0, a.c1, a.shift, a.rows, a.rps, a.slab); break;
-        case TN_STREAM4: FGC_LAUNCH(tag, st, gemm_tn_stream_kernel<4>, grid, dim3(256), 0, A, a.lda, a.P, x0, x1, a.c0, a.c1, a.shift, a.rows, a.rps, a.slab); break;
-        case TN_PLAIN_V4: FGC_LAUNCH(tag, st, (gemm_tn_kernel<true>), grid, dim3(256), 0, A, a.lda, a.P, x0, x1, a.c0, a.c1, a.shift, a.rows, a.rps, a.slab); break;
-        default: FGC_LAUNCH(tag, st, (gemm_tn_kernel<false>), grid, dim3(256), 0, A, a.lda, a.P, x0, x1, a.c0, a.c1, a.shift, a.rows, a.rps, a.slab); break;
-    }
-    FGC_CHECK_LAUNCH("fgc_conv_bwd/dW");
-    return FGC_OK;
-}
-// jobs of one variant in one launch (block ranges in job order; every tn_grid is a multiple of 8 workgroups)
-static int tn_launch_group(int variant, TnJobs& J, int nblocks, const char* tag, hipStream_t st) {
-    if (J.njobs == 0) return FGC_OK;
-    switch (variant) {
-        case TN_BF16_4: FGC_LAUNCH(tag, st, (gemm_tn_bf16_group_kernel<4>), dim3(nblocks), dim3(TNB_THREADS), 0, J); break;
-        case TN_BF16_2: FGC_LAUNCH(tag, st, (gemm_tn_bf16_group_kernel<2>), dim3(nblocks), dim3(TNB_THREADS), 0, J); break;
-        case TN_STREAM2_BF: FGC_LAUNCH(tag, st, (gemm_tn_stream_group_kernel<2, true>), dim3(nblocks), dim3(256), 0, J); break;
-        case TN_STREAM4_BF: FGC_LAUNCH(tag, st, (gemm_tn_stream_group_kernel<4, true>), dim3(nblocks), dim3(256), 0, J); break;
-        case TN_STREAM2: FGC_LAUNCH(tag, st, (gemm_tn_stream_group_kernel<2>), dim3(nblocks), dim3(256), 0, J); break;
-        default: FGC_LAUNCH(tag, st, (gemm_tn_stream_group_kernel<4>), dim3(nblocks), dim3(256), 0, J); break;
-    }
-    FGC_CHECK_LAUNCH("fgc_conv_bwd_reduce/dW");
-    J.njobs = 0;
-    return FGC_OK;
-}
-
-struct BwdWorkspace {
-    float* Wq;        // logits operand
-    float* Wpt;       // data-gradient operand
-    float* db_part;   // [nb][cout]
-    float* dc_part;   // [tiles][12]
-    float* slab;      // gemm_tn partials of [dW0; du; dv]
-    float* rtmp;      // scratch of the fixed-order reductions
-    float* narrow;    // first-layer path (cin <= 8): z buffer, partial slabs (fgc_conv_narrow.hip)
-    size_t bytes;
-    int nb_db, rows_per_db;
-    int splitW;
-};
-
-static BwdWorkspace plan_bwd(const fgc_conv_desc* d, char* base) {
-    BwdWorkspace w;
-    const int cin = d->c0 + d->c1;
-    const ConvGeom g1 = conv_geom(cin, d->cout);
-    const ConvGeom g2 = conv_geom(d->cout, cin);
-    const int opad = (d->cout + 15) / 16 * 16;
+BwdPlan plan_bwd(const fgc_conv_desc* d, char* base) {
+    BwdPlan w;
+    const int cin = d->c0 + d->c1, cout = d->cout;
+    w.pairs = pairs_ok(d);
+    w.narrow = narrow_supported(d);
+    w.bf16 = (d->flags & FGC_CONV_BF16) != 0;
+    w.g1 = conv_geom(cin, cout);
+    w.g2 = conv_geom(cout, cin);
+    w.opad = (cout + 15) / 16 * 16;
+    // ---- the d-logits form.  Deep gathers: every 32-channel pass from one source, 16-byte rows, 32-bit byte offsets
+    const bool k1m = opt(OPT_NO_K1M) != 1;
+    w.deep_ok = k1m && opt(OPT_NO_K1DEEP) != 1 && d->max_deg > 0 && d->max_deg <= KMAX && conv_vec4_ok(d) && cin % 32 == 0 &&
+                (d->c1 == 0 || d->c0 % 32 == 0) && (size_t)d->n * 4 * 128 < 0xFFFFFFFFull;
+    w.k1 = w.pairs ? K1_PAIR : w.bf16 ? K1_BF16 : w.deep_ok ? K1_DEEP : (k1m && d->max_deg > 0 && d->max_deg <= KMAX) ? K1_MFMA : K1_VALU;
+    w.k1_long = d->max_deg > 16;
+    // half tiles (16 nodes, four workgroups per CU) on regular graphs.  FGC_K1_NT16=0: 32-node tiles everywhere
+    w.k1_half = opt(OPT_K1_NT16) != 0 && w.deep_ok && !w.k1_long && !(w.bf16 && cout % 32 != 0);
+    // the dz GEMM of the half-tile kernel on split bf16 operands: the fp32 network's 32-wide layers.  It decides the layout
+    // (and size) of Wq.  NO_K1_SPLIT=1: fp32 MFMA
+    w.k1_split = opt(OPT_NO_K1_SPLIT) != 1 && !w.bf16 && w.k1_half && cout == 32 && !w.pairs;
+    // ---- partial-sum slots.  Pair form (fgc_conv_pair.hip): one db / dc partial per workgroup of its d-logits kernel, and the
+    // weight-gradient GEMM reduces over the n / 4 coarse rows
+    w.k1_nodes = w.pairs ? 4 * pair_blocks_per_wg(cout) : (w.k1_half ? 16 : TILE);
+    w.nred = w.pairs ? (d->n >> 2) : d->n;
+    w.n_dc = cdiv(d->n, w.k1_nodes);
+    // one bias-gradient partial per d-logits tile at every size: the fused prologue of the d-logits kernel (which needs
+    // exactly that) then also serves meshes beyond 131k nodes (it used to stop there: 4096 partials, ds_db launches)
+    w.rows_per_db = cdiv(d->n, w.n_dc);
+    w.nb_db = cdiv(d->n, w.rows_per_db);
+    // which widths the s = dy lrelu'(y) / deg prologue exists for (the bf16 kernel: any width it supports, and both degree
+    // forms keep the LDS copy; fp32 LONG above 32 columns keeps no LDS copy of the tile: a_global)
+    w.fusable = !w.pairs && w.deep_ok && w.nb_db == w.n_dc && opt(OPT_NO_FUSED_DS) != 1 &&
+                (w.bf16 ? ((cout == 32 || cout == 64 || cout == 128) && opt(OPT_NO_FUSED_DS_BF16) != 1)
+                        : ((cout == 32 || cout == 64 || (cout == 128 && w.k1_half && opt(OPT_NO_FUSED_DS128) != 1)) &&
+                           !(w.k1_long && cout > 32)));
+    // ---- packed operands (element counts: fragments of 512 bf16 per (k-step, column tile), or floats)
+    const size_t wq_f32 = (size_t)w.g1.passes * w.opad * w.g1.kpass, wq_frags = (size_t)w.g1.passes * (cout >> 5) * 18;
+    w.wq = w.pairs ? PackedOperand{PACK_LOGIT, 0}
+         : w.bf16 ? PackedOperand{PACK_LOGIT_BF16, wq_frags * 512}
+         : w.k1_split ? PackedOperand{PACK_LOGIT_SPLIT, wq_frags * 3 * 512} : PackedOperand{PACK_LOGIT, wq_f32};
+    w.wpt = PackedOperand{w.bf16 ? PACK_DATA_BF16 : PACK_DATA, (size_t)w.g2.passes * w.g2.kpass * w.g2.npad};
+    // ---- workspace
     size_t off = 0;
     auto take = [&](size_t nfloats) {
         float* ptr = base ? (float*)(base + off) : nullptr;
         off += align_up(nfloats * 4, 256);
         return ptr;
     };
-    w.Wq = take(k1_wq_floats(d));
-    w.Wpt = take((size_t)g2.passes * g2.kpass * g2.npad);
-    // pair form (fgc_conv_pair.hip): one db / dc partial per workgroup of its d-logits kernel (k1n fine nodes each), and the
-    // weight-gradient GEMM reduces over the n / 4 coarse rows
-    const bool pairs = pairs_ok(d);
-    const int k1n = pairs ? 4 * pair_blocks_per_wg(d->cout) : k1_nodes(d);
-    const int nred = pairs ? (d->n >> 2) : d->n;
-    // one bias-gradient partial per d-logits tile at every size: the fused prologue of the d-logits kernel (which needs
-    // exactly that) then also serves meshes beyond 131k nodes (it used to stop there: 4096 partials, ds_db launches)
-    w.nb_db = cdiv(d->n, k1n);
-    w.rows_per_db = cdiv(d->n, w.nb_db);
-    w.nb_db = cdiv(d->n, w.rows_per_db);
-    w.db_part = take((size_t)w.nb_db * d->cout);
-    w.dc_part = take((size_t)cdiv(d->n, k1n) * 12);
-    w.splitW = tn_splits(FGC_M * d->cout + 24, cin, nred);
-    if ((d->flags & FGC_CONV_BF16) && tn_bf16_ok(FGC_M * d->cout + 24, d->c0, d->c1)) {
+    // (room for either layout of Wq wherever the shape allows the split one: the workspace a caller sized before changing
+    //  NO_K1_SPLIT stays large enough; the operand itself must be packed again after such a change, like every packed operand)
+    w.Wq = take((!w.bf16 && cout == 32) ? std::max(wq_f32, wq_frags * 3 * 256) : wq_f32);
+    w.Wpt = take((size_t)w.g2.passes * w.g2.kpass * w.g2.npad);
+    w.db_part = take((size_t)w.nb_db * cout);
+    w.dc_part = take((size_t)w.n_dc * 12);
+    const int PL = FGC_M * cout + 24;
+    w.splitW = tn_splits(PL, cin, w.nred);
+    if (w.bf16 && tn_bf16_ok(PL, d->c0, d->c1)) {
         // the bf16 kernel's workgroups own up to 320 x 64 of the product: one or two per CU in all
         const int target = (int)opt(OPT_TNB_WGS);   // (developer knob)
-        const int tiles = cdiv(FGC_M * d->cout + 24, TNB_PC) * cdiv(cin, 64);
-        w.splitW = tn_balanced_splits(target / tiles, cdiv(nred, 256), nred);
+        w.splitW = tn_balanced_splits(target / (cdiv(PL, TNB_PC) * cdiv(cin, 64)), cdiv(w.nred, 256), w.nred);
     }
-    w.slab = take((size_t)w.splitW * (FGC_M * d->cout + 24) * cin);
-    w.rtmp = take(reduce_tmp_floats(w.splitW, (size_t)FGC_M * d->cout * cin) + 2 * reduce_tmp_floats(w.splitW, (size_t)FGC_M * cin) +
-                  reduce_tmp_floats(cdiv(d->n, k1n), 12) + reduce_tmp_floats(w.nb_db, d->cout) + 64);
+    w.slab = take((size_t)w.splitW * PL * cin);
+    w.rtmp = take(reduce_tmp_floats(w.splitW, (size_t)FGC_M * cout * cin) + 2 * reduce_tmp_floats(w.splitW, (size_t)FGC_M * cin) +
+                  reduce_tmp_floats(w.n_dc, 12) + reduce_tmp_floats(w.nb_db, cout) + 64);
     // (the first layer's scratch ends with the scratch of its fixed-order sums; the db partials of stage 1 are summed with
     //  them and need theirs behind it - it used to be missing: 64 groups x cout floats written past the workspace)
-    w.narrow = narrow_supported(d) ? take(narrow_bwd_floats(d) + reduce_tmp_floats(w.nb_db, d->cout) + 64) : nullptr;
+    w.narrow_ws = w.narrow ? take(narrow_bwd_floats(d) + reduce_tmp_floats(w.nb_db, cout) + 64) : nullptr;
     w.bytes = off;
     return w;
 }
 
+// Everything fgc_conv_pack branches on when it chooses what to write into a layer's workspaces, as one number: a caller keeps
+// it with the packed operands (fgc_conv_desc.packed_layout) and the FGC_CONV_PACKED calls compare.
+static uint64_t layout_id_of(const BwdPlan& w) {
+    return 1ull | (uint64_t)w.narrow << 1 | (uint64_t)w.pairs << 2 | (uint64_t)w.k1_split << 3 | (uint64_t)w.bf16 << 4;
+}
+uint64_t conv_layout_id(const fgc_conv_desc* d) { return layout_id_of(plan_bwd(d, nullptr)); }
+
+// What a call adds to the plan: the stages it asks for and what the alignment of its tensors allows.  Evaluated once per
+// call; the ds_db stage and the d-logits launch both read it.
+struct BwdCall {
+    int stages;
+    bool narrow_path;   // first layer over a narrow input, no input gradient wanted: vector-ALU path, no transposed graph, no r
+    bool fuse_ds;       // the d-logits kernel computes s (and the db partials) in its prologue: no ds_db launch
+    bool ds_vec;        // ds_db_vec_kernel serves these tensors
+    int okg;            // deep form: compile-time column groups of the ds tile (cout / 16), 0 = any width
+    bool a_global;      // deep LONG form: 24 edge slots + the ds tile of a 64- or 128-wide layer do not fit twice into a CU's LDS
+};
+static BwdCall bwd_call(const BwdPlan& w, const fgc_conv_desc* d, const fgc_conv_bwd_io* io) {
+    BwdCall c;
+    const int cout = d->cout;
+    auto al16 = [](const void* a, const void* b = nullptr, const void* e = nullptr) {
+        return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)e) % 16) == 0;
+    };
+    c.stages = io->stages ? io->stages : 15;
+    c.narrow_path = io->dx0 == nullptr && w.narrow;
+    const bool pool_al = !io->pool_dy || al16(io->pool_y, io->pool_dy);
+    // one launch and one pass over dy / y less, when stages 1 and 2 come in the same call (a facet-sharded caller runs stage
+    // 1 on its own: the halo rows of s travel under the d-logits kernel)
+    c.fuse_ds = (c.stages & 3) == 3 && !c.narrow_path && w.fusable && al16(io->ds, io->dy) && (!d->act || al16(io->y)) &&
+                (!io->pool_dy || al16(io->y)) && pool_al;
+    const int vw = w.bf16 ? 8 : 4;
+    c.ds_vec = cout % vw == 0 && 256 % (cout / vw) == 0 && cout <= 256 && al16(io->dy, io->y ? io->y : io->dy, io->ds) && pool_al &&
+               opt(OPT_NO_DS_VEC) != 1;
+    const bool al = al16(io->ds);
+    // (OKG = 8 only for its prologue: s and db in this launch)
+    c.okg = !al ? 0 : cout == 32 ? 2 : cout == 64 ? 4 : (cout == 128 && w.k1_half && c.fuse_ds) ? 8 : 0;
+    c.a_global = w.k1 == K1_DEEP && w.k1_long && cout > 32 && cout % 16 == 0 && al;
+    return c;
+}
+
 // the weight-gradient GEMM of a layer in the fine or in the pair form (not the narrow first layer: narrow_tn_operands)
-static TnPlan layer_tn_plan(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, const BwdWorkspace& w) {
-    const int cin = d->c0 + d->c1, cout = d->cout;
-    const int PL = FGC_M * cout + 24;
-    const bool bf16 = (d->flags & FGC_CONV_BF16) != 0;
-    if (pairs_ok(d)) {      // K = the n / 4 coarse rows, one source
-        const int nc = d->n >> 2;
-        return tn_plan_of(bf16, true, true, io->r, PL, d->x0, nullptr, d->c0, 0, 0, nc, tn_rows_per_slab(nc, w.splitW), w.slab,
-                          io_r_ld(io, cout, bf16));
-    }
+static TnPlan layer_tn_plan(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, const BwdPlan& w) {
+    const int cout = d->cout, PL = FGC_M * cout + 24;
+    const int rps = tn_rows_per_slab(w.nred, w.splitW), rld = io_r_ld(io, cout, w.bf16);
+    if (w.pairs)      // K = the n / 4 coarse rows, one source
+        return tn_plan_of(w.bf16, true, true, io->r, PL, d->x0, nullptr, d->c0, 0, 0, w.nred, rps, w.slab, rld);
     const bool v4 = conv_vec4_ok(d) && (cout % 4 == 0) && ((uintptr_t)io->r % 16 == 0);
     const bool stream_ok = v4 && !(opt(OPT_NO_TNSTREAM) == 1);
-    (void)cin;
-    return tn_plan_of(bf16, v4, stream_ok, io->r, PL, d->x0, d->x1, d->c0, d->c1, d->shift, d->n, tn_rows_per_slab(d->n, w.splitW),
-                      w.slab, io_r_ld(io, cout, bf16));
+    return tn_plan_of(w.bf16, v4, stream_ok, io->r, PL, d->x0, d->x1, d->c0, d->c1, d->shift, w.nred, rps, w.slab, rld);
 }
 
 // the five fixed-order sums behind a layer's parameter gradients (slabs of the weight-gradient GEMM, db and dc partials)
-static void conv_param_jobs(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, const BwdWorkspace& w, RedJob* jobs) {
+static void conv_param_jobs(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, const BwdPlan& w, RedJob* jobs) {
     const int cin = d->c0 + d->c1, cout = d->cout;
     const int P = FGC_M * cout, PL = P + 24;
-    const bool pairs = pairs_ok(d);
-    const int nred = pairs ? (d->n >> 2) : d->n;
-    const int ns = cdiv(nred, tn_rows_per_slab(nred, w.splitW));
+    const int ns = cdiv(w.nred, tn_rows_per_slab(w.nred, w.splitW));
     const size_t sst = (size_t)PL * cin;
     jobs[0] = RedJob{w.slab, sst, ns, P * cin, cin, cin, io->dW0, w.rtmp};
     jobs[1] = RedJob{w.slab + (size_t)P * cin, sst, ns, FGC_M * cin, cin, cin, io->du};
     jobs[2] = RedJob{w.slab + (size_t)(P + 12) * cin, sst, ns, FGC_M * cin, cin, cin, io->dv};
     jobs[3] = RedJob{w.db_part, (size_t)cout, w.nb_db, cout, cout, cout, io->db};
-    jobs[4] = RedJob{w.dc_part, (size_t)12, cdiv(d->n, pairs ? 4 * pair_blocks_per_wg(cout) : k1_nodes(d)), 12, 12, FGC_M, io->dc};
+    jobs[4] = RedJob{w.dc_part, (size_t)12, w.n_dc, 12, 12, FGC_M, io->dc};
+}
+
+// stage 1 as a launch of its own: s = dy * lrelu'(y) / deg and the db partials (summed with the other parameter gradients, stage 8)
+static int launch_ds_db(const BwdPlan& w, const BwdCall& c, const fgc_conv_desc* d, const fgc_conv_bwd_io* io, hipStream_t st) {
+    const LaunchCfg cfg{"ds_db_kernel", "fgc_conv_bwd/ds", st, w.nb_db, 256, 0};
+    const float *yy = io->y ? io->y : io->dy, *pool_y = io->pool_dy ? io->pool_y : nullptr;
+    const bool out_bf16 = w.bf16 && !c.narrow_path;     // (a narrow first layer keeps its ds in fp32)
+    if (!c.ds_vec) {
+        int cp2 = 1;
+        while (cp2 < d->cout) cp2 <<= 1;
+        return launch_kernel<ds_db_kernel>(cfg, io->dy, io->y, d->rowptr, d->n, d->cout, cp2, d->act, d->alpha, d->bias_mask, w.rows_per_db,
+                                           io->ds, w.db_part, w.bf16 ? 1 : 0, out_bf16 ? 1 : 0, pool_y, io->pool_dy);
+    }
+    auto vec = [&](auto bf_in, auto bf_out) {
+        return launch_kernel<ds_db_vec_kernel<decltype(bf_in)::value, decltype(bf_out)::value>>(
+            cfg, io->dy, yy, d->rowptr, d->n, d->cout, d->act, d->alpha, d->bias_mask, w.rows_per_db, io->ds, w.db_part, pool_y, io->pool_dy);
+    };
+    if (!w.bf16) return vec(std::false_type{}, std::false_type{});
+    return out_bf16 ? vec(std::true_type{}, std::true_type{}) : vec(std::true_type{}, std::false_type{});
+}
+
+// stage 2: the d-logits kernel the plan chose, with the column groups / ds source this call's pointers allow
+static int launch_k1(const BwdPlan& w, const BwdCall& c, const fgc_conv_desc* d, const CoreParams& p, const LogitParams& lp,
+                     hipStream_t st) {
+    const int nt = w.k1_nodes, cout = d->cout;
+    // LDS: aggregate tile + soft-assignment table (16 slots where no node has more edges) + degrees, the ds tile, 48 floats of
+    // reduction scratch.  (__syncthreads_or owns 256 B of static LDS: ask for exactly what this launch needs)
+    const int qs = ((w.k1 == K1_DEEP || w.k1 == K1_BF16) && !w.k1_long) ? 16 : KMAX;
+    const size_t core = smem_core_bytes(w.k1 == K1_BF16 ? ZSTRIDE_BF / 2 : w.g1.zstride, qs, nt);
+    const size_t tile = w.k1 == K1_BF16 ? (size_t)nt * (cout * 2 + 32) : lp.a_global ? 0 : (size_t)nt * lp.ostride * 4;
+    LaunchCfg cfg{"conv_bwd_logits_deep_kernel", "fgc_conv_bwd/logits_mfma", st, cdiv(d->n, nt), NTHREADS, core + tile + 48 * 4};
+    switch (w.k1) {
+        case K1_BF16:
+            cfg.name = "conv_bwd_logits_bf16_kernel";
+            cfg.what = "fgc_conv_bwd/logits_bf16";
+            if (w.k1_long) return launch_kernel<conv_bwd_logits_bf16_kernel<true>>(cfg, p, lp);
+            if (w.k1_half) return launch_kernel<conv_bwd_logits_bf16_kernel<false, 16, 4>>(cfg, p, lp);
+            return launch_kernel<conv_bwd_logits_bf16_kernel<false>>(cfg, p, lp);
+        case K1_DEEP:
+            if (w.k1_split) {
+                // (the packed operand is in the split layout whatever the pointers: no other kernel can take it)
+                FGC_CHECK_ARG(c.okg == 2, "fgc_conv_bwd: ds must be 16-byte aligned (cout=%d)", cout);
+                return launch_kernel<conv_bwd_logits_deep_kernel<false, 2, 16, 4, true>>(cfg, p, lp);
+            }
+            if (w.k1_half) switch (c.okg) {
+                case 2: return launch_kernel<conv_bwd_logits_deep_kernel<false, 2, 16, 4>>(cfg, p, lp);
+                case 4: return launch_kernel<conv_bwd_logits_deep_kernel<false, 4, 16, 4>>(cfg, p, lp);
+                case 8: return launch_kernel<conv_bwd_logits_deep_kernel<false, 8, 16, 4>>(cfg, p, lp);
+                default: return launch_kernel<conv_bwd_logits_deep_kernel<false, 0, 16, 4>>(cfg, p, lp);
+            }
+            if (w.k1_long) switch (c.okg) {
+                case 2: return launch_kernel<conv_bwd_logits_deep_kernel<true, 2>>(cfg, p, lp);
+                case 4: return launch_kernel<conv_bwd_logits_deep_kernel<true, 4>>(cfg, p, lp);
+                default: return launch_kernel<conv_bwd_logits_deep_kernel<true, 0>>(cfg, p, lp);
+            }
+            switch (c.okg) {
+                case 2: return launch_kernel<conv_bwd_logits_deep_kernel<false, 2>>(cfg, p, lp);
+                case 4: return launch_kernel<conv_bwd_logits_deep_kernel<false, 4>>(cfg, p, lp);
+                default: return launch_kernel<conv_bwd_logits_deep_kernel<false, 0>>(cfg, p, lp);
+            }
+        case K1_MFMA:
+            cfg.name = "conv_bwd_logits_mfma_kernel";
+            return conv_vec4_ok(d) ? launch_kernel<conv_bwd_logits_mfma_kernel<true>>(cfg, p, lp)
+                                   : launch_kernel<conv_bwd_logits_mfma_kernel<false>>(cfg, p, lp);
+        default:
+            cfg.what = "fgc_conv_bwd/logits";
+            if (conv_vec4_ok(d)) {
+                cfg.name = "conv_bwd_logits_kernel<LPN, true>";
+                return launch_kernel<conv_bwd_logits_kernel<8, true>>(cfg, p, lp);
+            }
+            cfg.name = "conv_bwd_logits_kernel<LPN, false>";
+            return launch_kernel<conv_bwd_logits_kernel<8, false>>(cfg, p, lp);
+    }
 }
 
 }  // namespace fgc
@@ -2123,71 +1625,36 @@ extern "C" int fgc_conv_bwd_needs_exchange(const fgc_conv_desc* d, const fgc_con
     return (io->dx0 == nullptr && narrow_supported(d)) ? 0 : 1;
 }
 
-template <int LPN>
-static int launch_logits(const CoreParams& p, const LogitParams& lp, bool vec4, size_t smem, hipStream_t st) {
-    const int grid = cdiv(p.n, TILE);
-    if (vec4) {
-        hipFuncSetAttribute((const void*)conv_bwd_logits_kernel<LPN, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-        FGC_LAUNCH("conv_bwd_logits_kernel<LPN, true>", st, (conv_bwd_logits_kernel<LPN, true>), dim3(grid), dim3(NTHREADS), smem, p, lp);
-    } else {
-        hipFuncSetAttribute((const void*)conv_bwd_logits_kernel<LPN, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-        FGC_LAUNCH("conv_bwd_logits_kernel<LPN, false>", st, (conv_bwd_logits_kernel<LPN, false>), dim3(grid), dim3(NTHREADS), smem, p, lp);
-    }
-    FGC_CHECK_LAUNCH("fgc_conv_bwd/logits");
-    return FGC_OK;
-}
-
-template <int LPN>
-static int launch_data(const CoreParams& p, const DataEpilogue& ep, bool vec4, size_t smem, hipStream_t st) {
-    const int grid = core_grid(p);
-    if (vec4) {
-        hipFuncSetAttribute((const void*)conv_bwd_data_kernel<LPN, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-        FGC_LAUNCH("conv_bwd_data_kernel<LPN, true>", st, (conv_bwd_data_kernel<LPN, true>), dim3(grid), dim3(NTHREADS), smem, p, ep);
-    } else {
-        hipFuncSetAttribute((const void*)conv_bwd_data_kernel<LPN, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-        FGC_LAUNCH("conv_bwd_data_kernel<LPN, false>", st, (conv_bwd_data_kernel<LPN, false>), dim3(grid), dim3(NTHREADS), smem, p, ep);
-    }
-    FGC_CHECK_LAUNCH("fgc_conv_bwd/data");
-    return FGC_OK;
-}
-
 extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, void* workspace,
                             size_t workspace_bytes, void* stream) {
     FGC_OPT_SCOPE(d);
     int rc = validate_conv_desc(d, "fgc_conv_bwd");
     if (rc) return rc;
+    const int cin = d->c0 + d->c1, cout = d->cout;
+    const BwdPlan w = plan_bwd(d, (char*)workspace);
+    const bool bf16 = w.bf16;
     FGC_CHECK_ARG(io != nullptr, "fgc_conv_bwd: null io");
     FGC_CHECK_ARG(io->trowptr && io->tcol && io->tedge, "fgc_conv_bwd: transposed CSR missing");
     FGC_CHECK_ARG(io->ag && io->dy && io->ds && io->dl && io->dag && io->r, "fgc_conv_bwd: null buffer");
     FGC_CHECK_ARG(!d->act || io->y, "fgc_conv_bwd: y required when an activation was applied");
     FGC_CHECK_ARG(io->dW0 && io->db && io->du && io->dc && io->dv, "fgc_conv_bwd: null parameter-gradient pointer");
     FGC_CHECK_ARG(io->dx0 != nullptr || io->dx1 == nullptr, "fgc_conv_bwd: dx1 without dx0");
-    FGC_CHECK_ARG(io_r_ld_ok(io, d->cout, (d->flags & FGC_CONV_BF16) != 0),
+    FGC_CHECK_ARG(io_r_ld_ok(io, cout, bf16),
                   "fgc_conv_bwd: r_ld = %d is not a row stride of r for cout = %d (0, or >= %d and congruent to it modulo %d)",
-                  io->r_ld, d->cout, FGC_M * d->cout + 24, (d->flags & FGC_CONV_BF16) ? 8 : 4);
-    FGC_CHECK_ARG(!(io->flags & FGC_CONV_PACKED) || d->packed_layout == 0 || d->packed_layout == conv_layout_id(d),
+                  io->r_ld, cout, FGC_M * cout + 24, bf16 ? 8 : 4);
+    FGC_CHECK_ARG(!(io->flags & FGC_CONV_PACKED) || d->packed_layout == 0 || d->packed_layout == layout_id_of(w),
                   "fgc_conv_bwd: FGC_CONV_PACKED, but the operands were packed in layout %llu and the options now select %llu "
                   "(an option changed between fgc_conv_pack and this call)", (unsigned long long)d->packed_layout,
-                  (unsigned long long)conv_layout_id(d));
-    FGC_CHECK_ARG(workspace && workspace_bytes >= fgc_conv_bwd_workspace_bytes(d) && (uintptr_t)workspace % 16 == 0,
-                  "fgc_conv_bwd: workspace too small or misaligned (%zu < %zu)", workspace_bytes,
-                  fgc_conv_bwd_workspace_bytes(d));
+                  (unsigned long long)layout_id_of(w));
+    FGC_CHECK_ARG(workspace && workspace_bytes >= w.bytes && (uintptr_t)workspace % 16 == 0,
+                  "fgc_conv_bwd: workspace too small or misaligned (%zu < %zu)", workspace_bytes, w.bytes);
     hipStream_t st = (hipStream_t)stream;
-    const int cin = d->c0 + d->c1;
-    const int cout = d->cout;
-    const BwdWorkspace w = plan_bwd(d, (char*)workspace);
-    const ConvGeom g1 = conv_geom(cin, cout);   // gathers x (cin wide)
-    const ConvGeom g2 = conv_geom(cout, cin);   // gathers s (cout wide), GEMM N = cin
-    const int opad = (cout + 15) / 16 * 16;
-    const int ostride = opad + 8;
-
-    const int stages = io->stages ? io->stages : 15;
-    const bool bf16 = (d->flags & FGC_CONV_BF16) != 0;
-    if (pairs_ok(d)) {
+    const BwdCall c = bwd_call(w, d, io);
+    const int stages = c.stages;
+    const bool pack_here = !(io->flags & FGC_CONV_PACKED);   // else fgc_conv_pack wrote the operands
+    PackJob pjobs[2];
+    size_t ptotals[2];
+    if (w.pairs) {
         // pair form: B1 (s, db, dt, dl, da, dc) on the pair graph, then the data kernel and the weight-gradient GEMM of a
         // convolution over the n / 4 coarse rows whose gathered operand is dt (one row per pair)
         FGC_CHECK_ARG(io->tpair_rowptr && io->tpair_col && io->tpair_edge && io->dt && d->max_pair_in_deg > 0,
@@ -2195,24 +1662,13 @@ extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, v
         FGC_CHECK_ARG(!io->pool_dy, "fgc_conv_bwd: the pair form has no pooled output");
         // (a tile list names 32-row tiles of the n / 4 COARSE rows the data kernel runs over: a facet-sharded caller computes the
         //  tiles whose in-pairs are all its own while the dt / d-logit rows of the others travel)
-        FGC_CHECK_ARG(io->data_tile_list == nullptr || (io->n_data_tiles >= 0 && io->n_data_tiles <= cdiv(d->n >> 2, TILE)),
-                      "fgc_conv_bwd: pair form: n_data_tiles=%d outside [0, %d]", io->n_data_tiles, cdiv(d->n >> 2, TILE));
+        FGC_CHECK_ARG(io->data_tile_list == nullptr || (io->n_data_tiles >= 0 && io->n_data_tiles <= cdiv(w.nred, TILE)),
+                      "fgc_conv_bwd: pair form: n_data_tiles=%d outside [0, %d]", io->n_data_tiles, cdiv(w.nred, TILE));
         FGC_CHECK_ARG(((uintptr_t)io->dt | (uintptr_t)io->dy | (uintptr_t)io->dl | (uintptr_t)io->dag | (uintptr_t)io->r) % 16 == 0,
                       "fgc_conv_bwd: the pair form needs 16-byte aligned buffers");
-        const int nc = d->n >> 2;
-        if ((stages & 4) && !(io->flags & FGC_CONV_PACKED) && bf16) {
-            PackJobs J;
-            J.njobs = 1;
-            const size_t t2 = (size_t)g2.passes * 9 * (g2.npad >> 4) * 512;
-            J.job[0] = PackJob{d->W0, w.Wpt, 5, cin, cout, cout, cin, g2.npad, g2.kc, g2.kpass, g2.passes, 0, 0};
-            J.nblocks = cdiv((int)t2, 1024);
-            FGC_LAUNCH("pack_many_kernel", st, pack_many_kernel, dim3(J.nblocks), dim3(256), 0, J);
-            FGC_CHECK_LAUNCH("fgc_conv_bwd/pack");
-        } else if ((stages & 4) && !(io->flags & FGC_CONV_PACKED)) {
-            const size_t tot2 = (size_t)g2.passes * g2.kpass * g2.npad;
-            FGC_LAUNCH("pack_weight_kernel", st, pack_weight_kernel, dim3(cdiv((int)tot2, 1024)), dim3(256), 0, d->W0, w.Wpt, cin, cout, cout,
-                       cin, g2.npad, g2.kc, g2.kpass, g2.passes, 1);
-            FGC_CHECK_LAUNCH("fgc_conv_bwd/pack");
+        if ((stages & 4) && pack_here) {
+            rc = launch_pack_jobs(pjobs, ptotals, conv_bwd_pack_jobs(d, w, pjobs, ptotals), "fgc_conv_bwd/pack", st);
+            if (rc) return rc;
         }
         if (stages & 3) {
             rc = launch_pair_bwd_logits(d, io, w.db_part, w.dc_part, st);
@@ -2220,11 +1676,11 @@ extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, v
         }
         if (stages & 4) {
             CoreParams p;
-            fill_core_params(p, g2, nc, io->tpair_rowptr, io->tpair_col, io->tpair_edge, io->dt, nullptr, cout, 0, 0, cin, io->ag,
+            fill_core_params(p, w.g2, w.nred, io->tpair_rowptr, io->tpair_col, io->tpair_edge, io->dt, nullptr, cout, 0, 0, cin, io->ag,
                              0, 12, 0, w.Wpt);
             DataEpilogue ep{io->dl, io->dag, io->r, io_r_ld(io, cout, bf16), d->u, d->v, cin, d->c0, 0, 0,
                             io->dx0, nullptr, io->accumulate0, 0};
-            const size_t smem = conv_smem_bytes(g2, (size_t)TILE * 24 * 4);
+            const size_t smem = conv_smem_bytes(w.g2, (size_t)TILE * 24 * 4);
             FGC_CHECK_ARG(w8_erow_supported(p, d->max_pair_in_deg) && (!bf16 || w8_bf16_supported(p, d->max_pair_in_deg)),
                           "fgc_conv_bwd: pair form: unsupported shape (cin=%d cout=%d max_pair_in_deg=%d)", cin, cout,
                           d->max_pair_in_deg);
@@ -2235,263 +1691,80 @@ extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, v
                 if (rc) return rc;
             }
         }
-        if (stages & 8) {
-            if (!(io->flags & FGC_CONV_DEFER_DW)) {
-                rc = tn_launch_one(layer_tn_plan(d, io, w), "gemm_tn_kernel:dW", st);
-                if (rc) return rc;
-            }
-            if (!(io->flags & FGC_CONV_DEFER_REDUCE)) {
-                RedJob jobs[5];
-                conv_param_jobs(d, io, w, jobs);
-                rc = reduce_jobs("reduce:params", jobs, 5, nullptr, st);
-                if (rc) return rc;
-            }
+    } else {
+        FGC_CHECK_ARG(io->data_tile_list == nullptr || (io->n_data_tiles >= 0 && io->n_data_tiles <= cdiv(d->n, TILE)),
+                      "fgc_conv_bwd: n_data_tiles=%d outside [0, %d]", io->n_data_tiles, cdiv(d->n, TILE));
+        FGC_CHECK_ARG(!bf16 || c.narrow_path || (w.deep_ok && cout % 32 == 0),
+                      "fgc_conv_bwd: FGC_CONV_BF16 needs widths that are multiples of 32, 16-byte aligned tensors and degrees <= %d "
+                      "(cin=%d cout=%d max_deg=%d)", KMAX, cin, cout, d->max_deg);
+        FGC_CHECK_ARG(!io->pool_dy || (io->pool_y && io->y && d->n % 4 == 0),
+                      "fgc_conv_bwd: pool_dy needs pool_y, y and a row count that is a multiple of 4 (n=%d)", d->n);
+        if ((stages & 1) && !c.fuse_ds && !(c.narrow_path && narrow_fuses_ds(d, io))) {
+            rc = launch_ds_db(w, c, d, io, st);
+            if (rc) return rc;
         }
-        return FGC_OK;
-    }
-    FGC_CHECK_ARG(io->data_tile_list == nullptr || (io->n_data_tiles >= 0 && io->n_data_tiles <= cdiv(d->n, TILE)),
-                  "fgc_conv_bwd: n_data_tiles=%d outside [0, %d]", io->n_data_tiles, cdiv(d->n, TILE));
-    // The deep d-logits kernel of the 32- and 64-wide layers can compute s (and the db partials) in its prologue: one
-    // launch and one pass over dy / y less, when stages 1 and 2 come in the same call (a facet-sharded caller runs stage
-    // 1 on its own: the halo rows of s travel under the d-logits kernel)
-    const bool narrow_path = io->dx0 == nullptr && w.narrow;
-    const bool deep_ok = !narrow_path && g1.lpn == 8 && d->max_deg > 0 && d->max_deg <= KMAX && conv_vec4_ok(d) &&
-                         cin % 32 == 0 && (d->c1 == 0 || d->c0 % 32 == 0) && (size_t)d->n * 4 * 128 < 0xFFFFFFFFull &&
-                         !(opt(OPT_NO_K1M) == 1) &&
-                         !(opt(OPT_NO_K1DEEP) == 1);
-    FGC_CHECK_ARG(!bf16 || narrow_path || (deep_ok && cout % 32 == 0),
-                  "fgc_conv_bwd: FGC_CONV_BF16 needs widths that are multiples of 32, 16-byte aligned tensors and degrees <= %d "
-                  "(cin=%d cout=%d max_deg=%d)", KMAX, cin, cout, d->max_deg);
-    FGC_CHECK_ARG(!io->pool_dy || (io->pool_y && io->y && d->n % 4 == 0),
-                  "fgc_conv_bwd: pool_dy needs pool_y, y and a row count that is a multiple of 4 (n=%d)", d->n);
-    // (the bf16 kernel: any width it supports - 32, 64, 128 - and both degree forms keep the LDS copy)
-    const bool fuse_ds = (stages & 3) == 3 && deep_ok && w.nb_db == cdiv(d->n, k1_nodes(d)) &&
-                         (bf16 ? (!narrow_path && (cout == 32 || cout == 64 || cout == 128) &&
-                                  !(opt(OPT_NO_FUSED_DS_BF16) == 1))
-                               : ((cout == 32 || cout == 64 || (cout == 128 && k1_nodes(d) == 16 &&
-                                                                   !(opt(OPT_NO_FUSED_DS128) == 1))) &&
-                                  !(d->max_deg > 16 && cout > 32))) &&   // that form keeps no LDS copy of the tile (a_global)
-                         ((uintptr_t)io->ds % 16) == 0 && ((uintptr_t)io->dy % 16) == 0 &&
-                         (!d->act || ((uintptr_t)io->y % 16) == 0) &&
-                         (!io->pool_dy || (((uintptr_t)io->y | (uintptr_t)io->pool_y | (uintptr_t)io->pool_dy) % 16) == 0) &&
-                         !(opt(OPT_NO_FUSED_DS) == 1);
-    // s = dy*lrelu'(y)/deg, db partials
-    if ((stages & 1) && !fuse_ds && !(narrow_path && narrow_fuses_ds(d, io))) {
-        int cp2 = 1;
-        while (cp2 < cout) cp2 <<= 1;
-        const int vw = bf16 ? 8 : 4;
-        const float* yy = io->y ? io->y : io->dy;
-        const bool vec = cout % vw == 0 && 256 % (cout / vw) == 0 && cout <= 256 &&
-                         (((uintptr_t)io->dy | (uintptr_t)yy | (uintptr_t)io->ds) % 16) == 0 &&
-                         (!io->pool_dy || (((uintptr_t)io->pool_y | (uintptr_t)io->pool_dy) % 16) == 0) &&
-                         !(opt(OPT_NO_DS_VEC) == 1);
-#define FGC_DS_VEC(BI, BO)                                                                                                  \
-    FGC_LAUNCH("ds_db_kernel", st, (ds_db_vec_kernel<BI, BO>), dim3(w.nb_db), dim3(256), 0, io->dy, yy, d->rowptr, d->n, cout,   \
-               d->act, d->alpha, d->bias_mask, w.rows_per_db, io->ds, w.db_part, io->pool_dy ? io->pool_y : nullptr, io->pool_dy)
-        if (vec && bf16 && !narrow_path) FGC_DS_VEC(true, true);
-        else if (vec && bf16) FGC_DS_VEC(true, false);
-        else if (vec) FGC_DS_VEC(false, false);
-        else
-        FGC_LAUNCH("ds_db_kernel", st, ds_db_kernel, dim3(w.nb_db), dim3(256), 0, io->dy, io->y, d->rowptr, d->n, cout, cp2,
-                   d->act, d->alpha, d->bias_mask, w.rows_per_db, io->ds, w.db_part, bf16 ? 1 : 0,
-                   (bf16 && !narrow_path) ? 1 : 0, io->pool_dy ? io->pool_y : nullptr, io->pool_dy);
-#undef FGC_DS_VEC
-        FGC_CHECK_LAUNCH("fgc_conv_bwd/ds");   // db partials are summed with the other parameter gradients (stage 8)
-    }
-    // first layer over a narrow input (no input gradient wanted): vector-ALU path, no transposed graph, no r buffer
-    if (io->dx0 == nullptr && w.narrow) {
+        if (c.narrow_path) {
+            if (stages & 2) {
+                rc = narrow_bwd_logits(d, io, w.narrow_ws, w.db_part, st);
+                if (rc) return rc;
+            }
+            if (stages & 8) {
+                rc = narrow_bwd_params(d, io, w.narrow_ws, w.db_part, narrow_db_partials(d, io, w.nb_db),
+                                       (io->flags & FGC_CONV_DEFER_REDUCE) ? 1 : 3, nullptr, st);
+                if (rc) return rc;
+            }
+            return FGC_OK;
+        }
+        if ((stages & 6) && pack_here) {
+            rc = launch_pack_jobs(pjobs, ptotals, conv_bwd_pack_jobs(d, w, pjobs, ptotals), "fgc_conv_bwd/pack", st);
+            if (rc) return rc;
+        }
+        // K1
         if (stages & 2) {
-            rc = narrow_bwd_logits(d, io, w.narrow, w.db_part, st);
-            if (rc) return rc;
+            CoreParams p;
+            fill_core_params(p, w.g1, d->n, d->rowptr, d->col, nullptr, d->x0, d->x1, d->c0, d->c1, d->shift, cout, io->ag,
+                             d->shift, 0, 12, nullptr);
+            LogitParams lp{io->ds, cout, w.opad, w.opad + 8, w.Wq, io->dl, io->dag, w.dc_part};
+            if (c.fuse_ds) {
+                lp.dy = io->dy;
+                lp.y = io->y ? io->y : io->dy;
+                lp.act = d->act;
+                lp.bias_mask = d->bias_mask;
+                lp.alpha = d->alpha;
+                lp.ds_out = io->ds;
+                lp.db_part = w.db_part;
+                lp.pool_y = io->pool_dy ? io->pool_y : nullptr;
+                lp.pool_dy = io->pool_dy;
+            }
+            lp.a_global = c.a_global;
+            rc = launch_k1(w, c, d, p, lp, st);
+            if (rc) return rc;   // dc partials: stage 8
         }
-        if (stages & 8) {
-            rc = narrow_bwd_params(d, io, w.narrow, w.db_part, narrow_db_partials(d, io, w.nb_db),
-                                   (io->flags & FGC_CONV_DEFER_REDUCE) ? 1 : 3, nullptr, st);
-            if (rc) return rc;
-        }
-        return FGC_OK;
-    }
-    // operand packing
-    if ((stages & 6) && !(io->flags & FGC_CONV_PACKED) && bf16) {
-        PackJobs J;
-        J.njobs = 2;
-        const size_t t1 = (size_t)g1.passes * (cout >> 5) * 18 * 512, t2 = (size_t)g2.passes * 9 * (g2.npad >> 4) * 512;
-        J.job[0] = PackJob{d->W0, w.Wq, 6, cin, cout, 0, 0, 0, g1.kc, g1.kpass, g1.passes, opad, 0};
-        J.job[1] = PackJob{d->W0, w.Wpt, 5, cin, cout, cout, cin, g2.npad, g2.kc, g2.kpass, g2.passes, 0, cdiv((int)t1, 1024)};
-        J.nblocks = cdiv((int)t1, 1024) + cdiv((int)t2, 1024);
-        FGC_LAUNCH("pack_many_kernel", st, pack_many_kernel, dim3(J.nblocks), dim3(256), 0, J);
-        FGC_CHECK_LAUNCH("fgc_conv_bwd/pack");
-    } else if ((stages & 6) && !(io->flags & FGC_CONV_PACKED)) {
-        const size_t tot = (size_t)g1.passes * opad * g1.kpass;
-        if (k1_split(d)) {
-            PackJobs J;
-            J.njobs = 1;
-            J.job[0] = PackJob{d->W0, w.Wq, 17, cin, cout, 0, 0, 0, g1.kc, g1.kpass, g1.passes, opad, 0};
-            J.nblocks = cdiv((int)((size_t)g1.passes * (cout >> 5) * 18 * 3 * 512), 1024);
-            FGC_LAUNCH("pack_many_kernel", st, pack_many_kernel, dim3(J.nblocks), dim3(256), 0, J);
-        } else
-        FGC_LAUNCH("pack_logit_weight_kernel", st, pack_logit_weight_kernel, dim3(cdiv((int)tot, 1024)), dim3(256), 0, d->W0, w.Wq, cin, cout,
-                           opad, g1.kc, g1.kpass, g1.passes);
-        const size_t tot2 = (size_t)g2.passes * g2.kpass * g2.npad;
-        FGC_LAUNCH("pack_weight_kernel", st, pack_weight_kernel, dim3(cdiv((int)tot2, 1024)), dim3(256), 0, d->W0, w.Wpt, cin, cout, cout,
-                           cin, g2.npad, g2.kc, g2.kpass, g2.passes, 1);
-        FGC_CHECK_LAUNCH("fgc_conv_bwd/pack");
-    }
-    // K1
-    if (stages & 2) {
-        CoreParams p;
-        fill_core_params(p, g1, d->n, d->rowptr, d->col, nullptr, d->x0, d->x1, d->c0, d->c1, d->shift, cout, io->ag,
-                         d->shift, 0, 12, nullptr);
-        LogitParams lp{io->ds, cout, opad, ostride, w.Wq, io->dl, io->dag, w.dc_part};
-        if (fuse_ds) {
-            lp.dy = io->dy;
-            lp.y = io->y ? io->y : io->dy;
-            lp.act = d->act;
-            lp.bias_mask = d->bias_mask;
-            lp.alpha = d->alpha;
-            lp.ds_out = io->ds;
-            lp.db_part = w.db_part;
-            lp.pool_y = io->pool_dy ? io->pool_y : nullptr;
-            lp.pool_dy = io->pool_dy;
-        }
-        size_t smem = smem_core_bytes(g1.zstride) + (size_t)(TILE * ostride + 48) * 4;
-        const bool vec4 = conv_vec4_ok(d);
-        if (bf16) {
-            const bool lng = d->max_deg > 16;
-            smem = smem_core_bytes(ZSTRIDE_BF / 2, lng ? KMAX : 16) + (size_t)TILE * (cout * 2 + 32) + 48 * 4;
-            if (lng) {
-                hipFuncSetAttribute((const void*)conv_bwd_logits_bf16_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem);
-                FGC_LAUNCH("conv_bwd_logits_bf16_kernel", st, (conv_bwd_logits_bf16_kernel<true>), dim3(cdiv(d->n, TILE)),
-                           dim3(NTHREADS), smem, p, lp);
-            } else if (k1_nodes(d) == 16) {
-                constexpr int NT = 16;
-                const size_t smem16 = (size_t)NT * (ZSTRIDE_BF / 2) * 4 + (size_t)NT * qnode_stride(16) * 4 + (2 * NT + 4) * 4 +
-                                      (size_t)NT * (cout * 2 + 32) + 48 * 4;
-                hipFuncSetAttribute((const void*)conv_bwd_logits_bf16_kernel<false, NT, 4>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem16);
-                FGC_LAUNCH("conv_bwd_logits_bf16_kernel", st, (conv_bwd_logits_bf16_kernel<false, NT, 4>), dim3(cdiv(d->n, NT)),
-                           dim3(256), smem16, p, lp);
+        // K2
+        if ((stages & 4) && !(io->data_tile_list && io->n_data_tiles == 0)) {
+            CoreParams p;
+            fill_core_params(p, w.g2, d->n, io->trowptr, io->tcol, io->tedge, io->ds, nullptr, cout, 0, 0, cin, io->ag,
+                             d->shift, 12, 0, w.Wpt);
+            p.tile_list = io->data_tile_list;
+            p.n_tiles = io->n_data_tiles;
+            DataEpilogue ep{io->dl, io->dag, io->r, io_r_ld(io, cout, bf16), d->u, d->v, cin, d->c0, d->c1, d->shift,
+                            io->dx0, io->dx1, io->accumulate0, io->accumulate1};
+            const size_t smem = conv_smem_bytes(w.g2, (size_t)TILE * 24 * 4);
+            if (bf16) {
+                FGC_CHECK_ARG(w8_bf16_supported(p, io->max_in_deg), "fgc_conv_bwd: FGC_CONV_BF16: unsupported shape for the data "
+                              "gradient (cin=%d cout=%d max_in_deg=%d)", cin, cout, io->max_in_deg);
+                rc = launch_data_w8(p, ep, smem, io->max_in_deg, st, true);
+            } else if (w8_supported(p, io->max_in_deg)) {
+                rc = launch_data_w8(p, ep, smem, io->max_in_deg, st);
+            } else if ((cout % 4 == 0) && ((uintptr_t)io->ds % 16 == 0) && ((uintptr_t)io->r % 16 == 0)) {
+                rc = launch_kernel<conv_bwd_data_kernel<8, true>>(
+                    LaunchCfg{"conv_bwd_data_kernel<LPN, true>", "fgc_conv_bwd/data", st, core_grid(p), NTHREADS, smem}, p, ep);
             } else {
-                hipFuncSetAttribute((const void*)conv_bwd_logits_bf16_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)smem);
-                FGC_LAUNCH("conv_bwd_logits_bf16_kernel", st, (conv_bwd_logits_bf16_kernel<false>), dim3(cdiv(d->n, TILE)),
-                           dim3(NTHREADS), smem, p, lp);
+                rc = launch_kernel<conv_bwd_data_kernel<8, false>>(
+                    LaunchCfg{"conv_bwd_data_kernel<LPN, false>", "fgc_conv_bwd/data", st, core_grid(p), NTHREADS, smem}, p, ep);
             }
-            FGC_CHECK_LAUNCH("fgc_conv_bwd/logits_bf16");
-            rc = 0;
-        } else if (g1.lpn == 8 && d->max_deg > 0 && d->max_deg <= KMAX &&
-            !(opt(OPT_NO_K1M) == 1)) {
-            static bool attr = false;
-            if (!attr) {
-                hipFuncSetAttribute((const void*)conv_bwd_logits_mfma_kernel<true>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                hipFuncSetAttribute((const void*)conv_bwd_logits_mfma_kernel<false>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-                attr = true;
-            }
-            const bool deep = vec4 && cin % 32 == 0 && (d->c1 == 0 || d->c0 % 32 == 0) &&
-                              (size_t)d->n * 4 * 128 < 0xFFFFFFFFull &&
-                              !(opt(OPT_NO_K1DEEP) == 1);
-            if (deep) {
-                // (__syncthreads_or owns 256 B of static LDS: ask for exactly what this launch needs)
-#define FGC_DEEP_LAUNCH(LONG_, OKG_)                                                                                  \
-    do {                                                                                                             \
-        hipFuncSetAttribute((const void*)conv_bwd_logits_deep_kernel<LONG_, OKG_>,                                   \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);                                  \
-        FGC_LAUNCH("conv_bwd_logits_deep_kernel", st, (conv_bwd_logits_deep_kernel<LONG_, OKG_>),                    \
-                   dim3(cdiv(d->n, TILE)), dim3(NTHREADS), smem, p, lp);                                             \
-    } while (0)
-                const bool lng = d->max_deg > 16;
-                if (!lng) smem = smem_core_bytes(g1.zstride, 16) + (size_t)(TILE * ostride + 48) * 4;
-                if (k1_nodes(d) == 16) {      // half tiles (implies !lng)
-                    constexpr int NT = 16;
-                    const size_t smem16 = (size_t)NT * g1.zstride * 4 + (size_t)NT * qnode_stride(16) * 4 + (2 * NT + 4) * 4 +
-                                          (size_t)(NT * ostride + 48) * 4;
-#define FGC_DEEP_HALF(OKG_)                                                                                          \
-    do {                                                                                                             \
-        hipFuncSetAttribute((const void*)conv_bwd_logits_deep_kernel<false, OKG_, NT, 4>,                            \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem16);                                \
-        FGC_LAUNCH("conv_bwd_logits_deep_kernel", st, (conv_bwd_logits_deep_kernel<false, OKG_, NT, 4>),             \
-                   dim3(cdiv(d->n, NT)), dim3(256), smem16, p, lp);                                                  \
-    } while (0)
-                    const bool al = ((uintptr_t)io->ds % 16) == 0;
-#define FGC_DEEP_HALF_SPLIT(OKG_)                                                                                    \
-    do {                                                                                                             \
-        hipFuncSetAttribute((const void*)conv_bwd_logits_deep_kernel<false, OKG_, NT, 4, true>,                      \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem16);                                \
-        FGC_LAUNCH("conv_bwd_logits_deep_kernel", st, (conv_bwd_logits_deep_kernel<false, OKG_, NT, 4, true>),       \
-                   dim3(cdiv(d->n, NT)), dim3(256), smem16, p, lp);                                                  \
-    } while (0)
-                    // 14-slot table (option K1_QS14, degrees <= 14): a fifth workgroup per CU
-                    const bool qs14 = opt(OPT_K1_QS14) == 1 && d->max_deg > 0 && d->max_deg <= 14;
-                    const size_t smem14 = smem16 - (size_t)NT * (qnode_stride(16) - qnode_stride(14)) * 4;
-#define FGC_DEEP_HALF14(OKG_, SPLIT_)                                                                                \
-    do {                                                                                                             \
-        hipFuncSetAttribute((const void*)conv_bwd_logits_deep_kernel<false, OKG_, NT, 4, SPLIT_, 14>,                \
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem14);                                \
-        FGC_LAUNCH("conv_bwd_logits_deep_kernel", st, (conv_bwd_logits_deep_kernel<false, OKG_, NT, 4, SPLIT_, 14>), \
-                   dim3(cdiv(d->n, NT)), dim3(256), smem14, p, lp);                                                  \
-    } while (0)
-                    if (k1_split(d)) {
-                        // (the packed operand is in the split layout whatever the pointers: no other kernel can take it)
-                        FGC_CHECK_ARG(al, "fgc_conv_bwd: ds must be 16-byte aligned (cout=%d)", cout);
-                        if (qs14) FGC_DEEP_HALF14(2, true);
-                        else FGC_DEEP_HALF_SPLIT(2);
-                    } else
-                    if (cout == 32 && al) FGC_DEEP_HALF(2);
-                    else if (cout == 64 && al && qs14) FGC_DEEP_HALF14(4, false);
-                    else if (cout == 64 && al) FGC_DEEP_HALF(4);
-                    else if (cout == 128 && al && fuse_ds) FGC_DEEP_HALF(8);   // (only for its prologue: s and db in this launch)
-                    else FGC_DEEP_HALF(0);
-#undef FGC_DEEP_HALF
-#undef FGC_DEEP_HALF_SPLIT
-                } else {
-                // 24 edge slots + the ds tile of a 64- or 128-wide layer do not fit twice into a CU's LDS
-                if (lng && cout > 32 && cout % 16 == 0 && ((uintptr_t)io->ds % 16) == 0) {
-                    lp.a_global = 1;
-                    smem = smem_core_bytes(g1.zstride) + (size_t)48 * 4;
-                }
-                const bool al16 = ((uintptr_t)io->ds % 16) == 0;
-                if (cout == 32 && al16) { if (lng) FGC_DEEP_LAUNCH(true, 2); else FGC_DEEP_LAUNCH(false, 2); }
-                else if (cout == 64 && al16) { if (lng) FGC_DEEP_LAUNCH(true, 4); else FGC_DEEP_LAUNCH(false, 4); }
-                else { if (lng) FGC_DEEP_LAUNCH(true, 0); else FGC_DEEP_LAUNCH(false, 0); }
-                }
-#undef FGC_DEEP_LAUNCH
-            } else if (vec4)
-                FGC_LAUNCH("conv_bwd_logits_mfma_kernel", st, (conv_bwd_logits_mfma_kernel<true>),
-                           dim3(cdiv(d->n, TILE)), dim3(NTHREADS), smem, p, lp);
-            else
-                FGC_LAUNCH("conv_bwd_logits_mfma_kernel", st, (conv_bwd_logits_mfma_kernel<false>),
-                           dim3(cdiv(d->n, TILE)), dim3(NTHREADS), smem, p, lp);
-            FGC_CHECK_LAUNCH("fgc_conv_bwd/logits_mfma");
-            rc = 0;
-        } else
-            rc = launch_logits<8>(p, lp, vec4, smem, st);
-        if (rc) return rc;   // dc partials: stage 8
-    }
-    // K2
-    if ((stages & 4) && !(io->data_tile_list && io->n_data_tiles == 0)) {
-        CoreParams p;
-        fill_core_params(p, g2, d->n, io->trowptr, io->tcol, io->tedge, io->ds, nullptr, cout, 0, 0, cin, io->ag,
-                         d->shift, 12, 0, w.Wpt);
-        p.tile_list = io->data_tile_list;
-        p.n_tiles = io->n_data_tiles;
-        DataEpilogue ep{io->dl, io->dag, io->r, io_r_ld(io, cout, bf16), d->u, d->v, cin, d->c0, d->c1, d->shift,
-                        io->dx0, io->dx1, io->accumulate0, io->accumulate1};
-        const size_t smem = conv_smem_bytes(g2, (size_t)TILE * 24 * 4);
-        const bool vec4 = (cout % 4 == 0) && ((uintptr_t)io->ds % 16 == 0) && ((uintptr_t)io->r % 16 == 0);
-        if (bf16) {
-            FGC_CHECK_ARG(w8_bf16_supported(p, io->max_in_deg), "fgc_conv_bwd: FGC_CONV_BF16: unsupported shape for the data "
-                          "gradient (cin=%d cout=%d max_in_deg=%d)", cin, cout, io->max_in_deg);
-            rc = launch_data_w8(p, ep, smem, io->max_in_deg, st, true);
             if (rc) return rc;
-        } else if (g2.lpn == 8 && w8_supported(p, io->max_in_deg)) {
-            rc = launch_data_w8(p, ep, smem, io->max_in_deg, st);
-            if (rc) return rc;
-        } else
-            rc = launch_data<8>(p, ep, vec4, smem, st);
-        if (rc) return rc;
+        }
     }
     // K3: dW0 = r^T x ; [du; dv] = dag^T x
     if (stages & 8) {
@@ -2511,100 +1784,6 @@ extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, v
             if (rc) return rc;
         }
     }
-    return FGC_OK;
-}
-
-
-// ---------------------------------------------------------------------------------------------
-// whole-network helpers: one launch where every layer used to bring its own
-// ---------------------------------------------------------------------------------------------
-extern "C" int fgc_conv_pack(const fgc_conv_desc* const* descs, const fgc_conv_bwd_io* const* ios, void* const* fwd_ws,
-                             void* const* bwd_ws, int32_t count, const fgc_pack_extra* extra, void* stream) {
-    FGC_CHECK_ARG((descs || count == 0) && count >= 0, "fgc_conv_pack: bad arguments");
-    hipStream_t st = (hipStream_t)stream;
-    PackJobs J;
-    J.njobs = 0;
-    J.nblocks = 0;
-    auto flush = [&]() {
-        if (J.njobs == 0) return;
-        FGC_LAUNCH("pack_many_kernel", st, pack_many_kernel, dim3(J.nblocks), dim3(256), 0, J);
-        J.njobs = 0;
-        J.nblocks = 0;
-    };
-    auto add = [&](const PackJob& j, size_t total) {
-        if (J.njobs == PACK_MAX_JOBS) flush();
-        PackJob& q = J.job[J.njobs++];
-        q = j;
-        q.block0 = J.nblocks;
-        J.nblocks += cdiv((int)total, 1024);
-    };
-    for (int i = 0; i < count; ++i) {
-        const fgc_conv_desc* d = descs[i];
-        FGC_OPT_SCOPE(d);      // (this layer's own option values, if its descriptor carries any)
-        int rc = validate_conv_desc(d, "fgc_conv_pack");
-        if (rc) return rc;
-        const int cin = d->c0 + d->c1, cout = d->cout;
-        const bool narrow = narrow_supported(d);
-        const bool bf16 = (d->flags & FGC_CONV_BF16) != 0;
-        const bool pairs = pairs_ok(d);     // reads W0 / u / v in place (bf16 storage: a bf16 copy of W0); backward packs only
-                                            // the data-gradient operand
-        if (fwd_ws && fwd_ws[i] && pairs && bf16)
-            add(PackJob{d->W0, (float*)fwd_ws[i], 7, cin, cout, FGC_M * cout * cin, 0, 0, 0, 0, 0, 0, 0}, (size_t)FGC_M * cout * cin);
-        if (fwd_ws && fwd_ws[i] && !narrow && !pairs) {
-            const ConvGeom g = conv_geom(cin, cout);
-            FGC_CHECK_ARG((uintptr_t)fwd_ws[i] % 16 == 0, "fgc_conv_pack: workspace %d misaligned", i);
-            add(PackJob{d->W0, (float*)fwd_ws[i], bf16 ? 4 : 0, cin, cout, cin, cout, g.npad, g.kc, g.kpass, g.passes, 0, 0},
-                (size_t)g.passes * g.kpass * g.npad);
-        }
-        const bool narrow_bwd = narrow && ios && ios[i] && ios[i]->dx0 == nullptr;   // vector-ALU path: nothing to pack
-        if (bwd_ws && bwd_ws[i] && !narrow_bwd) {
-            FGC_CHECK_ARG((uintptr_t)bwd_ws[i] % 16 == 0, "fgc_conv_pack: workspace %d misaligned", i);
-            const BwdWorkspace w = plan_bwd(d, (char*)bwd_ws[i]);
-            const ConvGeom g1 = conv_geom(cin, cout), g2 = conv_geom(cout, cin);
-            const int opad = (cout + 15) / 16 * 16;
-            if (bf16) {
-                if (!pairs)
-                add(PackJob{d->W0, w.Wq, 6, cin, cout, 0, 0, 0, g1.kc, g1.kpass, g1.passes, opad, 0},
-                    (size_t)g1.passes * (cout >> 5) * 18 * 512);
-                add(PackJob{d->W0, w.Wpt, 5, cin, cout, cout, cin, g2.npad, g2.kc, g2.kpass, g2.passes, 0, 0},
-                    (size_t)g2.passes * 9 * (g2.npad >> 4) * 512);
-            } else {
-            if (!pairs && k1_split(d))
-            add(PackJob{d->W0, w.Wq, 17, cin, cout, 0, 0, 0, g1.kc, g1.kpass, g1.passes, opad, 0},
-                (size_t)g1.passes * (cout >> 5) * 18 * 3 * 512);
-            else if (!pairs)
-            add(PackJob{d->W0, w.Wq, 2, cin, cout, 0, 0, 0, g1.kc, g1.kpass, g1.passes, opad, 0},
-                (size_t)g1.passes * opad * g1.kpass);
-            add(PackJob{d->W0, w.Wpt, 1, cin, cout, cout, cin, g2.npad, g2.kc, g2.kpass, g2.passes, 0, 0},
-                (size_t)g2.passes * g2.kpass * g2.npad);
-            }
-        }
-    }
-    if (extra && extra->rot_x) {
-        const int64_t nvec = (int64_t)extra->rot_rows * extra->rot_vecs;
-        FGC_CHECK_ARG(extra->rot_y && extra->rot_R && extra->rot_rows > 0 && extra->rot_vecs > 0 && nvec < (1ll << 31),
-                      "fgc_conv_pack: extra: bad rotation (rows=%lld vecs=%d)", (long long)extra->rot_rows, extra->rot_vecs);
-        if (extra->rot_ag) {
-            FGC_CHECK_ARG(extra->rot_u && extra->rot_c && extra->rot_v && extra->rot_vecs <= 2 && (uintptr_t)extra->rot_ag % 16 == 0,
-                          "fgc_conv_pack: extra: the first layer's logit table needs u, c, v and at most 6 input channels");
-            PackJob j{extra->rot_x, extra->rot_y, 14, extra->rot_vecs, 0, (int)extra->rot_rows, 0, 0, 0, 0, 0, 0, 0, extra->rot_R,
-                      extra->rot_u, extra->rot_c, extra->rot_v, extra->rot_ag};
-            add(j, (size_t)extra->rot_rows * 4);     // one row per thread
-        } else {
-            PackJob j{extra->rot_x, extra->rot_y, 8, 0, 0, (int)nvec, 0, 0, 0, 0, 0, 0, 0, extra->rot_R};
-            add(j, (size_t)nvec * 2);     // two 3-vectors per thread-iteration share
-        }
-    }
-    if (extra && extra->mlp_W1) {
-        PackJob mj[4];
-        size_t tot[4];
-        const int nj = extra->mlp_bf16 ? mlp_pack_jobs_bf16(extra, mj, tot) : mlp_pack_jobs_f32(extra, mj, tot);
-        FGC_CHECK_ARG(nj >= 0, "fgc_conv_pack: extra: MLP shape cin=%d hidden=%d cout=%d n=%d not served%s", extra->mlp_cin,
-                      extra->mlp_hidden, extra->mlp_cout, extra->mlp_n, extra->mlp_bf16 ? " (bf16)" : "");
-        for (int i = 0; i < nj; ++i) add(mj[i], tot[i]);
-    }
-    flush();
-    FGC_CHECK_LAUNCH("fgc_conv_pack");
     return FGC_OK;
 }
 
@@ -2632,13 +1811,13 @@ extern "C" int fgc_conv_bwd_reduce(const fgc_conv_desc* const* descs, const fgc_
             rc = validate_conv_desc(d, "fgc_conv_bwd_reduce");
             if (rc) return rc;
             FGC_CHECK_ARG(bwd_ws[i], "fgc_conv_bwd_reduce: layer %d: null workspace", i);
-            const BwdWorkspace w = plan_bwd(d, (char*)bwd_ws[i]);
+            const BwdPlan w = plan_bwd(d, (char*)bwd_ws[i]);
             TnPlan pl;
             if (io->dx0 == nullptr && w.narrow) {
                 const float* A;
                 float* slab;
                 int zld, rps;
-                narrow_tn_operands(d, io, w.narrow, &A, &zld, &slab, &rps);
+                narrow_tn_operands(d, io, w.narrow_ws, &A, &zld, &slab, &rps);
                 pl = tn_plan_of(false, true, true, A, zld, io->ds, nullptr, d->cout, 0, 0, d->n, rps, slab);
             } else {
                 FGC_CHECK_ARG(io->r, "fgc_conv_bwd_reduce: layer %d: FGC_CONV_DEFER_DW without r", i);
@@ -2674,10 +1853,10 @@ extern "C" int fgc_conv_bwd_reduce(const fgc_conv_desc* const* descs, const fgc_
         if (rc) return rc;
         FGC_CHECK_ARG(io && bwd_ws[i] && io->dW0 && io->db && io->du && io->dc && io->dv,
                       "fgc_conv_bwd_reduce: layer %d: null io / workspace / gradient pointer", i);
-        const BwdWorkspace w = plan_bwd(d, (char*)bwd_ws[i]);
+        const BwdPlan w = plan_bwd(d, (char*)bwd_ws[i]);
         if (nj + 5 > RED_MAX_JOBS && (rc = flush())) return rc;
         if (io->dx0 == nullptr && w.narrow) {
-            rc = narrow_bwd_params(d, io, w.narrow, w.db_part, narrow_db_partials(d, io, w.nb_db), 0, jobs + nj, st);
+            rc = narrow_bwd_params(d, io, w.narrow_ws, w.db_part, narrow_db_partials(d, io, w.nb_db), 0, jobs + nj, st);
             if (rc) return rc;
             nj += NARROW_RED_JOBS;
         } else {

@@ -93,8 +93,8 @@ __device__ __forceinline__ Smem carve(char* base, int zstride, int qslots = KMAX
     s.extra = reinterpret_cast<float*>(base + off);
     return s;
 }
-static inline size_t smem_core_bytes(int zstride, int qslots = KMAX) {
-    return (size_t)TILE * zstride * 4 + (size_t)TILE * qnode_stride(qslots) * 4 + (2 * TILE + 4) * 4;
+static inline size_t smem_core_bytes(int zstride, int qslots = KMAX, int nodes = TILE) {
+    return (size_t)nodes * zstride * 4 + (size_t)nodes * qnode_stride(qslots) * 4 + (2 * nodes + 4) * 4;
 }
 
 // ---- phase S: per-edge soft assignment ------------------------------------------------------

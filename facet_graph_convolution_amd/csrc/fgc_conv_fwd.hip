@@ -11,17 +11,6 @@
 namespace fgc {
 
 // ---------------------------------------------------------------------------------------------
-// weight packing: W0[m][o][c] -> k-interleaved B operand of the aggregate-first GEMM
-//   row kk = pass*kpass + m*kc + cl  (c = pass*kc + cl), column = o, stored [kk/4][npad][kk%4]
-// transposed = 1 packs the data-gradient operand instead: k runs over (pass, m, ol) with
-// o = pass*kc + ol and the column is c.
-// ---------------------------------------------------------------------------------------------
-__global__ void pack_weight_kernel(const float* __restrict__ W0, float* __restrict__ Wp, int cin, int cout,
-                                   int kdim, int ncols, int npad, int kc, int kpass, int passes, int transposed) {
-    pack_weight_body(W0, Wp, cin, cout, kdim, ncols, npad, kc, kpass, passes, transposed, blockIdx.x, gridDim.x);
-}
-
-// ---------------------------------------------------------------------------------------------
 // assignment logits on the matrix cores: ag[rows, 24] = x[rows, cin] * [u | v]^T (+ c).  One wave per 16 rows, A
 // fragments straight from global memory (one dwordx4 per lane per 16 channels), B = [u|v] staged once per workgroup
 // in LDS (column tile 0 = the 9 a-logits, tile 1 = the 9 g-logits).  Streams x exactly once: HBM-bound.
@@ -325,22 +314,6 @@ size_t conv_smem_bytes(const ConvGeom& g, size_t extra) {
 
 }  // namespace fgc
 
-template <int LPN>
-static int launch_fwd(const CoreParams& p, const FwdEpilogue& ep, bool vec4, size_t smem, hipStream_t st) {
-    const int grid = core_grid(p);
-    if (vec4) {
-        hipFuncSetAttribute((const void*)conv_fwd_kernel<LPN, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-        FGC_LAUNCH("conv_fwd_kernel<LPN, true>", st, (conv_fwd_kernel<LPN, true>), dim3(grid), dim3(NTHREADS), smem, p, ep);
-    } else {
-        hipFuncSetAttribute((const void*)conv_fwd_kernel<LPN, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)smem);
-        FGC_LAUNCH("conv_fwd_kernel<LPN, false>", st, (conv_fwd_kernel<LPN, false>), dim3(grid), dim3(NTHREADS), smem, p, ep);
-    }
-    FGC_CHECK_LAUNCH("fgc_conv_fwd");
-    return FGC_OK;
-}
-
 extern "C" int fgc_conv_fwd(const fgc_conv_desc* d, float* ag, float* y, float* y_pool, void* workspace,
                             size_t workspace_bytes, void* stream) {
     FGC_OPT_SCOPE(d);
@@ -376,19 +349,11 @@ extern "C" int fgc_conv_fwd(const fgc_conv_desc* d, float* ag, float* y, float* 
     FGC_CHECK_ARG(!bf16 || narrow || (conv_vec4_ok(d) && cin % 32 == 0 && (d->c1 == 0 || d->c0 % 32 == 0) && d->cout % 32 == 0),
                   "fgc_conv_fwd: FGC_CONV_BF16 needs widths that are multiples of 32 and 16-byte aligned tensors (c0=%d c1=%d "
                   "cout=%d)", d->c0, d->c1, d->cout);
-    if (!narrow && !(d->flags & FGC_CONV_PACKED) && bf16) {
-        PackJobs J;
-        J.njobs = 1;
-        const size_t tot = (size_t)g.passes * 9 * (g.npad >> 4) * 512;
-        J.job[0] = PackJob{d->W0, Wp, 4, cin, d->cout, cin, d->cout, g.npad, g.kc, g.kpass, g.passes, 0, 0};
-        J.nblocks = cdiv((int)tot, 1024);
-        FGC_LAUNCH("pack_many_kernel", st, pack_many_kernel, dim3(J.nblocks), dim3(256), 0, J);
-        FGC_CHECK_LAUNCH("fgc_conv_fwd/pack");
-    } else if (!narrow && !(d->flags & FGC_CONV_PACKED)) {
-        const size_t tot = packed_floats(g);
-        FGC_LAUNCH("pack_weight_kernel", st, pack_weight_kernel, dim3(cdiv((int)tot, 256 * 4)), dim3(256), 0, d->W0, Wp, cin,
-                   d->cout, cin, d->cout, g.npad, g.kc, g.kpass, g.passes, 0);
-        FGC_CHECK_LAUNCH("fgc_conv_fwd/pack");
+    if (!narrow && !(d->flags & FGC_CONV_PACKED)) {
+        PackJob job;
+        size_t total;
+        rc = launch_pack_jobs(&job, &total, conv_fwd_pack_jobs(d, Wp, &job, &total), "fgc_conv_fwd/pack", st);
+        if (rc) return rc;
     }
     if (prows > 0) {
         const int pg = std::min(cdiv(cdiv(prows, 16), 4), 1024);
@@ -434,12 +399,13 @@ extern "C" int fgc_conv_fwd(const fgc_conv_desc* d, float* ag, float* y, float* 
     p.n_tiles = d->n_tiles;
     FwdEpilogue ep{d->b, d->bias_mask, d->act, d->alpha, y, y_pool};
     const size_t smem = conv_smem_bytes(g, 0);
-    const bool vec4 = conv_vec4_ok(d);
     if (bf16) {
         FGC_CHECK_ARG(w8_bf16_supported(p, d->max_deg), "fgc_conv_fwd: FGC_CONV_BF16: unsupported shape (cin=%d cout=%d "
                       "max_deg=%d)", cin, d->cout, d->max_deg);
         return launch_fwd_w8(p, ep, smem, d->max_deg, st, true);
     }
-    if (g.lpn == 8 && w8_supported(p, d->max_deg)) return launch_fwd_w8(p, ep, smem, d->max_deg, st);
-    return launch_fwd<8>(p, ep, vec4, smem, st);
+    if (w8_supported(p, d->max_deg)) return launch_fwd_w8(p, ep, smem, d->max_deg, st);
+    if (conv_vec4_ok(d))
+        return launch_kernel<conv_fwd_kernel<8, true>>(LaunchCfg{"conv_fwd_kernel<LPN, true>", "fgc_conv_fwd", st, core_grid(p), NTHREADS, smem}, p, ep);
+    return launch_kernel<conv_fwd_kernel<8, false>>(LaunchCfg{"conv_fwd_kernel<LPN, false>", "fgc_conv_fwd", st, core_grid(p), NTHREADS, smem}, p, ep);
 }

@@ -19,6 +19,7 @@
 #include "fgc_conv_narrow.h"
 #include <type_traits>
 
+#include "fgc_gemm_tn.h"
 #include "fgc_reduce.h"
 
 namespace fgc {

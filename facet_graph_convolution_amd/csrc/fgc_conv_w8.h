@@ -45,8 +45,16 @@ static inline bool io_r_ld_ok(const fgc_conv_bwd_io* io, int cout, bool bf16) {
 }
 
 // which packed-operand layouts the option values in force select for the descriptor (include/fgc.h: fgc_conv_layout_id);
-// defined beside the pack code in fgc_conv_bwd.hip
+// read off the backward plan (fgc_conv_bwd.hip)
 uint64_t conv_layout_id(const fgc_conv_desc* d);
+
+// host helpers of the tiled kernels (fgc_conv_fwd.hip)
+int validate_conv_desc(const fgc_conv_desc* d, const char* who);
+bool conv_vec4_ok(const fgc_conv_desc* d);
+void fill_core_params(CoreParams& p, const ConvGeom& g, int n, const int* rowptr, const int* col, const int* eid,
+                      const float* s0, const float* s1, int c0, int c1, int shift, int nout, const float* ag,
+                      int ag_shift, int ctr_off, int nbr_off, const float* Wp);
+size_t conv_smem_bytes(const ConvGeom& g, size_t extra);
 
 bool w8_supported(const CoreParams& p, int max_deg);
 // max_deg: the largest degree of the gathered graph (<= KMAX); <= 16 selects the 16-slot form of the fast kernel

@@ -508,11 +508,11 @@ int mlp_pack_jobs_f32(const fgc_pack_extra* e, PackJob* jobs, size_t* totals) {
     if (e->mlp_fwd_ws) {
         if ((uintptr_t)e->mlp_fwd_ws % 16 != 0) return -1;
         if (mlp_fwd_split_ok(nullptr, cin, hidden, cout)) {
-            jobs[nj] = PackJob{e->mlp_W1, (float*)e->mlp_fwd_ws, 10, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
+            jobs[nj] = PackJob{e->mlp_W1, (float*)e->mlp_fwd_ws, PACK_MLP_SPLIT, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
             totals[nj++] = (size_t)cin * hidden;
         } else {
             const int kpad = mlp_kpad(cin);
-            jobs[nj] = PackJob{e->mlp_W1, (float*)e->mlp_fwd_ws, 9, cin, cout, kpad, hidden, 0, 0, 0, 0, 0, 0};
+            jobs[nj] = PackJob{e->mlp_W1, (float*)e->mlp_fwd_ws, PACK_MLP, cin, cout, kpad, hidden, 0, 0, 0, 0, 0, 0};
             totals[nj++] = (size_t)kpad * hidden;
         }
     }
@@ -523,7 +523,7 @@ int mlp_pack_jobs_f32(const fgc_pack_extra* e, PackJob* jobs, size_t* totals) {
             return k < 0 ? -1 : nj + k;
         }
         const int kpad = mlp_bwd_kpad(cin);
-        jobs[nj] = PackJob{e->mlp_W1, (float*)e->mlp_bwd_ws, 9, cin, cout, kpad, hidden, 0, 0, 0, 0, 0, 0};
+        jobs[nj] = PackJob{e->mlp_W1, (float*)e->mlp_bwd_ws, PACK_MLP, cin, cout, kpad, hidden, 0, 0, 0, 0, 0, 0};
         totals[nj++] = (size_t)kpad * hidden;
     }
     return nj;

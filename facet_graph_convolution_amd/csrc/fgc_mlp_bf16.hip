@@ -1105,11 +1105,11 @@ int mlp_bwd_split_pack_jobs(const fgc_pack_extra* e, PackJob* jobs, size_t* tota
     if (e->mlp_n <= 0 || !e->mlp_W2 || (uintptr_t)e->mlp_bwd_ws % 16 != 0) return -1;
     const SplitBwdWs w = split_bwd_plan(e->mlp_n, cin, hidden);
     char* base = (char*)e->mlp_bwd_ws;
-    jobs[0] = PackJob{e->mlp_W1, (float*)(base + w.wp), 10, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
+    jobs[0] = PackJob{e->mlp_W1, (float*)(base + w.wp), PACK_MLP_SPLIT, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
     totals[0] = (size_t)cin * hidden;
-    jobs[1] = PackJob{e->mlp_W1, (float*)(base + w.w1d), 15, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
+    jobs[1] = PackJob{e->mlp_W1, (float*)(base + w.w1d), PACK_MLP_W1DX_SPLIT, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
     totals[1] = (size_t)cin * hidden;
-    jobs[2] = PackJob{e->mlp_W2, (float*)(base + w.w2s), 16, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
+    jobs[2] = PackJob{e->mlp_W2, (float*)(base + w.w2s), PACK_MLP_W2_SPLIT, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
     totals[2] = (size_t)cdiv((hidden >> 4) * 64, 256) * 1024;
     return 3;
 }
@@ -1190,17 +1190,17 @@ int mlp_pack_jobs_bf16(const fgc_pack_extra* e, PackJob* jobs, size_t* totals) {
     int nj = 0;
     if (e->mlp_fwd_ws) {
         if ((uintptr_t)e->mlp_fwd_ws % 16 != 0) return -1;
-        jobs[nj] = PackJob{e->mlp_W1, (float*)e->mlp_fwd_ws, 11, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
+        jobs[nj] = PackJob{e->mlp_W1, (float*)e->mlp_fwd_ws, PACK_MLP_BF16, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
         totals[nj++] = (size_t)cin * hidden;
     }
     if (e->mlp_bwd_ws) {
         if ((uintptr_t)e->mlp_bwd_ws % 16 != 0 || cin == 128 || cout > 3 || e->mlp_n <= 0 || !e->mlp_W2) return -1;
         char* w = (char*)e->mlp_bwd_ws;
-        jobs[nj] = PackJob{e->mlp_W1, (float*)w, 11, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
+        jobs[nj] = PackJob{e->mlp_W1, (float*)w, PACK_MLP_BF16, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
         totals[nj++] = (size_t)cin * hidden;
-        jobs[nj] = PackJob{e->mlp_W1, (float*)(w + align_up((size_t)cin * hidden * 2, 256)), 12, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
+        jobs[nj] = PackJob{e->mlp_W1, (float*)(w + align_up((size_t)cin * hidden * 2, 256)), PACK_MLP_W1DX_BF16, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
         totals[nj++] = (size_t)cin * hidden;
-        jobs[nj] = PackJob{e->mlp_W2, (float*)(w + mb_w2p_offset(e->mlp_n, cin, hidden)), 13, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
+        jobs[nj] = PackJob{e->mlp_W2, (float*)(w + mb_w2p_offset(e->mlp_n, cin, hidden)), PACK_MLP_W2_BF16, cin, cout, 0, hidden, 0, 0, 0, 0, 0, 0};
         totals[nj++] = (size_t)cdiv((hidden >> 4) * 32, 256) * 1024;
     }
     return nj;

@@ -348,22 +348,34 @@ __device__ __forceinline__ void rotate_rows_body(const float* __restrict__ x, fl
     }
 }
 
-// every packed operand of several layers in one launch (fgc_conv_pack)
+// every packed operand of several layers in one launch (fgc_conv_pack); `kind` selects the device body
+enum PackKind {
+    PACK_FWD = 0,              // forward operand (pack_weight_body)
+    PACK_DATA = 1,             // data-gradient operand (pack_weight_body, transposed)
+    PACK_LOGIT = 2,            // d-logits operand
+    PACK_FWD_BF16 = 4,         // the bf16 forms of the three (= fp32 kind + 4)
+    PACK_DATA_BF16 = 5,
+    PACK_LOGIT_BF16 = 6,
+    PACK_PLAIN_BF16 = 7,       // plain bf16 copy of W0 (pair form; kdim = element count)
+    PACK_ROTATE = 8,           // rotate_rows_body (W0 = x, dst = y, aux = R, kdim = 3-vectors)
+    PACK_MLP = 9,              // MLP operands, W0 = W1 [cin, ncols]: mlp_pack_body (kdim = kpad),
+    PACK_MLP_SPLIT = 10,       // mlp_pack_split_body,
+    PACK_MLP_BF16 = 11,        // mlp_pack_bf16_body,
+    PACK_MLP_W1DX_BF16 = 12,   // mlp_pack_w1dx_bf16_body;
+    PACK_MLP_W2_BF16 = 13,     // mlp_pack_w2_bf16_body (W0 = W2 [ncols, cout])
+    PACK_ROTATE_LOGITS = 14,   // rotate_logits_body (W0 = x, dst = y, aux = R, kdim = rows, cin = 3-vectors per row, lg_* = the table)
+    PACK_MLP_W1DX_SPLIT = 15,  // mlp_pack_w1dx_split_body
+    PACK_MLP_W2_SPLIT = 16,    // mlp_pack_w2_split_body (W0 = W2 [ncols, cout])
+    PACK_LOGIT_SPLIT = 17      // pack_logit_weight_split_body
+};
 struct PackJob {
     const float* W0;
     float* dst;
-    int kind;   // 0: forward operand, 1: data-gradient operand (transposed), 2: d-logits operand; +4: the bf16 forms;
-                // 7: plain bf16 copy of W0 (pair form; kdim = element count);
-                // 8: rotate_rows_body (W0 = x, dst = y, aux = R, kdim = 3-vectors);
-                // 14: rotate_logits_body (W0 = x, dst = y, aux = R, kdim = rows, cin = 3-vectors per row, lg_* = the table);
-                // MLP operands, W0 = W1 [cin, ncols]: 9 mlp_pack_body (kdim = kpad), 10 mlp_pack_split_body,
-                // 11 mlp_pack_bf16_body, 12 mlp_pack_w1dx_bf16_body; 13 mlp_pack_w2_bf16_body (W0 = W2 [ncols, cout]);
-                // 15 mlp_pack_w1dx_split_body, 16 mlp_pack_w2_split_body (W0 = W2 [ncols, cout])
-                // 17 pack_logit_weight_split_body
+    int kind;   // PackKind
     int cin, cout, kdim, ncols, npad, kc, kpass, passes, opad;
     int block0;
     const float* aux;
-    const float *lg_u, *lg_c, *lg_v;     // kind 14: the first layer's assignment parameters and its logit table
+    const float *lg_u, *lg_c, *lg_v;     // PACK_ROTATE_LOGITS: the first layer's assignment parameters and its logit table
     float* lg_ag;
 };
 constexpr int PACK_MAX_JOBS = 28;
@@ -371,7 +383,19 @@ struct PackJobs {
     PackJob job[PACK_MAX_JOBS];
     int njobs, nblocks;
 };
-__global__ void pack_many_kernel(PackJobs J);
+// host side: jobs collected in block order (a workgroup takes 1024 elements of its job) and launched as pack_many_kernel
+// (fgc_conv_pack.hip); a full batch launches itself
+struct PackBatch {
+    PackJobs J;
+    hipStream_t st;
+    explicit PackBatch(hipStream_t s) : st(s) { J.njobs = J.nblocks = 0; }
+    void add(const PackJob& j, size_t total);
+    void flush();
+};
+// ... a layer's own jobs in one launch (the per-layer route, no FGC_CONV_PACKED); `what` prefixes the error message
+int launch_pack_jobs(const PackJob* jobs, const size_t* totals, int n, const char* what, hipStream_t st);
+// the packed forward operand of a conv layer as a job: returns the number of jobs written (0: the layer packs nothing, or 1)
+int conv_fwd_pack_jobs(const fgc_conv_desc* d, void* fwd_ws, PackJob* jobs, size_t* totals);
 
 // host side: the jobs that leave an MLP's operands in the workspaces of fgc_mlp_fwd / fgc_mlp_bwd (fgc_mlp.hip) or of their
 // bf16 forms (fgc_mlp_bf16.hip) exactly as those entry points lay them out themselves; `totals[i]` = elements of job i (a

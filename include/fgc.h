@@ -53,8 +53,10 @@ extern "C" {
  * point-set and face-normal losses together.
  * 108: fgc_bilateral_filter / fgc_bilateral_workspace_bytes (bilateral normal filtering, the classical baseline).
  * 109: fgc_synth_noise / fgc_face_features_rows (+ fgc_synth_scratch_floats, fgc_philox_words): per-step noise synthesis on
- * a clean mesh. */
-#define FGC_ABI_VERSION 109
+ * a clean mesh.
+ * 110: options K1_QS14 and W8_HALF2 removed with the two kernel forms they selected (both measured slower; the later option
+ * indices do not move: the two were last in the table). */
+#define FGC_ABI_VERSION 110
 
 const char* fgc_last_error(void);
 int fgc_version(void);

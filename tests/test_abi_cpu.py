@@ -70,6 +70,8 @@ def test_options_are_a_table_not_the_environment(monkeypatch):
     L = _lib.lib()
     names = _lib.option_names()
     assert "NO_PAIRS" in names and "W8_DATA16_MIN_N" in names and len(names) == L.fgc_option_count()
+    assert "K1_QS14" not in names and "W8_HALF2" not in names      # the two forms that lost are gone, not switched off
+    assert L.fgc_set_option(b"K1_QS14", 1) == -22 and L.fgc_set_option(b"W8_HALF2", 1) == -22
     assert _lib.get_option("FGC_W8_DATA16_MIN_N") == _lib.get_option("W8_DATA16_MIN_N")
     old = _lib.get_option("NO_PAIRS")
     monkeypatch.setenv("FGC_NO_PAIRS", str(1 - old))          # too late: the table was filled at the first read
