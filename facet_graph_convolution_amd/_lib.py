@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FGC_LIB", os.path.join(_HERE, "csrc", "libfgc.so"))  # FGC_LIB: developer A/B builds
 
-ABI_VERSION = 110  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
+ABI_VERSION = 111  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
 FGC_M = 9
 AG_LD = 24
 DL_LD = 12
@@ -157,6 +157,7 @@ _SIGS = {
     "fgc_conv_layout_id": (C.c_uint64, [C.POINTER(ConvDesc)]),
     "fgc_mlp_layout_id": (C.c_int32, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "fgc_conv_bwd": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvBwdIO), C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgc_conv_forms": (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvBwdIO), C.c_char_p, C.c_int32]),
     "fgc_conv_pack": (C.c_int, [C.POINTER(C.POINTER(ConvDesc)), C.POINTER(C.POINTER(ConvBwdIO)), C.POINTER(C.c_void_p),
                                 C.POINTER(C.c_void_p), C.c_int32, C.POINTER(PackExtra), C.c_void_p]),
     "fgc_conv_bwd_reduce": (C.c_int, [C.POINTER(C.POINTER(ConvDesc)), C.POINTER(C.POINTER(ConvBwdIO)),
@@ -324,6 +325,15 @@ class options:
     def __exit__(self, *a):
         for k, v in self.old.items():
             set_option(k, v)
+
+
+def conv_forms(desc, io=None):
+    """fgc_conv_forms as a dict of strings: which kernel form every launch of the layer takes (keys: include/fgc.h)."""
+    buf = C.create_string_buffer(1024)
+    n = lib().fgc_conv_forms(C.byref(desc), C.byref(io) if io is not None else None, buf, len(buf))
+    if n < 0:
+        check(n, "fgc_conv_forms")
+    return dict(kv.split("=", 1) for kv in buf.value.decode().split())
 
 
 def check(rc, what="libfgc"):

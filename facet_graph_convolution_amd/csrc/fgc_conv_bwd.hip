@@ -14,7 +14,9 @@
 //   K3  reductions over nodes (f32 MFMA, K = nodes; fgc_gemm_tn.hip):  dW0 = r^T x,  [du; dv] = dag^T x ; db, dc column sums
 // Which form of each kernel a layer takes is decided once, by plan_bwd (fgc_conv_bwd.h); the operand packs are fgc_conv_pack.hip.
 // No float atomics anywhere: every sum has a fixed order, results are bitwise reproducible.
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include <algorithm>
 #include <type_traits>
@@ -1470,11 +1472,35 @@ static uint64_t layout_id_of(const BwdPlan& w) {
 }
 uint64_t conv_layout_id(const fgc_conv_desc* d) { return layout_id_of(plan_bwd(d, nullptr)); }
 
+// The plan of one CALL.  The split layout of the d-logits operand has one kernel, and that kernel reads the ds tile in 16-byte
+// pieces; the plan cannot know the call's pointers (fgc_conv_pack may write the operand long before).  A call that packs its own
+// operands and brings a ds that is not 16-byte aligned therefore takes the fp32 layout and the fp32-MFMA form of the same
+// half-tile kernel (the workspace has room for either layout) - it used to be refused (FGC_EINVAL) although nothing the
+// caller could see asked for the alignment.  With FGC_CONV_PACKED the operand is what it is, and launch_k1 still refuses.
+static BwdPlan call_plan(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, char* base) {
+    BwdPlan w = plan_bwd(d, base);
+    if (w.k1_split && io && ((uintptr_t)io->ds % 16) != 0 && !(io->flags & FGC_CONV_PACKED)) {
+        w.k1_split = false;
+        w.wq = PackedOperand{PACK_LOGIT, (size_t)w.g1.passes * w.opad * w.g1.kpass};
+    }
+    return w;
+}
+
 // What a call adds to the plan: the stages it asks for and what the alignment of its tensors allows.  Evaluated once per
 // call; the ds_db stage and the d-logits launch both read it.
+enum DsForm {
+    DS_PAIR,           // inside pair_bwd_logits_kernel
+    DS_FUSED,          // prologue of the d-logits kernel
+    DS_NARROW_FUSED,   // ... of the first layer's (fgc_conv_narrow.hip)
+    DS_VEC,            // ds_db_vec_kernel
+    DS_SCALAR          // ds_db_kernel
+};
 struct BwdCall {
     int stages;
     bool narrow_path;   // first layer over a narrow input, no input gradient wanted: vector-ALU path, no transposed graph, no r
+    int k1;             // K1Form of this call: the plan's, or K1_NARROW
+    bool k1_vec4;       // K1_MFMA / K1_VALU: gathers of 16-byte pieces
+    int ds;             // DsForm: who computes s and the db partials (stage 1)
     bool fuse_ds;       // the d-logits kernel computes s (and the db partials) in its prologue: no ds_db launch
     bool ds_vec;        // ds_db_vec_kernel serves these tensors
     int okg;            // deep form: compile-time column groups of the ds tile (cout / 16), 0 = any width
@@ -1500,6 +1526,10 @@ static BwdCall bwd_call(const BwdPlan& w, const fgc_conv_desc* d, const fgc_conv
     // (OKG = 8 only for its prologue: s and db in this launch)
     c.okg = !al ? 0 : cout == 32 ? 2 : cout == 64 ? 4 : (cout == 128 && w.k1_half && c.fuse_ds) ? 8 : 0;
     c.a_global = w.k1 == K1_DEEP && w.k1_long && cout > 32 && cout % 16 == 0 && al;
+    c.k1 = c.narrow_path ? K1_NARROW : w.k1;
+    c.k1_vec4 = conv_vec4_ok(d);
+    c.ds = w.pairs ? DS_PAIR : c.fuse_ds ? DS_FUSED : (c.narrow_path && narrow_fuses_ds(d, io)) ? DS_NARROW_FUSED
+         : c.ds_vec ? DS_VEC : DS_SCALAR;
     return c;
 }
 
@@ -1532,7 +1562,7 @@ static int launch_ds_db(const BwdPlan& w, const BwdCall& c, const fgc_conv_desc*
     const LaunchCfg cfg{"ds_db_kernel", "fgc_conv_bwd/ds", st, w.nb_db, 256, 0};
     const float *yy = io->y ? io->y : io->dy, *pool_y = io->pool_dy ? io->pool_y : nullptr;
     const bool out_bf16 = w.bf16 && !c.narrow_path;     // (a narrow first layer keeps its ds in fp32)
-    if (!c.ds_vec) {
+    if (c.ds == DS_SCALAR) {
         int cp2 = 1;
         while (cp2 < d->cout) cp2 <<= 1;
         return launch_kernel<ds_db_kernel>(cfg, io->dy, io->y, d->rowptr, d->n, d->cout, cp2, d->act, d->alpha, d->bias_mask, w.rows_per_db,
@@ -1556,7 +1586,7 @@ static int launch_k1(const BwdPlan& w, const BwdCall& c, const fgc_conv_desc* d,
     const size_t core = smem_core_bytes(w.k1 == K1_BF16 ? ZSTRIDE_BF / 2 : w.g1.zstride, qs, nt);
     const size_t tile = w.k1 == K1_BF16 ? (size_t)nt * (cout * 2 + 32) : lp.a_global ? 0 : (size_t)nt * lp.ostride * 4;
     LaunchCfg cfg{"conv_bwd_logits_deep_kernel", "fgc_conv_bwd/logits_mfma", st, cdiv(d->n, nt), NTHREADS, core + tile + 48 * 4};
-    switch (w.k1) {
+    switch (c.k1) {
         case K1_BF16:
             cfg.name = "conv_bwd_logits_bf16_kernel";
             cfg.what = "fgc_conv_bwd/logits_bf16";
@@ -1587,17 +1617,54 @@ static int launch_k1(const BwdPlan& w, const BwdCall& c, const fgc_conv_desc* d,
             }
         case K1_MFMA:
             cfg.name = "conv_bwd_logits_mfma_kernel";
-            return conv_vec4_ok(d) ? launch_kernel<conv_bwd_logits_mfma_kernel<true>>(cfg, p, lp)
-                                   : launch_kernel<conv_bwd_logits_mfma_kernel<false>>(cfg, p, lp);
+            return c.k1_vec4 ? launch_kernel<conv_bwd_logits_mfma_kernel<true>>(cfg, p, lp)
+                             : launch_kernel<conv_bwd_logits_mfma_kernel<false>>(cfg, p, lp);
         default:
             cfg.what = "fgc_conv_bwd/logits";
-            if (conv_vec4_ok(d)) {
+            if (c.k1_vec4) {
                 cfg.name = "conv_bwd_logits_kernel<LPN, true>";
                 return launch_kernel<conv_bwd_logits_kernel<8, true>>(cfg, p, lp);
             }
             cfg.name = "conv_bwd_logits_kernel<LPN, false>";
             return launch_kernel<conv_bwd_logits_kernel<8, false>>(cfg, p, lp);
     }
+}
+
+// stage 4: the data-gradient kernel's parameters and the form it takes - the one answer fgc_conv_bwd switches on and
+// fgc_conv_forms prints
+enum DataKind { DATA_NONE, DATA_W8, DATA_TILED };
+struct DataForm {
+    int kind;      // DataKind (DATA_NONE: a narrow first layer without an input gradient)
+    W8Form w8;     // DATA_W8
+    bool vec4;     // DATA_TILED: 16-byte rows of ds and r
+    int max_deg;   // of the graph the kernel walks (in-edges, or in-pairs of the pair form)
+};
+static DataForm data_form(const BwdPlan& w, const BwdCall& c, const fgc_conv_desc* d, const fgc_conv_bwd_io* io, CoreParams& p,
+                          DataEpilogue& ep) {
+    DataForm f{};
+    const int cin = d->c0 + d->c1, cout = d->cout;
+    if (c.narrow_path) return f;
+    if (w.pairs) {
+        fill_core_params(p, w.g2, w.nred, io->tpair_rowptr, io->tpair_col, io->tpair_edge, io->dt, nullptr, cout, 0, 0, cin, io->ag,
+                         0, 12, 0, w.Wpt);
+        ep = DataEpilogue{io->dl, io->dag, io->r, io_r_ld(io, cout, w.bf16), d->u, d->v, cin, d->c0, 0, 0,
+                          io->dx0, nullptr, io->accumulate0, 0};
+        f.max_deg = d->max_pair_in_deg;
+        f.kind = DATA_W8;
+    } else {
+        fill_core_params(p, w.g2, d->n, io->trowptr, io->tcol, io->tedge, io->ds, nullptr, cout, 0, 0, cin, io->ag,
+                         d->shift, 12, 0, w.Wpt);
+        ep = DataEpilogue{io->dl, io->dag, io->r, io_r_ld(io, cout, w.bf16), d->u, d->v, cin, d->c0, d->c1, d->shift,
+                          io->dx0, io->dx1, io->accumulate0, io->accumulate1};
+        f.max_deg = io->max_in_deg;
+        // (bf16 storage has the eight-wave kernel only: fgc_conv_bwd refuses the shapes it does not serve)
+        f.kind = (w.bf16 || w8_supported(p, f.max_deg)) ? DATA_W8 : DATA_TILED;
+        f.vec4 = (cout % 4 == 0) && ((uintptr_t)io->ds % 16 == 0) && ((uintptr_t)io->r % 16 == 0);
+    }
+    p.tile_list = io->data_tile_list;
+    p.n_tiles = io->n_data_tiles;
+    if (f.kind == DATA_W8) f.w8 = w8_form(p, &ep, f.max_deg, w.bf16);
+    return f;
 }
 
 }  // namespace fgc
@@ -1625,13 +1692,93 @@ extern "C" int fgc_conv_bwd_needs_exchange(const fgc_conv_desc* d, const fgc_con
     return (io->dx0 == nullptr && narrow_supported(d)) ? 0 : 1;
 }
 
+extern "C" int fgc_conv_forms(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, char* buf, int32_t buf_bytes) {
+    FGC_OPT_SCOPE(d);
+    int rc = validate_conv_desc(d, "fgc_conv_forms");
+    if (rc) return rc;
+    FGC_CHECK_ARG(buf && buf_bytes > 0, "fgc_conv_forms: no buffer");
+    int len = 0;
+    bool full = false;
+    auto put = [&](const char* key, const char* fmt, auto value) {
+        char tmp[96];
+        int k = snprintf(tmp, sizeof tmp, "%s%s=", len ? " " : "", key);
+        k += snprintf(tmp + k, sizeof tmp - k, fmt, value);
+        if (len + k + 1 > buf_bytes) { full = true; return; }
+        memcpy(buf + len, tmp, (size_t)k + 1);
+        len += k;
+    };
+    auto put_w8 = [&](const char* pre, const W8Form& f, bool vec4) {
+        char key[32];
+        auto k = [&](const char* name) { snprintf(key, sizeof key, "%s_%s", pre, name); return key; };
+        put(k("fast"), "%d", (int)f.fast);
+        put(k("slots"), "%d", f.qs);
+        put(k("nt"), "%d", f.nt);
+        put(k("bfm"), "%d", (int)f.bfm);
+        put(k("vec4"), "%d", (int)vec4);
+    };
+    static const char* const fwd_names[] = {"pair", "narrow", "w8", "tiled"};
+    static const char* const proj_names[] = {"pair", "narrow", "bf16", "stream", "block", "block"};
+    static const char* const ds_names[] = {"pair", "fused", "narrow-fused", "vec", "scalar"};
+    static const char* const k1_names[] = {"pair", "narrow", "bf16", "deep", "mfma", "valu"};
+    static const char* const k2_names[] = {"none", "w8", "tiled"};
+    static const char* const tn_names[] = {"stream2", "stream4", "stream2_bf", "stream4_bf", "bf16_4", "bf16_2", "plain_v4", "plain"};
+    buf[0] = 0;
+    // ---- forward (the logit table of the call: io->ag if given; fgc_conv_fwd wants it 16-byte aligned)
+    CoreParams p;
+    const FwdForm ff = conv_fwd_form(d, io ? io->ag : nullptr, nullptr, &p);
+    put("fwd", "%s", fwd_names[ff.kind]);
+    if (ff.kind == FWD_NARROW) put("fwd_mma", "%d", (int)narrow_fwd_mma(d, nullptr));
+    put_w8("fwd", ff.kind == FWD_W8 ? ff.w8 : W8Form{false, false, KMAX, TILE}, ff.vec4);
+    put("proj", "%s", proj_names[ff.proj]);
+    // ---- backward: the plan, then what this call's pointers add
+    const BwdPlan w = call_plan(d, io, nullptr);
+    const int rps = tn_rows_per_slab(w.nred, w.splitW);
+    const BwdCall c = io ? bwd_call(w, d, io) : BwdCall{};
+    if (io) {
+        put("ds", "%s", ds_names[c.ds]);
+        put("k1", "%s", k1_names[c.k1]);
+        if (c.k1 == K1_NARROW) put("k1_mma", "%d", (int)narrow_bwd_mma(d, io));
+        put("k1_okg", "%d", c.okg);
+        put("k1_aglobal", "%d", (int)c.a_global);
+        put("k1_vec4", "%d", (int)c.k1_vec4);
+    } else {
+        put("k1", "%s", k1_names[w.k1]);
+    }
+    put("k1_long", "%d", (int)w.k1_long);
+    put("k1_half", "%d", (int)w.k1_half);
+    put("k1_split", "%d", (int)w.k1_split);
+    put("k1_nodes", "%d", w.k1_nodes);
+    if (io) {
+        DataEpilogue ep;
+        const DataForm df = data_form(w, c, d, io, p, ep);
+        put("k2", "%s", k2_names[df.kind]);
+        put_w8("k2", df.kind == DATA_W8 ? df.w8 : W8Form{false, false, KMAX, TILE}, df.kind == DATA_W8 || df.vec4);
+        put("k2_chunks", "%d", df.max_deg > 0 ? cdiv(df.max_deg, KMAX) : 0);
+        if (c.k1 == K1_NARROW) put("k3", "%s", "narrow");
+        else {
+            const TnPlan pl = layer_tn_plan(d, io, w);
+            put("k3", "%s", tn_names[pl.variant]);
+            put("k3_slabs", "%d", pl.nsplits);
+            put("k3_rows", "%d", pl.a.rps);
+        }
+    } else {
+        put("k3_slabs", "%d", cdiv(w.nred, rps));
+        put("k3_rows", "%d", rps);
+    }
+    put("nb_db", "%d", w.nb_db);
+    put("n_dc", "%d", w.n_dc);
+    put("layout_id", "%llu", (unsigned long long)layout_id_of(w));
+    FGC_CHECK_ARG(!full, "fgc_conv_forms: buffer of %d bytes too small", buf_bytes);
+    return len;
+}
+
 extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, void* workspace,
                             size_t workspace_bytes, void* stream) {
     FGC_OPT_SCOPE(d);
     int rc = validate_conv_desc(d, "fgc_conv_bwd");
     if (rc) return rc;
     const int cin = d->c0 + d->c1, cout = d->cout;
-    const BwdPlan w = plan_bwd(d, (char*)workspace);
+    const BwdPlan w = call_plan(d, io, (char*)workspace);
     const bool bf16 = w.bf16;
     FGC_CHECK_ARG(io != nullptr, "fgc_conv_bwd: null io");
     FGC_CHECK_ARG(io->trowptr && io->tcol && io->tedge, "fgc_conv_bwd: transposed CSR missing");
@@ -1676,16 +1823,12 @@ extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, v
         }
         if (stages & 4) {
             CoreParams p;
-            fill_core_params(p, w.g2, w.nred, io->tpair_rowptr, io->tpair_col, io->tpair_edge, io->dt, nullptr, cout, 0, 0, cin, io->ag,
-                             0, 12, 0, w.Wpt);
-            DataEpilogue ep{io->dl, io->dag, io->r, io_r_ld(io, cout, bf16), d->u, d->v, cin, d->c0, 0, 0,
-                            io->dx0, nullptr, io->accumulate0, 0};
+            DataEpilogue ep;
+            data_form(w, c, d, io, p, ep);
             const size_t smem = conv_smem_bytes(w.g2, (size_t)TILE * 24 * 4);
             FGC_CHECK_ARG(w8_erow_supported(p, d->max_pair_in_deg) && (!bf16 || w8_bf16_supported(p, d->max_pair_in_deg)),
                           "fgc_conv_bwd: pair form: unsupported shape (cin=%d cout=%d max_pair_in_deg=%d)", cin, cout,
                           d->max_pair_in_deg);
-            p.tile_list = io->data_tile_list;
-            p.n_tiles = io->n_data_tiles;
             if (!p.tile_list || p.n_tiles > 0) {
                 rc = launch_data_w8_erow(p, ep, smem, d->max_pair_in_deg, st, bf16);
                 if (rc) return rc;
@@ -1699,11 +1842,11 @@ extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, v
                       "(cin=%d cout=%d max_deg=%d)", KMAX, cin, cout, d->max_deg);
         FGC_CHECK_ARG(!io->pool_dy || (io->pool_y && io->y && d->n % 4 == 0),
                       "fgc_conv_bwd: pool_dy needs pool_y, y and a row count that is a multiple of 4 (n=%d)", d->n);
-        if ((stages & 1) && !c.fuse_ds && !(c.narrow_path && narrow_fuses_ds(d, io))) {
+        if ((stages & 1) && (c.ds == DS_VEC || c.ds == DS_SCALAR)) {
             rc = launch_ds_db(w, c, d, io, st);
             if (rc) return rc;
         }
-        if (c.narrow_path) {
+        if (c.k1 == K1_NARROW) {
             if (stages & 2) {
                 rc = narrow_bwd_logits(d, io, w.narrow_ws, w.db_part, st);
                 if (rc) return rc;
@@ -1743,20 +1886,15 @@ extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, v
         // K2
         if ((stages & 4) && !(io->data_tile_list && io->n_data_tiles == 0)) {
             CoreParams p;
-            fill_core_params(p, w.g2, d->n, io->trowptr, io->tcol, io->tedge, io->ds, nullptr, cout, 0, 0, cin, io->ag,
-                             d->shift, 12, 0, w.Wpt);
-            p.tile_list = io->data_tile_list;
-            p.n_tiles = io->n_data_tiles;
-            DataEpilogue ep{io->dl, io->dag, io->r, io_r_ld(io, cout, bf16), d->u, d->v, cin, d->c0, d->c1, d->shift,
-                            io->dx0, io->dx1, io->accumulate0, io->accumulate1};
+            DataEpilogue ep;
+            const DataForm f = data_form(w, c, d, io, p, ep);
             const size_t smem = conv_smem_bytes(w.g2, (size_t)TILE * 24 * 4);
-            if (bf16) {
+            if (bf16)
                 FGC_CHECK_ARG(w8_bf16_supported(p, io->max_in_deg), "fgc_conv_bwd: FGC_CONV_BF16: unsupported shape for the data "
                               "gradient (cin=%d cout=%d max_in_deg=%d)", cin, cout, io->max_in_deg);
-                rc = launch_data_w8(p, ep, smem, io->max_in_deg, st, true);
-            } else if (w8_supported(p, io->max_in_deg)) {
-                rc = launch_data_w8(p, ep, smem, io->max_in_deg, st);
-            } else if ((cout % 4 == 0) && ((uintptr_t)io->ds % 16 == 0) && ((uintptr_t)io->r % 16 == 0)) {
+            if (f.kind == DATA_W8) {
+                rc = launch_data_w8(p, ep, smem, io->max_in_deg, st, bf16);
+            } else if (f.vec4) {
                 rc = launch_kernel<conv_bwd_data_kernel<8, true>>(
                     LaunchCfg{"conv_bwd_data_kernel<LPN, true>", "fgc_conv_bwd/data", st, core_grid(p), NTHREADS, smem}, p, ep);
             } else {

@@ -312,6 +312,39 @@ size_t conv_smem_bytes(const ConvGeom& g, size_t extra) {
     return core + extra;
 }
 
+// Which kernels a forward call takes: the one answer fgc_conv_fwd switches on and fgc_conv_forms prints.  ag: the logit table
+// of the call (only its alignment is read); p receives the tiled kernels' parameters (not for the pair and narrow kinds).
+FwdForm conv_fwd_form(const fgc_conv_desc* d, const float* ag, const float* Wp, CoreParams* p) {
+    FwdForm f{};
+    const int cin = d->c0 + d->c1;
+    if (pairs_ok(d)) {   // 4x-upsampled input, pair graph given: the layer on its coarse source rows (fgc_conv_pair.hip)
+        f.kind = FWD_PAIR;
+        f.proj = PROJ_PAIR;
+        return f;
+    }
+    const bool narrow = narrow_supported(d);   // cin <= 8: vector-ALU kernel, no packed operand (fgc_conv_narrow.hip)
+    const bool bf16 = (d->flags & FGC_CONV_BF16) != 0;
+    f.vec4 = conv_vec4_ok(d);
+    const float* pag = ag + (size_t)(d->proj_rows ? d->proj_row0 : 0) * FGC_AG_LD;
+    f.proj = narrow ? PROJ_NARROW
+           : bf16 ? PROJ_BF16
+           : (f.vec4 && (cin == 32 || cin == 64 || cin == 128) && d->c0 % 16 == 0 && (uintptr_t)pag % 16 == 0 &&
+              ((uintptr_t)d->u | (uintptr_t)d->v) % 16 == 0 && opt(OPT_NO_PROJ_STREAM) != 1) ? PROJ_STREAM
+           : f.vec4 ? PROJ_BLOCK_V4 : PROJ_BLOCK;
+    if (narrow) {
+        f.kind = FWD_NARROW;
+        return f;
+    }
+    fill_core_params(*p, conv_geom(cin, d->cout), d->n, d->rowptr, d->col, nullptr, d->x0, d->x1, d->c0, d->c1, d->shift, d->cout, ag,
+                     d->shift, 0, 12, Wp);
+    p->tile_list = d->tile_list;
+    p->n_tiles = d->n_tiles;
+    // (bf16 storage has the eight-wave kernels only: fgc_conv_fwd refuses the shapes they do not serve)
+    f.kind = (bf16 || w8_supported(*p, d->max_deg)) ? FWD_W8 : FWD_TILED;
+    if (f.kind == FWD_W8) f.w8 = w8_form(*p, nullptr, d->max_deg, bf16);
+    return f;
+}
+
 }  // namespace fgc
 
 extern "C" int fgc_conv_fwd(const fgc_conv_desc* d, float* ag, float* y, float* y_pool, void* workspace,
@@ -340,11 +373,13 @@ extern "C" int fgc_conv_fwd(const fgc_conv_desc* d, float* ag, float* y, float* 
     FGC_CHECK_ARG(d->tile_list == nullptr || (d->n_tiles >= 0 && d->n_tiles <= cdiv(d->n, TILE)),
                   "fgc_conv_fwd: n_tiles=%d outside [0, %d]", d->n_tiles, cdiv(d->n, TILE));
 
-    if (pairs_ok(d)) {   // 4x-upsampled input, pair graph given: the layer on its coarse source rows (fgc_conv_pair.hip)
+    CoreParams p;
+    const FwdForm f = conv_fwd_form(d, ag, Wp, &p);
+    if (f.kind == FWD_PAIR) {
         FGC_CHECK_ARG(y_pool == nullptr, "fgc_conv_fwd: the pair form has no pooled output");
         return launch_pair_fwd(d, ag, y, workspace, st);
     }
-    const bool narrow = narrow_supported(d);   // cin <= 8: vector-ALU kernel, no packed operand (fgc_conv_narrow.hip)
+    const bool narrow = f.kind == FWD_NARROW;
     const bool bf16 = (d->flags & FGC_CONV_BF16) != 0;
     FGC_CHECK_ARG(!bf16 || narrow || (conv_vec4_ok(d) && cin % 32 == 0 && (d->c1 == 0 || d->c0 % 32 == 0) && d->cout % 32 == 0),
                   "fgc_conv_fwd: FGC_CONV_BF16 needs widths that are multiples of 32 and 16-byte aligned tensors (c0=%d c1=%d "
@@ -357,55 +392,52 @@ extern "C" int fgc_conv_fwd(const fgc_conv_desc* d, float* ag, float* y, float* 
     }
     if (prows > 0) {
         const int pg = std::min(cdiv(cdiv(prows, 16), 4), 1024);
-        const bool xbf = bf16 && !narrow;        // (a narrow first layer reads its fp32 input)
-        const size_t esz = xbf ? 2 : 4;
+        const size_t esz = f.proj == PROJ_BF16 ? 2 : 4;        // (a narrow first layer reads its fp32 input)
         const float* px0 = reinterpret_cast<const float*>(reinterpret_cast<const char*>(d->x0) + (size_t)prow0 * d->c0 * esz);
         const float* px1 = d->x1 ? reinterpret_cast<const float*>(reinterpret_cast<const char*>(d->x1) + (size_t)prow0 * d->c1 * esz)
                                  : nullptr;
         float* pag = ag + (size_t)prow0 * FGC_AG_LD;
-        if (narrow)
-            FGC_LAUNCH("proj_mfma_kernel", st, proj_narrow_kernel, dim3(cdiv(prows, 256)), dim3(256), 0, px0, prows, d->c0, d->u, d->c,
-                       d->v, pag);
-        else if (xbf)
-            FGC_LAUNCH("proj_mfma_kernel", st, (proj_mfma_kernel<true, true>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1,
-                       prows, d->u, d->c, d->v, pag);
-        else if (conv_vec4_ok(d) && (cin == 32 || cin == 64 || cin == 128) && d->c0 % 16 == 0 && (uintptr_t)pag % 16 == 0 &&
-                 ((uintptr_t)d->u | (uintptr_t)d->v) % 16 == 0 && opt(OPT_NO_PROJ_STREAM) != 1) {
-            if (cin == 32)
-                FGC_LAUNCH("proj_mfma_kernel", st, (proj_stream_kernel<2>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1, prows, d->u,
+        switch (f.proj) {
+            case PROJ_NARROW:
+                FGC_LAUNCH("proj_mfma_kernel", st, proj_narrow_kernel, dim3(cdiv(prows, 256)), dim3(256), 0, px0, prows, d->c0, d->u,
                            d->c, d->v, pag);
-            else if (cin == 64)
-                FGC_LAUNCH("proj_mfma_kernel", st, (proj_stream_kernel<4>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1, prows, d->u,
-                           d->c, d->v, pag);
-            else
-                FGC_LAUNCH("proj_mfma_kernel", st, (proj_stream_kernel<8>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1, prows, d->u,
-                           d->c, d->v, pag);
-        } else if (conv_vec4_ok(d))
-            FGC_LAUNCH("proj_mfma_kernel", st, (proj_mfma_kernel<true>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1,
-                       prows, d->u, d->c, d->v, pag);
-        else
-            FGC_LAUNCH("proj_mfma_kernel", st, (proj_mfma_kernel<false>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1,
-                       prows, d->u, d->c, d->v, pag);
+                break;
+            case PROJ_BF16:
+                FGC_LAUNCH("proj_mfma_kernel", st, (proj_mfma_kernel<true, true>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1,
+                           prows, d->u, d->c, d->v, pag);
+                break;
+            case PROJ_STREAM:
+                if (cin == 32)
+                    FGC_LAUNCH("proj_mfma_kernel", st, (proj_stream_kernel<2>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1, prows,
+                               d->u, d->c, d->v, pag);
+                else if (cin == 64)
+                    FGC_LAUNCH("proj_mfma_kernel", st, (proj_stream_kernel<4>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1, prows,
+                               d->u, d->c, d->v, pag);
+                else
+                    FGC_LAUNCH("proj_mfma_kernel", st, (proj_stream_kernel<8>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1, prows,
+                               d->u, d->c, d->v, pag);
+                break;
+            case PROJ_BLOCK_V4:
+                FGC_LAUNCH("proj_mfma_kernel", st, (proj_mfma_kernel<true>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1,
+                           prows, d->u, d->c, d->v, pag);
+                break;
+            default:
+                FGC_LAUNCH("proj_mfma_kernel", st, (proj_mfma_kernel<false>), dim3(pg), dim3(256), 0, px0, px1, d->c0, d->c1,
+                           prows, d->u, d->c, d->v, pag);
+        }
         FGC_CHECK_LAUNCH("fgc_conv_fwd/proj");
     }
     if (d->tile_list && d->n_tiles == 0) return FGC_OK;
     if (narrow)
         return launch_narrow_fwd(d, ag, y, y_pool, (d->flags & FGC_CONV_SAVE_Z) ? (float*)workspace : nullptr, st, bf16);
 
-    CoreParams p;
-    fill_core_params(p, g, d->n, d->rowptr, d->col, nullptr, d->x0, d->x1, d->c0, d->c1, d->shift, d->cout, ag,
-                     d->shift, 0, 12, Wp);
-    p.tile_list = d->tile_list;
-    p.n_tiles = d->n_tiles;
     FwdEpilogue ep{d->b, d->bias_mask, d->act, d->alpha, y, y_pool};
     const size_t smem = conv_smem_bytes(g, 0);
-    if (bf16) {
+    if (bf16)
         FGC_CHECK_ARG(w8_bf16_supported(p, d->max_deg), "fgc_conv_fwd: FGC_CONV_BF16: unsupported shape (cin=%d cout=%d "
                       "max_deg=%d)", cin, d->cout, d->max_deg);
-        return launch_fwd_w8(p, ep, smem, d->max_deg, st, true);
-    }
-    if (w8_supported(p, d->max_deg)) return launch_fwd_w8(p, ep, smem, d->max_deg, st);
-    if (conv_vec4_ok(d))
+    if (f.kind == FWD_W8) return launch_fwd_w8(p, ep, smem, d->max_deg, st, bf16);
+    if (f.vec4)
         return launch_kernel<conv_fwd_kernel<8, true>>(LaunchCfg{"conv_fwd_kernel<LPN, true>", "fgc_conv_fwd", st, core_grid(p), NTHREADS, smem}, p, ep);
     return launch_kernel<conv_fwd_kernel<8, false>>(LaunchCfg{"conv_fwd_kernel<LPN, false>", "fgc_conv_fwd", st, core_grid(p), NTHREADS, smem}, p, ep);
 }

@@ -11,6 +11,10 @@ bool narrow_supported(const fgc_conv_desc* d);
 int launch_narrow_fwd(const fgc_conv_desc* d, const float* ag, float* y, float* y_pool, float* zsave, hipStream_t st,
                       bool out_bf16 = false);
 
+// per-node products on the matrix cores (6 -> 32 and 3 -> 32; option NO_NARROW_MMA = 1: the vector ALU), forward / backward
+bool narrow_fwd_mma(const fgc_conv_desc* d, const float* zsave);
+bool narrow_bwd_mma(const fgc_conv_desc* d, const fgc_conv_bwd_io* io);
+
 // backward of a narrow FIRST layer (io->dx0 == NULL).  `scratch` holds narrow_bwd_floats(d) floats and must survive
 // from the stage-2 call to the stage-8 call.
 int narrow_zld(int cin);

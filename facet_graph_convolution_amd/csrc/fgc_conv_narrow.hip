@@ -670,15 +670,16 @@ static int launch_narrow_fwd_mma_t(const NarrowFwd& p, hipStream_t st) {
     return FGC_OK;
 }
 
+bool narrow_fwd_mma(const fgc_conv_desc* d, const float* zsave) {
+    return !(opt(OPT_NO_NARROW_MMA) == 1) && d->cout == 32 && ((uintptr_t)zsave % 16) == 0 && (d->c0 == 6 || d->c0 == 3);
+}
+
 int launch_narrow_fwd(const fgc_conv_desc* d, const float* ag, float* y, float* y_pool, float* zsave, hipStream_t st,
                       bool out_bf16) {
     NarrowFwd p{d->n,    d->rowptr,    d->col, d->x0,   ag, d->W0, d->b, d->c0, d->cout, d->bias_mask, d->act,
                 d->alpha, y, y_pool, zsave, narrow_zld(d->c0), d->tile_list, d->n_tiles, out_bf16 ? 1 : 0};
     // the network's first layer (6 -> 32) and its 3-channel sibling: per-node products on the matrix cores
-    const bool mma = !(opt(OPT_NO_NARROW_MMA) == 1) && d->cout == 32 &&
-                     ((uintptr_t)zsave % 16) == 0;
-    if (mma && d->c0 == 6) return launch_narrow_fwd_mma_t<6, 2>(p, st);
-    if (mma && d->c0 == 3) return launch_narrow_fwd_mma_t<3, 2>(p, st);
+    if (narrow_fwd_mma(d, zsave)) return d->c0 == 6 ? launch_narrow_fwd_mma_t<6, 2>(p, st) : launch_narrow_fwd_mma_t<3, 2>(p, st);
     return launch_narrow_fwd_z<false>(p, st);
 }
 
@@ -696,7 +697,7 @@ int narrow_splits(const fgc_conv_desc* d) {
     return tn_balanced_splits(768 / cdiv(d->cout, 64), cdiv(d->n, 256), d->n);
 }
 
-static bool narrow_bwd_mma(const fgc_conv_desc* d, const fgc_conv_bwd_io* io) {
+bool narrow_bwd_mma(const fgc_conv_desc* d, const fgc_conv_bwd_io* io) {
     return !(opt(OPT_NO_NARROW_MMA) == 1) && d->cout == 32 &&
            ((uintptr_t)io->ds % 16) == 0 && (d->c0 == 6 || d->c0 == 3);
 }

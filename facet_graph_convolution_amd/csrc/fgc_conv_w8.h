@@ -48,6 +48,10 @@ static inline bool io_r_ld_ok(const fgc_conv_bwd_io* io, int cout, bool bf16) {
 // read off the backward plan (fgc_conv_bwd.hip)
 uint64_t conv_layout_id(const fgc_conv_desc* d);
 
+// which kernels a forward call takes (fgc_conv_fwd.hip: conv_fwd_form)
+enum FwdKind { FWD_PAIR, FWD_NARROW, FWD_W8, FWD_TILED };
+enum ProjForm { PROJ_PAIR, PROJ_NARROW, PROJ_BF16, PROJ_STREAM, PROJ_BLOCK_V4, PROJ_BLOCK };
+
 // host helpers of the tiled kernels (fgc_conv_fwd.hip)
 int validate_conv_desc(const fgc_conv_desc* d, const char* who);
 bool conv_vec4_ok(const fgc_conv_desc* d);
@@ -57,6 +61,21 @@ void fill_core_params(CoreParams& p, const ConvGeom& g, int n, const int* rowptr
 size_t conv_smem_bytes(const ConvGeom& g, size_t extra);
 
 bool w8_supported(const CoreParams& p, int max_deg);
+// the form of the eight-wave kernel a supported launch takes (fgc_conv_w8.hip: w8_form)
+struct W8Form {
+    bool bfm;    // bf16 storage: aggregation on the matrix pipe (fgc_conv_bfm.hip)
+    bool fast;   // the fast shapes' kernel (else the generic one: per-lane degree tests, 24 slots, 32-node tiles)
+    int qs;      // edge slots per node: 16 or KMAX
+    int nt;      // nodes per workgroup: 16 (half tiles) or TILE
+};
+W8Form w8_form(const CoreParams& p, const DataEpilogue* de, int max_deg, bool bf16);
+struct FwdForm {
+    int kind;     // FwdKind
+    W8Form w8;    // FWD_W8 only
+    bool vec4;    // 16-byte rows (conv_vec4_ok): FWD_TILED's gather form
+    int proj;     // ProjForm: the kernel that writes the logit table
+};
+FwdForm conv_fwd_form(const fgc_conv_desc* d, const float* ag, const float* Wp, CoreParams* p);
 // max_deg: the largest degree of the gathered graph (<= KMAX); <= 16 selects the 16-slot form of the fast kernel
 // bf16 = FGC_CONV_BF16 storage (needs w8_bf16_supported)
 bool w8_bf16_supported(const CoreParams& p, int max_deg);

@@ -635,15 +635,15 @@ static bool w8_fast(const CoreParams& p) {
 // runs five as well: level 0 128.6 / 112.5 -> 121.5 / 103.4 us, but the small coarse levels (a few hundred workgroups)
 // got slower (level 2: 29.6 -> 32.3), so it switches at FGC_W8_DATA16_MIN_N nodes (default 81920 = four rounds of
 // workgroups).  FGC_W8_NT16 = 0: never, 2: the data kernel always (developer switch).
-template <bool DATA>
-static bool w8_half_tiles(const CoreParams& p) {
+static bool w8_half_tiles(const CoreParams& p, bool data) {
     const int mode = (int)opt(OPT_W8_NT16), min_n = (int)opt(OPT_W8_DATA16_MIN_N);
     if ((p.npad >> 4) > 4 || mode < 1) return false;
-    return !DATA || mode >= 2 || p.n >= min_n;
+    return !data || mode >= 2 || p.n >= min_n;
 }
 
 template <bool DATA, bool FAST, int QS, bool BF = false, bool EROW = false>
-static int launch_w8f(const CoreParams& p, const FwdEpilogue& fe, const DataEpilogue& de, size_t smem, hipStream_t st) {
+static int launch_w8f(const CoreParams& p, const FwdEpilogue& fe, const DataEpilogue& de, size_t smem, const W8Form& f,
+                      hipStream_t st) {
     static bool attr = false;
     if (!attr) {
         hipFuncSetAttribute((const void*)conv_w8_kernel<DATA, FAST, QS, BF, 32, EROW>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -651,7 +651,7 @@ static int launch_w8f(const CoreParams& p, const FwdEpilogue& fe, const DataEpil
         attr = true;
     }
     if constexpr (FAST && QS == 16) {
-        if (w8_half_tiles<DATA>(p)) {
+        if (f.nt == 16) {
             constexpr int NT = 16;
             const size_t zrow = BF ? (size_t)ZSTRIDE_BF * 2 : (size_t)ZSTRIDE * 4;
             size_t smem16 = NT * zrow + (size_t)NT * qnode_stride(16) * 4 + (2 * NT + 4) * 4 + 64;
@@ -679,19 +679,30 @@ bool w8_bf16_supported(const CoreParams& p, int max_deg) {
 // (the matrix-pipe form stores r in 16-byte pieces)
 static bool bfm_r_ok(const DataEpilogue& de) { return ((uintptr_t)de.r & 15) == 0 && de.rld % 8 == 0; }
 
+// Which form of the eight-wave kernel a launch takes: the one answer launch_w8 / launch_data_w8_erow switch on and
+// fgc_conv_forms prints.  de: the data-gradient epilogue (NULL: forward).
+W8Form w8_form(const CoreParams& p, const DataEpilogue* de, int max_deg, bool bf16) {
+    W8Form f;
+    const bool data = de != nullptr;
+    // bf16 storage, degrees <= 16: the aggregation on the bf16 matrix pipe (fgc_conv_bfm.hip; option NO_BFM = 1: the vector form)
+    f.bfm = bf16 && bfm_supported(p, max_deg, data, data ? de->cin : 0) && (!data || bfm_r_ok(*de));
+    f.fast = bf16 || w8_fast(p);          // (bf16 storage: fast shapes only, w8_bf16_supported)
+    f.qs = (f.fast && max_deg <= 16) ? 16 : KMAX;
+    f.nt = ((f.bfm || (f.fast && f.qs == 16)) && w8_half_tiles(p, data)) ? 16 : TILE;
+    return f;
+}
+
 template <bool DATA>
 static int launch_w8(const CoreParams& p, const FwdEpilogue& fe, const DataEpilogue& de, size_t smem, int max_deg,
                      bool bf16, hipStream_t st) {
-    if (bf16) {
-        // degrees <= 16: the aggregation on the bf16 matrix pipe (fgc_conv_bfm.hip; option NO_BFM = 1: the vector form)
-        if (bfm_supported(p, max_deg, DATA, de.cin) && (!DATA || bfm_r_ok(de)))
-            return DATA ? launch_data_bfm(p, de, w8_half_tiles<DATA>(p), false, st) : launch_fwd_bfm(p, fe, w8_half_tiles<DATA>(p), st);
-        return max_deg <= 16 ? launch_w8f<DATA, true, 16, true>(p, fe, de, smem, st)
-                             : launch_w8f<DATA, true, KMAX, true>(p, fe, de, smem, st);
-    }
-    if (!w8_fast(p)) return launch_w8f<DATA, false, KMAX>(p, fe, de, smem, st);
-    return max_deg <= 16 ? launch_w8f<DATA, true, 16>(p, fe, de, smem, st)
-                         : launch_w8f<DATA, true, KMAX>(p, fe, de, smem, st);
+    const W8Form f = w8_form(p, DATA ? &de : nullptr, max_deg, bf16);
+    if (f.bfm) return DATA ? launch_data_bfm(p, de, f.nt == 16, false, st) : launch_fwd_bfm(p, fe, f.nt == 16, st);
+    if (bf16)
+        return f.qs == 16 ? launch_w8f<DATA, true, 16, true>(p, fe, de, smem, f, st)
+                          : launch_w8f<DATA, true, KMAX, true>(p, fe, de, smem, f, st);
+    if (!f.fast) return launch_w8f<DATA, false, KMAX>(p, fe, de, smem, f, st);
+    return f.qs == 16 ? launch_w8f<DATA, true, 16>(p, fe, de, smem, f, st)
+                      : launch_w8f<DATA, true, KMAX>(p, fe, de, smem, f, st);
 }
 
 int launch_fwd_w8(const CoreParams& p, const FwdEpilogue& ep, size_t smem, int max_deg, hipStream_t st, bool bf16) {
@@ -706,12 +717,13 @@ int launch_data_w8(const CoreParams& p, const DataEpilogue& ep, size_t smem, int
 bool w8_erow_supported(const CoreParams& p, int max_deg) { return w8_supported(p, max_deg) && w8_fast(p) && p.eid != nullptr; }
 int launch_data_w8_erow(const CoreParams& p, const DataEpilogue& ep, size_t smem, int max_deg, hipStream_t st, bool bf16) {
     FwdEpilogue fe{};
-    if (bf16 && bfm_supported(p, max_deg, true, ep.cin) && bfm_r_ok(ep)) return launch_data_bfm(p, ep, w8_half_tiles<true>(p), true, st);
+    const W8Form f = w8_form(p, &ep, max_deg, bf16);
+    if (f.bfm) return launch_data_bfm(p, ep, f.nt == 16, true, st);
     if (bf16)
-        return max_deg <= 16 ? launch_w8f<true, true, 16, true, true>(p, fe, ep, smem, st)
-                             : launch_w8f<true, true, KMAX, true, true>(p, fe, ep, smem, st);
-    return max_deg <= 16 ? launch_w8f<true, true, 16, false, true>(p, fe, ep, smem, st)
-                         : launch_w8f<true, true, KMAX, false, true>(p, fe, ep, smem, st);
+        return f.qs == 16 ? launch_w8f<true, true, 16, true, true>(p, fe, ep, smem, f, st)
+                          : launch_w8f<true, true, KMAX, true, true>(p, fe, ep, smem, f, st);
+    return f.qs == 16 ? launch_w8f<true, true, 16, false, true>(p, fe, ep, smem, f, st)
+                      : launch_w8f<true, true, KMAX, false, true>(p, fe, ep, smem, f, st);
 }
 
 }  // namespace fgc

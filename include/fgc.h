@@ -55,8 +55,9 @@ extern "C" {
  * 109: fgc_synth_noise / fgc_face_features_rows (+ fgc_synth_scratch_floats, fgc_philox_words): per-step noise synthesis on
  * a clean mesh.
  * 110: options K1_QS14 and W8_HALF2 removed with the two kernel forms they selected (both measured slower; the later option
- * indices do not move: the two were last in the table). */
-#define FGC_ABI_VERSION 110
+ * indices do not move: the two were last in the table).
+ * 111: fgc_conv_forms (which kernel form every launch of a layer takes, as text). */
+#define FGC_ABI_VERSION 111
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -400,6 +401,31 @@ int fgc_conv_pairs_allowed(int64_t rows, int64_t n_pairs, int32_t max_pair_in_de
 uint64_t fgc_conv_layout_id(const fgc_conv_desc* d);
 int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, void* workspace, size_t workspace_bytes,
                  void* stream);
+/* Which kernel form every launch of fgc_conv_fwd / fgc_conv_bwd takes for this descriptor (and this io), under the option
+ * values in force (process options, then the descriptor's own overrides), as ONE line of space-separated key=value pairs in
+ * buf.  Host only: launches nothing and dereferences no device pointer (addresses are read for their alignment and for being
+ * NULL).  Every value is the answer of the function the launch itself branches on.  io == NULL: the forward keys and what the
+ * backward plan decides without the call's pointers.  Returns the length written (without the NUL), FGC_EINVAL if the
+ * descriptor is invalid or buf too small (512 bytes are enough).  Keys (k2_* / k3 / ds and the starred k1 keys need io):
+ *   fwd        pair | narrow | w8 (eight-wave kernel) | tiled (conv_fwd_kernel)
+ *   fwd_mma    narrow only: per-node products on the matrix cores
+ *   fwd_fast fwd_slots fwd_nt fwd_bfm   w8: fast-shape kernel; edge slots 16 / 24; nodes per workgroup 16 / 32; bf16 matrix-pipe
+ *              aggregation (0 / 24 / 32 / 0 for the other kinds)
+ *   fwd_vec4   16-byte input rows (conv_fwd_kernel<vec4> against <scalar>; the blocking logit kernel likewise)
+ *   proj       logit-table kernel: pair | narrow | bf16 | stream | block
+ *   ds         who computes s = dy lrelu'(y) / deg and the db partials: pair | fused (d-logits prologue) | narrow-fused |
+ *              vec (ds_db_vec_kernel) | scalar (ds_db_kernel)
+ *   k1         d-logits kernel: pair | narrow | bf16 | deep | mfma | valu;  k1_mma* (narrow only)
+ *   k1_long k1_half k1_split k1_nodes   17..24 edge slots; 16-node workgroups; dz GEMM on split bf16 operands; nodes per workgroup
+ *   k1_okg* k1_aglobal* k1_vec4*        deep: compile-time column groups (0 = any width); ds tile read from global memory;
+ *              mfma / valu: 16-byte gathers
+ *   k2         data-gradient kernel: none (narrow first layer without dx) | w8 | tiled (conv_bwd_data_kernel)
+ *   k2_fast k2_slots k2_nt k2_bfm k2_vec4   as for fwd (tiled: vec4 = 16-byte rows of ds and r)
+ *   k2_chunks  ceil(max in-degree / 24): passes of the tiled kernel over a node's in-edge list (0: degree not stated)
+ *   k3         weight-gradient GEMM: stream2 | stream4 | stream2_bf | stream4_bf | bf16_4 | bf16_2 | plain_v4 | plain | narrow
+ *   k3_slabs k3_rows   slabs of the GEMM and rows per slab (the last slab holds the rest)
+ *   nb_db n_dc layout_id   db / dc partial-sum slots; fgc_conv_layout_id */
+int fgc_conv_forms(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, char* buf, int32_t buf_bytes);
 
 /* Extra jobs of fgc_conv_pack's launch (each part optional: rot_x == NULL / mlp_W1 == NULL skips it). */
 typedef struct fgc_pack_extra {

@@ -212,7 +212,14 @@ OP_TESTS = [
     ("test_gpu_model_api", "test_custom_conv2d_signature_and_return", {}),
     ("test_gpu_model_api", "test_multiscale_heads_train_through_the_operator_api", {}),
     ("test_gpu_bf16", "test_bf16_mlp_kernels_against_torch", {}),
-]
+] + [("test_gpu_conv_forms", "test_conv_form_against_float64", dict(name=name)) for name in (
+    # one per d-logits form, one per data-gradient kind, every misaligned case, the accumulate and pool_dy cases
+    "plain_32_32", "plain_64_128", "long_128_64", "odd_30_20", "NO_K1M_128_64", "narrow_6_32_nodx", "hub_64_128", "odd_5_7",
+    "x0p4_32_32", "x0p8_32_32", "dyp4_32_32", "rp4_32_32", "x0p4_128_64", "x0p8_128_64", "dyp4_128_64", "rp4_128_64",
+    "x0p4_64_128", "x0p8_64_128", "dyp4_64_128", "rp4_64_128", "rp4_hub_64_64",
+    "acc0_32_32", "acc01_concat_64+64_64", "acc1_concat_32+32_32", "acc0_up_64_32", "acc0_hub_64_64", "acc01_concat_48+16_32",
+    "pool_32_32", "pool_128_64", "pool_64_128", "pool_32_96", "pool_concat_48+16_32", "pool_6_32_nodx", "K1_NT16=0_pool_64_128",
+    "NO_FUSED_DS_pool_32_32")]
 
 
 @pytest.mark.parametrize("module,name,kw", OP_TESTS, ids=["%s-%s" % (n, "-".join(str(v) for v in k.values()) if isinstance(k, dict) else "all")
