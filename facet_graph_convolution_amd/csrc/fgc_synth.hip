@@ -2,11 +2,15 @@
 // fgc_face_features_rows): per step, every vertex of a clean mesh is displaced by a counter-based Gaussian draw and the
 // six input channels of every node row are rebuilt from the displaced vertices, bit for bit as the host routine
 // fgc_face_features computes them.  Plain bandwidth work: one thread per vertex, one thread per node row.
+// fgc_point_sets_prepare: the displaced vertices and the ground-truth vertices divided by the bounding-box diagonal of
+// their union and rotated, for the point-set loss - one thread per 3-vector.
 //
-// The features must carry the host routine's roundings: no fused multiply-add anywhere in this file.
+// The features must carry the host routine's roundings: no fused multiply-add anywhere in this file but the explicit
+// fmaf of rot3 (fgc_pack.h), which are the rotation's definition.
 #include <algorithm>
 
 #include "fgc_common.h"
+#include "fgc_pack.h"
 #include "fgc_synth.h"
 #pragma clang fp contract(off)      // (and -ffp-contract=off for the file: Makefile)
 
@@ -188,6 +192,61 @@ __global__ __launch_bounds__(SY_THREADS) void face_features_rows_kernel(const fl
     dst[2] = f32x2c{row[4], row[5]};
 }
 
+// One thread per 3-vector of the two point sets (the nv vectors of v, then the ngt of gt; no stride: a workgroup's 256
+// vectors): out = R (p / diag), diag the bounding-box diagonal of the UNION of the two sets - utils.normalizePointSets
+// followed by rotate_rows_kernel, bit for bit.  Every workgroup first reduces the n_partials boxes of v (the noise
+// launch's, or synth_bbox_kernel's: at most SY_MAX_BLOCKS x 24 bytes, from the L2) together with the box of gt (gt_box:
+// six floats, made once per mesh) to the diagonal, as face_features_rows_kernel does: no launch of its own for that.
+// The coordinates are DIVIDED (numpy divides; a multiply by the reciprocal differs in the last bit).  R == nullptr: no
+// rotation.
+__global__ __launch_bounds__(SY_THREADS) void point_sets_prepare_kernel(const float* __restrict__ v, int nv,
+                                                                        const float* __restrict__ gt, int ngt,
+                                                                        const float* __restrict__ gt_box,
+                                                                        const float* __restrict__ partials, int n_partials,
+                                                                        const float* __restrict__ Rd,
+                                                                        float* __restrict__ v_out, float* __restrict__ gt_out) {
+    __shared__ float red[SY_THREADS / 64][6];
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int j = threadIdx.x; j < n_partials; j += SY_THREADS)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            mn[t] = fminf(mn[t], partials[6 * j + t]);
+            mx[t] = fmaxf(mx[t], partials[6 * j + 3 + t]);
+        }
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            mn[t] = fminf(mn[t], gt_box[t]);
+            mx[t] = fmaxf(mx[t], gt_box[3 + t]);
+        }
+    block_minmax(mn, mx, red);
+    // the diagonal in double from the fp32 extents, then rounded to fp32 (what numpy's float32 / python float divides by)
+    double diag2 = 0.0;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const double e = (double)(mx[t] - mn[t]);
+        diag2 += e * e;
+    }
+    const float diag = (float)sqrt(diag2);
+    const int64_t i = (int64_t)blockIdx.x * SY_THREADS + threadIdx.x;
+    if (i >= (int64_t)nv + ngt) return;
+    const bool first = i < nv;
+    const size_t o = 3 * (size_t)(first ? i : i - nv);
+    const float* __restrict__ src = first ? v : gt;
+    float* __restrict__ dst = first ? v_out : gt_out;
+    const float a = src[o] / diag, b = src[o + 1] / diag, c = src[o + 2] / diag;
+    if (Rd) {
+        float r[9];
+#pragma unroll
+        for (int t = 0; t < 9; ++t) r[t] = Rd[t];
+        rot3(r, a, b, c, dst[o], dst[o + 1], dst[o + 2]);
+    } else {
+        dst[o] = a;
+        dst[o + 1] = b;
+        dst[o + 2] = c;
+    }
+}
+
 }  // namespace fgc
 
 using namespace fgc;
@@ -238,5 +297,26 @@ extern "C" int fgc_face_features_rows(const float* v, int32_t nv, const int32_t*
     FGC_LAUNCH("face_features_rows_kernel", st, face_features_rows_kernel, dim3(cdiv(n, SY_THREADS)), dim3(SY_THREADS), 0,
                v, nv, faces_rows, n, ctl, (const float*)scratch, nblk, x);
     FGC_CHECK_LAUNCH("fgc_face_features_rows");
+    return FGC_OK;
+}
+
+extern "C" int fgc_point_sets_prepare(const float* v, int32_t nv, const float* gt, int32_t ngt, const float* gt_box,
+                                      const float* R, int32_t have_bbox, float* v_out, float* gt_out, float* scratch,
+                                      size_t scratch_floats, void* stream) {
+    FGC_CHECK_ARG(v && gt && gt_box && v_out && gt_out && scratch, "fgc_point_sets_prepare: null pointer");
+    FGC_CHECK_ARG(nv > 0 && ngt > 0, "fgc_point_sets_prepare: nv=%d, ngt=%d (> 0)", nv, ngt);
+    FGC_CHECK_ARG(v_out != v && gt_out != gt && v_out != gt_out, "fgc_point_sets_prepare: the outputs must be buffers of their own");
+    const size_t need = fgc_synth_scratch_floats(nv);
+    FGC_CHECK_ARG(scratch_floats >= need, "fgc_point_sets_prepare: scratch too small (%zu < %zu floats)", scratch_floats,
+                  need);
+    hipStream_t st = (hipStream_t)stream;
+    const int nblk = synth_blocks(nv);
+    if (!have_bbox)
+        FGC_LAUNCH("synth_bbox_kernel", st, synth_bbox_kernel, dim3(nblk), dim3(SY_THREADS), 0, v, nv,
+                   (const uint32_t*)nullptr, scratch);
+    const int64_t total = (int64_t)nv + ngt;
+    FGC_LAUNCH("point_sets_prepare_kernel", st, point_sets_prepare_kernel, dim3((unsigned)((total + SY_THREADS - 1) / SY_THREADS)),
+               dim3(SY_THREADS), 0, v, nv, gt, ngt, gt_box, (const float*)scratch, nblk, R, v_out, gt_out);
+    FGC_CHECK_LAUNCH("fgc_point_sets_prepare");
     return FGC_OK;
 }

@@ -240,8 +240,28 @@ class TrainingSet(PreprocessedData):
                             ("clean_edge_len", float(utils.getAverageEdgeLength(V, faces)[0]))):
             self.__dict__.setdefault(name, []).append(value)
 
+    def addCleanMeshWithVertices(self, V, faces, seed=None, parents=None):
+        """Build extension: a CLEAN mesh for training the vertex networks (trainAccuracyNet / trainDoubleLossNet with
+        noise_levels=...) on noise synthesised per step on the GPU (FacetDenoiser.bind_clean_vertices).  Arrays
+        addCleanMeshWithVertices(V, faces) or the file form addCleanMeshWithVertices(path, filename).  Everything
+        addMeshWithVerticesAndGT(V, faces, V) does - the clean mesh is its own ground truth in gtv_list and gt_list - plus
+        the three per-mesh fields of addCleanMesh: clean_vertices (the RAW vertices, float32 [1, V, 3]), clean_faces_rows
+        (int32 [1, N0, 3], the values of faces_list) and clean_edge_len.  Patch mode (more faces than maxSize) is refused."""
+        if isinstance(V, str):
+            V, _, _, faces, _ = utils.load_mesh(V, faces, 0, False)
+            seed = parents = None
+        V = np.ascontiguousarray(np.asarray(V, dtype=np.float32))
+        faces = np.asarray(faces)
+        if faces.shape[0] > self.maxSize:
+            raise NotImplementedError("addCleanMeshWithVertices keeps a mesh whole: %d faces > maxSize %d (patch mode)"
+                                      % (faces.shape[0], self.maxSize))
+        self.addMeshWithVerticesAndGT(V, faces, V, seed=seed, parents=parents)
+        for name, value in (("clean_vertices", V[np.newaxis]), ("clean_faces_rows", self.faces_list[-1].astype(np.int32)),
+                            ("clean_edge_len", float(utils.getAverageEdgeLength(V, faces)[0]))):
+            self.__dict__.setdefault(name, []).append(value)
+
     def is_clean(self):
-        """Every mesh of the set came through addCleanMesh (what trainNet(noise_levels=...) needs)."""
+        """Every mesh of the set came through addCleanMesh or addCleanMeshWithVertices (what noise_levels=... needs)."""
         n = len(self.in_list)
         return n > 0 and all(len(self.__dict__.get(k, ())) == n for k in ("clean_vertices", "clean_faces_rows",
                                                                             "clean_edge_len"))

@@ -628,6 +628,15 @@ class FacetDenoiser:
                 raise ValueError("mesh %r is bound with another seed / stream / direction" % (key,))
             self._mesh = M
             return self
+        S = self._synth_state(x, verts, faces_rows, edge_len, seed, stream, direction)
+        M = self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt))
+        M["synth"] = S
+        # (a step captured while the mesh was bound by bind_cached under this key has no synthesis nodes: record it again)
+        M["captured"].clear()
+        return self
+
+    def _synth_state(self, x, verts, faces_rows, edge_len, seed, stream, direction):
+        """The checked arguments of bind_clean / bind_clean_vertices as the synthesis state kept with the mesh."""
         if direction not in ("random", "normal"):
             raise ValueError("direction must be 'random' or 'normal'")
         vx = np.ascontiguousarray(np.asarray(verts, dtype=np.float32).reshape(-1, 3))
@@ -640,7 +649,6 @@ class FacetDenoiser:
             raise ValueError("faces_rows names vertex %d of %d" % (fr.max(), vx.shape[0]))
         if not (np.isfinite(edge_len) and edge_len > 0):
             raise ValueError("edge_len must be a positive length")
-        M = self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt))
         dev = self.device
         S = dict(v=torch.as_tensor(vx, device=dev), faces=torch.as_tensor(fr, device=dev), vn=None,
                  edge_len=float(edge_len), seed=int(seed), stream=int(stream), direction=direction)
@@ -649,14 +657,11 @@ class FacetDenoiser:
             S["vn"] = torch.as_tensor(areaWeightedVertexNormals(vx, fr[fr[:, 0] >= 0]).astype(np.float32), device=dev)
         S["v_out"] = S["v"].clone()
         S["scratch"] = torch.zeros(max(self.L.fgc_synth_scratch_floats(vx.shape[0]), 1), dtype=torch.float32, device=dev)
-        M["synth"] = S
-        # (a step captured while the mesh was bound by bind_cached under this key has no synthesis nodes: record it again)
-        M["captured"].clear()
-        return self
+        return S
 
     def _require_synth(self):
         if "synth" not in (self._mesh or {}):
-            raise RuntimeError("bind_clean(...) is required for noise synthesis")
+            raise RuntimeError("bind_clean(...) or bind_clean_vertices(...) is required for noise synthesis")
         return self._mesh["synth"]
 
     def _enqueue_synth(self):
@@ -674,6 +679,45 @@ class FacetDenoiser:
     def noisy_vertices(self):
         """The displaced vertices [V,3] of the last step that synthesised noise (device tensor, overwritten by the next)."""
         return self._require_synth()["v_out"]
+
+    def bind_clean_vertices(self, key, x, adjs, verts, faces_rows, v_faces, edge_len, gt_normals=None, iters=VERTEX_ITERS,
+                            seed=0, stream=0, direction="random"):
+        """Build extension: bind a CLEAN mesh for the point-set and double-loss steps on noise synthesised per step -
+        bind_vertices plus bind_clean's synthesis state, kept with the mesh under `key`.  verts [V,3]: the RAW clean
+        vertices (TrainingSet.addCleanMeshWithVertices' clean_vertices), which are also the ground-truth vertices;
+        faces_rows int [N0,3]: the faces in node order (-1 rows = fake nodes), v_faces [V,K], edge_len, seed, stream,
+        direction as in bind_clean; gt_normals: the clean face normals [N0,3] in node order, for the double loss.
+        Every step then runs three launches in front: fgc_synth_noise, fgc_face_features_rows (the input rows) and
+        fgc_point_sets_prepare, which normalises the displaced and the clean vertices by the diagonal of their union box
+        and rotates both, straight into the buffers the vertex update and fgc_point_loss read - in the place of the two
+        fgc_rotate_rows launches of a mesh bound by bind_vertices.  The last launch has no control word: while the noise
+        words are zero (right after binding, or set_noise(step, None)) a step runs on the vertices the last
+        synthesising step left; right after binding these are the clean ones."""
+        if self.comm is not None or (self._mesh is not None and self.sharded):
+            raise NotImplementedError("noise synthesis runs on an unsharded network")
+        if not self.multi_scale or self.dtype != "f32":
+            raise NotImplementedError("point-set training: unsharded fp32 multi-scale network only")
+        M = self._mesh_cache.get(key)
+        if M is not None and ("synth" in M or "verts" in M):
+            if "gt_box" not in M.get("synth", {}) or "verts" not in M:
+                raise ValueError("mesh %r is bound under this key without synthesised point sets" % (key,))
+            if (M["synth"]["seed"], M["synth"]["stream"], M["synth"]["direction"]) != (int(seed), int(stream), direction):
+                raise ValueError("mesh %r is bound with another seed / stream / direction" % (key,))
+            return self.bind_vertices(key, x, adjs, None, None, None, None, gt_normals=gt_normals)
+        S = self._synth_state(x, verts, faces_rows, edge_len, seed, stream, direction)
+        # (the plain vertex state holds the clean mesh normalised by its own box; the steps read xr / gtr instead)
+        from .utils import normalizePointSets
+        vx = S["v"].cpu().numpy()
+        vn = normalizePointSets(vx, vx)[0]
+        self.bind_vertices(key, x, adjs, vn, faces_rows, v_faces, vn, iters=iters, gt_normals=gt_normals)
+        M, nv, sc = self._mesh, S["v"].shape[0], S["scratch"]
+        S["gt_box"] = torch.cat([S["v"].min(0).values, S["v"].max(0).values])
+        # the boxes of the clean vertices (and the clean input rows once more): what a step without noise words runs on
+        _lib.check(self.L.fgc_face_features_rows(_p(S["v_out"]), nv, _p(S["faces"]), M["ns"][0], None, 0, _p(M["B"]["x"]),
+                                                 _p(sc), sc.numel(), self._st()), "clean features")
+        M["synth"] = S
+        M["captured"].clear()
+        return self
 
     # ------------------------------------------------------------------------------------------
     # enqueue helpers (no allocation, no sync).  The schedules are GENERATORS: they yield an exchange request
@@ -1306,10 +1350,10 @@ class FacetDenoiser:
         self._upload(self._mesh["B"]["R"], np.asarray(R, dtype=np.float32).reshape(9))
 
     def set_noise(self, step, level):
-        """Build extension (bind_clean): the next steps draw the noise of counter `step` (64-bit) at `level` x the bound
-        clean mesh's mean edge length; level 0 rebuilds the clean input, level None switches the synthesis off (the
-        steps read x as the last synthesis left it).  Filled the way set_rotation fills R; the kernels read the words
-        from device memory, so a captured step replays with the new values."""
+        """Build extension (bind_clean, bind_clean_vertices): the next steps draw the noise of counter `step` (64-bit) at
+        `level` x the bound clean mesh's mean edge length; level 0 rebuilds the clean input, level None switches the
+        synthesis off (the steps read x as the last synthesis left it).  Filled the way set_rotation fills R; the kernels
+        read the words from device memory, so a captured step replays with the new values."""
         S = self._require_synth()
         self._own_step_inputs()
         words = ops.noise_words(step, None if level is None else np.float32(level) * np.float32(S["edge_len"]))
@@ -1627,9 +1671,19 @@ class FacetDenoiser:
                 _lib.check(L.fgc_normalize_fwd(_p(y), M["ns"][int(k)], _p(part), part.numel(), _p(B["nconv" + k]),
                                                _p(sc), st), "normalize head" + k)
             heads = (B["nconv"], B["nconv1"], B["nconv2"])
-        self._tag("pts:rotate")
         x, gt = V["x"], V["gt"]
-        if rotate:
+        if "gt_box" in M.get("synth", ()):
+            # a clean mesh (bind_clean_vertices): the displaced and the clean vertices over the diagonal of their union
+            # box, rotated - one launch behind the two of _enqueue_synth, whose boxes it reads
+            self._tag("pts:prepare")
+            S = M["synth"]
+            sc = S["scratch"]
+            _lib.check(L.fgc_point_sets_prepare(_p(S["v_out"]), nv, _p(S["v"]), nv, _p(S["gt_box"]),
+                                                _p(B["R"]) if rotate else None, 1, _p(V["xr"]), _p(V["gtr"]), _p(sc),
+                                                sc.numel(), st), "point sets")
+            x, gt = V["xr"], V["gtr"]
+        elif rotate:
+            self._tag("pts:rotate")
             _lib.check(L.fgc_rotate_rows(_p(x), _p(V["xr"]), nv, 1, _p(B["R"]), st), "rotate vertices")
             _lib.check(L.fgc_rotate_rows(_p(gt), _p(V["gtr"]), gt.shape[0], 1, _p(B["R"]), st), "rotate gt vertices")
             x, gt = V["xr"], V["gtr"]
@@ -1701,10 +1755,13 @@ class FacetDenoiser:
         self._pointset_forward(rotate, False)
         return self._mesh["verts"]["loss"]
 
-    def pointset_step(self, sample_ind0, sample_ind1, R, capture=False):
-        """One iteration of trainAccuracyNet's loop body (train.py:800-840): samples, rotation, forward, backward, Adam."""
+    def pointset_step(self, sample_ind0, sample_ind1, R, capture=False, noise=None):
+        """One iteration of trainAccuracyNet's loop body (train.py:800-840): samples, rotation, forward, backward, Adam.
+        noise = (step, level) (build extension, a mesh bound by bind_clean_vertices): set_noise(step, level) first."""
         self.set_point_samples(sample_ind0, sample_ind1)
         self.set_rotation(R)
+        if noise is not None:
+            self.set_noise(*noise)
         loss = self.pointset_forward_backward(rotate=True, capture=capture)
         self.adam_step()
         return loss
@@ -1733,10 +1790,13 @@ class FacetDenoiser:
         self._pointset_forward(rotate, False, True)
         return self._mesh["verts"]["dl_out"][:3]
 
-    def double_loss_step(self, sample_ind0, sample_ind1, R, capture=False):
-        """One iteration of trainDoubleLossNet's loop body (train.py:1160-1243): samples, rotation, step, Adam."""
+    def double_loss_step(self, sample_ind0, sample_ind1, R, capture=False, noise=None):
+        """One iteration of trainDoubleLossNet's loop body (train.py:1160-1243): samples, rotation, step, Adam.
+        noise = (step, level) (build extension, bind_clean_vertices): set_noise(step, level) first."""
         self.set_point_samples(sample_ind0, sample_ind1)
         self.set_rotation(R)
+        if noise is not None:
+            self.set_noise(*noise)
         out = self.double_loss_forward_backward(rotate=True, capture=capture)
         self.adam_step()
         return out

@@ -667,6 +667,37 @@ def synth_noise(verts, sigma, step, seed=0, stream=0, normals=None, out=None, sc
     return out
 
 
+def point_sets_prepare(v, gt, R=None, gt_box=None, scratch=None, have_bbox=False, out=None):
+    """Build extension (include/fgc.h: fgc_point_sets_prepare): the displaced vertices v [V,3] and the ground-truth
+    vertices gt [Vgt,3] (raw units) divided by the bounding-box diagonal of their union and rotated by R (3x3 array-like or
+    device tensor; None: no rotation) - bit-identical to utils.normalizePointSets(v, gt) followed by rotate_rows.
+    Returns (v_out [V,3], gt_out [Vgt,3]) (`out`: the pair to write into).  gt_box: float32 [6] on the device, {min xyz,
+    max xyz} of gt (computed here when None); have_bbox: `scratch` holds the bounding-box partials synth_noise has just
+    left for v."""
+    _req_cuda(v, gt, gt_box, scratch, *(out or ()))
+    v, gt = _f32c(v.reshape(-1, 3)), _f32c(gt.reshape(-1, 3))
+    nv, ngt = v.shape[0], gt.shape[0]
+    if R is not None:
+        if not isinstance(R, torch.Tensor) or not R.is_cuda:
+            R = torch.as_tensor(np.asarray(R, dtype=np.float32).reshape(9)).to(v.device)
+        R = R.reshape(9).float().contiguous()
+    if gt_box is None:
+        if ngt == 0:
+            raise ValueError("no ground-truth vertices")
+        gt_box = torch.cat([gt.min(0).values, gt.max(0).values])
+    gt_box = _f32c(gt_box.reshape(6))
+    v_out, gt_out = out if out is not None else (torch.empty_like(v), torch.empty_like(gt))
+    need = _lib.lib().fgc_synth_scratch_floats(nv)
+    if scratch is None:
+        if have_bbox:
+            raise ValueError("have_bbox needs the scratch synth_noise filled")
+        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=v.device)
+    check(_lib.lib().fgc_point_sets_prepare(ptr(v), nv, ptr(gt), ngt, ptr(gt_box), ptr(R), 1 if have_bbox else 0, ptr(v_out),
+                                            ptr(gt_out), ptr(scratch), scratch.numel(), stream_ptr()),
+          "fgc_point_sets_prepare")
+    return v_out, gt_out
+
+
 def philox_words(first, n, step, seed=0, stream=0, device="cuda"):
     """The raw Philox4x32-10 words of synth_noise (include/fgc.h: fgc_philox_words): int32 [n,4] on the device (view as
     uint32), row i for the counter (first + i, step low, step high, stream) and the key seed."""

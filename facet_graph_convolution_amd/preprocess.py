@@ -15,7 +15,8 @@ Build extension - training from clean meshes, the noise synthesised per step on 
     python -m facet_graph_convolution_amd.preprocess CLEAN_DIR DUMP_DIR --clean [--valid CLEAN_VALID_DIR] [--redundancy R]
 
 takes every OBJ of CLEAN_DIR as its own ground truth (TrainingSet.addCleanMesh) and writes `trainingSetClean.pkl` /
-`validSetClean.pkl`.
+`validSetClean.pkl`.  With --with-vertices every mesh also keeps its vertex data (TrainingSet.addCleanMeshWithVertices) for
+`train --with-vertices --synth-noise`, pickled as `trainingSetCleanWithVertices.pkl` / `validSetCleanWithVertices.pkl`.
 """
 import argparse
 import os
@@ -58,12 +59,15 @@ def pickleData(training_dir, gt_dir, dump_dir, valid_dir=None, redundancy=1, gt_
     return out
 
 
-def pickleCleanData(clean_dir, dump_dir, valid_dir=None, redundancy=1, log=print):
+def pickleCleanData(clean_dir, dump_dir, valid_dir=None, redundancy=1, log=print, withVerts=False):
     """Build extension: `trainingSetClean.pkl` / `validSetClean.pkl` from folders of CLEAN OBJ files
-    (TrainingSet.addCleanMesh), `redundancy` coarsenings per training mesh."""
+    (TrainingSet.addCleanMesh), `redundancy` coarsenings per training mesh.  withVerts: with the vertex data
+    (addCleanMeshWithVertices), as `trainingSetCleanWithVertices.pkl` / `validSetCleanWithVertices.pkl`."""
     os.makedirs(dump_dir, exist_ok=True)
     out = {}
-    for tag, folder, rep in (("trainingSetClean.pkl", clean_dir, redundancy), ("validSetClean.pkl", valid_dir, 1)):
+    names = (("trainingSetCleanWithVertices.pkl", "validSetCleanWithVertices.pkl") if withVerts
+             else ("trainingSetClean.pkl", "validSetClean.pkl"))
+    for tag, folder, rep in ((names[0], clean_dir, redundancy), (names[1], valid_dir, 1)):
         if not folder or not os.path.isdir(folder):
             continue
         ds = TrainingSet()
@@ -72,7 +76,10 @@ def pickleCleanData(clean_dir, dump_dir, valid_dir=None, redundancy=1, log=print
                 continue
             log("Adding %s (%i)" % (f, ds.mesh_count))
             for _ in range(rep):
-                ds.addCleanMesh(folder, f)
+                if withVerts:
+                    ds.addCleanMeshWithVertices(folder, f)
+                else:
+                    ds.addCleanMesh(folder, f)
         if ds.mesh_count:
             with open(os.path.join(dump_dir, tag), "wb") as fp:
                 pickle.dump(ds, fp)
@@ -87,17 +94,16 @@ def main(argv=None):
     ap.add_argument("dump_dir", nargs="?", default=None, help="where the pickles go (not with --clean)")
     ap.add_argument("--valid", default=None)
     ap.add_argument("--redundancy", type=int, default=1)
-    ap.add_argument("--with-vertices", action="store_true", help="keep the vertex data trainAccuracyNet needs")
+    ap.add_argument("--with-vertices", action="store_true",
+                    help="keep the vertex data trainAccuracyNet needs (with --clean: trainingSetCleanWithVertices.pkl)")
     ap.add_argument("--clean", action="store_true",
                     help="build extension: CLEAN_DIR DUMP_DIR - clean meshes for training on synthesised noise")
     args = ap.parse_args(argv)
     if args.clean:
         if args.dump_dir is not None:
             ap.error("--clean takes two folders: CLEAN_DIR DUMP_DIR (a clean mesh is its own ground truth)")
-        if args.with_vertices:
-            ap.error("--clean does not go with --with-vertices: point-set training on synthesised noise is not built")
         dump = args.gt_dir
-        if not pickleCleanData(args.training_dir, dump, args.valid, args.redundancy):
+        if not pickleCleanData(args.training_dir, dump, args.valid, args.redundancy, withVerts=args.with_vertices):
             ap.error("no OBJ file in %s" % args.training_dir)
     else:
         if args.dump_dir is None:

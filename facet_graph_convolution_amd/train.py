@@ -15,8 +15,9 @@ Training command (the reference's ``train(withVerts)``, train.py:1894-1921):
         [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal]
 
 loads the pickles `preprocess` wrote and runs trainNet, trainAccuracyNet (--with-vertices) or trainDoubleLossNet
-(--with-vertices --double-loss).  --synth-noise (build extension) loads the CLEAN pickles of `preprocess --clean` and
-runs trainNet on noise synthesised per step on the GPU.
+(--with-vertices --double-loss).  --synth-noise (build extension) loads the CLEAN pickles of `preprocess --clean`
+(with --with-vertices: of `preprocess --clean --with-vertices`) and runs the same trainer on noise synthesised per step
+on the GPU.
 """
 import argparse
 import os
@@ -249,7 +250,7 @@ def _resume(net, network_path, net_name):
 
 
 def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
-                     capture=False, validSet=None):
+                     capture=False, validSet=None, noise_levels=None, noise_direction="random"):
     """train.py:636-916: the multi-scale network trained through update_position_MS on the point-set loss fullLoss.
     trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT.  One iteration = a random mesh
     (meshes without ground-truth vertices are skipped), SAMP_NUM = 500 random rows of the vertices and of the
@@ -266,13 +267,20 @@ def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net"
     loss in column 0, validation loss in column 1, the previous row's validation entry set to the mean of its two
     neighbours as the reference does), and the block is appended to `<net_name>.csv` at every save.
 
+    noise_levels (build extension; None = the loop above, untouched, with its random stream): trainSet / validSet hold
+    CLEAN meshes (TrainingSet.addCleanMeshWithVertices, otherwise ValueError) and every iteration trains on fresh
+    Gaussian vertex noise made on the GPU (FacetDenoiser.bind_clean_vertices): a level drawn from the list (after the
+    rotation) x the mesh's mean edge length, along noise_direction, with the global iteration as the noise counter; the
+    ground truth is the clean mesh.  Validation: synthVertexValidationLoss, every 20 iterations and - in this mode
+    only - at iteration 0 as well.
+
     Returns (net, lossArray of the last block, per-iteration training losses [num_iterations])."""
     return _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
-                                double=False)
+                                False, noise_levels, noise_direction)
 
 
 def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
-                       capture=False, validSet=None):
+                       capture=False, validSet=None, noise_levels=None, noise_direction="random"):
     """train.py:919-1268: the multi-scale network trained on the point-set loss fullLoss PLUS the dense face-normal loss
     faceNormalsLoss of head 0 against the rotated ground-truth face normals (customLoss = pointsLoss + normalsLoss,
     unweighted, train.py:1100-1102).  trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT
@@ -287,9 +295,11 @@ def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="ne
     1, the previous row's validation entry set to the mean of its two neighbours), and the block is appended to
     `<net_name>.csv` at every save.
 
+    noise_levels / noise_direction (build extension): as in trainAccuracyNet; the ground-truth normals are the clean ones.
+
     Returns (net, lossArray of the last block, per-iteration {total, points, normals} [num_iterations, 3])."""
     return _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
-                                double=True)
+                                True, noise_levels, noise_direction)
 
 
 def _vertex_meshes(ds, double, strict):
@@ -312,12 +322,55 @@ def _vertex_meshes(ds, double, strict):
     return out
 
 
-def _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet, double):
+def _clean_vertex_meshes(ds, what):
+    """The meshes of a clean vertex TrainingSet (addCleanMeshWithVertices): (x, adjs, raw clean vertices, faces_rows,
+    v_faces, edge_len, clean normals) - the arguments of FacetDenoiser.bind_clean_vertices behind the key."""
+    n = len(getattr(ds, "in_list", ()))
+    if not (hasattr(ds, "is_clean") and ds.is_clean() and len(ds.v_faces_list) == n and len(ds.gt_list) == n):
+        raise ValueError("noise_levels needs a %s of clean meshes with their vertex data (TrainingSet."
+                         "addCleanMeshWithVertices, preprocess --clean --with-vertices)" % what)
+    return [(ds.in_list[i], ds.adj_list[i], ds.clean_vertices[i], ds.clean_faces_rows[i], ds.v_faces_list[i],
+             ds.clean_edge_len[i], ds.gt_list[i]) for i in range(n)]
+
+
+def synthVertexValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", double=False):
+    """Build extension: {total, points, normals} (double) or {points, 0, 0} - the mean loss over every clean validation
+    mesh (tuples of _clean_vertex_meshes) at every noise level, with stream = 1 + mesh index and step = level index: the
+    SAME noisy meshes at every call, and for the same seed the ones makeNoisy writes.  R: the rotation; rs: the
+    RandomState the 500 + 500 rows are drawn from."""
+    vsum = np.zeros(3)
+    for vbm, m in enumerate(valid):
+        net.bind_clean_vertices(("valid", vbm), *m[:6], gt_normals=m[6] if double else None, seed=seed, stream=1 + vbm,
+                                direction=direction)
+        nv = np.asarray(m[2]).reshape(-1, 3).shape[0]
+        for k, level in enumerate(noise_levels):
+            net.set_point_samples(rs.randint(nv, size=POINT_SAMPLES), rs.randint(nv, size=POINT_SAMPLES))
+            net.set_rotation(R)
+            net.set_noise(k, level)
+            if double:
+                vsum += net.double_loss(rotate=True).cpu().numpy()
+            else:
+                vsum[0] += net.pointset_loss(rotate=True)[0].item()
+    return vsum / (len(valid) * len(noise_levels))
+
+
+def _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet, double,
+                         noise_levels=None, noise_direction="random"):
     """The loop of trainAccuracyNet (double=False) and trainDoubleLossNet (double=True)."""
-    meshes = _vertex_meshes(trainSet, double, True)
-    if not meshes:
-        raise ValueError("no training mesh has ground-truth vertices (addMeshWithVerticesAndGT)")
-    valid = _vertex_meshes(validSet, double, True) if validSet is not None else []
+    synth = noise_levels is not None
+    if synth:
+        noise_levels = tuple(float(l) for l in noise_levels)
+        if not noise_levels or not all(np.isfinite(l) and l >= 0 for l in noise_levels):
+            raise ValueError("noise_levels: a non-empty list of levels >= 0")
+        if noise_direction not in ("random", "normal"):
+            raise ValueError("noise_direction must be 'random' or 'normal'")
+        meshes = _clean_vertex_meshes(trainSet, "training set")
+        valid = _clean_vertex_meshes(validSet, "validation set") if validSet is not None else []
+    else:
+        meshes = _vertex_meshes(trainSet, double, True)
+        if not meshes:
+            raise ValueError("no training mesh has ground-truth vertices (addMeshWithVerticesAndGT)")
+        valid = _vertex_meshes(validSet, double, True) if validSet is not None else []
     net = FacetDenoiser(device, multi_scale=True, seed=seed)
     ckpt = os.path.join(network_path, net_name) if network_path else None
     start = _resume(net, network_path, net_name) if ckpt else 0
@@ -331,7 +384,10 @@ def _train_with_vertices(trainSet, num_iterations, network_path, net_name, devic
 
     def bind(key, m):
         # (a cached mesh returns at once; bind_vertices reshapes the [1, ...] arrays)
-        if double:
+        if synth:
+            net.bind_clean_vertices(key, *m[:6], gt_normals=m[6] if double else None, seed=seed, stream=0,
+                                    direction=noise_direction)
+        elif double:
             net.bind_vertices(key, *m[:6], gt_normals=m[6])
         else:
             net.bind_vertices(key, *m)
@@ -344,24 +400,31 @@ def _train_with_vertices(trainSet, num_iterations, network_path, net_name, devic
     for it in range(num_iterations):
         b = rs.randint(len(meshes))
         num_v = np.asarray(meshes[b][2]).reshape(-1, 3).shape[0]
-        num_vgt = np.asarray(meshes[b][5]).reshape(-1, 3).shape[0]
+        num_vgt = num_v if synth else np.asarray(meshes[b][5]).reshape(-1, 3).shape[0]
         i0 = rs.randint(num_v, size=POINT_SAMPLES)
         i1 = rs.randint(num_vgt, size=POINT_SAMPLES)
         R_it = rand_rotation_matrix(randnums=rs.uniform(size=3))
+        # (drawn in this mode only, after the rotation: the random stream of a plain run is what it was)
+        noise_it = (start + it, noise_levels[rs.randint(len(noise_levels))]) if synth else None
         row = (it % block) // evalStepNum
-        if valid and it % validStepNum == 0 and it > 0:
-            vsum = np.zeros(3)
-            for vbm, m in enumerate(valid):
-                bind(("valid", vbm), m)
-                nvv = np.asarray(m[2]).reshape(-1, 3).shape[0]
-                nvg = np.asarray(m[5]).reshape(-1, 3).shape[0]
-                net.set_point_samples(rs.randint(nvv, size=POINT_SAMPLES), rs.randint(nvg, size=POINT_SAMPLES))
-                net.set_rotation(R_it)
-                if double:
-                    vsum += net.double_loss(rotate=True).cpu().numpy()
-                else:
-                    vsum[0] += net.pointset_loss(rotate=True)[0].item()
-            vsum /= len(valid)
+        # (synthesis mode scores its fixed noisy validation meshes at iteration 0 too, as trainNet does: the curve starts
+        #  at the restored weights, before this run's first step)
+        if valid and it % validStepNum == 0 and (it > 0 or synth):
+            if synth:
+                vsum = synthVertexValidationLoss(net, valid, noise_levels, R_it, rs, seed, noise_direction, double)
+            else:
+                vsum = np.zeros(3)
+                for vbm, m in enumerate(valid):
+                    bind(("valid", vbm), m)
+                    nvv = np.asarray(m[2]).reshape(-1, 3).shape[0]
+                    nvg = np.asarray(m[5]).reshape(-1, 3).shape[0]
+                    net.set_point_samples(rs.randint(nvv, size=POINT_SAMPLES), rs.randint(nvg, size=POINT_SAMPLES))
+                    net.set_rotation(R_it)
+                    if double:
+                        vsum += net.double_loss(rotate=True).cpu().numpy()
+                    else:
+                        vsum[0] += net.pointset_loss(rotate=True)[0].item()
+                vsum /= len(valid)
             valid_loss = vsum[0]
             if double:
                 log("Iteration %d, validation loss = %g (points %g, normals %g)" % (it, vsum[0], vsum[1], vsum[2]))
@@ -373,11 +436,11 @@ def _train_with_vertices(trainSet, num_iterations, network_path, net_name, devic
             last_loss = valid_loss
         bind(b, meshes[b])
         if double:
-            out = net.double_loss_step(i0, i1, R_it, capture=capture)
+            out = net.double_loss_step(i0, i1, R_it, capture=capture, noise=noise_it)
             hist[it].copy_(out)
             loss = out[0:1]
         else:
-            loss = net.pointset_step(i0, i1, R_it, capture=capture)
+            loss = net.pointset_step(i0, i1, R_it, capture=capture, noise=noise_it)
             hist[it:it + 1].copy_(loss)
         acc += loss
         acc_n += 1
@@ -584,7 +647,8 @@ def inferNetOld(inputMesh, net_or_checkpoint, device="cuda", update_vertices=Fal
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Train the network on the pickles of `preprocess` (the reference's train()).")
-    ap.add_argument("dump_dir", help="folder of trainingSet.pkl / validSet.pkl (or the ...WithVertices.pkl pair)")
+    ap.add_argument("dump_dir", help="folder of trainingSet.pkl / validSet.pkl (or the ...WithVertices.pkl / ...Clean.pkl / "
+                    "...CleanWithVertices.pkl pair)")
     ap.add_argument("network_dir", help="checkpoint folder (created; a checkpoint of --net-name there is resumed)")
     ap.add_argument("--num-iterations", type=int, default=NUM_ITERATIONS)
     ap.add_argument("--net-name", default="net")
@@ -595,7 +659,8 @@ def main(argv=None):
     ap.add_argument("--capture", action="store_true", help="replay every training step from a hipGraph")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--synth-noise", nargs="?", const=",".join(str(l) for l in DEFAULT_NOISE_LEVELS), default=None,
-                    metavar="LEVELS", help="build extension: train on the clean pickles of `preprocess --clean`, Gaussian "
+                    metavar="LEVELS", help="build extension: train on the clean pickles of `preprocess --clean` (with "
+                    "--with-vertices: of `preprocess --clean --with-vertices`), Gaussian "
                     "vertex noise made on the GPU every step; LEVELS = comma-separated multiples of the mean edge length "
                     "(default %(const)s; the value is optional, so write the option BEHIND the two folders or as --synth-noise=LEVELS)")
     ap.add_argument("--noise-direction", choices=("random", "normal"), default="random",
@@ -607,21 +672,20 @@ def main(argv=None):
         ap.error("--num-iterations must be >= 0")
     levels = None
     if args.synth_noise is not None:
-        if args.with_vertices:
-            ap.error("--synth-noise does not go with --with-vertices: point-set training on synthesised noise is not built")
         try:
             levels = tuple(float(t) for t in args.synth_noise.split(","))
         except ValueError:
             ap.error("--synth-noise takes comma-separated numbers, e.g. 0.1,0.2,0.3 (got %r)" % args.synth_noise)
         if not all(np.isfinite(l) and l >= 0 for l in levels):
             ap.error("--synth-noise levels must be >= 0 (got %r)" % args.synth_noise)
-    names = (("trainingSetWithVertices.pkl", "validSetWithVertices.pkl") if args.with_vertices
+    names = (("trainingSetCleanWithVertices.pkl", "validSetCleanWithVertices.pkl") if args.with_vertices and levels is not None
+             else ("trainingSetWithVertices.pkl", "validSetWithVertices.pkl") if args.with_vertices
              else ("trainingSetClean.pkl", "validSetClean.pkl") if levels is not None
              else ("trainingSet.pkl", "validSet.pkl"))
     ts_path, vs_path = (os.path.join(args.dump_dir, n) for n in names)
     if not os.path.isfile(ts_path) and levels is not None:
-        ap.error("no clean training set at %s: run `python -m facet_graph_convolution_amd.preprocess CLEAN_DIR %s --clean` "
-                 "first" % (ts_path, args.dump_dir))
+        ap.error("no clean training set at %s: run `python -m facet_graph_convolution_amd.preprocess CLEAN_DIR %s --clean%s` "
+                 "first" % (ts_path, args.dump_dir, " --with-vertices" if args.with_vertices else ""))
     if not os.path.isfile(ts_path):
         ap.error("no training set at %s: run `python -m facet_graph_convolution_amd.preprocess TRAINING_DIR GT_DIR %s%s` "
                  "first" % (ts_path, args.dump_dir, " --with-vertices" if args.with_vertices else ""))

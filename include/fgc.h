@@ -56,8 +56,10 @@ extern "C" {
  * a clean mesh.
  * 110: options K1_QS14 and W8_HALF2 removed with the two kernel forms they selected (both measured slower; the later option
  * indices do not move: the two were last in the table).
- * 111: fgc_conv_forms (which kernel form every launch of a layer takes, as text). */
-#define FGC_ABI_VERSION 111
+ * 111: fgc_conv_forms (which kernel form every launch of a layer takes, as text).
+ * 112: fgc_point_sets_prepare (the two point sets of the point-set loss normalised together and rotated, on the device:
+ * the vertex networks trained from clean meshes). */
+#define FGC_ABI_VERSION 112
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -822,6 +824,29 @@ int fgc_face_features_rows(const float* v, int32_t nv, const int32_t* faces_rows
 /* The raw generator of fgc_synth_noise, for known-answer tests: out [n,4] uint32 (device, 16-byte aligned),
  * out[i] = Philox4x32-10 of counter (first + i mod 2^32, step & 0xffffffff, step >> 32, stream_id) and key seed.  One launch. */
 int fgc_philox_words(uint32_t first, int32_t n, uint64_t step, uint64_t seed, uint32_t stream_id, uint32_t* out, void* stream);
+
+/* The two point sets of the point-set loss (fgc_point_loss) from displaced vertices: what the host does with
+ * normalizePointSets (utils.py:2077-2104) and two fgc_rotate_rows, in ONE launch per step.
+ *   v [nv,3]: the displaced vertices (fgc_synth_noise's v_out); gt [ngt,3]: the ground-truth vertices in the same raw
+ *   units; gt_box (device, 6 floats): {min xyz, max xyz} of gt, made once per mesh; R: device pointer to 9 floats
+ *   (row-major, applied as fgc_rotate_rows does) or NULL (identity).
+ *   scratch (device floats) >= fgc_synth_scratch_floats(nv): with have_bbox = 1 it holds the per-workgroup bounding
+ *   boxes fgc_synth_noise left for v (same nv, same scratch, right behind it on the stream - fgc_face_features_rows in
+ *   between leaves them alone); have_bbox = 0 computes them from v first, one more launch.
+ * Arithmetic: the bounding box of the UNION = the boxes of v reduced together with gt_box (min / max are exact: any
+ *   order); the diagonal in double from the fp32 extents, rounded to fp32; every coordinate is DIVIDED by it in IEEE fp32
+ *   (not multiplied by a reciprocal: numpy divides, and the two differ in the last bit); then out = R q with
+ *   out_i = fma(R_i2, q_2, fma(R_i1, q_1, R_i0 q_0)), the association of fgc_rotate_rows.  So v_out / gt_out are
+ *   bit-identical to normalizePointSets(v, gt) followed by fgc_rotate_rows (R given) or to normalizePointSets alone
+ *   (R == NULL).  A union box of zero extent divides by zero, as the host routine does.
+ * There is NO control word: the launch always runs, on what v and scratch hold (a step whose noise words are zero
+ *   normalises what the last ON step left).  v_out [nv,3], gt_out [ngt,3]: buffers of their own (not v, not gt).
+ * One thread per 3-vector of the two sets; every workgroup reads the boxes (at most 1024 x 24 bytes + gt_box), R and its
+ *   256 vectors.  Enqueue-only, nothing allocated, no atomics: one launch (have_bbox) or two.  A NULL among v, gt, gt_box,
+ *   v_out, gt_out, scratch, nv <= 0, ngt <= 0 or a scratch below fgc_synth_scratch_floats(nv): FGC_EINVAL, nothing launched. */
+int fgc_point_sets_prepare(const float* v, int32_t nv, const float* gt, int32_t ngt, const float* gt_box, const float* R,
+                           int32_t have_bbox, float* v_out, float* gt_out, float* scratch, size_t scratch_floats,
+                           void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Checkpoint files (CPU; HOST pointers)

@@ -8,7 +8,14 @@ every launch) beside the bytes they move and bytes / 8 TB/s, and what a back-to-
 pair (event time over `steps` calls: the enqueue rate of the Python wrappers where that is the larger); and, for the
 largest size, the captured training step with the synthesis (a clean mesh, new noise every step) against the captured
 plain step (the same mesh bound with bind_mesh), alternating `rounds` times in this one process, with the launches
-per step of both and the synthesis kernels' own device time from the library's hipEvent hooks."""
+per step of both and the synthesis kernels' own device time from the library's hipEvent hooks.
+
+    python tools/synth_probe.py --points [--faces 20480 100000] [--steps 50] [--rounds 5] [--out FILE]
+
+The same for the vertex networks (FacetDenoiser.bind_clean_vertices): per mesh size the DEVICE time of
+fgc_point_sets_prepare (both point sets normalised by their union box and rotated, one launch) beside its bytes / 8 TB/s;
+and, for the largest size, the captured point-set step with the synthesis against the captured plain step (the same
+graph levels and host-made inputs of one noisy draw, bound with bind_vertices), alternating `rounds` times in this one process, with the launches per step of both."""
 import argparse
 import json
 import os
@@ -35,13 +42,120 @@ def timed(fn, steps, warmup=5):
     return a.elapsed_time(b) / steps
 
 
+def _clean_mesh(nf):
+    from facet_graph_convolution_amd.meshgen import torus, icosphere
+    if nf == 20480:
+        return icosphere(5)
+    n = int(round((nf / 2) ** 0.5))
+    return torus(n, n)
+
+
+def points(args):
+    """--points: fgc_point_sets_prepare alone, and the captured point-set step with and without the synthesis."""
+    import ctypes as C
+    from facet_graph_convolution_amd import ops, _lib
+    L = _lib.lib()
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    from facet_graph_convolution_amd.dataClasses import TrainingSet
+    from facet_graph_convolution_amd.utils import rand_rotation_matrix
+    res = []
+    dev = "cuda:0"
+    for nf in args.faces:
+        V, F = _clean_mesh(nf)
+        nv = V.shape[0]
+        Vd = torch.as_tensor(V, device=dev)
+        gt_box = torch.cat([Vd.min(0).values, Vd.max(0).values])
+        R = torch.as_tensor(rand_rotation_matrix(randnums=np.random.RandomState(0).uniform(size=3)).astype(np.float32),
+                            device=dev).reshape(9)
+        scratch = torch.empty(6 * 1024, dtype=torch.float32, device=dev)
+        out_v = ops.synth_noise(Vd, 0.01, 3, seed=1, scratch=scratch)
+        outs = (torch.empty_like(Vd), torch.empty_like(Vd))
+        prepare = lambda: ops.point_sets_prepare(out_v, Vd, R=R, gt_box=gt_box, scratch=scratch, have_bbox=True,  # noqa: E731
+                                                 out=outs)
+        # bytes: both sets are read once and written once (the boxes, at most 24 KB per workgroup, come from the L2)
+        nbytes = 24 * (nv + nv)
+        prepare()
+        torch.cuda.synchronize()
+        L.fgc_profile_enable(1)
+        for _ in range(args.steps):
+            prepare()
+        torch.cuda.synchronize()
+        buf = C.create_string_buffer(1 << 16)
+        L.fgc_profile_collect(buf, len(buf))
+        L.fgc_profile_enable(0)
+        dev_us = {}
+        for line in buf.value.decode().splitlines():
+            name, cnt, ms = line.rsplit(" ", 2)
+            dev_us[name.split("/")[-1]] = float(ms) / int(cnt) * 1e3
+        row = dict(faces=int(F.shape[0]), vertices=int(nv), prepare_bytes=nbytes,
+                   prepare_floor_us=nbytes / HBM_BYTES_PER_S * 1e6, kernel_device_us=dev_us,
+                   enqueued_back_to_back_us=timed(prepare, args.steps) * 1e3)
+        if nf == max(args.faces):
+            # the plain step runs on the SAME graph levels and on host-made inputs of the noisy vertices counter 1 draws:
+            # the convolutions' work depends on the levels and fgc_point_loss's search on the points
+            from facet_graph_convolution_amd.makeNoisy import make_noisy
+            from facet_graph_convolution_amd.utils import face_features, normalizePointSets
+            clean = TrainingSet()
+            clean.addCleanMeshWithVertices(V, F, seed=0)
+            Vn = make_noisy(V, F, 0.2, seed=0, step=1)
+            n0 = clean.in_list[0].shape[1]
+            per_face = np.concatenate([a.astype(np.float32) for a in face_features(Vn, F)], axis=1)
+            new_to_old = np.empty(n0, dtype=np.int64)
+            new_to_old[np.asarray(clean.permutations[0])] = np.arange(n0)
+            rows = np.concatenate([per_face, np.zeros((n0 - len(per_face), 6), np.float32)])[new_to_old]
+            vn, gn = normalizePointSets(Vn, V)
+            rs = np.random.RandomState(0)
+            i0, i1, Rm = rs.randint(nv, size=500), rs.randint(nv, size=500), rand_rotation_matrix(randnums=rs.uniform(size=3))
+            nets = {"synth": FacetDenoiser(dev, multi_scale=True, seed=0), "plain": FacetDenoiser(dev, multi_scale=True, seed=0)}
+            nets["synth"].bind_clean_vertices(0, clean.in_list[0], clean.adj_list[0], clean.clean_vertices[0],
+                                              clean.clean_faces_rows[0], clean.v_faces_list[0], clean.clean_edge_len[0])
+            nets["plain"].bind_vertices(0, rows, clean.adj_list[0], vn, clean.clean_faces_rows[0], clean.v_faces_list[0], gn)
+            for net in nets.values():
+                net.set_point_samples(i0, i1)
+                net.set_rotation(Rm)
+            nets["synth"].set_noise(1, 0.2)      # (the draw the plain step's inputs were made from: the same data)
+            step = {k: (lambda net=net: net.pointset_forward_backward(rotate=True, capture=True)) for k, net in nets.items()}
+            times = {"synth": [], "plain": []}
+            for r in range(args.rounds):
+                for k in ("synth", "plain"):
+                    times[k].append(timed(step[k], args.steps))
+            row["captured_synth_ms"] = times["synth"]
+            row["captured_plain_ms"] = times["plain"]
+            row["captured_difference_us"] = (float(np.median(times["synth"])) - float(np.median(times["plain"]))) * 1e3
+            for k, net in nets.items():
+                net.pointset_forward_backward(rotate=True)
+                torch.cuda.synchronize()
+                net.profile_start()
+                for _ in range(10):
+                    net.pointset_forward_backward(rotate=True)
+                torch.cuda.synchronize()
+                prof = net.profile_stop()
+                row[k + "_launches_per_step"] = sum(c for c, _ in prof.values()) / 10.0
+                if k == "synth":
+                    row["synth_kernels_us"] = {name: ms / cnt * 1e3 for name, (cnt, ms) in prof.items()
+                                               if "synth" in name or "prepare" in name}
+            del nets
+        print(json.dumps(row), flush=True)
+        res.append(row)
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--faces", type=int, nargs="+", default=[20480, 100000])
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--points", action="store_true", help="the point sets of the vertex networks (fgc_point_sets_prepare)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
+    if args.points:
+        res = points(args)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        return
     import ctypes as C
     from facet_graph_convolution_amd import ops, _lib
     L = _lib.lib()
