@@ -24,7 +24,7 @@ import ctypes as C
 import gc
 import os
 import warnings
-import math
+import types
 
 import numpy as np
 import torch
@@ -327,9 +327,13 @@ class FacetDenoiser:
         B = {"x": xt.contiguous().to(dev)}
         B["xr"] = torch.empty_like(B["x"])
         self._alloc_step_inputs(B, COST_SAMPLES)
-        # (captured: the mesh's captured steps by form - "angular", "points", "double" -, each (graph or segments, rotate))
+        # (captured: the mesh's captured steps by form - "angular", "points", "double" -, each (graph or segments, rotate);
+        #  mode: what the mesh is bound for, written by the bind methods, read by the steps and the _require_* checks - clean:
+        #  a synthesis state M["synth"]; verts: a vertex state M["verts"]; gt_normals: the double loss's ground truth in it;
+        #  synth_points: the point sets come from fgc_point_sets_prepare)
+        mode = types.SimpleNamespace(clean=False, verts=False, gt_normals=False, synth_points=False)
         return dict(graphs=graphs, B=B, ns=ns, nh=nh, nhp=nhp, has_gt=training, plan=plan, n_total=n_total,
-                    own_lo=own_lo, captured={})
+                    own_lo=own_lo, captured={}, mode=mode)
 
     def _bind_activations(self, M):
         """Every activation and its gradient twin, the aggregate tables, and the heads' output and loss buffers."""
@@ -619,21 +623,34 @@ class FacetDenoiser:
         multiple of it), the Philox key `seed` and `stream` id (training 0, validation mesh i 1 + i) and the
         direction - "random", or "normal": along the clean mesh's area-weighted vertex normals.  x: the clean mesh's own
         rows (what the steps read until set_noise switches the synthesis on); gt: the clean normals.  Unsharded only."""
+        self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction), False,
+                         lambda: self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt)))
+        return self
+
+    def _bind_synth(self, key, synth_args, points, bind):
+        """What bind_clean and bind_clean_vertices (points=True) share: the refusals, the mesh cached under `key` (a training
+        loop rebinds its meshes every iteration: a lookup, as in bind_cached), otherwise the synthesis state of synth_args =
+        (x, verts, faces_rows, edge_len, seed, stream, direction) on the mesh bind() returns.  Returns (mesh, newly bound)."""
         if self.comm is not None or (self._mesh is not None and self.sharded):
             raise NotImplementedError("noise synthesis runs on an unsharded network")
+        if points:
+            self._require_vertex_network()
         M = self._mesh_cache.get(key)
-        if M is not None and "synth" in M:
-            # (a training loop rebinds its meshes every iteration: a cached mesh costs this lookup, as in bind_cached)
-            if (M["synth"]["seed"], M["synth"]["stream"], M["synth"]["direction"]) != (int(seed), int(stream), direction):
+        if M is not None and (M["mode"].clean or (points and M["mode"].verts)):
+            if points and not M["mode"].synth_points:
+                raise ValueError("mesh %r is bound under this key without synthesised point sets" % (key,))
+            S = M["synth"]
+            if (S["seed"], S["stream"], S["direction"]) != (int(synth_args[4]), int(synth_args[5]), synth_args[6]):
                 raise ValueError("mesh %r is bound with another seed / stream / direction" % (key,))
             self._mesh = M
-            return self
-        S = self._synth_state(x, verts, faces_rows, edge_len, seed, stream, direction)
-        M = self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt))
+            return M, False
+        S = self._synth_state(*synth_args)
+        M = bind()
         M["synth"] = S
-        # (a step captured while the mesh was bound by bind_cached under this key has no synthesis nodes: record it again)
+        M["mode"].clean = True
+        # (a step captured while the mesh was bound without the synthesis under this key has no synthesis nodes: record it again)
         M["captured"].clear()
-        return self
+        return M, True
 
     def _synth_state(self, x, verts, faces_rows, edge_len, seed, stream, direction):
         """The checked arguments of bind_clean / bind_clean_vertices as the synthesis state kept with the mesh."""
@@ -660,7 +677,7 @@ class FacetDenoiser:
         return S
 
     def _require_synth(self):
-        if "synth" not in (self._mesh or {}):
+        if self._mesh is None or not self._mesh["mode"].clean:
             raise RuntimeError("bind_clean(...) or bind_clean_vertices(...) is required for noise synthesis")
         return self._mesh["synth"]
 
@@ -693,30 +710,23 @@ class FacetDenoiser:
         fgc_rotate_rows launches of a mesh bound by bind_vertices.  The last launch has no control word: while the noise
         words are zero (right after binding, or set_noise(step, None)) a step runs on the vertices the last
         synthesising step left; right after binding these are the clean ones."""
-        if self.comm is not None or (self._mesh is not None and self.sharded):
-            raise NotImplementedError("noise synthesis runs on an unsharded network")
-        if not self.multi_scale or self.dtype != "f32":
-            raise NotImplementedError("point-set training: unsharded fp32 multi-scale network only")
-        M = self._mesh_cache.get(key)
-        if M is not None and ("synth" in M or "verts" in M):
-            if "gt_box" not in M.get("synth", {}) or "verts" not in M:
-                raise ValueError("mesh %r is bound under this key without synthesised point sets" % (key,))
-            if (M["synth"]["seed"], M["synth"]["stream"], M["synth"]["direction"]) != (int(seed), int(stream), direction):
-                raise ValueError("mesh %r is bound with another seed / stream / direction" % (key,))
-            return self.bind_vertices(key, x, adjs, None, None, None, None, gt_normals=gt_normals)
-        S = self._synth_state(x, verts, faces_rows, edge_len, seed, stream, direction)
-        # (the plain vertex state holds the clean mesh normalised by its own box; the steps read xr / gtr instead)
-        from .utils import normalizePointSets
-        vx = S["v"].cpu().numpy()
-        vn = normalizePointSets(vx, vx)[0]
-        self.bind_vertices(key, x, adjs, vn, faces_rows, v_faces, vn, iters=iters, gt_normals=gt_normals)
-        M, nv, sc = self._mesh, S["v"].shape[0], S["scratch"]
-        S["gt_box"] = torch.cat([S["v"].min(0).values, S["v"].max(0).values])
-        # the boxes of the clean vertices (and the clean input rows once more): what a step without noise words runs on
-        _lib.check(self.L.fgc_face_features_rows(_p(S["v_out"]), nv, _p(S["faces"]), M["ns"][0], None, 0, _p(M["B"]["x"]),
-                                                 _p(sc), sc.numel(), self._st()), "clean features")
-        M["synth"] = S
-        M["captured"].clear()
+        def bind():
+            # (the plain vertex state holds the clean mesh normalised by its own box; the steps read xr / gtr instead)
+            from .utils import normalizePointSets
+            vx = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
+            vn = normalizePointSets(vx, vx)[0]
+            self.bind_vertices(key, x, adjs, vn, faces_rows, v_faces, vn, iters=iters)
+            return self._mesh
+        M, fresh = self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction), True, bind)
+        if fresh:
+            S = M["synth"]
+            nv, sc = S["v"].shape[0], S["scratch"]
+            S["gt_box"] = torch.cat([S["v"].min(0).values, S["v"].max(0).values])
+            # the boxes of the clean vertices (and the clean input rows once more): what a step without noise words runs on
+            _lib.check(self.L.fgc_face_features_rows(_p(S["v_out"]), nv, _p(S["faces"]), M["ns"][0], None, 0,
+                                                     _p(M["B"]["x"]), _p(sc), sc.numel(), self._st()), "clean features")
+            M["mode"].synth_points = True
+        self._attach_gt_normals(M, gt_normals)
         return self
 
     # ------------------------------------------------------------------------------------------
@@ -804,7 +814,7 @@ class FacetDenoiser:
         prologue = self.batched and self.step_prologue
         mlp_packed = _lib.MLP_PACKED if (prologue and not self.multi_scale) else 0
         M["mlp_packed"] = mlp_packed
-        if "synth" in M:
+        if M["mode"].clean:
             # a clean mesh (bind_clean): this step's noisy vertices and input rows, in front of everything that reads x;
             # inside a captured step these launches are nodes of its graph
             self._enqueue_synth()
@@ -1451,18 +1461,25 @@ class FacetDenoiser:
         """The multi-scale forward as a schedule: the network, then normalizeTensor on the two coarse heads (on a
         facet-sharded run one scalar all-reduce each: utils.py:1705 takes the mean over the whole tensor)."""
         yield from self._forward_gen(rotate)
-        M, L, st = self._mesh, self.L, self._st()
-        B = M["B"]
+        if not self.sharded:
+            self._normalize_coarse_heads()
+            return
+        M, B = self._mesh, self._mesh["B"]
         for k, level in (("1", 1), ("2", 2)):
-            nk = M["ns"][level]
-            y, out, part, sc = B["y" + k], B["nconv" + k], B["abs_part" + k], B["norm_scratch" + k]
-            if not self.sharded:
-                _lib.check(L.fgc_normalize_fwd(_p(y), nk, _p(part), part.numel(), _p(out), _p(sc), st), "normalize")
-            else:
-                tot = part.sum().reshape(1)
-                yield ("sum", tot)
-                sc[0:1] = tot / (3.0 * M["n_total"][level]) + 1e-5
-                _lib.check(L.fgc_normalize_apply(_p(y), nk, _p(sc), _p(out), st), "normalize")
+            y, part, sc = B["y" + k], B["abs_part" + k], B["norm_scratch" + k]
+            tot = part.sum().reshape(1)
+            yield ("sum", tot)
+            sc[0:1] = tot / (3.0 * M["n_total"][level]) + 1e-5
+            _lib.check(self.L.fgc_normalize_apply(_p(y), M["ns"][level], _p(sc), _p(B["nconv" + k]), self._st()),
+                       "normalize")
+
+    def _normalize_coarse_heads(self):
+        """normalizeTensor on the coarse heads 1 and 2 of an unsharded mesh: y1 / y2 -> nconv1 / nconv2, one launch each."""
+        B, ns = self._mesh["B"], self._mesh["ns"]
+        for k in ("1", "2"):
+            y, part, sc = B["y" + k], B["abs_part" + k], B["norm_scratch" + k]
+            _lib.check(self.L.fgc_normalize_fwd(_p(y), ns[int(k)], _p(part), part.numel(), _p(B["nconv" + k]), _p(sc),
+                                                self._st()), "normalize head" + k)
 
     def forward_multi_scale(self, rotate=False):
         """The multi-scale denoising forward of inferNet (train.py:188-193): the three heads, each through
@@ -1549,34 +1566,31 @@ class FacetDenoiser:
 
     def forward_backward(self, rotate=True, capture=False):
         """One forward + backward (train.py:492-520 without the optimiser); loss in buffers['loss'][0]."""
-        if not self._mesh["has_gt"]:
-            raise RuntimeError("bind_mesh(..., gt=...) is required for training")
-        if not (capture and self.sharded):
-            self._run_step("angular", rotate, capture, lambda: self._angular_step(rotate))
-        else:
-            # one hipGraph per stretch of launches between two exchanges (17 collectives -> ~25 graphs per step instead of
-            # ~110 launches); the recording call runs one step eagerly (lazy one-time set-up inside the library must not
-            # happen under capture), every later one replays
-            require_graph_replay_safe()
-            g = self._graph_fb
-            if g is None or g[1] != rotate:
-                self._own_step_inputs()
-                self._angular_step(rotate)
-                torch.cuda.synchronize()
-                self._graph_fb = ((self._capture_segments(lambda: self._forward_gen(rotate, self._fused_loss_now())),
-                                   self._capture_segments(lambda: self._loss_backward_gen(rotate))), rotate)
-            else:
-                for segs in g[0]:
-                    self._replay_segments(segs)
-        return self._mesh["B"]["loss"]
+        return self._forward_backward("angular", rotate, capture)
 
-    def eval_loss(self, rotate=True):
-        """Forward + sampled angular loss, no gradients: the validation pass of trainNet (train.py:588-617 runs
-        customLoss alone on the validation feed).  Uses the bound rotation and samples; loss in buffers['loss'][0]."""
+    def _angular_step_segments(self, rotate):
+        """A facet-sharded captured step: one hipGraph per stretch of launches between two exchanges (17 collectives -> ~25
+        graphs per step instead of ~110 launches); the recording call runs one step eagerly (lazy one-time set-up inside
+        the library must not happen under capture), every later one replays."""
+        require_graph_replay_safe()
+        g = self._graph_fb
+        if g is None or g[1] != rotate:
+            self._own_step_inputs()
+            self._angular_step(rotate)
+            torch.cuda.synchronize()
+            self._graph_fb = ((self._capture_segments(lambda: self._forward_gen(rotate, self._fused_loss_now())),
+                               self._capture_segments(lambda: self._loss_backward_gen(rotate))), rotate)
+        else:
+            for segs in g[0]:
+                self._replay_segments(segs)
+
+    def _require_gt(self, loss_only):
         if not self._mesh["has_gt"]:
-            raise RuntimeError("bind_mesh(..., gt=...) is required for a loss")
-        if self.sharded:
+            raise RuntimeError("bind_mesh(..., gt=...) is required for " + ("a loss" if loss_only else "training"))
+        if loss_only and self.sharded:
             raise NotImplementedError("validation runs on an unsharded network")
+
+    def _angular_loss(self, rotate):
         self._drain(self._forward_gen(rotate))
         B, L, st = self._mesh["B"], self.L, self._st()
         gt = B["gt"]
@@ -1585,7 +1599,11 @@ class FacetDenoiser:
             gt = B["gtr"]
         samp = B["sample_ind"]
         _lib.check(L.fgc_angular_loss_fwd(_p(B["nconv"]), _p(gt), _p(samp), samp.numel(), _p(B["loss"]), st), "loss")
-        return B["loss"]
+
+    def eval_loss(self, rotate=True):
+        """Forward + sampled angular loss, no gradients: the validation pass of trainNet (train.py:588-617 runs
+        customLoss alone on the validation feed).  Uses the bound rotation and samples; loss in buffers['loss'][0]."""
+        return self._loss_only("angular", rotate)
 
     # ------------------------------------------------------------------------------------------
     # point-set training (trainAccuracyNet, train.py:636-916): network -> update_position_MS -> fullLoss
@@ -1596,15 +1614,14 @@ class FacetDenoiser:
         ground-truth vertices [Vgt,3] and the two inverse tables of the vertex-update adjoint (ops.vertex_ms_tables) -
         all cached with the graph, like bind_cached.  gt_normals: the ground-truth face normals [N0,3] in node order
         (gt_list), for the double-loss step; uploaded into the cached vertex state (the first time they are given)."""
-        if not self.multi_scale or self.dtype != "f32":      # (bind_cached binds unsharded)
-            raise NotImplementedError("point-set training: unsharded fp32 multi-scale network only")
+        self._require_vertex_network()
 
         def bind():
             # the backward buffers of the heads come with a ground truth; the point-set step never reads its values
             xa = np.asarray(x)
             self.bind_mesh(x, adjs, gt=np.zeros((1, xa.size // xa.shape[-1], 3), dtype=np.float32))
         M = self._cached(key, bind)      # (a training loop rebinds its meshes every iteration)
-        if "verts" not in M:
+        if not M["mode"].verts:
             dev, n0 = self.device, M["ns"][0]
             vx = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
             fc = np.asarray(faces).reshape(-1, 3).astype(np.int32)
@@ -1632,8 +1649,17 @@ class FacetDenoiser:
                                        + 256, dtype=torch.uint8, device=dev)
             V["threshold"] = POINT_LOSS_THRESHOLD
             M["verts"] = V
-        if gt_normals is not None and "gtn" not in M["verts"]:
-            # the ground-truth face normals and the buffers of the double-loss step
+            M["mode"].verts = True
+        self._attach_gt_normals(M, gt_normals)
+        return self
+
+    def _require_vertex_network(self):
+        if not self.multi_scale or self.dtype != "f32":      # (bind_cached binds unsharded)
+            raise NotImplementedError("point-set training: unsharded fp32 multi-scale network only")
+
+    def _attach_gt_normals(self, M, gt_normals):
+        """The ground-truth face normals and the double-loss step's buffers into the vertex state, the first time given."""
+        if gt_normals is not None and not M["mode"].gt_normals:
             g = np.asarray(gt_normals.cpu() if isinstance(gt_normals, torch.Tensor) else gt_normals, dtype=np.float32)
             g = g.reshape(-1, 3)
             if g.shape[0] != M["ns"][0]:
@@ -1643,7 +1669,7 @@ class FacetDenoiser:
             V["dl_out"] = torch.zeros(4, dtype=torch.float32, device=self.device)      # {total, points, normals, real rows}
             V["dl_scratch"] = torch.zeros(self.L.fgc_dense_normals_loss_scratch_floats(M["ns"][0]), dtype=torch.float32,
                                           device=self.device)
-        return self
+            M["mode"].gt_normals = True
 
     def set_point_samples(self, sample_ind0, sample_ind1):
         """The 500 + 500 sampled rows of fullLoss (train.py:810-811): rows of the vertices and of the ground truth."""
@@ -1654,6 +1680,12 @@ class FacetDenoiser:
                 raise ValueError("the point-set step samples %d rows per side" % dst.numel())
             self._upload(dst, a)
 
+    def _vertex_heads(self, double):
+        """(the three normal fields the vertex update reads, where its adjoint writes their gradients): head 0 normalised and
+        the RAW coarse heads (train.py:767-773), or - double - all three normalised (train.py:1079-1081)."""
+        B, names = self._mesh["B"], ("nconv", "nconv1", "nconv2") if double else ("nconv", "y1", "y2")
+        return tuple(B[k] for k in names), tuple(B["g_" + k] for k in names)
+
     def _pointset_forward(self, rotate, want_grad, double=False):
         """Network (normalizeTensor on head 0 only, train.py:767-773), the rotated vertices moved by update_position_MS
         with its trajectory, fullLoss (and its gradient on the moved vertices).  double: trainDoubleLossNet's form
@@ -1663,16 +1695,12 @@ class FacetDenoiser:
         B, V = M["B"], M["verts"]
         n0, nv = M["ns"][0], V["x"].shape[0]
         self._drain(self._forward_gen(rotate))
-        heads = (B["nconv"], B["y1"], B["y2"])
         if double:
             self._tag("dl:normalize")
-            for k in ("1", "2"):
-                y, part, sc = B["y" + k], B["abs_part" + k], B["norm_scratch" + k]
-                _lib.check(L.fgc_normalize_fwd(_p(y), M["ns"][int(k)], _p(part), part.numel(), _p(B["nconv" + k]),
-                                               _p(sc), st), "normalize head" + k)
-            heads = (B["nconv"], B["nconv1"], B["nconv2"])
+            self._normalize_coarse_heads()
+        heads = self._vertex_heads(double)[0]
         x, gt = V["x"], V["gt"]
-        if "gt_box" in M.get("synth", ()):
+        if M["mode"].synth_points:
             # a clean mesh (bind_clean_vertices): the displaced and the clean vertices over the diagonal of their union
             # box, rotated - one launch behind the two of _enqueue_synth, whose boxes it reads
             self._tag("pts:prepare")
@@ -1720,8 +1748,7 @@ class FacetDenoiser:
         wsv = V["bwd_ws"]
         # dL/d normals: head 0 into g_nconv (then through normalizeTensor), the raw coarse heads straight into g_y1 / g_y2
         # (double: the normalised coarse heads into g_nconv1 / g_nconv2, then through their own normalizeTensor)
-        heads = (B["nconv"], B["nconv1"], B["nconv2"]) if double else (B["nconv"], B["y1"], B["y2"])
-        g_heads = (B["g_nconv"], B["g_nconv1"], B["g_nconv2"]) if double else (B["g_nconv"], B["g_y1"], B["g_y2"])
+        heads, g_heads = self._vertex_heads(double)
         _lib.check(L.fgc_vertex_update_ms_bwd(_p(V["traj"]), V["traj"].numel(), nv, _p(V["faces"]), n0, _p(V["v_faces"]),
                                               V["v_faces"].shape[1], _p(heads[0]), _p(heads[1]), _p(heads[2]), it,
                                               _p(sp), _p(sv), _p(ip), _p(fi), _p(V["g_p"]), _p(V["g_x"]),
@@ -1743,61 +1770,95 @@ class FacetDenoiser:
             self._coarse_head_bwd(k)
         yield from self._params_backward_gen(False)
 
+    def _require_verts(self, double=False):
+        if self._mesh is None or not self._mesh["mode"].verts:
+            raise RuntimeError("bind_vertices(...) is required for the %s step" % ("double-loss" if double else "point-set"))
+        if double and not self._mesh["mode"].gt_normals:
+            raise RuntimeError("the double-loss step needs the ground-truth face normals: bind_vertices(..., gt_normals=...)")
+
     def pointset_forward_backward(self, rotate=True, capture=False):
         """One point-set step without the optimiser: loss in the returned device tensor [1], every parameter gradient
         in params.grads.  capture=True: the whole step as ONE hipGraph (recorded on the first call, replayed after)."""
-        self._require_verts()
-        self._run_step("points", rotate, capture, lambda: self._drain(self._pointset_gen(rotate)))
-        return self._mesh["verts"]["loss"]
+        return self._forward_backward("points", rotate, capture)
 
     def pointset_loss(self, rotate=True):
         """The point-set loss alone (the validation pass of trainAccuracyNet, keep_prob 1): device tensor [1]."""
-        self._pointset_forward(rotate, False)
-        return self._mesh["verts"]["loss"]
+        return self._loss_only("points", rotate)
 
     def pointset_step(self, sample_ind0, sample_ind1, R, capture=False, noise=None):
         """One iteration of trainAccuracyNet's loop body (train.py:800-840): samples, rotation, forward, backward, Adam.
         noise = (step, level) (build extension, a mesh bound by bind_clean_vertices): set_noise(step, level) first."""
-        self.set_point_samples(sample_ind0, sample_ind1)
-        self.set_rotation(R)
-        if noise is not None:
-            self.set_noise(*noise)
-        loss = self.pointset_forward_backward(rotate=True, capture=capture)
-        self.adam_step()
-        return loss
+        return self._step("points", (sample_ind0, sample_ind1), R, capture, noise)
 
-    # ------------------------------------------------------------------------------------------
     # double-loss training (trainDoubleLossNet, train.py:919-1268): the point-set loss + the dense face-normal loss
-    # ------------------------------------------------------------------------------------------
-    def _require_verts(self, double=False):
-        if "verts" not in (self._mesh or {}):
-            raise RuntimeError("bind_vertices(...) is required for the %s step" % ("double-loss" if double else "point-set"))
-        if double and "gtn" not in self._mesh["verts"]:
-            raise RuntimeError("the double-loss step needs the ground-truth face normals: bind_vertices(..., gt_normals=...)")
-
     def double_loss_forward_backward(self, rotate=True, capture=False):
         """One double-loss step without the optimiser (train.py:1079-1102): all three heads normalised, update_position_MS
         on them, fullLoss + faceNormalsLoss(head 0, the rotated ground-truth normals); the returned device tensor [3] =
         {total, points, normals}, every parameter gradient in params.grads.  capture=True: ONE hipGraph per mesh."""
-        self._require_verts(double=True)
-        self._run_step("double", rotate, capture, lambda: self._drain(self._pointset_gen(rotate, True)))
-        return self._mesh["verts"]["dl_out"][:3]
+        return self._forward_backward("double", rotate, capture)
 
     def double_loss(self, rotate=True):
         """The double loss alone (the validation pass of trainDoubleLossNet, keep_prob 1): device tensor [3] = {total,
         points, normals}."""
-        self._require_verts(double=True)
-        self._pointset_forward(rotate, False, True)
-        return self._mesh["verts"]["dl_out"][:3]
+        return self._loss_only("double", rotate)
 
     def double_loss_step(self, sample_ind0, sample_ind1, R, capture=False, noise=None):
         """One iteration of trainDoubleLossNet's loop body (train.py:1160-1243): samples, rotation, step, Adam.
         noise = (step, level) (build extension, bind_clean_vertices): set_noise(step, level) first."""
-        self.set_point_samples(sample_ind0, sample_ind1)
+        return self._step("double", (sample_ind0, sample_ind1), R, capture, noise)
+
+    # The step forms behind the *_step, *_forward_backward and loss-only entries: require(self, loss_only) raises unless the
+    # bound mesh can run the form, set_samples(self, *samples), enqueue(self, rotate) the forward + backward launches,
+    # enqueue_loss(self, rotate) the forward and the loss alone, result(mesh state) the loss tensor, trainer(self) trainer_form.
+    _StepForm = collections.namedtuple("_StepForm", "require set_samples enqueue enqueue_loss result trainer")
+    _TrainerForm = collections.namedtuple("_TrainerForm", "bind bind_clean set_samples step loss samples outputs gt_normals")
+    _STEP_FORMS = {
+        "angular": _StepForm(_require_gt, set_samples, _angular_step, _angular_loss, lambda M: M["B"]["loss"],
+                             lambda self: self._TrainerForm(self.bind_cached, self.bind_clean, self.set_samples,
+                                                            self.train_step, self.eval_loss, COST_SAMPLES, 1, False)),
+        "points": _StepForm(lambda self, _: self._require_verts(), set_point_samples,
+                            lambda self, rotate: self._drain(self._pointset_gen(rotate)),
+                            lambda self, rotate: self._pointset_forward(rotate, False), lambda M: M["verts"]["loss"],
+                            lambda self: self._TrainerForm(self.bind_vertices, self.bind_clean_vertices, self.set_point_samples,
+                                                           self.pointset_step, self.pointset_loss, POINT_SAMPLES, 1, False)),
+        "double": _StepForm(lambda self, _: self._require_verts(True), set_point_samples,
+                            lambda self, rotate: self._drain(self._pointset_gen(rotate, True)),
+                            lambda self, rotate: self._pointset_forward(rotate, False, True), lambda M: M["verts"]["dl_out"][:3],
+                            lambda self: self._TrainerForm(self.bind_vertices, self.bind_clean_vertices, self.set_point_samples,
+                                                           self.double_loss_step, self.double_loss, POINT_SAMPLES, 3, True)),
+    }
+
+    def trainer_form(self, form):
+        """What a training loop (train.py) calls for `form`, as bound methods: bind a plain / a clean mesh, set the samples, one
+        iteration, the loss alone; the rows per sample set, the loss's entries {total[, points, normals]}, binds take gt_normals."""
+        return self._STEP_FORMS[form].trainer(self)
+
+    def _loss_only(self, form, rotate):
+        """Forward and the loss of `form`, no gradients: the validation passes."""
+        F = self._STEP_FORMS[form]
+        F.require(self, True)
+        F.enqueue_loss(self, rotate)
+        return F.result(self._mesh)
+
+    def _forward_backward(self, form, rotate, capture):
+        """One step of `form` without the optimiser: _run_step, or the segments of a facet-sharded captured (angular) step."""
+        F = self._STEP_FORMS[form]
+        F.require(self, False)
+        if capture and self.sharded:
+            if form != "angular":
+                raise NotImplementedError("a facet-sharded captured step exists for the angular form only")
+            self._angular_step_segments(rotate)
+        else:
+            self._run_step(form, rotate, capture, lambda: F.enqueue(self, rotate))
+        return F.result(self._mesh)
+
+    def _step(self, form, samples, R, capture, noise):
+        """One training iteration of `form`: samples, rotation, the noise words when given, forward + backward, Adam."""
+        self._STEP_FORMS[form].set_samples(self, *samples)
         self.set_rotation(R)
         if noise is not None:
             self.set_noise(*noise)
-        out = self.double_loss_forward_backward(rotate=True, capture=capture)
+        out = self._forward_backward(form, True, capture)
         self.adam_step()
         return out
 
@@ -1811,19 +1872,12 @@ class FacetDenoiser:
     def train_step(self, sample_ind=None, R=None, capture=False, noise=None):
         """One iteration of trainNet's loop body (train.py:558-575,619): returns the loss tensor (device, [2]).
         noise = (step, level) (build extension, a mesh bound by bind_clean): set_noise(step, level) first."""
-        n0 = self._mesh["ns"][0]
         if sample_ind is None:
-            sample_ind = np.random.randint(n0, size=COST_SAMPLES)
+            sample_ind = np.random.randint(self._mesh["ns"][0], size=COST_SAMPLES)
         if R is None:
             from .utils import rand_rotation_matrix
             R = rand_rotation_matrix()
-        self.set_samples(sample_ind)
-        self.set_rotation(R)
-        if noise is not None:
-            self.set_noise(*noise)
-        loss = self.forward_backward(rotate=True, capture=capture)
-        self.adam_step()
-        return loss
+        return self._step("angular", (sample_ind,), R, capture, noise)
 
     def infer_normals(self, permutations, num_faces):
         """Denoised unit normals in the ORIGINAL face order, [F,3] (train.py:115-121,136)."""

@@ -20,6 +20,7 @@ loads the pickles `preprocess` wrote and runs trainNet, trainAccuracyNet (--with
 on the GPU.
 """
 import argparse
+import collections
 import os
 import pickle
 
@@ -111,129 +112,121 @@ def load_checkpoint(path, net):
 
 DEFAULT_NOISE_LEVELS = (0.1, 0.2, 0.3)      # --synth-noise without a value: a choice of this build (README)
 
+# One mesh of a trainer's input: `args` follow the key in the bind call, `gt_normals` go with them (a keyword) for the
+# double loss only, rows = the number of rows each sample set of a step is drawn from: (N0,), or (V, Vgt).
+_Mesh = collections.namedtuple("_Mesh", "args gt_normals rows")
+_VALID_LOG = {1: "Iteration %d, validation loss %g", 3: "Iteration %d, validation loss = %g (points %g, normals %g)"}
+
+
+def _rows(a):
+    return np.asarray(a).reshape(-1, 3).shape[0]
+
+
+def _meshes(ds):
+    """The meshes of a TrainingSet (addMeshWithGT): bind_cached(key, x, adjs, gt)."""
+    return [_Mesh((ds.in_list[i], ds.adj_list[i], ds.gt_list[i]), None, (ds.in_list[i].shape[1],))
+            for i in range(len(ds.in_list))]
+
 
 def _clean_meshes(ds, what):
-    """The meshes of a clean TrainingSet (addCleanMesh): (x, adjs, gt, vertices, faces_rows, edge_len)."""
+    """The meshes of a clean TrainingSet (addCleanMesh): bind_clean(key, x, adjs, gt, vertices, faces_rows, edge_len)."""
     if not (hasattr(ds, "is_clean") and ds.is_clean()):
         raise ValueError("noise_levels needs a %s of clean meshes (TrainingSet.addCleanMesh, preprocess --clean)" % what)
-    return [(ds.in_list[i], ds.adj_list[i], ds.gt_list[i], ds.clean_vertices[i], ds.clean_faces_rows[i],
-             ds.clean_edge_len[i]) for i in range(len(ds.in_list))]
+    return [_Mesh((ds.in_list[i], ds.adj_list[i], ds.gt_list[i], ds.clean_vertices[i], ds.clean_faces_rows[i],
+                   ds.clean_edge_len[i]), None, (np.asarray(ds.in_list[i]).shape[1],)) for i in range(len(ds.in_list))]
+
+
+def _vertex_meshes(ds, double):
+    """The meshes of a TrainingSet that have ground-truth vertices: bind_vertices(key, features, adjacency, vertices,
+    faces, v_faces, gt vertices[, gt_normals=gt normals])."""
+    gtv, gtn = getattr(ds, "gtv_list", []), getattr(ds, "gt_list", [])
+    out = []
+    for i in range(len(ds.in_list)):
+        if i >= len(gtv) or _rows(gtv[i]) == 0:
+            continue        # train.py:792-796 draws again when a mesh has no ground-truth vertices
+        if double and (i >= len(gtn) or _rows(gtn[i]) == 0):
+            raise ValueError("mesh %d has no ground-truth face normals (gt_list) for the double loss" % i)
+        out.append(_Mesh((ds.in_list[i], ds.adj_list[i], ds.v_list[i], ds.faces_list[i], ds.v_faces_list[i], gtv[i]),
+                         gtn[i] if double else None, (_rows(ds.v_list[i]), _rows(gtv[i]))))
+    return out
+
+
+def _clean_vertex_meshes(ds, what):
+    """The meshes of a clean vertex TrainingSet (addCleanMeshWithVertices): bind_clean_vertices(key, x, adjs, raw clean
+    vertices, faces_rows, v_faces, edge_len[, gt_normals=clean normals]); the clean vertices are the ground truth too."""
+    n = len(getattr(ds, "in_list", ()))
+    if not (hasattr(ds, "is_clean") and ds.is_clean() and len(ds.v_faces_list) == n and len(ds.gt_list) == n):
+        raise ValueError("noise_levels needs a %s of clean meshes with their vertex data (TrainingSet."
+                         "addCleanMeshWithVertices, preprocess --clean --with-vertices)" % what)
+    return [_Mesh((ds.in_list[i], ds.adj_list[i], ds.clean_vertices[i], ds.clean_faces_rows[i], ds.v_faces_list[i],
+                   ds.clean_edge_len[i]), ds.gt_list[i], (_rows(ds.clean_vertices[i]),) * 2) for i in range(n)]
+
+
+def _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction):
+    """The checked noise levels (None: the plain mode) and the training and validation meshes of a trainer."""
+    if noise_levels is None:
+        plain = _meshes if form == "angular" else lambda ds: _vertex_meshes(ds, form == "double")
+        sets = [plain(ds) if ds is not None else [] for ds in (trainSet, validSet)]
+        if form != "angular" and not sets[0]:
+            raise ValueError("no training mesh has ground-truth vertices (addMeshWithVerticesAndGT)")
+        return None, sets[0], sets[1]
+    levels = tuple(float(l) for l in noise_levels)
+    if not levels or not all(np.isfinite(l) and l >= 0 for l in levels):
+        raise ValueError("noise_levels: a non-empty list of levels >= 0")
+    if noise_direction not in ("random", "normal"):
+        raise ValueError("noise_direction must be 'random' or 'normal'")
+    clean = _clean_meshes if form == "angular" else _clean_vertex_meshes
+    return levels, clean(trainSet, "training set"), clean(validSet, "validation set") if validSet is not None else []
+
+
+def _bind(F, key, m, noise=None):
+    """Bind mesh record m under `key` through F = net.trainer_form(form): plain, or - noise = (seed, stream, direction) -
+    clean for noise synthesis.  (A cached mesh returns at once; the bind methods reshape the [1, ...] arrays.)"""
+    kw = {"gt_normals": m.gt_normals} if F.gt_normals else {}
+    if noise is not None:
+        kw.update(seed=noise[0], stream=noise[1], direction=noise[2])
+    (F.bind if noise is None else F.bind_clean)(key, *m.args, **kw)
+
+
+def _draw_samples(rs, F, m):
+    """A step's sample sets: COST_SAMPLES rows of N0, or POINT_SAMPLES of V, then POINT_SAMPLES of Vgt."""
+    return tuple(rs.randint(n, size=F.samples) for n in m.rows)
+
+
+def _draw_step(rs, F, m, levels, counter):
+    """A training step's draws, in their order: the sample sets, three uniforms for the rotation and - in synthesis mode
+    only: the random stream of a plain run is what it was - the level of noise = (counter, level)."""
+    return (_draw_samples(rs, F, m), rand_rotation_matrix(randnums=rs.uniform(size=3)),
+            None if levels is None else (counter, levels[rs.randint(len(levels))]))
+
+
+def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="random"):
+    """The mean {total, points, normals} (entries a form does not have stay 0) of the loss alone over the validation mesh
+    records, with rotation R and fresh rows from rs: one pass per mesh, or - levels given - per clean mesh and noise level
+    with stream = 1 + mesh index and step = level index: the SAME noisy meshes at every call (and what makeNoisy writes for
+    the same seed), so the validation curve is comparable along a run."""
+    F, vsum = net.trainer_form(form), np.zeros(3)
+    for vbm, m in enumerate(valid):
+        _bind(F, ("valid", vbm), m, None if levels is None else (seed, 1 + vbm, direction))
+        for k, level in enumerate((None,) if levels is None else levels):
+            F.set_samples(*_draw_samples(rs, F, m))
+            net.set_rotation(R)
+            if level is not None:
+                net.set_noise(k, level)
+            vsum[:F.outputs] += F.loss(rotate=True)[:F.outputs].cpu().numpy()
+    return vsum / (len(valid) * (1 if levels is None else len(levels)))
 
 
 def synthValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random"):
-    """Build extension: the mean loss over every clean validation mesh (tuples of _clean_meshes) at every noise level,
-    with stream = 1 + mesh index and step = level index - the SAME noisy meshes at every call (they are also what
-    makeNoisy writes for the same seed), so the validation curve is comparable along a run.  R: the rotation; rs: the
-    RandomState the loss rows are drawn from."""
-    total = 0.0
-    for vbm, m in enumerate(valid):
-        net.bind_clean(("valid", vbm), *m, seed=seed, stream=1 + vbm, direction=direction)
-        for k, level in enumerate(noise_levels):
-            net.set_samples(rs.randint(np.asarray(m[0]).shape[1], size=COST_SAMPLES))
-            net.set_rotation(R)
-            net.set_noise(k, level)
-            total += net.eval_loss(rotate=True)[0].item()
-    return total / (len(valid) * len(noise_levels))
+    """Build extension: the mean loss over every clean validation mesh (records of _clean_meshes) at every noise level
+    (_validation_loss).  R: the rotation; rs: the RandomState the loss rows are drawn from."""
+    return float(_validation_loss(net, "angular", valid, R, rs, noise_levels, seed, direction)[0])
 
 
-def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
-             capture=False, validSet=None, noise_levels=None, noise_direction="random"):
-    """train.py:380-632.  trainSet / validSet: dataClasses.TrainingSet.  Returns (net, lossArray [iters/50, 2]).
-
-    noise_levels (build extension; None = the reference's loop, untouched): trainSet / validSet hold CLEAN meshes
-    (TrainingSet.addCleanMesh, otherwise ValueError) and every iteration trains on fresh Gaussian vertex noise made on
-    the GPU (FacetDenoiser.bind_clean): a level drawn from the list x the mesh's mean edge length, along
-    noise_direction ("random" / "normal"), with the global iteration as the noise counter - a resumed run goes on with
-    new noise.  Validation: synthValidationLoss."""
-    synth = noise_levels is not None
-    if synth:
-        noise_levels = tuple(float(l) for l in noise_levels)
-        if not noise_levels or not all(np.isfinite(l) and l >= 0 for l in noise_levels):
-            raise ValueError("noise_levels: a non-empty list of levels >= 0")
-        if noise_direction not in ("random", "normal"):
-            raise ValueError("noise_direction must be 'random' or 'normal'")
-        meshes = _clean_meshes(trainSet, "training set")
-    else:
-        meshes = [(trainSet.in_list[i], trainSet.adj_list[i], trainSet.gt_list[i]) for i in range(len(trainSet.in_list))]
-    net = FacetDenoiser(device, seed=seed)
-
-    def bind(b):
-        if synth:
-            net.bind_clean(b, *meshes[b], seed=seed, stream=0, direction=noise_direction)
-        else:
-            net.bind_cached(b, *meshes[b][:2], gt=meshes[b][2])
-    start = 0
-    ckpt = os.path.join(network_path, net_name) if network_path else None
-    if ckpt:
-        # resume from the directory's latest checkpoint if it belongs to this network (train.py:525-533)
-        st = tfckpt.get_checkpoint_state(network_path)
-        if st and st.model_checkpoint_path:
-            split = os.path.basename(st.model_checkpoint_path).split('-')
-            if split[0] == net_name:
-                load_checkpoint(st.model_checkpoint_path, net)
-                start = int(split[1]) if len(split) > 1 and split[1].isdigit() else 0
-        elif os.path.exists(ckpt + ".pt"):
-            start = load_checkpoint(ckpt + ".pt", net)
-    rs = np.random.RandomState(seed + 1)
-    evalStepNum = 50
-    lossArray = np.zeros([max(num_iterations // evalStepNum, 1), 2])
-    bound = -1
-    train_loss, train_samp, hasNan = 0.0, 0, False
-    valid, last_loss = [], 0.0
-    if validSet is not None and synth:
-        valid = _clean_meshes(validSet, "validation set")
-    elif validSet is not None:
-        valid = [(validSet.in_list[i], validSet.adj_list[i], validSet.gt_list[i]) for i in range(len(validSet.in_list))]
-    for it in range(num_iterations):
-        if ckpt and it % SAVEITER == 0 and it > 0:
-            save_checkpoint(ckpt, net, start + it)
-        b = rs.randint(len(meshes))
-        if b != bound:       # the reference feeds a new patch through feed_dict; here every mesh stays bound in HBM
-            bind(b)
-            bound = b
-        n0 = meshes[b][0].shape[1]
-        samp_it = rs.randint(n0, size=COST_SAMPLES)
-        R_it = rand_rotation_matrix(randnums=rs.uniform(size=3))
-        # (drawn in this mode only: the random stream of a plain run is what it was)
-        noise_it = (start + it, noise_levels[rs.randint(len(noise_levels))]) if synth else None
-        if valid and it % (evalStepNum * 2) == 0:
-            # train.py:588-617: every 100 iterations the loss alone on every validation mesh, with this iteration's
-            # rotation and fresh random rows, BEFORE the training step; the previous row of the CSV gets the mean of
-            # this and the last value
-            if synth:
-                valid_loss = synthValidationLoss(net, valid, noise_levels, R_it, rs, seed, noise_direction)
-            else:
-                valid_loss = 0.0
-                for vbm, (vx, vadj, vgt) in enumerate(valid):
-                    net.bind_cached(("valid", vbm), vx, vadj, gt=vgt)
-                    net.set_samples(rs.randint(vx.shape[1], size=COST_SAMPLES))
-                    net.set_rotation(R_it)
-                    valid_loss += net.eval_loss(rotate=True)[0].item()
-                valid_loss /= len(valid)
-            log("Iteration %d, validation loss %g" % (it, valid_loss))
-            row = min(it // evalStepNum, len(lossArray) - 1)
-            lossArray[row, 1] = valid_loss
-            if it > 0:
-                lossArray[row - 1, 1] = (valid_loss + last_loss) / 2
-                last_loss = valid_loss
-            bind(b)
-        loss = net.train_step(sample_ind=samp_it, R=R_it, capture=capture, noise=noise_it)
-        if it % evalStepNum == 0 or it == num_iterations - 1:
-            lv = loss[0].item()      # the only host sync of the loop
-            if not np.isfinite(lv):  # NaN watchdog (train.py:620-623)
-                hasNan = True
-                log("WARNING! NAN FOUND AFTER TRAINING!!!! training example %d/%d" % (b, len(meshes)))
-            train_loss += lv
-            train_samp += 1
-            if it % evalStepNum == 0:
-                log("Iteration %d, training loss %g" % (it, train_loss / train_samp))
-                lossArray[min(it // evalStepNum, len(lossArray) - 1), 0] = train_loss / train_samp
-                train_loss, train_samp = 0.0, 0
-    if ckpt:
-        save_checkpoint(ckpt, net, start + num_iterations)
-        with open(os.path.join(network_path, net_name + ".csv"), "ab") as fh:
-            np.savetxt(fh, lossArray, delimiter=",")
-    return net, lossArray
+def synthVertexValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", double=False):
+    """Build extension: {total, points, normals} (double) or {points, 0, 0} - the mean loss over every clean validation mesh
+    (records of _clean_vertex_meshes) at every noise level (_validation_loss).  R: rotation; rs draws the 500 + 500 rows."""
+    return _validation_loss(net, "double" if double else "points", valid, R, rs, noise_levels, seed, direction)
 
 
 def _resume(net, network_path, net_name):
@@ -247,6 +240,64 @@ def _resume(net, network_path, net_name):
     elif os.path.exists(os.path.join(network_path, net_name) + ".pt"):
         return load_checkpoint(os.path.join(network_path, net_name) + ".pt", net)
     return 0
+
+
+def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
+             capture=False, validSet=None, noise_levels=None, noise_direction="random"):
+    """train.py:380-632.  trainSet / validSet: dataClasses.TrainingSet.  Returns (net, lossArray [iters/50, 2]).
+
+    noise_levels (build extension; None = the reference's loop, untouched): trainSet / validSet hold CLEAN meshes
+    (TrainingSet.addCleanMesh, otherwise ValueError) and every iteration trains on fresh Gaussian vertex noise made on
+    the GPU (FacetDenoiser.bind_clean): a level drawn from the list x the mesh's mean edge length, along
+    noise_direction ("random" / "normal"), with the global iteration as the noise counter - a resumed run goes on with
+    new noise.  Validation: synthValidationLoss."""
+    form = "angular"
+    levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
+    train_noise = None if levels is None else (seed, 0, noise_direction)
+    net = FacetDenoiser(device, seed=seed)
+    F = net.trainer_form(form)
+    ckpt = os.path.join(network_path, net_name) if network_path else None
+    start = _resume(net, network_path, net_name) if ckpt else 0
+    rs = np.random.RandomState(seed + 1)
+    evalStepNum = 50
+    lossArray = np.zeros([max(num_iterations // evalStepNum, 1), 2])
+    bound, train_loss, train_samp, last_loss = -1, 0.0, 0, 0.0
+    for it in range(num_iterations):
+        if ckpt and it % SAVEITER == 0 and it > 0:
+            save_checkpoint(ckpt, net, start + it)
+        b = rs.randint(len(meshes))
+        if b != bound:       # the reference feeds a new patch through feed_dict; here every mesh stays bound in HBM
+            _bind(F, b, meshes[b], train_noise)
+            bound = b
+        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it)
+        if valid and it % (evalStepNum * 2) == 0:
+            # train.py:588-617: every 100 iterations the loss alone on every validation mesh, with this iteration's
+            # rotation and fresh random rows, BEFORE the training step; the previous row of the CSV gets the mean of
+            # this and the last value
+            valid_loss = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction)[0]
+            log("Iteration %d, validation loss %g" % (it, valid_loss))
+            row = min(it // evalStepNum, len(lossArray) - 1)
+            lossArray[row, 1] = valid_loss
+            if it > 0:
+                lossArray[row - 1, 1] = (valid_loss + last_loss) / 2
+                last_loss = valid_loss
+            _bind(F, b, meshes[b], train_noise)
+        loss = F.step(*samp_it, R_it, capture=capture, noise=noise_it)
+        if it % evalStepNum == 0 or it == num_iterations - 1:
+            lv = loss[0].item()      # the only host sync of the loop
+            if not np.isfinite(lv):  # NaN watchdog (train.py:620-623)
+                log("WARNING! NAN FOUND AFTER TRAINING!!!! training example %d/%d" % (b, len(meshes)))
+            train_loss += lv
+            train_samp += 1
+            if it % evalStepNum == 0:
+                log("Iteration %d, training loss %g" % (it, train_loss / train_samp))
+                lossArray[min(it // evalStepNum, len(lossArray) - 1), 0] = train_loss / train_samp
+                train_loss, train_samp = 0.0, 0
+    if ckpt:
+        save_checkpoint(ckpt, net, start + num_iterations)
+        with open(os.path.join(network_path, net_name + ".csv"), "ab") as fh:
+            np.savetxt(fh, lossArray, delimiter=",")
+    return net, lossArray
 
 
 def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
@@ -275,8 +326,8 @@ def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net"
     only - at iteration 0 as well.
 
     Returns (net, lossArray of the last block, per-iteration training losses [num_iterations])."""
-    return _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
-                                False, noise_levels, noise_direction)
+    return _train_with_vertices("points", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
+                                validSet, noise_levels, noise_direction)
 
 
 def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
@@ -298,99 +349,28 @@ def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="ne
     noise_levels / noise_direction (build extension): as in trainAccuracyNet; the ground-truth normals are the clean ones.
 
     Returns (net, lossArray of the last block, per-iteration {total, points, normals} [num_iterations, 3])."""
-    return _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
-                                True, noise_levels, noise_direction)
+    return _train_with_vertices("double", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
+                                validSet, noise_levels, noise_direction)
 
 
-def _vertex_meshes(ds, double, strict):
-    """The meshes of a TrainingSet that have ground-truth vertices: (features, adjacency, vertices, faces, v_faces,
-    gt vertices[, gt normals])."""
-    gtv = getattr(ds, "gtv_list", [])
-    gtn = getattr(ds, "gt_list", [])
-    out = []
-    for i in range(len(ds.in_list)):
-        if i >= len(gtv) or np.asarray(gtv[i]).reshape(-1, 3).shape[0] == 0:
-            continue        # train.py:792-796 draws again when a mesh has no ground-truth vertices
-        m = (ds.in_list[i], ds.adj_list[i], ds.v_list[i], ds.faces_list[i], ds.v_faces_list[i], gtv[i])
-        if double:
-            if i >= len(gtn) or np.asarray(gtn[i]).reshape(-1, 3).shape[0] == 0:
-                if strict:
-                    raise ValueError("mesh %d has no ground-truth face normals (gt_list) for the double loss" % i)
-                continue
-            m = m + (gtn[i],)
-        out.append(m)
-    return out
-
-
-def _clean_vertex_meshes(ds, what):
-    """The meshes of a clean vertex TrainingSet (addCleanMeshWithVertices): (x, adjs, raw clean vertices, faces_rows,
-    v_faces, edge_len, clean normals) - the arguments of FacetDenoiser.bind_clean_vertices behind the key."""
-    n = len(getattr(ds, "in_list", ()))
-    if not (hasattr(ds, "is_clean") and ds.is_clean() and len(ds.v_faces_list) == n and len(ds.gt_list) == n):
-        raise ValueError("noise_levels needs a %s of clean meshes with their vertex data (TrainingSet."
-                         "addCleanMeshWithVertices, preprocess --clean --with-vertices)" % what)
-    return [(ds.in_list[i], ds.adj_list[i], ds.clean_vertices[i], ds.clean_faces_rows[i], ds.v_faces_list[i],
-             ds.clean_edge_len[i], ds.gt_list[i]) for i in range(n)]
-
-
-def synthVertexValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", double=False):
-    """Build extension: {total, points, normals} (double) or {points, 0, 0} - the mean loss over every clean validation
-    mesh (tuples of _clean_vertex_meshes) at every noise level, with stream = 1 + mesh index and step = level index: the
-    SAME noisy meshes at every call, and for the same seed the ones makeNoisy writes.  R: the rotation; rs: the
-    RandomState the 500 + 500 rows are drawn from."""
-    vsum = np.zeros(3)
-    for vbm, m in enumerate(valid):
-        net.bind_clean_vertices(("valid", vbm), *m[:6], gt_normals=m[6] if double else None, seed=seed, stream=1 + vbm,
-                                direction=direction)
-        nv = np.asarray(m[2]).reshape(-1, 3).shape[0]
-        for k, level in enumerate(noise_levels):
-            net.set_point_samples(rs.randint(nv, size=POINT_SAMPLES), rs.randint(nv, size=POINT_SAMPLES))
-            net.set_rotation(R)
-            net.set_noise(k, level)
-            if double:
-                vsum += net.double_loss(rotate=True).cpu().numpy()
-            else:
-                vsum[0] += net.pointset_loss(rotate=True)[0].item()
-    return vsum / (len(valid) * len(noise_levels))
-
-
-def _train_with_vertices(trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet, double,
+def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
                          noise_levels=None, noise_direction="random"):
-    """The loop of trainAccuracyNet (double=False) and trainDoubleLossNet (double=True)."""
-    synth = noise_levels is not None
-    if synth:
-        noise_levels = tuple(float(l) for l in noise_levels)
-        if not noise_levels or not all(np.isfinite(l) and l >= 0 for l in noise_levels):
-            raise ValueError("noise_levels: a non-empty list of levels >= 0")
-        if noise_direction not in ("random", "normal"):
-            raise ValueError("noise_direction must be 'random' or 'normal'")
-        meshes = _clean_vertex_meshes(trainSet, "training set")
-        valid = _clean_vertex_meshes(validSet, "validation set") if validSet is not None else []
-    else:
-        meshes = _vertex_meshes(trainSet, double, True)
-        if not meshes:
-            raise ValueError("no training mesh has ground-truth vertices (addMeshWithVerticesAndGT)")
-        valid = _vertex_meshes(validSet, double, True) if validSet is not None else []
+    """The loop of trainAccuracyNet (form "points") and trainDoubleLossNet ("double")."""
+    levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
+    train_noise = None if levels is None else (seed, 0, noise_direction)
     net = FacetDenoiser(device, multi_scale=True, seed=seed)
+    F = net.trainer_form(form)
     ckpt = os.path.join(network_path, net_name) if network_path else None
     start = _resume(net, network_path, net_name) if ckpt else 0
     rs = np.random.RandomState(seed + 1)
     evalStepNum, validStepNum, block = 10, 20, 500
+    # (synthesis mode scores its fixed noisy validation meshes at iteration 0 too, as trainNet does: the curve starts at the
+    #  restored weights, before this run's first step; the plain mode's first pass is iteration 20)
+    first_valid = validStepNum if levels is None else 0
     lossArray = np.zeros([block // evalStepNum, 2])
-    hist = torch.zeros((max(num_iterations, 1), 3) if double else max(num_iterations, 1), dtype=torch.float32,
-                       device=net.device)
+    hist = torch.zeros(max(num_iterations, 1), F.outputs, dtype=torch.float32, device=net.device)
     acc = torch.zeros(1, dtype=torch.float32, device=net.device)
     acc_n, last_loss = 0, 0.0
-
-    def bind(key, m):
-        # (a cached mesh returns at once; bind_vertices reshapes the [1, ...] arrays)
-        if synth:
-            net.bind_clean_vertices(key, *m[:6], gt_normals=m[6] if double else None, seed=seed, stream=0,
-                                    direction=noise_direction)
-        elif double:
-            net.bind_vertices(key, *m[:6], gt_normals=m[6])
-        else:
-            net.bind_vertices(key, *m)
 
     def save(iteration):
         save_checkpoint(ckpt, net, iteration)
@@ -399,50 +379,19 @@ def _train_with_vertices(trainSet, num_iterations, network_path, net_name, devic
 
     for it in range(num_iterations):
         b = rs.randint(len(meshes))
-        num_v = np.asarray(meshes[b][2]).reshape(-1, 3).shape[0]
-        num_vgt = num_v if synth else np.asarray(meshes[b][5]).reshape(-1, 3).shape[0]
-        i0 = rs.randint(num_v, size=POINT_SAMPLES)
-        i1 = rs.randint(num_vgt, size=POINT_SAMPLES)
-        R_it = rand_rotation_matrix(randnums=rs.uniform(size=3))
-        # (drawn in this mode only, after the rotation: the random stream of a plain run is what it was)
-        noise_it = (start + it, noise_levels[rs.randint(len(noise_levels))]) if synth else None
+        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it)
         row = (it % block) // evalStepNum
-        # (synthesis mode scores its fixed noisy validation meshes at iteration 0 too, as trainNet does: the curve starts
-        #  at the restored weights, before this run's first step)
-        if valid and it % validStepNum == 0 and (it > 0 or synth):
-            if synth:
-                vsum = synthVertexValidationLoss(net, valid, noise_levels, R_it, rs, seed, noise_direction, double)
-            else:
-                vsum = np.zeros(3)
-                for vbm, m in enumerate(valid):
-                    bind(("valid", vbm), m)
-                    nvv = np.asarray(m[2]).reshape(-1, 3).shape[0]
-                    nvg = np.asarray(m[5]).reshape(-1, 3).shape[0]
-                    net.set_point_samples(rs.randint(nvv, size=POINT_SAMPLES), rs.randint(nvg, size=POINT_SAMPLES))
-                    net.set_rotation(R_it)
-                    if double:
-                        vsum += net.double_loss(rotate=True).cpu().numpy()
-                    else:
-                        vsum[0] += net.pointset_loss(rotate=True)[0].item()
-                vsum /= len(valid)
-            valid_loss = vsum[0]
-            if double:
-                log("Iteration %d, validation loss = %g (points %g, normals %g)" % (it, vsum[0], vsum[1], vsum[2]))
-            else:
-                log("Iteration %d, validation loss %g" % (it, valid_loss))
-            lossArray[row, 1] = valid_loss
+        if valid and it % validStepNum == 0 and it >= first_valid:
+            vsum = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction)
+            log(_VALID_LOG[F.outputs] % ((it,) + tuple(vsum[:F.outputs])))      # (the double loss with its points / normals split)
+            lossArray[row, 1] = vsum[0]
             if row > 0:
-                lossArray[row - 1, 1] = (valid_loss + last_loss) / 2
-            last_loss = valid_loss
-        bind(b, meshes[b])
-        if double:
-            out = net.double_loss_step(i0, i1, R_it, capture=capture, noise=noise_it)
-            hist[it].copy_(out)
-            loss = out[0:1]
-        else:
-            loss = net.pointset_step(i0, i1, R_it, capture=capture, noise=noise_it)
-            hist[it:it + 1].copy_(loss)
-        acc += loss
+                lossArray[row - 1, 1] = (vsum[0] + last_loss) / 2
+            last_loss = vsum[0]
+        _bind(F, b, meshes[b], train_noise)
+        out = F.step(*samp_it, R_it, capture=capture, noise=noise_it)
+        hist[it].copy_(out)
+        acc += out[0:1]
         acc_n += 1
         if it % evalStepNum == 0:
             lv = acc.item() / acc_n           # the only host sync of a training iteration, every 10 iterations
@@ -457,14 +406,14 @@ def _train_with_vertices(trainSet, num_iterations, network_path, net_name, devic
             lossArray = np.zeros_like(lossArray)
     if ckpt:
         save(start + num_iterations)
-    return net, lossArray, hist[:num_iterations].cpu().numpy()
+    hist = hist[:num_iterations].cpu().numpy()
+    return net, lossArray, hist if F.outputs > 1 else hist[:, 0]
 
 
 def update_position2(x, face_normals, edge_map, v_edges, iter_num=20, max_edges=20):
     """train.py:1467-1557, same argument layout on torch GPU tensors: x [1,V,3], face_normals [1,F,3], edge_map
     int [1,E,4], v_edges int [1,V,max_edges] (-1 = unused slot); returns the updated positions [1,V,3].
     lambda = 1/18 as in the reference (:1469)."""
-    from . import ops, tfckpt
     if v_edges.shape[-1] != max_edges:
         raise ValueError("v_edges has %d slots per vertex, max_edges says %d" % (v_edges.shape[-1], max_edges))
     out = ops.vertex_update(x.reshape(-1, 3), face_normals.reshape(-1, 3), edge_map.reshape(-1, 4),
@@ -474,7 +423,6 @@ def update_position2(x, face_normals, edge_map, v_edges, iter_num=20, max_edges=
 
 def updateFacesCenter(vertices, faces, coarsening_steps):
     """train.py:1768-1798: node centres of the three levels, [fpos0 [1,N0,3], fpos1 [1,N0/4,3], fpos2 [1,N0/16,3]]."""
-    from . import ops, tfckpt
     if coarsening_steps != 2:
         raise NotImplementedError("libfgc pools 4:1 (coarsening_steps = 2, settings.py:31)")
     f0 = ops.face_centers(vertices.reshape(-1, 3), faces.reshape(-1, 3))
@@ -514,7 +462,6 @@ def update_position_MS(x, face_normals_list, faces, v_faces0, coarsening_steps, 
     tables: the mesh's inverse tables (ops.vertex_ms_tables, as device tensors) for the backward; without them every
     backward copies faces and v_faces to the host and rebuilds them there (a host synchronisation per call) - pass them
     when the same mesh is differentiated repeatedly.  (FacetDenoiser.pointset_step keeps them per bound mesh.)"""
-    from . import ops, tfckpt
     if coarsening_steps != 2 or len(face_normals_list) != 3:
         raise NotImplementedError("three levels pooled 4:1, as the network has them (settings.py:31-32)")
     if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in face_normals_list)):
@@ -535,7 +482,6 @@ def inferNet(inputMesh, net_or_checkpoint, device="cuda"):
     Returns the reference's 9-tuple
     (points, points_mid, points_coarse, fine / mid / coarse normals [F,3] in face order, fine / mid / coarse positions
     [F,3]; as in the reference the three position arrays are the input barycentre channels)."""
-    from . import ops, tfckpt
     if isinstance(net_or_checkpoint, FacetDenoiser):
         net = net_or_checkpoint
     else:

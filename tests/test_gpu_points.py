@@ -246,6 +246,47 @@ def test_train_accuracy_net_lowers_the_loss():
     assert np.isfinite(hist).all() and last < first
 
 
+@pytest.mark.parametrize("synth", [False, True])
+@pytest.mark.parametrize("double", [False, True])
+def test_vertex_trainers_capture_equals_eager_across_mesh_switches_and_validation(monkeypatch, double, synth):
+    """trainAccuracyNet / trainDoubleLossNet(capture=True) on two meshes with a validation set, plain and on synthesised
+    noise: each training mesh's step is recorded once and kept with the mesh across the switches and the validation
+    passes (iteration 20; on synthesised noise iteration 0 too), and the run computes bit for bit what the eager run does."""
+    from facet_graph_convolution_amd import train as T
+    from facet_graph_convolution_amd.dataClasses import TrainingSet
+    from facet_graph_convolution_amd.meshgen import icosphere
+    from facet_graph_convolution_amd.net import FacetDenoiser
+
+    def clean_set(seeds):
+        V, F = icosphere(2)
+        ds = TrainingSet()
+        for s in seeds:
+            ds.addCleanMeshWithVertices(V, F, seed=s)
+        return ds
+    ts, vs = (clean_set([1, 2]), clean_set([3])) if synth else (_small_set([1, 2]), _small_set([3]))
+    form = "double" if double else "points"
+    trainer = T.trainDoubleLossNet if double else T.trainAccuracyNet
+    extra = dict(noise_levels=(0.1, 0.3)) if synth else {}
+    steps = []
+    adam = FacetDenoiser.adam_step
+
+    def adam_step(self, *a, **k):     # (right behind each step's forward + backward)
+        steps.append((self._mesh["captured"].get(form) or (None,))[0])
+        return adam(self, *a, **k)
+    monkeypatch.setattr(FacetDenoiser, "adam_step", adam_step)
+    logs = []
+    net, arr, hist = trainer(ts, 25, capture=True, validSet=vs, log=logs.append, **extra)
+    graphs = list(steps)
+    switches = sum(1 for a, b in zip(graphs, graphs[1:]) if a is not b)
+    assert len(graphs) == 25 and None not in graphs and len({id(g) for g in graphs}) == 2 and switches >= 3
+    assert all(set(net._mesh_cache[b]["captured"]) == {form} for b in (0, 1))
+    logs_e = []
+    net_e, arr_e, hist_e = trainer(ts, 25, validSet=vs, log=logs_e.append, **extra)
+    assert sum("validation loss" in s for s in logs) == (2 if synth else 1) and logs == logs_e
+    assert np.isfinite(hist).all() and hist.shape == ((25, 3) if double else (25,))
+    assert np.array_equal(hist, hist_e) and np.array_equal(arr, arr_e) and torch.equal(net.params.theta, net_e.params.theta)
+
+
 def test_pointset_step_matches_reference_fixture(golden_dir):
     """One point-set step against the reference's own chain executed on tf_shim (tests/golden/gen/make_golden_points.py):
     refined vertices, loss and every weight gradient (large tensors at the fixture's sampled entries), relative to each
