@@ -137,8 +137,8 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const float* __restrict__ 
 template <int NJ, bool BF>
 __device__ __forceinline__ void tn_stream_body(const float* __restrict__ A, int lda, int P, const float* __restrict__ x0,
                                                const float* __restrict__ x1, int c0, int c1, int shift, int rows,
-                                               int rows_per_split, float* __restrict__ slab, int vblock) {
-    __shared__ float red[2][64][65];
+                                               int rows_per_split, float* __restrict__ slab, int vblock,
+                                               float (*red)[64][65]) {
     const int Q = c0 + c1;
     const int npt = (P + 63) >> 6;
     int tile_id, split_id;
@@ -249,18 +249,193 @@ __device__ __forceinline__ void tn_stream_body(const float* __restrict__ A, int 
         if (p0 + pp < P && q0 + qq < Q) out[(size_t)(p0 + pp) * Q + q0 + qq] = red[0][pp][qq] + red[1][pp][qq];
     }
 }
+
+// Direct form of the fp32 streaming body: the same tiles, k-step order, operand sets and sums, with the address and tail work
+// taken off the vector ALU (v_mfma_f32_16x16x4_f32 and VALU instructions do not co-issue: every vector instruction in the loop
+// costs a SIMD 4 cycles next to the 32 of an MFMA).
+//   * A goes through a buffer descriptor that starts at the split's first row and ends at its last: a row past r_end comes
+//     back as zeros from the range check, so the clamp of the row and the select on the fragment are gone.  The lane's byte
+//     offset is computed once and advances by the constant 16 rows per load (all four operand sets share one running
+//     offset: consecutive loads of a wave are always four k-steps apart).
+//   * X goes through one descriptor per HALF tile of 32 columns (lane lr owns columns 2*lr, 2*lr + 1 of each half: b[2h],
+//     b[2h + 1]), from the split's first row to the operand's end.  A half lies in one source whenever c0 % 32 == 0 (or there
+//     is one source), so the descriptor is wave-uniform even in a tile that the concat boundary cuts; rows past r_end read
+//     the rows that follow (finite, times the zero of A) or zeros past the operand's end (0 * 0): + 0 either way, as the
+//     clamped row gives in tn_stream_body.  Which column a lane holds does not enter an element's sum: same bits.
+//   * the sum over the four waves goes through LDS in the accumulators' own layout (element (i, j) of lane l at
+//     ((i * NJ + j) * 64 + l) as an f32x4: ds_write_b128 / ds_read_b128 at constant offsets), (w0 + w1) + (w2 + w3) as
+//     before, and wave 0 stores the tile from registers, two columns per store.
+// Offsets are 32 bits relative to the split's first row; tn_direct_ok is the (wave-uniform) test that they fit, that a
+// k-step's 16 rows advance X by whole rows and that no half tile straddles the sources.  Where it fails the workgroup runs
+// tn_stream_body.
+__device__ __forceinline__ bool tn_direct_ok(int lda, int c0, int c1, int shift, int rows_per_split) {
+    // (a wave requests at most 4 * 28 + 3 rows past the end of its split)
+    return (c1 == 0 || (c0 & 31) == 0) && shift <= 4 &&
+           (long long)(rows_per_split + 160) * max(lda, max(c0, c1)) < (1ll << 29);   // (and P * Q: a weight matrix)
+}
+
+template <int NJ>
+__device__ __forceinline__ void tn_direct_body(const float* __restrict__ A, int lda, int P, const float* __restrict__ x0,
+                                               const float* __restrict__ x1, int c0, int c1, int shift, int rows,
+                                               int rows_per_split, float* __restrict__ slab, int vblock, f32x4* red) {
+    constexpr int NH = NJ / 2;   // half tiles of 32 columns
+    const int Q = c0 + c1;
+    const int npt = (P + 63) >> 6;
+    int tile_id, split_id;
+    if (!tn_block(npt * ((Q + 16 * NJ - 1) / (16 * NJ)), (rows + rows_per_split - 1) / rows_per_split, tile_id, split_id, vblock))
+        return;
+    const int pt = tile_id % npt, qt = tile_id / npt;
+    const int p0 = pt * 64, q0 = qt * (16 * NJ);
+    const int tid = threadIdx.x, lane = tid & 63, lr = lane & 15, lq = lane >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int r_begin = split_id * rows_per_split;
+    const int r_end = min(rows, r_begin + rows_per_split);
+    const int nsteps = (r_end - r_begin + 3) >> 2;
+    const int row0 = 4 * wave + lq;   // this lane's row of the wave's first k-step, from r_begin
+    // column quad / pairs of this lane, clamped into the operands (results of clamped columns are never stored)
+    const int pc = min(p0 + 4 * lr, P - 4);
+    const __amdgpu_buffer_rsrc_t a_rs = __builtin_amdgcn_make_buffer_rsrc(
+        const_cast<float*>(A + (size_t)r_begin * lda), 0, (r_end - r_begin) * lda * 4, 0x00020000);
+    unsigned ao = (unsigned)(row0 * lda + pc) * 4u;
+    const unsigned astep = 16u * (unsigned)lda * 4u;
+    const int xr0 = r_begin >> shift, xrows = ((rows - 1) >> shift) + 1;   // X: first row of the split, rows of the operand
+    const int xrow0 = ((r_begin + row0) >> shift) - xr0;
+    __amdgpu_buffer_rsrc_t b_rs[NH];
+    unsigned bo[NH], bstep[NH];
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        const int hs = q0 + 32 * h;
+        const bool first = hs < c0 || c1 == 0;
+        const int ld = first ? c0 : c1;
+        const size_t bytes = (size_t)(xrows - xr0) * ld * 4;
+        b_rs[h] = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>((first ? x0 : x1) + (size_t)xr0 * ld), 0,
+                                                    (int)(unsigned)std::min<size_t>(bytes, 0xffffffffu), 0x00020000);
+        bo[h] = (unsigned)(xrow0 * ld + min(hs + 2 * lr, Q - 2) - (first ? 0 : c0)) * 4u;
+        bstep[h] = (unsigned)((16 >> shift) * ld) * 4u;
+    }
+    f32x4 acc[4][NJ];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < NJ; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    struct Set {
+        f32x4 a;
+        f32x2c b[NH];
+    };
+    // (the empty asm pins the running offset in its register: left alone, loop strength reduction turns each into four
+    //  induction variables plus a base and the loop pays 21 vector instructions for what takes 12)
+    auto ld = [&](Set& s) {   // the wave's next k-step
+        s.a = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(a_rs, ao, 0, 0));
+        ao += astep;
+        asm volatile("" : "+v"(ao));
+#pragma unroll
+        for (int h = 0; h < NH; ++h) {
+            s.b[h] = __builtin_bit_cast(f32x2c, __builtin_amdgcn_raw_buffer_load_b64(b_rs[h], bo[h], 0, 0));
+            bo[h] += bstep[h];
+            asm volatile("" : "+v"(bo[h]));
+        }
+    };
+    auto mm = [&](const Set& s) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < NJ; ++j)
+                acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(s.a[i], s.b[j >> 1][j & 1], acc[i][j], 0, 0, 0);
+    };
+    // sched_barrier: keep the program order "16 MFMAs, then the refill of the set they consumed" (see tn_stream_body), and
+    // the first four requests in the order of the refills: s_waitcnt counts from the older of the two histories that meet
+    // at the loop's head
+    if (wave < nsteps) {   // (a split shorter than four k-steps leaves waves without one)
+        Set s0, s1, s2, s3;
+        ld(s0);
+        __builtin_amdgcn_sched_barrier(0);
+        ld(s1);
+        __builtin_amdgcn_sched_barrier(0);
+        ld(s2);
+        __builtin_amdgcn_sched_barrier(0);
+        ld(s3);
+        __builtin_amdgcn_sched_barrier(0);
+#define FGC_TN_STEP(S_)                         \
+    mm(S_);                                     \
+    __builtin_amdgcn_sched_barrier(0);          \
+    ld(S_);                                     \
+    __builtin_amdgcn_sched_barrier(0);
+        int s = wave;
+        do {   // steps past the end multiply zeros
+            FGC_TN_STEP(s0)
+            FGC_TN_STEP(s1)
+            FGC_TN_STEP(s2)
+            FGC_TN_STEP(s3)
+            s += 16;
+        } while (s < nsteps);
+    }
+#undef FGC_TN_STEP
+    // (w0 + w1) + (w2 + w3), as gemm_tn_kernel sums them; a lane only ever meets its own slots
+    auto put = [&](int slot) {
+#pragma unroll
+        for (int e = 0; e < 4 * NJ; ++e) red[(slot * 4 * NJ + e) * 64 + lane] = acc[e / NJ][e % NJ];
+    };
+    auto add = [&](int slot) {
+#pragma unroll
+        for (int e = 0; e < 4 * NJ; ++e) acc[e / NJ][e % NJ] += red[(slot * 4 * NJ + e) * 64 + lane];
+    };
+    if (wave == 1) put(0);
+    if (wave == 3) put(1);
+    __syncthreads();
+    if (wave == 0) add(0);
+    if (wave == 2) {
+        add(1);
+        put(1);
+    }
+    __syncthreads();
+    if (wave != 0) return;
+    add(1);
+    // C layout of acc[i][j]: column lr of half j >> 1 -> q = 32 * (j >> 1) + 2 * lr + (j & 1), row lq*4+reg -> p = 4*(lq*4+reg) + i.
+    // The slab tile goes out through a descriptor of exactly this split's [P, Q]: rows >= P fall to its range check, lanes
+    // whose columns are >= Q (whole pairs: Q is even) get an offset that no addition brings back into range.
+    const __amdgpu_buffer_rsrc_t c_rs =
+        __builtin_amdgcn_make_buffer_rsrc(slab + (size_t)split_id * P * Q, 0, P * Q * 4, 0x00020000);
+#pragma unroll
+    for (int h = 0; h < NH; ++h) {
+        const int q = q0 + 32 * h + 2 * lr;
+        const unsigned co = q < Q ? (unsigned)((p0 + 16 * lq) * Q + q) * 4u : 0x80000000u;
+#pragma unroll
+        for (int t = 0; t < 4; ++t)
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, f32x2c{acc[i][2 * h][t], acc[i][2 * h + 1][t]}), c_rs,
+                                                      co + (unsigned)((4 * t + i) * Q) * 4u, 0, 0);
+    }
+}
+
+// (the LDS of the 4-wave sum: 2 x 16 KB; tn_stream_body pads its rows, hence the 65)
+template <int NJ, bool BF>
+__device__ __forceinline__ void tn_stream_any(const float* __restrict__ A, int lda, int P, const float* __restrict__ x0,
+                                              const float* __restrict__ x1, int c0, int c1, int shift, int rows,
+                                              int rows_per_split, float* __restrict__ slab, int vblock) {
+    __shared__ __attribute__((aligned(16))) float red[2][64][65];
+    if constexpr (!BF) {
+        if (tn_direct_ok(lda, c0, c1, shift, rows_per_split)) {
+            tn_direct_body<NJ>(A, lda, P, x0, x1, c0, c1, shift, rows, rows_per_split, slab, vblock,
+                               reinterpret_cast<f32x4*>(&red[0][0][0]));
+            return;
+        }
+    }
+    tn_stream_body<NJ, BF>(A, lda, P, x0, x1, c0, c1, shift, rows, rows_per_split, slab, vblock, red);
+}
 template <int NJ, bool BF = false>
 __global__ __launch_bounds__(256, 4) void gemm_tn_stream_kernel(const float* __restrict__ A, int lda, int P,
                                                                 const float* __restrict__ x0,
                                                                 const float* __restrict__ x1, int c0, int c1, int shift,
                                                                 int rows, int rows_per_split, float* __restrict__ slab) {
-    tn_stream_body<NJ, BF>(A, lda, P, x0, x1, c0, c1, shift, rows, rows_per_split, slab, -1);
+    tn_stream_any<NJ, BF>(A, lda, P, x0, x1, c0, c1, shift, rows, rows_per_split, slab, -1);
 }
 template <int NJ, bool BF = false>
 __global__ __launch_bounds__(256, 4) void gemm_tn_stream_group_kernel(TnJobs J) {
     const TnArgs& a = J.job[tn_job_of(J)];
-    tn_stream_body<NJ, BF>((const float*)a.A, a.lda, a.P, (const float*)a.x0, (const float*)a.x1, a.c0, a.c1, a.shift, a.rows,
-                           a.rps, a.slab, (int)blockIdx.x - a.block0);
+    tn_stream_any<NJ, BF>((const float*)a.A, a.lda, a.P, (const float*)a.x0, (const float*)a.x1, a.c0, a.c1, a.shift, a.rows,
+                          a.rps, a.slab, (int)blockIdx.x - a.block0);
 }
 
 // ---------------------------------------------------------------------------------------------
