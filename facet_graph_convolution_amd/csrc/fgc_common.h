@@ -58,11 +58,12 @@ struct LaunchCfg {
     hipStream_t st;
     int grid, block;
     size_t smem;        // dynamic LDS bytes
+    int gy = 1;         // second grid dimension
 };
 template <auto Kernel, typename... Args>
 static inline int launch_kernel(const LaunchCfg& c, const Args&... args) {
     if (c.smem) hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.smem);
-    FGC_LAUNCH(c.name, c.st, Kernel, dim3(c.grid), dim3(c.block), c.smem, args...);
+    FGC_LAUNCH(c.name, c.st, Kernel, dim3(c.grid, c.gy), dim3(c.block), c.smem, args...);
     FGC_CHECK_LAUNCH(c.what);
     return FGC_OK;
 }

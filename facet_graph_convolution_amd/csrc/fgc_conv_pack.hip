@@ -3,6 +3,7 @@
 #include "fgc_conv_bwd.h"
 #include "fgc_conv_narrow.h"
 #include "fgc_conv_pair.h"
+#include "fgc_mlp.h"
 
 namespace fgc {
 
@@ -134,7 +135,7 @@ extern "C" int fgc_conv_pack(const fgc_conv_desc* const* descs, const fgc_conv_b
     if (extra && extra->mlp_W1) {
         PackJob mj[4];
         size_t tot[4];
-        const int nj = extra->mlp_bf16 ? mlp_pack_jobs_bf16(extra, mj, tot) : mlp_pack_jobs_f32(extra, mj, tot);
+        const int nj = mlp_pack_jobs(extra, mj, tot);
         FGC_CHECK_ARG(nj >= 0, "fgc_conv_pack: extra: MLP shape cin=%d hidden=%d cout=%d n=%d not served%s", extra->mlp_cin,
                       extra->mlp_hidden, extra->mlp_cout, extra->mlp_n, extra->mlp_bf16 ? " (bf16)" : "");
         for (int i = 0; i < nj; ++i) batch.add(mj[i], tot[i]);

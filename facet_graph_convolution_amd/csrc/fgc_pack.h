@@ -93,7 +93,7 @@ __device__ __forceinline__ void pack_plain_bf16_body(const float* __restrict__ W
     for (int i = bid * blockDim.x + threadIdx.x; i < count; i += nb * blockDim.x) Wb[i] = f_to_bf(W0[i]);
 }
 
-// ---- operands of the per-facet MLP (fgc_mlp.hip, fgc_mlp_bf16.hip) and the rotation of the input rows: device bodies here so
+// ---- operands of the per-facet MLP (fgc_mlp.h: the plan names them by PackKind) and the rotation of the input rows: device bodies here so
 // ---- that the step's one housekeeping launch (fgc_conv_pack with an fgc_pack_extra) can run them beside the conv packs
 
 // W1 [cin, hidden] -> Wp1[k/4][hidden][k%4], k padded to kpad with zeros
@@ -180,7 +180,7 @@ __device__ __forceinline__ void mlp_pack_w1dx_bf16_body(const float* __restrict_
     }
 }
 
-// ---- the fp32 network's MLP BACKWARD on split operands (fgc_mlp_bf16.hip: mlp_bwd_dx_split_kernel / mlp_bwd_w_split_kernel) ----
+// ---- the fp32 network's MLP BACKWARD on split operands (fgc_mlp_split.hip: mlp_bwd_dx_split_kernel / mlp_bwd_w_split_kernel) ----
 // three-term split of one fp32 value, v = p[0] + p[1] + p[2] (each a bf16, round to nearest even)
 __device__ __forceinline__ void split3_scalar(float v, unsigned short (&p)[3]) {
     p[0] = f_to_bf(v);
@@ -396,11 +396,6 @@ struct PackBatch {
 int launch_pack_jobs(const PackJob* jobs, const size_t* totals, int n, const char* what, hipStream_t st);
 // the packed forward operand of a conv layer as a job: returns the number of jobs written (0: the layer packs nothing, or 1)
 int conv_fwd_pack_jobs(const fgc_conv_desc* d, void* fwd_ws, PackJob* jobs, size_t* totals);
-
-// host side: the jobs that leave an MLP's operands in the workspaces of fgc_mlp_fwd / fgc_mlp_bwd (fgc_mlp.hip) or of their
-// bf16 forms (fgc_mlp_bf16.hip) exactly as those entry points lay them out themselves; `totals[i]` = elements of job i (a
-// workgroup takes 1024).  Return the number of jobs written (<= 4), or -1 for a shape the entry points refuse.
-int mlp_pack_jobs_f32(const fgc_pack_extra* e, PackJob* jobs, size_t* totals);
-int mlp_pack_jobs_bf16(const fgc_pack_extra* e, PackJob* jobs, size_t* totals);
+// (the MLP head's operands as jobs: mlp_pack_jobs, fgc_mlp.h)
 
 }  // namespace fgc

@@ -1,5 +1,5 @@
 // Device helpers of the fp32-on-the-bf16-matrix-pipe products (three-term operand splits): shared by the per-facet MLP
-// (fgc_mlp_bf16.hip, where the scheme is described) and the dz GEMM of the d-logits kernel (fgc_conv_bwd.hip).
+// (fgc_mlp_split.hip, where the scheme is described) and the dz GEMM of the d-logits kernel (fgc_conv_bwd.hip).
 #pragma once
 #include "fgc_common.h"
 

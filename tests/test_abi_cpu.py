@@ -199,3 +199,62 @@ def test_packed_operands_carry_the_identity_of_their_layout():
         assert L.fgc_mlp_layout_id(32, 1024, 3, 1) == L.fgc_mlp_layout_id(32, 1024, 3, 1)
     assert len({m, m1, m2}) == 3
     assert _lib.mlp_layout(m) == m << 8
+
+
+# fgc_mlp_bwd_workspace_bytes(n, cin, hidden, .) for n = 1, 31, 32, 33, 4065, 100000, recorded from the library before the MLP
+# head's host side was rebuilt around one plan (the sizes and layout ids are part of the contract with callers that allocate
+# once and pack ahead): with the options at their defaults; where NO_MLP_SPLIT or NO_MLP_BWD_SPLIT changes a size, the second row
+_MLP_NS = (1, 31, 32, 33, 4065, 100000)
+_MLP_BWD_BYTES = {
+    (6, 256): (61184, 61696, 61696, 73216, 1611776, 3913984),
+    (6, 1024): (193280, 196096, 196096, 241408, 6395648, 15605248),
+    (16, 256): (71424, 73216, 73216, 94976, 3105536, 9245184),
+    (16, 1024): (234240, 241920, 242176, 328448, 12370688, 36930048),
+    (32, 256): (283136, 283136, 283136, 283136, 5495552, 17775104),
+    (32, 1024): (1081856, 1081856, 1081856, 1081856, 21931008, 71049728),
+    (48, 256): (137216, 148736, 148992, 203776, 8698880, 45537792),
+    (48, 1024): (497664, 543744, 545280, 763904, 34744320, 182100480),
+    (64, 256): (153600, 168960, 169472, 240640, 11348992, 60467712),
+    (64, 1024): (563712, 625152, 627200, 911872, 45345280, 241820160),
+    (128, 256): (286208, 347648, 349696, 487936, 26178048, 222652928),
+    (128, 1024): (1094144, 1339904, 1348096, 1901056, 104661504, 890561024),
+}
+_MLP_BWD_BYTES_NO_SPLIT = {
+    (32, 256): (87808, 91648, 91648, 129792, 5495552, 17775104),
+    (32, 1024): (300032, 315392, 315904, 467968, 21931008, 71049728),
+}
+_MLP_FWD_BYTES = {(6, 256): 16384, (6, 1024): 65536, (16, 256): 24576, (16, 1024): 98304, (32, 256): 49152, (32, 1024): 196608,
+                  (48, 256): 73728, (48, 1024): 294912, (64, 256): 98304, (64, 1024): 393216, (128, 256): 196608, (128, 1024): 786432}
+_MLP_IDS = {"default": {32: 7, 64: 3}, "NO_MLP_SPLIT": {}, "NO_MLP_BWD_SPLIT": {32: 3, 64: 3}}      # every other width: 1
+_MLP_BF16_FWD_BYTES = {(32, 256): 16384, (32, 1024): 65536, (64, 256): 32768, (64, 1024): 131072, (128, 256): 65536,
+                       (128, 1024): 262144}
+_MLP_BF16_BWD_BYTES = {
+    (32, 256): (217600, 217600, 217600, 217600, 4991488, 4991488),
+    (32, 1024): (819712, 819712, 819712, 819712, 19915264, 19915264),
+    (64, 256): (381440, 381440, 381440, 381440, 9284096, 9284096),
+    (64, 1024): (1475072, 1475072, 1475072, 1475072, 37085696, 37085696),
+    (128, 256): (709120, 709120, 709120, 709120, 17869312, 17869312),
+    (128, 1024): (2785792, 2785792, 2785792, 2785792, 71426560, 71426560),
+}
+
+
+@pytest.mark.parametrize("option", ["default", "NO_MLP_SPLIT", "NO_MLP_BWD_SPLIT"])
+def test_mlp_workspace_sizes_and_layout_ids_are_the_recorded_ones(option):
+    """The four fgc_mlp*_workspace_bytes functions and fgc_mlp_layout_id read one plan; they must return what the library
+    returned before, for every width, both hidden sizes, cout 1 and 3 (no size depends on it) and under the two split switches.
+    The backward size keeps room for the fp32-MFMA layout wherever the split form may fall back to it."""
+    L = _lib.lib()
+    with _lib.options(**({} if option == "default" else {option: 1})):
+        for cout in (1, 3):
+            for (cin, hidden), want in _MLP_BWD_BYTES.items():
+                if option != "default":
+                    want = _MLP_BWD_BYTES_NO_SPLIT.get((cin, hidden), want)
+                got = tuple(L.fgc_mlp_bwd_workspace_bytes(n, cin, hidden, cout) for n in _MLP_NS)
+                assert got == want, (option, cin, hidden, cout, got)
+                assert L.fgc_mlp_workspace_bytes(cin, hidden, cout) == _MLP_FWD_BYTES[(cin, hidden)], (option, cin, hidden)
+                assert L.fgc_mlp_layout_id(cin, hidden, cout, 0) == _MLP_IDS[option].get(cin, 1), (option, cin, hidden, cout)
+            for (cin, hidden), want in _MLP_BF16_BWD_BYTES.items():
+                got = tuple(L.fgc_mlp_bwd_bf16_workspace_bytes(n, cin, hidden, cout) for n in _MLP_NS)
+                assert got == want, (option, cin, hidden, cout, got)
+                assert L.fgc_mlp_bf16_workspace_bytes(cin, hidden, cout) == _MLP_BF16_FWD_BYTES[(cin, hidden)]
+                assert L.fgc_mlp_layout_id(cin, hidden, cout, 1) == 9

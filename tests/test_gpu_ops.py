@@ -29,7 +29,7 @@ def test_mlp_forward(n, cin):
 
 def test_mlp_forward_split_operands_are_as_accurate_as_the_fp32_mfma():
     """fgc_mlp_fwd runs its 1024-wide product on the bf16 matrix pipe with three-term operand splits (six bf16 MFMAs
-    per product, fp32 accumulation; fgc_mlp_bf16.hip) and keeps the fp32-MFMA kernel behind FGC_NO_MLP_SPLIT=1.  Both
+    per product, fp32 accumulation; fgc_mlp_split.hip) and keeps the fp32-MFMA kernel behind FGC_NO_MLP_SPLIT=1.  Both
     against a float64 reference on the same inputs: the split form must be as close as the fp32 MFMA is."""
     import subprocess, sys, textwrap
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -58,7 +58,7 @@ def test_mlp_forward_split_operands_are_as_accurate_as_the_fp32_mfma():
 
 def test_mlp_backward_split_operands_are_as_accurate_as_the_fp32_mfma():
     """fgc_mlp_bwd with 32 input channels (the network's head) runs every 1024-wide product on the bf16 matrix pipe with
-    three-term operand splits (mlp_bwd_dx_split_kernel / mlp_bwd_w_split_kernel, fgc_mlp_bf16.hip) and keeps the fused
+    three-term operand splits (mlp_bwd_dx_split_kernel / mlp_bwd_w_split_kernel, fgc_mlp_split.hip) and keeps the fused
     fp32-MFMA kernel behind FGC_NO_MLP_BWD_SPLIT=1.  Both against float64 on the same inputs, 5 000 rows (several tiles per
     walker, a ragged last tile): the split form must be as close as the fp32 MFMA is."""
     import subprocess, sys, textwrap
@@ -139,6 +139,126 @@ def test_mlp_operands_packed_by_the_step_prologue(n, cin):
     assert torch.equal(y, y_ref)
     for a, b in zip([dx] + g, g_ref):
         assert torch.equal(a, b)
+
+
+def _mlp_inputs(n, cin, seed):
+    rs = np.random.RandomState(seed)
+    x, dy = _t(rs.normal(size=(n, cin))).to(DEV), _t(rs.normal(size=(n, 3))).to(DEV)
+    W1, b1 = _t(rs.normal(0, 0.05, (cin, 1024))).to(DEV), _t(rs.normal(0, 0.01, 1024)).to(DEV)
+    W2, b2 = _t(rs.normal(0, 0.05, (1024, 3))).to(DEV), _t(rs.normal(0, 0.01, 3)).to(DEV)
+    return x, dy, W1, b1, W2, b2
+
+
+def _mlp_ws(n, cin):
+    from facet_graph_convolution_amd import _lib
+    L = _lib.lib()
+    return (torch.empty(L.fgc_mlp_workspace_bytes(cin, 1024, 3), dtype=torch.uint8, device=DEV),
+            torch.empty(L.fgc_mlp_bwd_workspace_bytes(n, cin, 1024, 3), dtype=torch.uint8, device=DEV))
+
+
+def _mlp_fwd_rc(x, W1, b1, W2, b2, flags, ws):
+    """fgc_mlp_fwd on a workspace of the caller's: (return code, y)"""
+    from facet_graph_convolution_amd import _lib
+    L, p = _lib.lib(), _lib.ptr
+    n, cin = x.shape
+    y = torch.empty(n, 3, device=DEV)
+    rc = L.fgc_mlp_fwd(p(x), n, cin, 1024, 3, p(W1), p(b1), p(W2), p(b2), 0.1, p(y), None, flags, p(ws), ws.numel(), _lib.stream_ptr())
+    return rc, y
+
+
+def _mlp_bwd_rc(x, dy, W1, b1, W2, flags, ws):
+    """fgc_mlp_bwd on a workspace of the caller's: (return code, [dx, dW1, db1, dW2, db2])"""
+    from facet_graph_convolution_amd import _lib
+    L, p = _lib.lib(), _lib.ptr
+    n, cin = x.shape
+    g = [torch.empty(n, cin, device=DEV), torch.empty_like(W1), torch.empty_like(b1), torch.empty_like(W2), torch.empty(3, device=DEV)]
+    rc = L.fgc_mlp_bwd(p(x), p(dy), n, cin, 1024, 3, p(W1), p(b1), p(W2), 0.1, p(g[0]), p(g[1]), p(g[2]), p(g[3]), p(g[4]), flags,
+                       p(ws), ws.numel(), _lib.stream_ptr())
+    return rc, g
+
+
+@pytest.mark.parametrize("n", [6, 70])
+@pytest.mark.parametrize("option", ["NO_MLP_SPLIT", "NO_MLP_BWD_SPLIT"])
+def test_mlp_packed_equals_self_packed_under_options(option, n):
+    """The head's width (cin = 32) in the layouts the two split switches select - fp32 MFMA both ways, and split forward with
+    fp32-MFMA backward: operands packed by fgc_conv_pack under the option, handed over with FGC_MLP_PACKED and the layout id read
+    under the same option, give bit for bit what the entry points give when they pack themselves.  n = 6: one ragged tile;
+    n = 70: two forward tiles, three backward tiles with a ragged last one."""
+    import ctypes as C
+    from facet_graph_convolution_amd import _lib
+    L, p = _lib.lib(), _lib.ptr
+    x, dy, W1, b1, W2, b2 = _mlp_inputs(n, 32, n)
+    with _lib.options(**{option: 1}):
+        flags = _lib.MLP_PACKED | _lib.mlp_layout(L.fgc_mlp_layout_id(32, 1024, 3, 0))
+        wsf, wsb = _mlp_ws(n, 32)
+        rc, y_ref = _mlp_fwd_rc(x, W1, b1, W2, b2, 0, wsf)
+        _lib.check(rc)
+        rc, g_ref = _mlp_bwd_rc(x, dy, W1, b1, W2, 0, wsb)
+        _lib.check(rc)
+        pf, pb = _mlp_ws(n, 32)
+        ex = _lib.PackExtra(mlp_bf16=0, mlp_W1=p(W1), mlp_W2=p(W2), mlp_n=n, mlp_cin=32, mlp_hidden=1024, mlp_cout=3, mlp_fwd_ws=p(pf),
+                            mlp_bwd_ws=p(pb))
+        _lib.check(L.fgc_conv_pack(None, None, None, None, 0, C.byref(ex), _lib.stream_ptr()))
+        rc, y = _mlp_fwd_rc(x, W1, b1, W2, b2, flags, pf)
+        _lib.check(rc)
+        rc, g = _mlp_bwd_rc(x, dy, W1, b1, W2, flags, pb)
+        _lib.check(rc)
+        torch.cuda.synchronize()
+    assert torch.equal(y, y_ref)
+    for a, b in zip(g, g_ref):
+        assert torch.equal(a, b)
+
+
+@pytest.mark.parametrize("n", [6, 70])
+def test_mlp_bf16_forward_at_128_channels_packed_equals_self_packed(n):
+    """fgc_mlp_fwd_bf16 at the widest multi-scale head (cin = 128, forward only: mlp_bwd_ws = NULL in the extra): packed by
+    fgc_conv_pack against self-packed, bit for bit."""
+    import ctypes as C
+    from facet_graph_convolution_amd import _lib
+    L, p, st = _lib.lib(), _lib.ptr, _lib.stream_ptr()
+    x, _, W1, b1, W2, b2 = _mlp_inputs(n, 128, n + 3)
+    xb = x.to(torch.bfloat16)
+    ys = []
+    for packed in (False, True):
+        ws = torch.empty(L.fgc_mlp_bf16_workspace_bytes(128, 1024, 3), dtype=torch.uint8, device=DEV)
+        flags = 0
+        if packed:
+            ex = _lib.PackExtra(mlp_bf16=1, mlp_W1=p(W1), mlp_W2=p(W2), mlp_n=n, mlp_cin=128, mlp_hidden=1024, mlp_cout=3,
+                                mlp_fwd_ws=p(ws), mlp_bwd_ws=None)
+            _lib.check(L.fgc_conv_pack(None, None, None, None, 0, C.byref(ex), st))
+            flags = _lib.MLP_PACKED | _lib.mlp_layout(L.fgc_mlp_layout_id(128, 1024, 3, 1))
+        y = torch.empty(n, 3, device=DEV)
+        _lib.check(L.fgc_mlp_fwd_bf16(p(xb), n, 128, 1024, 3, p(W1), p(b1), p(W2), p(b2), 0.1, p(y), None, flags, p(ws), ws.numel(), st))
+        ys.append(y)
+    torch.cuda.synchronize()
+    assert torch.isfinite(ys[0]).all() and ys[0].abs().max().item() > 0
+    assert torch.equal(ys[0], ys[1])
+
+
+@pytest.mark.parametrize("n", [6, 70])
+def test_mlp_forward_falls_back_to_the_fp32_kernel_for_misaligned_rows(n):
+    """x four bytes into a buffer, cin = 32: the split kernel reads rows in 16-byte pieces, so fgc_mlp_fwd takes the fp32-MFMA
+    kernel - the one NO_MLP_SPLIT=1 selects - and gives its bits.  With FGC_MLP_PACKED the workspace holds the split planes
+    and the call is refused; so is fgc_mlp_bwd, before any launch."""
+    from facet_graph_convolution_amd import _lib
+    L = _lib.lib()
+    x, dy, W1, b1, W2, b2 = _mlp_inputs(n, 32, n + 7)
+    buf = torch.empty(n * 32 + 1, device=DEV)
+    xm = buf[1:].view(n, 32)
+    xm.copy_(x)
+    assert xm.data_ptr() % 16 == 4
+    wsf, wsb = _mlp_ws(n, 32)
+    rc, y = _mlp_fwd_rc(xm, W1, b1, W2, b2, 0, wsf)
+    _lib.check(rc)
+    with _lib.options(NO_MLP_SPLIT=1):
+        rc, y_ref = _mlp_fwd_rc(x, W1, b1, W2, b2, 0, wsf)
+        _lib.check(rc)
+    torch.cuda.synchronize()
+    assert torch.equal(y, y_ref)
+    rc, _ = _mlp_fwd_rc(xm, W1, b1, W2, b2, _lib.MLP_PACKED, wsf)
+    assert rc == -22 and b"needs 16-byte aligned" in L.fgc_last_error()
+    rc, _ = _mlp_bwd_rc(xm, dy, W1, b1, W2, _lib.MLP_PACKED, wsb)
+    assert rc == -22 and b"needs 16-byte aligned" in L.fgc_last_error()
 
 
 @pytest.mark.parametrize("n,cin", [(1000, 32), (77, 32), (5000, 32), (6, 32), (900, 64), (333, 128), (70, 48)])

@@ -12,7 +12,7 @@ for f in $(ls fgc_*.hip); do
   o=${f%.hip}.o
   if echo " $(echo $srcs) " | grep -q " $f "; then
     # (the Makefile's per-file flags)
-    pf=""; case " fgc_mlp_bf16.hip fgc_mlp.hip fgc_conv_bwd.hip fgc_gemm_tn.hip fgc_conv_pack.hip fgc_conv_narrow.hip " in *" $f "*) pf="-fno-slp-vectorize";; esac
+    pf=""; case " fgc_mlp_bf16.hip fgc_mlp_split.hip fgc_mlp_f32.hip fgc_mlp.hip fgc_conv_bwd.hip fgc_gemm_tn.hip fgc_conv_pack.hip fgc_conv_narrow.hip " in *" $f "*) pf="-fno-slp-vectorize";; esac
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-result $pf $flags -c $f -o ../../gpurun_variants/obj_$tag/$o &
     objs="$objs ../../gpurun_variants/obj_$tag/$o"
   else
