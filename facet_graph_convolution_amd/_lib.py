@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FGC_LIB", os.path.join(_HERE, "csrc", "libfgc.so"))  # FGC_LIB: developer A/B builds
 
-ABI_VERSION = 112  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
+ABI_VERSION = 113  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
 FGC_M = 9
 AG_LD = 24
 DL_LD = 12
@@ -179,6 +179,8 @@ _SIGS = {
     "fgc_mlp_bwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_int32, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgc_mlp_forms": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                C.c_void_p, C.c_void_p, C.c_char_p, C.c_int32]),
     "fgc_pool4_bwd_bf16": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                                      C.c_void_p]),
     "fgc_lrelu_fwd": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_void_p]),
@@ -335,6 +337,16 @@ def conv_forms(desc, io=None):
     n = lib().fgc_conv_forms(C.byref(desc), C.byref(io) if io is not None else None, buf, len(buf))
     if n < 0:
         check(n, "fgc_conv_forms")
+    return dict(kv.split("=", 1) for kv in buf.value.decode().split())
+
+
+def mlp_forms(n, cin, hidden, cout, bf16=False, x=None, dx=None, b1=None, fwd_ws=None, bwd_ws=None):
+    """fgc_mlp_forms as a dict of strings: which kernel form a call of the MLP head takes (keys: include/fgc.h).  The
+    pointers are addresses (int, or None for an aligned one); nothing is read through them."""
+    buf = C.create_string_buffer(1024)
+    n = lib().fgc_mlp_forms(n, cin, hidden, cout, int(bool(bf16)), x, dx, b1, fwd_ws, bwd_ws, buf, len(buf))
+    if n < 0:
+        check(n, "fgc_mlp_forms")
     return dict(kv.split("=", 1) for kv in buf.value.decode().split())
 
 

@@ -71,8 +71,8 @@ struct MlpBwdPlan {
     MlpOperand op[3];
     int nops;
 };
-// aligned: the 16-byte alignment the matrix-pipe forms need holds (fwd: x, workspace; bwd: x, dx, b1, workspace).  The default
-// plans for the shape alone.  Reads the options in force.
+// aligned: the 16-byte alignment the matrix-pipe forms need holds (fwd: x; bwd: x, dx, b1; every form needs it of the
+// workspace, which the entry points check themselves).  The default plans for the shape alone.  Reads the options in force.
 MlpFwdPlan plan_mlp_fwd(const MlpShape& s, bool aligned = true);
 MlpBwdPlan plan_mlp_bwd(const MlpShape& s, bool aligned = true);
 

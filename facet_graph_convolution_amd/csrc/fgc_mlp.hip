@@ -3,6 +3,8 @@
 // and their launch functions: fgc_mlp_f32.hip (fp32 MFMA), fgc_mlp_split.hip (fp32 through split bf16 operands),
 // fgc_mlp_bf16.hip (bf16-stored activations).
 #include <algorithm>
+#include <cstdio>
+#include <cstring>
 
 #include "fgc_mlp.h"
 #include "fgc_mlp_mb.h"
@@ -78,7 +80,7 @@ static MlpBwdPlan bwd_layout(const MlpShape& s, MlpForm form) {
         w2_bytes = 0;
     } else {
         const bool bf = form == MLP_BF16;
-        p.ok = bf ? mlp_bf16_shape_ok(s) && s.cin != 128 && s.cout <= 3 : true;   // (split: bwd_shape_form admits the shape)
+        p.ok = bf ? mlp_bf16_shape_ok(s) && s.cin != 128 && s.cout <= 3 : mlp_f32_shape_ok(s, 256);   // (split: cin and the upper end of cout by bwd_shape_form)
         p.mt = s.cin / 16;
         p.co = 3;
         p.slabs = mb_gx(s.n);
@@ -168,6 +170,16 @@ static int mlp_layout_id(const MlpShape& s) {
     return 1 | (plan_mlp_fwd(s).form == MLP_SPLIT ? 2 : 0) | (plan_mlp_bwd(s).form == MLP_SPLIT ? 4 : 0);
 }
 
+// ---- what a call's pointers add to the plan: asked by the entry points and by fgc_mlp_forms alike ----------------------------------
+// every kernel form reads its packed W1 out of the workspace in 16-byte pieces (and pack_many_kernel writes it so)
+static bool mlp_ws_aligned(const void* ws) { return (uintptr_t)ws % 16 == 0; }
+// the 16-byte alignment the split forms need beyond that (NULL counts as aligned); without it an fp32 call takes the fp32 MFMA,
+// which reads rows and b1 element by element (the split dx kernel reads b1 in 16-byte pieces as well)
+static bool mlp_fwd_call_aligned(const void* x) { return (uintptr_t)x % 16 == 0; }
+static bool mlp_bwd_call_aligned(const void* x, const void* dx, const void* b1) {
+    return (uintptr_t)x % 16 == 0 && (uintptr_t)dx % 16 == 0 && (uintptr_t)b1 % 16 == 0;
+}
+
 // ---- argument checks: one for the fp32 entry points, one for the bf16 ones ---------------------------------------------------------
 // an FGC_MLP_PACKED call whose flags carry the layout the workspace was packed in (FGC_MLP_LAYOUT): refuse if the options moved
 static int mlp_check_common(const char* who, const MlpShape& s, float alpha, int flags) {
@@ -188,7 +200,7 @@ static int mlp_bf16_check(const char* who, const MlpShape& s, const void* x, flo
     FGC_CHECK_ARG(s.cin == 32 || s.cin == 64 || s.cin == 128, "%s: cin=%d (the bf16 MLP takes 32, 64 or 128 input channels)", who, s.cin);
     FGC_CHECK_ARG(s.hidden > 0 && s.hidden % 256 == 0, "%s: hidden=%d must be a multiple of 256", who, s.hidden);
     FGC_CHECK_ARG(s.cout > 0 && s.cout <= 4, "%s: cout=%d outside [1,4]", who, s.cout);
-    FGC_CHECK_ARG((uintptr_t)x % 16 == 0, "%s: x needs 16-byte alignment", who);
+    FGC_CHECK_ARG(mlp_fwd_call_aligned(x), "%s: x needs 16-byte alignment", who);
     return mlp_check_common(who, s, alpha, flags);
 }
 
@@ -271,10 +283,11 @@ extern "C" int fgc_mlp_fwd(const float* x, int32_t n, int32_t cin, int32_t hidde
     const int rc = mlp_f32_check("fgc_mlp_fwd", s, 64, alpha, flags);
     if (rc) return rc;
     FGC_CHECK_ARG(workspace && workspace_bytes >= fgc_mlp_workspace_bytes(cin, hidden, cout), "fgc_mlp_fwd: workspace too small");
-    const MlpFwdPlan p = plan_mlp_fwd(s, (uintptr_t)x % 16 == 0 && (uintptr_t)workspace % 16 == 0);
+    FGC_CHECK_ARG(mlp_ws_aligned(workspace), "fgc_mlp_fwd: workspace needs 16-byte alignment (the packed W1 is read in 16-byte pieces)");
+    const MlpFwdPlan p = plan_mlp_fwd(s, mlp_fwd_call_aligned(x));
     // (the operands fgc_conv_pack leaves are the split planes whenever the SHAPE takes the split path)
     FGC_CHECK_ARG(!(flags & FGC_MLP_PACKED) || p.form == p.shape_form,
-                  "fgc_mlp_fwd: FGC_MLP_PACKED needs 16-byte aligned x and workspace for this shape");
+                  "fgc_mlp_fwd: FGC_MLP_PACKED needs 16-byte aligned x for this shape");
     return mlp_fwd_run("fgc_mlp_fwd", s, p, MlpFwdArgs{x, W1, b1, W2, b2, alpha, y, abs_partial, (char*)workspace}, flags,
                        (hipStream_t)stream);
 }
@@ -289,11 +302,10 @@ extern "C" int fgc_mlp_bwd(const float* x, const float* dy, int32_t n, int32_t c
     if (rc) return rc;
     FGC_CHECK_ARG(workspace && workspace_bytes >= fgc_mlp_bwd_workspace_bytes(n, cin, hidden, cout),
                   "fgc_mlp_bwd: workspace too small (%zu < %zu)", workspace_bytes, fgc_mlp_bwd_workspace_bytes(n, cin, hidden, cout));
-    // (the split dx kernel reads b1 in 16-byte pieces as well)
-    const MlpBwdPlan p = plan_mlp_bwd(s, (uintptr_t)x % 16 == 0 && (uintptr_t)dx % 16 == 0 && (uintptr_t)workspace % 16 == 0 &&
-                                             (uintptr_t)b1 % 16 == 0);
+    FGC_CHECK_ARG(mlp_ws_aligned(workspace), "fgc_mlp_bwd: workspace needs 16-byte alignment (the packed W1 is read in 16-byte pieces)");
+    const MlpBwdPlan p = plan_mlp_bwd(s, mlp_bwd_call_aligned(x, dx, b1));
     FGC_CHECK_ARG(!(flags & FGC_MLP_PACKED) || p.form == p.shape_form,
-                  "fgc_mlp_bwd: FGC_MLP_PACKED needs 16-byte aligned x, dx, b1 and workspace for this shape");
+                  "fgc_mlp_bwd: FGC_MLP_PACKED needs 16-byte aligned x, dx and b1 for this shape");
     return mlp_bwd_run("fgc_mlp_bwd", s, p, MlpBwdArgs{x, dy, W1, b1, W2, alpha, dx, (char*)workspace}, dW1, db1, dW2, db2, flags,
                        (hipStream_t)stream);
 }
@@ -306,7 +318,7 @@ extern "C" int fgc_mlp_fwd_bf16(const void* x, int32_t n, int32_t cin, int32_t h
     if (rc) return rc;
     FGC_CHECK_ARG(W1 && b1 && W2 && b2 && y, "fgc_mlp_fwd_bf16: null pointer");
     const MlpFwdPlan p = plan_mlp_fwd(s);
-    FGC_CHECK_ARG(workspace && workspace_bytes >= p.bytes && (uintptr_t)workspace % 16 == 0,
+    FGC_CHECK_ARG(workspace && workspace_bytes >= p.bytes && mlp_ws_aligned(workspace),
                   "fgc_mlp_fwd_bf16: workspace too small or misaligned");
     return mlp_fwd_run("fgc_mlp_fwd_bf16", s, p, MlpFwdArgs{x, W1, b1, W2, b2, alpha, y, abs_partial, (char*)workspace}, flags,
                        (hipStream_t)stream);
@@ -322,8 +334,50 @@ extern "C" int fgc_mlp_bwd_bf16(const void* x, const float* dy, int32_t n, int32
     FGC_CHECK_ARG(dy && W1 && b1 && W2 && dx && dW1 && db1 && dW2 && db2, "fgc_mlp_bwd_bf16: null pointer");
     const MlpBwdPlan p = plan_mlp_bwd(s);
     FGC_CHECK_ARG(p.ok, "fgc_mlp_bwd_bf16: cin=%d cout=%d (cin 32 or 64, cout <= 3)", cin, cout);
-    FGC_CHECK_ARG(workspace && workspace_bytes >= p.bytes && (uintptr_t)workspace % 16 == 0,
+    FGC_CHECK_ARG(workspace && workspace_bytes >= p.bytes && mlp_ws_aligned(workspace),
                   "fgc_mlp_bwd_bf16: workspace too small or misaligned");
     return mlp_bwd_run("fgc_mlp_bwd_bf16", s, p, MlpBwdArgs{x, dy, W1, b1, W2, alpha, dx, (char*)workspace}, dW1, db1, dW2, db2, flags,
                        (hipStream_t)stream);
+}
+
+extern "C" int fgc_mlp_forms(int32_t n, int32_t cin, int32_t hidden, int32_t cout, int32_t bf16, const void* x, const void* dx,
+                             const void* b1, const void* fwd_ws, const void* bwd_ws, char* buf, int32_t buf_bytes) {
+    FGC_CHECK_ARG(buf && buf_bytes > 0, "fgc_mlp_forms: no buffer");
+    int len = 0;
+    bool full = false;
+    auto put = [&](const char* key, const char* fmt, auto value) {
+        char tmp[96];
+        int k = snprintf(tmp, sizeof tmp, "%s%s=", len ? " " : "", key);
+        k += snprintf(tmp + k, sizeof tmp - k, fmt, value);
+        if (full || len + k + 1 > buf_bytes) { full = true; return; }
+        memcpy(buf + len, tmp, (size_t)k + 1);
+        len += k;
+    };
+    static const char* const names[] = {"f32", "split", "bf16"};
+    buf[0] = 0;
+    const MlpShape s{n, cin, hidden, cout, bf16 != 0};
+    // the plans exactly as the entry points ask for them; `none` where the entry point returns before any launch (the bf16
+    // forms have no kernel for rows that are not 16-byte aligned)
+    const MlpFwdPlan f = plan_mlp_fwd(s, s.bf16 || mlp_fwd_call_aligned(x));
+    const MlpBwdPlan b = plan_mlp_bwd(s, s.bf16 || mlp_bwd_call_aligned(x, dx, b1));
+    const bool rows_ok = n > 0 && (!s.bf16 || mlp_fwd_call_aligned(x));
+    put("fwd", "%s", f.ok && rows_ok && mlp_ws_aligned(fwd_ws) ? names[f.form] : "none");
+    put("fwd_ks", "%d", f.ks);
+    put("fwd_co", "%d", f.co);
+    put("fwd_kpad", "%d", f.kpad);
+    put("fwd_gx", "%d", f.gx);
+    put("bwd", "%s", b.ok && rows_ok && mlp_ws_aligned(bwd_ws) ? names[b.form] : "none");
+    put("bwd_mt", "%d", b.mt);
+    put("bwd_ctw", "%d", b.ctw);
+    put("bwd_co", "%d", b.co);
+    put("bwd_slabs", "%d", b.slabs);
+    put("bwd_dx_slabs", "%d", b.dx_slabs);
+    put("bwd_dx_gx", "%d", b.dx_gx);
+    put("bwd_gx", "%d", b.gx);
+    put("bwd_gy", "%d", b.gy);
+    put("fwd_shape", "%s", names[f.shape_form]);
+    put("bwd_shape", "%s", names[b.shape_form]);
+    put("layout", "%d", mlp_layout_id(s));
+    FGC_CHECK_ARG(!full, "fgc_mlp_forms: buffer of %d bytes too small", buf_bytes);
+    return len;
 }

@@ -58,8 +58,10 @@ extern "C" {
  * indices do not move: the two were last in the table).
  * 111: fgc_conv_forms (which kernel form every launch of a layer takes, as text).
  * 112: fgc_point_sets_prepare (the two point sets of the point-set loss normalised together and rotated, on the device:
- * the vertex networks trained from clean meshes). */
-#define FGC_ABI_VERSION 112
+ * the vertex networks trained from clean meshes).
+ * 113: fgc_mlp_forms (which kernel form a call of the MLP head takes, as text); fgc_mlp_fwd / fgc_mlp_bwd refuse a workspace
+ * that is not 16-byte aligned (every kernel form reads its packed W1 in 16-byte pieces). */
+#define FGC_ABI_VERSION 113
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -488,6 +490,8 @@ int fgc_conv_bwd_reduce(const fgc_conv_desc* const* descs, const fgc_conv_bwd_io
  * three-term operand splits (v = bf16(v) + bf16(v - v0) + bf16(v - v0 - v1); six exact partial products per product,
  * fp32 accumulation): as close to a float64 reference as the fp32 MFMA kernel it replaces (1.7e-7 vs 2.0e-7 on outputs
  * of size 1).  FGC_NO_MLP_SPLIT=1 in the environment keeps the fp32 MFMA.  alpha must be in [0, 1].
+ * hidden: a multiple of 64 (forward) / 256 (backward); cout 1 ... 4; cin 1 ... 128.  The workspace must be 16-byte aligned;
+ * x, dx and b1 need not be (a call whose rows, dx or b1 are not takes the fp32 MFMA: fgc_mlp_forms tells).
  * flags: FGC_MLP_PACKED = the workspace already holds this call's weight operands (fgc_conv_pack with an
  * fgc_pack_extra naming it, same W1 / W2 / shape, nothing written to it since): the call skips its own pack launch.
  * ---------------------------------------------------------------------------------- */
@@ -521,6 +525,22 @@ int fgc_mlp_fwd_bf16(const void* x, int32_t n, int32_t cin, int32_t hidden, int3
 int fgc_mlp_bwd_bf16(const void* x, const float* dy, int32_t n, int32_t cin, int32_t hidden, int32_t cout,
                      const float* W1, const float* b1, const float* W2, float alpha, void* dx, float* dW1, float* db1,
                      float* dW2, float* db2, int32_t flags, void* workspace, size_t workspace_bytes, void* stream);
+
+/* Which kernel form the MLP entry points (bf16 != 0: the _bf16 ones) take for a shape under the options in force and with
+ * the pointers of a call, as ONE line of space-separated key=value pairs: the plan the launches follow, printed.  Launches
+ * nothing and follows no pointer: x, dx, b1, fwd_ws, bwd_ws are looked at for their alignment only, NULL stands for an aligned
+ * pointer.  Returns the length written (without the NUL), FGC_EINVAL if buf is NULL or too small (512 bytes are enough).
+ *   fwd        f32 (fp32 MFMA) | split (three-term bf16 operand splits) | bf16 | none (fgc_mlp_fwd[_bf16] refuses the call)
+ *   fwd_ks fwd_co fwd_kpad fwd_gx   template selector (f32: k groups known at compile time, 0 = any; else cin / 32); output
+ *              columns carried in registers; f32: input channels padded to the k group; workgroups
+ *   bwd        f32 | split | bf16 | none
+ *   bwd_mt bwd_ctw bwd_co   template selectors: input-channel tiles of 16; f32: column tiles per wave; output columns
+ *   bwd_slabs bwd_dx_slabs bwd_dx_gx bwd_gx bwd_gy   parameter-gradient slabs (= row walkers); f32: dx slabs; workgroups of
+ *              the dx kernel (0: one fused kernel); grid of the parameter-gradient kernel
+ *   fwd_shape bwd_shape   the form the shape alone selects: what fgc_conv_pack leaves in the workspace
+ *   layout     fgc_mlp_layout_id */
+int fgc_mlp_forms(int32_t n, int32_t cin, int32_t hidden, int32_t cout, int32_t bf16, const void* x, const void* dx,
+                  const void* b1, const void* fwd_ws, const void* bwd_ws, char* buf, int32_t buf_bytes);
 
 /* ------------------------------------------------------------------------------------
  * Element-wise / reduction ops

@@ -46,30 +46,32 @@ def _graph(case, dev):
 
 
 class _Slices:
-    """Device tensors at a byte offset from 16-byte alignment: slices of larger tensors filled with a sentinel."""
+    """Device tensors at a byte offset from 16-byte alignment: slices of larger tensors filled with a sentinel (`fill`; NaN makes
+    a value read from the surroundings show in whatever it is multiplied into, zero included).  padded: surroundings even at
+    offset 0.  (Shared with tests/test_gpu_mlp_forms.py.)"""
 
-    def __init__(self, dev):
-        self.dev, self.made = dev, []
+    def __init__(self, dev, fill=SENTINEL):
+        self.dev, self.made, self.fill = dev, [], fill
 
-    def empty(self, shape, off_bytes=0):
-        if not off_bytes:
+    def empty(self, shape, off_bytes=0, padded=False):
+        if not off_bytes and not padded:
             return torch.empty(*shape, dtype=torch.float32, device=self.dev)
         numel = int(np.prod(shape))
         base = torch.empty(numel + 2 * PAD, dtype=torch.float32, device=self.dev)
-        base.fill_(SENTINEL)
+        base.fill_(self.fill)
         start = PAD + off_bytes // 4
         view = base[start:start + numel].view(*shape)
         assert view.data_ptr() % 16 == off_bytes % 16
         self.made.append((base, start, numel))
         return view
 
-    def copy(self, t, off_bytes=0):
-        return self.empty(tuple(t.shape), off_bytes).copy_(t)
+    def copy(self, t, off_bytes=0, padded=False):
+        return self.empty(tuple(t.shape), off_bytes, padded).copy_(t)
 
     def check(self):
+        untouched = (lambda t: bool(torch.isnan(t).all())) if self.fill != self.fill else (lambda t: bool((t == self.fill).all()))
         for base, start, numel in self.made:
-            assert bool((base[:start] == SENTINEL).all()) and bool((base[start + numel:] == SENTINEL).all()), \
-                "the surroundings of an offset tensor were written"
+            assert untouched(base[:start]) and untouched(base[start + numel:]), "the surroundings of an offset tensor were written"
 
 
 def _fp32_conv_fwd_bwd(case, dev):

@@ -219,7 +219,13 @@ OP_TESTS = [
     "x0p4_64_128", "x0p8_64_128", "dyp4_64_128", "rp4_64_128", "rp4_hub_64_64",
     "acc0_32_32", "acc01_concat_64+64_64", "acc1_concat_32+32_32", "acc0_up_64_32", "acc0_hub_64_64", "acc01_concat_48+16_32",
     "pool_32_32", "pool_128_64", "pool_64_128", "pool_32_96", "pool_concat_48+16_32", "pool_6_32_nodx", "K1_NT16=0_pool_64_128",
-    "NO_FUSED_DS_pool_32_32")]
+    "NO_FUSED_DS_pool_32_32")] + [("test_gpu_mlp_forms", "test_mlp_form_against_float64", dict(name=name)) for name in (
+    # one per form at hidden = 256, cout = 4 and cout = 1, the 33-row split and bf16 backward (idle walkers), a 4097-row case per
+    # backward form (a walker's second tile), the misaligned cases
+    "f32_1_256_3_n33", "f32_48_256_4_n33", "f32_5_256_1_n33", "split_32_256_3_n33", "split_32_256_1_n33", "split_32_256_4_n33",
+    "bf16_32_256_3_n33", "bf16_64_256_2_n33", "bf16_128_512_4_n65_bwd_refused", "f32_48_256_4_n4097_a1", "f32_128_1024_3_n4097_a1",
+    "split_32_256_3_n4097_a1", "bf16_32_256_3_n4097_a1", "xp4_32_256_3_n33", "xp8_32_256_3_n33", "dxp4_32_256_3_n33",
+    "b1p4_32_256_3_n33", "wsp4_32_256_3_n33_refused")]
 
 
 @pytest.mark.parametrize("module,name,kw", OP_TESTS, ids=["%s-%s" % (n, "-".join(str(v) for v in k.values()) if isinstance(k, dict) else "all")

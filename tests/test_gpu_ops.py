@@ -309,42 +309,10 @@ def test_mlp_backward_at_a_coarse_head_size_is_exact_up_to_the_sign_of_zero_prea
            "db2": dyd.sum(0)}
     got = dict(zip(["dx", "dW1", "db1", "dW2", "db2"],
                    [t.cpu().double() for t in ops.mlp_bwd(x.to(DEV), dy.to(DEV), W1.to(DEV), b1.to(DEV), W2.to(DEV), 0.1)]))
-    amb = (h.abs() < 1e-6).nonzero().tolist()
-    assert len(amb) < 400, "ambiguous units must be few"
-    import itertools
-
-    def moves(i, k):
-        """what dh[i, k] changes by if the unit takes one of the two slopes the reference did not: the other side of the kink,
-        or 0 - the gradient of relu(x) - alpha relu(-x) at a pre-activation that is EXACTLY zero in fp32 (model.py:828-830)"""
-        s0 = slope[i, k].item()
-        return [0.0] + [g[i, k].item() * (s1 - s0) for s1 in (1.0, 0.1, 0.0) if s1 != s0]
-
-    by_col = {}
-    for i, k in amb:
-        by_col.setdefault(k, []).append(i)
-    moved = 0
-    for k, rows in by_col.items():
-        assert len(rows) <= 6
-        res = got["db1"][k].item() - ref["db1"][k].item()
-        # the choice per ambiguous unit of the column that explains the residual of db1[k] best (usually one unit, in or out)
-        best = min(itertools.product(*[moves(i, k) for i in rows]), key=lambda c: abs(res - sum(c)))
-        for i, delta in zip(rows, best):
-            if delta != 0.0:
-                moved += 1
-                ref["db1"][k] += delta
-                ref["dW1"][:, k] += delta * xd[i]
-    # dx comes from a kernel of its own where the backward is two launches (32 input channels: mlp_bwd_dx_split_kernel and
-    # mlp_bwd_w_split_kernel each recompute the hidden layer, in different summation orders): its decision per unit is read
-    # off the unit's row of dx - the component of the row's residual along W1[:, k]
-    moved_dx = 0
-    for i, k in amb:
-        w = W1d[:, k]
-        c = ((got["dx"][i] - ref["dx"][i]) @ w).item() / (w @ w).item()
-        delta = min(moves(i, k), key=lambda d: abs(c - d))
-        if delta != 0.0:
-            moved_dx += 1
-            ref["dx"][i] += delta * w
-    moved = (moved, moved_dx)
+    # (the resolution itself: tests/mlp_kink.py, shared with tests/test_gpu_mlp_forms.py; fewer than 400 units, at most 6 per column)
+    import mlp_kink
+    amb = mlp_kink.ambiguous_units(h)
+    moved = mlp_kink.resolve(ref, got, amb, g, slope, xd, W1d, alpha=0.1, max_units=399, max_per_col=6)
     print("n = %d, cin = %d: %d pre-activations within 1e-6 of zero, the kernel took the other slope at %d (dW1 / db1) and %d (dx) of them" % ((n, cin, len(amb)) + moved))
     for name in ("dx", "dW1", "db1", "dW2", "db2"):
         err = (got[name] - ref[name]).abs().max().item() / max(1.0, ref[name].abs().max().item())
