@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FGC_LIB", os.path.join(_HERE, "csrc", "libfgc.so"))  # FGC_LIB: developer A/B builds
 
-ABI_VERSION = 113  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
+ABI_VERSION = 114  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
 FGC_M = 9
 AG_LD = 24
 DL_LD = 12
@@ -97,6 +97,7 @@ CONV_SAVE_Z = 4
 CONV_BF16 = 8
 CONV_R_PAD = 32
 SYNTH_ON = 0x80000000   # FGC_SYNTH_ON: the on flag of the noise control word (include/fgc.h)
+SYNTH_LF_MAX_BUMPS = 1 << 20   # FGC_SYNTH_LF_MAX_BUMPS
 
 
 def mlp_layout(layout_id):
@@ -252,6 +253,9 @@ _SIGS = {
     "fgc_synth_scratch_floats": (C.c_size_t, [C.c_int32]),
     "fgc_synth_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgc_synth_lf_scratch_floats": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "fgc_synth_noise_lf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                     C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "fgc_philox_words": (C.c_int, [C.c_uint32, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "fgc_face_features_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -4,6 +4,10 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <algorithm>
+
+#include "fgc_common.h"
+
 #define FGC_HD __device__ __forceinline__
 
 namespace fgc {
@@ -58,6 +62,50 @@ FGC_HD void synth_displace(uint32_t i, uint32_t step_lo, uint32_t step_hi, uint3
     const float d[3] = {along_normal ? nrm[0] : z0 * inv, along_normal ? nrm[1] : z1 * inv, along_normal ? nrm[2] : z2 * inv};
     const float len = sigma * z3;
     for (int t = 0; t < 3; ++t) out[t] = sigma == 0.0f ? v[t] : v[t] + d[t] * len;
+}
+
+// ---- what the noise launches share (fgc_synth.hip, fgc_synth_lf.hip): launch shape and the workgroup's bounding box ----
+constexpr int SY_THREADS = 256;
+constexpr int SY_MAX_BLOCKS = 1024;      // vertex blocks of a launch = bounding-box partials the feature kernel re-reduces
+
+static inline int synth_blocks(int nv) { return std::min(cdiv(nv, SY_THREADS), SY_MAX_BLOCKS); }
+
+// min over mn[0..2] / max over mx[0..2] of the workgroup's threads; the result in every thread.  min / max are exact:
+// the order of the reduction is free.
+__device__ __forceinline__ void block_minmax(float mn[3], float mx[3], float (*red)[6]) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            mn[t] = fminf(mn[t], __shfl_xor(mn[t], off, 64));
+            mx[t] = fmaxf(mx[t], __shfl_xor(mx[t], off, 64));
+        }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            red[wave][t] = mn[t];
+            red[wave][3 + t] = mx[t];
+        }
+    __syncthreads();
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        mn[t] = red[0][t];
+        mx[t] = red[0][3 + t];
+#pragma unroll
+        for (int w = 1; w < SY_THREADS / 64; ++w) {
+            mn[t] = fminf(mn[t], red[w][t]);
+            mx[t] = fmaxf(mx[t], red[w][3 + t]);
+        }
+    }
+}
+
+__device__ __forceinline__ void store_box(float* __restrict__ dst, const float mn[3], const float mx[3]) {
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {      // (constant indices: the arrays stay in registers)
+        dst[t] = mn[t];
+        dst[3 + t] = mx[t];
+    }
 }
 
 }  // namespace fgc

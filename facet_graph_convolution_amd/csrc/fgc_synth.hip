@@ -16,49 +16,6 @@
 
 namespace fgc {
 
-constexpr int SY_THREADS = 256;
-constexpr int SY_MAX_BLOCKS = 1024;      // vertex blocks of a launch = bounding-box partials the feature kernel re-reduces
-
-static inline int synth_blocks(int nv) { return std::min(cdiv(nv, SY_THREADS), SY_MAX_BLOCKS); }
-
-// min over mn[0..2] / max over mx[0..2] of the workgroup's threads; the result in every thread.  min / max are exact:
-// the order of the reduction is free.
-__device__ __forceinline__ void block_minmax(float mn[3], float mx[3], float (*red)[6]) {
-#pragma unroll
-    for (int t = 0; t < 3; ++t)
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[t] = fminf(mn[t], __shfl_xor(mn[t], off, 64));
-            mx[t] = fmaxf(mx[t], __shfl_xor(mx[t], off, 64));
-        }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            red[wave][t] = mn[t];
-            red[wave][3 + t] = mx[t];
-        }
-    __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        mn[t] = red[0][t];
-        mx[t] = red[0][3 + t];
-#pragma unroll
-        for (int w = 1; w < SY_THREADS / 64; ++w) {
-            mn[t] = fminf(mn[t], red[w][t]);
-            mx[t] = fmaxf(mx[t], red[w][3 + t]);
-        }
-    }
-}
-
-__device__ __forceinline__ void store_box(float* __restrict__ dst, const float mn[3], const float mx[3]) {
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {      // (constant indices: the arrays stay in registers)
-        dst[t] = mn[t];
-        dst[3 + t] = mx[t];
-    }
-}
-
 // One thread per vertex (grid-stride above SY_MAX_BLOCKS workgroups): v_out = v + direction * sigma z3, and the
 // workgroup's bounding box of v_out into partials[6 * blockIdx.x ..] = {min xyz, max xyz}.
 // ctl (device): {step low, step high, sigma word}; sigma word 0 = off (nothing is read or written), otherwise bit 31 is

@@ -2,14 +2,16 @@
 downloads that ship their noisy meshes):
 
     python -m facet_graph_convolution_amd.makeNoisy CLEAN_DIR OUT_DIR [--levels 0.1,0.2,0.3] [--seed S]
-        [--direction random|normal] [--overwrite]
+        [--direction random|normal] [--lf-levels 0.3,0.2,0.1] [--lf-width 3] [--lf-bumps K] [--overwrite]
 
 For every `name.obj` of CLEAN_DIR (sorted) and level k = 1, 2, ... the file `name_n<k>.obj` with the input's faces and
 its vertices displaced by Gaussian noise of standard deviation level x mean edge length - the names getGTFilename,
 `infer` and `computeMetrics` expect.  The noise comes from the kernel the training steps use (ops.synth_noise,
 include/fgc.h: fgc_synth_noise) with stream = 1 + file index and step = level index: for the same seed these are the
 meshes trainNet(noise_levels=...) validates on when the same folder was preprocessed as its validation set.
-Existing files are skipped unless --overwrite.
+--lf-levels (one value, or one per level; level 0 in --levels gives bumps alone) adds the low-frequency field of
+ops.synth_noise_lf (include/fgc.h: fgc_synth_noise_lf): file `_n<k>` is the pair (level k, lf level k), what
+trainNet(noise_levels=..., lf_levels=...) validates on.  Existing files are skipped unless --overwrite.
 """
 import argparse
 import os
@@ -19,20 +21,44 @@ import numpy as np
 DEFAULT_LEVELS = (0.1, 0.2, 0.3)
 
 
-def make_noisy(V, faces, level, seed=0, stream=0, step=0, direction="random", device="cuda"):
-    """The vertices V [V,3] of a clean mesh displaced at `level` x its mean edge length: float32 numpy [V,3]."""
+def make_noisy(V, faces, level, seed=0, stream=0, step=0, direction="random", device="cuda", lf_level=None, lf_width=3.0,
+               lf_bumps=None):
+    """The vertices V [V,3] of a clean mesh displaced at `level` x its mean edge length: float32 numpy [V,3].  lf_level
+    (None: white noise only): plus the low-frequency field of RMS lf_level mean edge lengths, bumps of width lf_width mean
+    edge lengths, lf_bumps of them (None: ceil(faces / 6)) - what FacetDenoiser.set_noise(step, level, lf_level) makes on
+    a mesh bound with lf=(lf_width, lf_bumps)."""
     import torch
     from . import ops
     from .utils import getAverageEdgeLength, areaWeightedVertexNormals
     V = np.ascontiguousarray(np.asarray(V, dtype=np.float32))
     if direction not in ("random", "normal"):
         raise ValueError("direction must be 'random' or 'normal'")
-    sigma = np.float32(level) * np.float32(getAverageEdgeLength(V, faces)[0])
+    edge_len = getAverageEdgeLength(V, faces)[0]
+    sigma = np.float32(level) * np.float32(edge_len)
     normals = None
-    if direction == "normal":
+    if direction == "normal" or lf_level is not None:
         normals = torch.as_tensor(areaWeightedVertexNormals(V, faces).astype(np.float32), device=device)
-    out = ops.synth_noise(torch.as_tensor(V, device=device), sigma, step, seed=seed, stream=stream, normals=normals)
+    Vd = torch.as_tensor(V, device=device)
+    if lf_level is None:
+        out = ops.synth_noise(Vd, sigma, step, seed=seed, stream=stream, normals=normals)
+    else:
+        if not (np.isfinite(lf_level) and lf_level >= 0):
+            raise ValueError("lf_level must be finite and >= 0 (got %r)" % (lf_level,))
+        K, width, area = ops.lf_plan(V, faces, edge_len, lf_width, lf_bumps)
+        out = ops.synth_noise_lf(Vd, normals, sigma, step, ops.lf_amplitude(lf_level, edge_len, width, K, area), width, K,
+                                 seed=seed, stream=stream, white_normals=normals if direction == "normal" else None)
     return out.cpu().numpy()
+
+
+def pair_lf_levels(lf_levels, n_levels):
+    """The lf levels that go with n_levels noise levels (level index k pairs with lf level k; a single lf level goes with
+    every noise level) as a tuple of floats >= 0 - the one check of --lf-levels here and of lf_levels in train.py."""
+    lf = tuple(float(l) for l in lf_levels)
+    if len(lf) == 1:
+        lf = lf * n_levels
+    if len(lf) != n_levels or not all(np.isfinite(l) and l >= 0 for l in lf):
+        raise ValueError("lf_levels: one level >= 0, or one per noise level (%d)" % n_levels)
+    return lf
 
 
 def main(argv=None):
@@ -43,6 +69,10 @@ def main(argv=None):
                     help="comma-separated multiples of the mean edge length, at most 9 (default %(default)s)")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--direction", choices=("random", "normal"), default="random")
+    ap.add_argument("--lf-levels", default=None, help="low-frequency noise on top: comma-separated RMS levels in mean "
+                    "edge lengths, one or one per --levels entry (pair k = level k with lf level k)")
+    ap.add_argument("--lf-width", type=float, default=3.0, help="bump width in mean edge lengths (default %(default)s)")
+    ap.add_argument("--lf-bumps", type=int, default=None, help="bumps per mesh (default: faces / 6, rounded up)")
     ap.add_argument("--overwrite", action="store_true")
     args = ap.parse_args(argv)
     try:
@@ -51,6 +81,16 @@ def main(argv=None):
         ap.error("--levels takes comma-separated numbers (got %r)" % args.levels)
     if not levels or len(levels) > 9 or not all(np.isfinite(l) and l >= 0 for l in levels):
         ap.error("--levels: 1 to 9 levels >= 0 (the ground truth of <name>_n<k>.obj is found by dropping 7 characters)")
+    lf_levels = [None] * len(levels)
+    if args.lf_levels is not None:
+        try:
+            lf_levels = pair_lf_levels(args.lf_levels.split(","), len(levels))
+        except ValueError as e:
+            ap.error("--lf-levels: %s (got %r)" % (e, args.lf_levels))
+        if not (np.isfinite(args.lf_width) and args.lf_width > 0):
+            ap.error("--lf-width must be > 0")
+        if args.lf_bumps is not None and args.lf_bumps < 1:
+            ap.error("--lf-bumps must be >= 1")
     if not os.path.isdir(args.clean_dir):
         ap.error("no folder %s" % args.clean_dir)
     from .utils import load_mesh, write_mesh
@@ -63,7 +103,8 @@ def main(argv=None):
             if os.path.isfile(out) and not args.overwrite:
                 print("Skipping %s. File already exists." % os.path.basename(out))
                 continue
-            write_mesh(make_noisy(V, faces, level, args.seed, 1 + i, k, args.direction), faces, out)
+            write_mesh(make_noisy(V, faces, level, args.seed, 1 + i, k, args.direction, lf_level=lf_levels[k],
+                                  lf_width=args.lf_width, lf_bumps=args.lf_bumps), faces, out)
             written.append(out)
     return written
 

@@ -615,22 +615,26 @@ class FacetDenoiser:
     # ------------------------------------------------------------------------------------------
     # training from clean meshes (BUILD EXTENSION): per-step noise synthesis on the GPU
     # ------------------------------------------------------------------------------------------
-    def bind_clean(self, key, x, adjs, gt, verts, faces_rows, edge_len, seed=0, stream=0, direction="random"):
+    def bind_clean(self, key, x, adjs, gt, verts, faces_rows, edge_len, seed=0, stream=0, direction="random", lf=None):
         """Build extension: bind a CLEAN mesh whose input rows every step rebuilds from freshly displaced vertices
         (include/fgc.h: fgc_synth_noise, fgc_face_features_rows).  bind_cached(key, x, adjs, gt=gt) plus a synthesis
         state kept with the mesh: the clean vertices verts [V,3], faces_rows int [N0,3] (the faces in node order, -1 rows
         = fake nodes: TrainingSet.addCleanMesh's clean_faces_rows), the mean edge length edge_len (a noise level is a
         multiple of it), the Philox key `seed` and `stream` id (training 0, validation mesh i 1 + i) and the
         direction - "random", or "normal": along the clean mesh's area-weighted vertex normals.  x: the clean mesh's own
-        rows (what the steps read until set_noise switches the synthesis on); gt: the clean normals.  Unsharded only."""
-        self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction), False,
+        rows (what the steps read until set_noise switches the synthesis on); gt: the clean normals.  Unsharded only.
+        lf = (width_rel, bumps) (None: white noise only): low-frequency noise on top (include/fgc.h: fgc_synth_noise_lf),
+        a field of `bumps` Gaussian bumps (None: ceil(real faces / 6), the count of the reference's addLFGaussianNoise
+        stub) of width width_rel mean edge lengths along the clean vertex normals, switched on per step by
+        set_noise(step, level, lf_level).  Centres are uniform over the vertices, distances Euclidean."""
+        self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf), False,
                          lambda: self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt)))
         return self
 
     def _bind_synth(self, key, synth_args, points, bind):
         """What bind_clean and bind_clean_vertices (points=True) share: the refusals, the mesh cached under `key` (a training
         loop rebinds its meshes every iteration: a lookup, as in bind_cached), otherwise the synthesis state of synth_args =
-        (x, verts, faces_rows, edge_len, seed, stream, direction) on the mesh bind() returns.  Returns (mesh, newly bound)."""
+        (x, verts, faces_rows, edge_len, seed, stream, direction, lf) on the mesh bind() returns.  Returns (mesh, newly bound)."""
         if self.comm is not None or (self._mesh is not None and self.sharded):
             raise NotImplementedError("noise synthesis runs on an unsharded network")
         if points:
@@ -642,6 +646,8 @@ class FacetDenoiser:
             S = M["synth"]
             if (S["seed"], S["stream"], S["direction"]) != (int(synth_args[4]), int(synth_args[5]), synth_args[6]):
                 raise ValueError("mesh %r is bound with another seed / stream / direction" % (key,))
+            if S["lf_key"] != self._lf_key(synth_args[7]):
+                raise ValueError("mesh %r is bound with another lf setting (%r)" % (key, S["lf_key"]))
             self._mesh = M
             return M, False
         S = self._synth_state(*synth_args)
@@ -652,10 +658,22 @@ class FacetDenoiser:
         M["captured"].clear()
         return M, True
 
-    def _synth_state(self, x, verts, faces_rows, edge_len, seed, stream, direction):
+    @staticmethod
+    def _lf_key(lf):
+        """lf = (width_rel, bumps) of bind_clean / bind_clean_vertices as the value two binds are compared by."""
+        if lf is None:
+            return None
+        width_rel, bumps = lf
+        return (float(width_rel), None if bumps is None else int(bumps))
+
+    def _synth_state(self, x, verts, faces_rows, edge_len, seed, stream, direction, lf=None):
         """The checked arguments of bind_clean / bind_clean_vertices as the synthesis state kept with the mesh."""
         if direction not in ("random", "normal"):
             raise ValueError("direction must be 'random' or 'normal'")
+        lf_key = self._lf_key(lf)
+        if lf_key is not None:
+            if not 0 <= int(stream) < 1 << 31:
+                raise ValueError("lf: stream must lie below 2^31 (the top bit marks the bump counters)")
         vx = np.ascontiguousarray(np.asarray(verts, dtype=np.float32).reshape(-1, 3))
         fr = np.ascontiguousarray(np.asarray(faces_rows).reshape(-1, 3).astype(np.int32))
         xa = np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)
@@ -668,12 +686,21 @@ class FacetDenoiser:
             raise ValueError("edge_len must be a positive length")
         dev = self.device
         S = dict(v=torch.as_tensor(vx, device=dev), faces=torch.as_tensor(fr, device=dev), vn=None,
-                 edge_len=float(edge_len), seed=int(seed), stream=int(stream), direction=direction)
-        if direction == "normal":
+                 edge_len=float(edge_len), seed=int(seed), stream=int(stream), direction=direction, lf_key=lf_key, lf=None)
+        real = fr[fr[:, 0] >= 0]
+        if direction == "normal" or lf_key is not None:
             from .utils import areaWeightedVertexNormals
-            S["vn"] = torch.as_tensor(areaWeightedVertexNormals(vx, fr[fr[:, 0] >= 0]).astype(np.float32), device=dev)
+            vn = torch.as_tensor(areaWeightedVertexNormals(vx, real).astype(np.float32), device=dev)
+            if direction == "normal":
+                S["vn"] = vn
         S["v_out"] = S["v"].clone()
-        S["scratch"] = torch.zeros(max(self.L.fgc_synth_scratch_floats(vx.shape[0]), 1), dtype=torch.float32, device=dev)
+        need = self.L.fgc_synth_scratch_floats(vx.shape[0])
+        if lf_key is not None:
+            K, width, area = ops.lf_plan(vx, real, edge_len, *lf_key)
+            # (the bumps always go along the clean vertex normals, whatever the white direction)
+            S["lf"] = dict(vn=vn, K=K, width=width, area=area, ctl=torch.zeros(4, dtype=torch.int32, device=dev))
+            need = self.L.fgc_synth_lf_scratch_floats(vx.shape[0], K)      # (its head: the same bounding boxes)
+        S["scratch"] = torch.zeros(max(need, 1), dtype=torch.float32, device=dev)
         return S
 
     def _require_synth(self):
@@ -683,13 +710,20 @@ class FacetDenoiser:
 
     def _enqueue_synth(self):
         """Two launches: noise (+ per-workgroup bounding boxes), then the input rows (each workgroup reduces the boxes).
-        Both read the step's noise words from device memory and return at once while they are zero."""
+        Both read the step's noise words from device memory and return at once while they are zero.  A mesh bound with
+        lf=: three launches, the bump table and field + displacement of fgc_synth_noise_lf in the place of the first."""
         M, L, st = self._mesh, self.L, self._st()
         B, S = M["B"], M["synth"]
         self._tag("fwd:synth")
         nv, sc = S["v"].shape[0], S["scratch"]
-        _lib.check(L.fgc_synth_noise(_p(S["v"]), _p(S["vn"]), nv, _p(B["noise"]), S["seed"] & 0xFFFFFFFFFFFFFFFF,
-                                     S["stream"] & 0xFFFFFFFF, _p(S["v_out"]), _p(sc), sc.numel(), st), "synth noise")
+        if S["lf"] is not None:
+            lf = S["lf"]
+            _lib.check(L.fgc_synth_noise_lf(_p(S["v"]), _p(lf["vn"]), _p(S["vn"]), nv, _p(B["noise"]), _p(lf["ctl"]), lf["K"],
+                                            S["seed"] & 0xFFFFFFFFFFFFFFFF, S["stream"] & 0xFFFFFFFF, _p(S["v_out"]),
+                                            _p(sc), sc.numel(), st), "synth lf noise")
+        else:
+            _lib.check(L.fgc_synth_noise(_p(S["v"]), _p(S["vn"]), nv, _p(B["noise"]), S["seed"] & 0xFFFFFFFFFFFFFFFF,
+                                         S["stream"] & 0xFFFFFFFF, _p(S["v_out"]), _p(sc), sc.numel(), st), "synth noise")
         _lib.check(L.fgc_face_features_rows(_p(S["v_out"]), nv, _p(S["faces"]), M["ns"][0], _p(B["noise"]), 1, _p(B["x"]),
                                             _p(sc), sc.numel(), st), "synth features")
 
@@ -698,14 +732,14 @@ class FacetDenoiser:
         return self._require_synth()["v_out"]
 
     def bind_clean_vertices(self, key, x, adjs, verts, faces_rows, v_faces, edge_len, gt_normals=None, iters=VERTEX_ITERS,
-                            seed=0, stream=0, direction="random"):
+                            seed=0, stream=0, direction="random", lf=None):
         """Build extension: bind a CLEAN mesh for the point-set and double-loss steps on noise synthesised per step -
         bind_vertices plus bind_clean's synthesis state, kept with the mesh under `key`.  verts [V,3]: the RAW clean
         vertices (TrainingSet.addCleanMeshWithVertices' clean_vertices), which are also the ground-truth vertices;
         faces_rows int [N0,3]: the faces in node order (-1 rows = fake nodes), v_faces [V,K], edge_len, seed, stream,
-        direction as in bind_clean; gt_normals: the clean face normals [N0,3] in node order, for the double loss.
-        Every step then runs three launches in front: fgc_synth_noise, fgc_face_features_rows (the input rows) and
-        fgc_point_sets_prepare, which normalises the displaced and the clean vertices by the diagonal of their union box
+        direction, lf as in bind_clean; gt_normals: the clean face normals [N0,3] in node order, for the double loss.
+        Every step then runs three launches in front (four with lf=: the two of fgc_synth_noise_lf in the place of the
+        first): fgc_synth_noise, fgc_face_features_rows (the input rows) and fgc_point_sets_prepare, which normalises the displaced and the clean vertices by the diagonal of their union box
         and rotates both, straight into the buffers the vertex update and fgc_point_loss read - in the place of the two
         fgc_rotate_rows launches of a mesh bound by bind_vertices.  The last launch has no control word: while the noise
         words are zero (right after binding, or set_noise(step, None)) a step runs on the vertices the last
@@ -717,7 +751,7 @@ class FacetDenoiser:
             vn = normalizePointSets(vx, vx)[0]
             self.bind_vertices(key, x, adjs, vn, faces_rows, v_faces, vn, iters=iters)
             return self._mesh
-        M, fresh = self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction), True, bind)
+        M, fresh = self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf), True, bind)
         if fresh:
             S = M["synth"]
             nv, sc = S["v"].shape[0], S["scratch"]
@@ -1359,15 +1393,30 @@ class FacetDenoiser:
         self._own_step_inputs()
         self._upload(self._mesh["B"]["R"], np.asarray(R, dtype=np.float32).reshape(9))
 
-    def set_noise(self, step, level):
+    def set_noise(self, step, level, lf_level=None):
         """Build extension (bind_clean, bind_clean_vertices): the next steps draw the noise of counter `step` (64-bit) at
         `level` x the bound clean mesh's mean edge length; level 0 rebuilds the clean input, level None switches the
         synthesis off (the steps read x as the last synthesis left it).  Filled the way set_rotation fills R; the kernels
-        read the words from device memory, so a captured step replays with the new values."""
+        read the words from device memory, so a captured step replays with the new values.
+        lf_level (a mesh bound with lf=; None: bumps off, the white noise alone, bit for bit): the target RMS displacement
+        of the low-frequency field in mean edge lengths; the amplitude is ops.lf_amplitude of it, the bound width, bump
+        count and the clean mesh's area.  The bump words live in a buffer of their own, beside the packed step inputs: a
+        packed row carries the white words only, and the last set_noise holds for the bumps."""
         S = self._require_synth()
+        lf = S["lf"]
+        if lf_level is not None:
+            if lf is None:
+                raise ValueError("lf_level needs a mesh bound with lf=(width, bumps)")
+            if level is None:
+                raise ValueError("lf_level needs a level (0 for bumps alone): level None switches the synthesis off")
+            if not (np.isfinite(lf_level) and lf_level >= 0):
+                raise ValueError("lf_level must be finite and >= 0 (got %r)" % (lf_level,))
         self._own_step_inputs()
         words = ops.noise_words(step, None if level is None else np.float32(level) * np.float32(S["edge_len"]))
         self._upload(self._mesh["B"]["noise"], words.view(np.int32))
+        if lf is not None:
+            amp = None if lf_level is None else ops.lf_amplitude(lf_level, S["edge_len"], lf["width"], lf["K"], lf["area"])
+            self._upload(lf["ctl"], ops.lf_words(amp, lf["width"]).view(np.int32))
 
     def set_samples(self, sample_ind):
         """Indices of the rows the loss is evaluated on (train.py:561), any of the N0 padded rows."""
@@ -1787,7 +1836,8 @@ class FacetDenoiser:
 
     def pointset_step(self, sample_ind0, sample_ind1, R, capture=False, noise=None):
         """One iteration of trainAccuracyNet's loop body (train.py:800-840): samples, rotation, forward, backward, Adam.
-        noise = (step, level) (build extension, a mesh bound by bind_clean_vertices): set_noise(step, level) first."""
+        noise = (step, level) or (step, level, lf_level) (build extension, a mesh bound by bind_clean_vertices):
+        set_noise(*noise) first."""
         return self._step("points", (sample_ind0, sample_ind1), R, capture, noise)
 
     # double-loss training (trainDoubleLossNet, train.py:919-1268): the point-set loss + the dense face-normal loss
@@ -1804,7 +1854,7 @@ class FacetDenoiser:
 
     def double_loss_step(self, sample_ind0, sample_ind1, R, capture=False, noise=None):
         """One iteration of trainDoubleLossNet's loop body (train.py:1160-1243): samples, rotation, step, Adam.
-        noise = (step, level) (build extension, bind_clean_vertices): set_noise(step, level) first."""
+        noise = (step, level) or (step, level, lf_level) (build extension, bind_clean_vertices): set_noise(*noise) first."""
         return self._step("double", (sample_ind0, sample_ind1), R, capture, noise)
 
     # The step forms behind the *_step, *_forward_backward and loss-only entries: require(self, loss_only) raises unless the
@@ -1871,7 +1921,8 @@ class FacetDenoiser:
 
     def train_step(self, sample_ind=None, R=None, capture=False, noise=None):
         """One iteration of trainNet's loop body (train.py:558-575,619): returns the loss tensor (device, [2]).
-        noise = (step, level) (build extension, a mesh bound by bind_clean): set_noise(step, level) first."""
+        noise = (step, level) or (step, level, lf_level) (build extension, a mesh bound by bind_clean):
+        set_noise(*noise) first."""
         if sample_ind is None:
             sample_ind = np.random.randint(self._mesh["ns"][0], size=COST_SAMPLES)
         if R is None:

@@ -667,6 +667,80 @@ def synth_noise(verts, sigma, step, seed=0, stream=0, normals=None, out=None, sc
     return out
 
 
+def lf_words(amplitude, width):
+    """The four control words of the low-frequency noise (include/fgc.h: fgc_synth_noise_lf) as uint32 numpy:
+    FGC_SYNTH_ON | float bits of the amplitude, float bits of the width, 0, 0 - both ABSOLUTE, in mesh units.  amplitude
+    None: four zeros, bumps off."""
+    if amplitude is None:
+        return np.zeros(4, dtype=np.uint32)
+    amplitude, width = np.float32(amplitude), np.float32(width)
+    if not np.isfinite(amplitude) or amplitude < 0:
+        raise ValueError("amplitude must be finite and >= 0 (got %r)" % (amplitude,))
+    if not np.isfinite(width) or width <= 0:
+        raise ValueError("width must be finite and > 0 (got %r)" % (width,))
+    bits = np.array([amplitude, width], dtype=np.float32).view(np.uint32)
+    return np.array([(int(bits[0]) & 0x7FFFFFFF) | _lib.SYNTH_ON, int(bits[1]), 0, 0], dtype=np.uint32)
+
+
+def lf_amplitude(lf_level, edge_len, width, bumps, area):
+    """The bump amplitude A for a target RMS displacement of lf_level mean edge lengths: K bumps of absolute width w on a
+    surface of `area` give, as planar shot noise, the variance A^2 (K / area) pi w^2, so
+    A = lf_level * edge_len / sqrt(max(1, K pi w^2 / area)); with less than one bump per pi w^2 the PEAK is held at the
+    level instead."""
+    density = float(bumps) * np.pi * float(width) ** 2 / float(area)
+    return float(lf_level) * float(edge_len) / np.sqrt(max(1.0, density))
+
+
+def lf_plan(verts, faces, edge_len, width_rel=3.0, bumps=None):
+    """What bind_clean(lf=(width_rel, bumps)) and makeNoisy derive from a clean mesh (host arrays; faces: the REAL faces):
+    (K, absolute width, total area) - K = bumps, or ceil(faces / 6), the count of the reference's addLFGaussianNoise
+    stub; width = width_rel mean edge lengths; the area in float64."""
+    if not (np.isfinite(width_rel) and width_rel > 0):
+        raise ValueError("lf: the width must be a positive number of mean edge lengths (got %r)" % (width_rel,))
+    faces = np.asarray(faces).reshape(-1, 3)
+    K = int(bumps) if bumps is not None else -(-faces.shape[0] // 6)
+    if not 1 <= K <= _lib.SYNTH_LF_MAX_BUMPS:
+        raise ValueError("lf: %d bumps (1 ... %d)" % (K, _lib.SYNTH_LF_MAX_BUMPS))
+    p = np.asarray(verts, dtype=np.float64).reshape(-1, 3)
+    area = 0.5 * np.linalg.norm(np.cross(p[faces[:, 1]] - p[faces[:, 0]], p[faces[:, 2]] - p[faces[:, 0]]), axis=1).sum()
+    if not area > 0:
+        raise ValueError("lf: the clean mesh has no area")
+    return K, float(width_rel) * float(edge_len), float(area)
+
+
+def synth_noise_lf(verts, normals, sigma, step, amplitude, width, bumps, seed=0, stream=0, white_normals=None, out=None,
+                   scratch=None, ctl=None, lf_ctl=None):
+    """Build extension (include/fgc.h: fgc_synth_noise_lf): synth_noise(verts, sigma, step, seed, stream, white_normals)
+    plus a smooth field of `bumps` Gaussian bumps of absolute `amplitude` and `width`, centred on random clean vertices,
+    along the unit vertex `normals` [V,3] (required).  ctl / lf_ctl: the control words already on the device (int32 [3] /
+    [4]) instead of (step, sigma) / (amplitude, width); scratch: float32, at least fgc_synth_lf_scratch_floats(V, bumps) -
+    its head receives the bounding-box partials face_features_rows(have_bbox=True) reads."""
+    if normals is None:
+        raise ValueError("the bumps go along the vertex normals: normals is required")
+    _req_cuda(verts, normals, white_normals, out, scratch, ctl, lf_ctl)
+    verts = _f32c(verts.reshape(-1, 3))
+    nv = verts.shape[0]
+    normals = _f32c(normals.reshape(-1, 3))
+    if white_normals is not None:
+        white_normals = _f32c(white_normals.reshape(-1, 3))
+    if normals.shape[0] != nv or (white_normals is not None and white_normals.shape[0] != nv):
+        raise ValueError("one normal per vertex")
+    bumps = int(bumps)      # (the library refuses a count outside 1 ... FGC_SYNTH_LF_MAX_BUMPS and a stream >= 2^31)
+    if ctl is None:
+        ctl = torch.from_numpy(noise_words(step, sigma).view(np.int32)).to(verts.device)
+    if lf_ctl is None:
+        lf_ctl = torch.from_numpy(lf_words(amplitude, width).view(np.int32)).to(verts.device)
+    if out is None:
+        out = torch.empty_like(verts)
+    need = _lib.lib().fgc_synth_lf_scratch_floats(nv, bumps)
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=verts.device)
+    check(_lib.lib().fgc_synth_noise_lf(ptr(verts), ptr(normals), ptr(white_normals), nv, ptr(ctl), ptr(lf_ctl), bumps,
+                                        int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, ptr(out), ptr(scratch),
+                                        scratch.numel(), stream_ptr()), "fgc_synth_noise_lf")
+    return out
+
+
 def point_sets_prepare(v, gt, R=None, gt_box=None, scratch=None, have_bbox=False, out=None):
     """Build extension (include/fgc.h: fgc_point_sets_prepare): the displaced vertices v [V,3] and the ground-truth
     vertices gt [Vgt,3] (raw units) divided by the bounding-box diagonal of their union and rotated by R (3x3 array-like or

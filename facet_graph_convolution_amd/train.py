@@ -12,7 +12,7 @@ Training command (the reference's ``train(withVerts)``, train.py:1894-1921):
 
     python -m facet_graph_convolution_amd.train DUMP_DIR NETWORK_DIR [--num-iterations N] [--net-name NAME]
         [--with-vertices] [--double-loss] [--capture] [--seed S]
-        [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal]
+        [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal] [--lf-noise 0.3,0.2,0.1[:WIDTH[:BUMPS]]]
 
 loads the pickles `preprocess` wrote and runs trainNet, trainAccuracyNet (--with-vertices) or trainDoubleLossNet
 (--with-vertices --double-loss).  --synth-noise (build extension) loads the CLEAN pickles of `preprocess --clean`
@@ -28,6 +28,7 @@ import numpy as np
 import torch
 
 from . import ops, tfckpt
+from .makeNoisy import pair_lf_levels
 from .net import FacetDenoiser, COST_SAMPLES, POINT_SAMPLES, POINT_LOSS_THRESHOLD
 from .settings import SAVEITER, NUM_ITERATIONS
 from .utils import rand_rotation_matrix
@@ -179,12 +180,30 @@ def _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction):
     return levels, clean(trainSet, "training set"), clean(validSet, "validation set") if validSet is not None else []
 
 
+def _lf_inputs(levels, lf_levels, lf_width, lf_bumps):
+    """The checked low-frequency setting of a trainer: None, or (one lf level per noise level, (width, bumps)) - level
+    index k pairs levels[k] with lf_levels[k]; a single lf level goes with every noise level."""
+    if lf_levels is None:
+        return None
+    if levels is None:
+        raise ValueError("lf_levels needs noise_levels (noise_levels=(0,) for bumps alone)")
+    lf = pair_lf_levels(lf_levels, len(levels))
+    if not (np.isfinite(lf_width) and lf_width > 0):
+        raise ValueError("lf_width must be a positive number of mean edge lengths")
+    if lf_bumps is not None and int(lf_bumps) < 1:
+        raise ValueError("lf_bumps must be >= 1")
+    return lf, (float(lf_width), None if lf_bumps is None else int(lf_bumps))
+
+
 def _bind(F, key, m, noise=None):
-    """Bind mesh record m under `key` through F = net.trainer_form(form): plain, or - noise = (seed, stream, direction) -
-    clean for noise synthesis.  (A cached mesh returns at once; the bind methods reshape the [1, ...] arrays.)"""
+    """Bind mesh record m under `key` through F = net.trainer_form(form): plain, or - noise = (seed, stream, direction
+    [, lf = (width, bumps)]) - clean for noise synthesis.  (A cached mesh returns at once; the bind methods reshape the
+    [1, ...] arrays.)"""
     kw = {"gt_normals": m.gt_normals} if F.gt_normals else {}
     if noise is not None:
         kw.update(seed=noise[0], stream=noise[1], direction=noise[2])
+        if len(noise) > 3 and noise[3] is not None:
+            kw.update(lf=noise[3])
     (F.bind if noise is None else F.bind_clean)(key, *m.args, **kw)
 
 
@@ -193,40 +212,45 @@ def _draw_samples(rs, F, m):
     return tuple(rs.randint(n, size=F.samples) for n in m.rows)
 
 
-def _draw_step(rs, F, m, levels, counter):
+def _draw_step(rs, F, m, levels, counter, lf_levels=None):
     """A training step's draws, in their order: the sample sets, three uniforms for the rotation and - in synthesis mode
-    only: the random stream of a plain run is what it was - the level of noise = (counter, level)."""
-    return (_draw_samples(rs, F, m), rand_rotation_matrix(randnums=rs.uniform(size=3)),
-            None if levels is None else (counter, levels[rs.randint(len(levels))]))
+    only: the random stream of a plain run is what it was - the level of noise = (counter, level).  lf_levels (one per
+    level): the same draw picks the pair, noise = (counter, level, lf level) - no draw of its own."""
+    samples, R = _draw_samples(rs, F, m), rand_rotation_matrix(randnums=rs.uniform(size=3))
+    if levels is None:
+        return samples, R, None
+    k = rs.randint(len(levels))
+    return samples, R, (counter, levels[k]) if lf_levels is None else (counter, levels[k], lf_levels[k])
 
 
-def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="random"):
+def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="random", lf=None):
     """The mean {total, points, normals} (entries a form does not have stay 0) of the loss alone over the validation mesh
     records, with rotation R and fresh rows from rs: one pass per mesh, or - levels given - per clean mesh and noise level
     with stream = 1 + mesh index and step = level index: the SAME noisy meshes at every call (and what makeNoisy writes for
-    the same seed), so the validation curve is comparable along a run."""
+    the same seed), so the validation curve is comparable along a run.  lf = (lf levels, (width, bumps)) of _lf_inputs:
+    level k goes with lf level k."""
     F, vsum = net.trainer_form(form), np.zeros(3)
     for vbm, m in enumerate(valid):
-        _bind(F, ("valid", vbm), m, None if levels is None else (seed, 1 + vbm, direction))
+        _bind(F, ("valid", vbm), m, None if levels is None else (seed, 1 + vbm, direction, lf and lf[1]))
         for k, level in enumerate((None,) if levels is None else levels):
             F.set_samples(*_draw_samples(rs, F, m))
             net.set_rotation(R)
             if level is not None:
-                net.set_noise(k, level)
+                net.set_noise(k, level, *((lf[0][k],) if lf else ()))
             vsum[:F.outputs] += F.loss(rotate=True)[:F.outputs].cpu().numpy()
     return vsum / (len(valid) * (1 if levels is None else len(levels)))
 
 
-def synthValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random"):
+def synthValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", lf=None):
     """Build extension: the mean loss over every clean validation mesh (records of _clean_meshes) at every noise level
     (_validation_loss).  R: the rotation; rs: the RandomState the loss rows are drawn from."""
-    return float(_validation_loss(net, "angular", valid, R, rs, noise_levels, seed, direction)[0])
+    return float(_validation_loss(net, "angular", valid, R, rs, noise_levels, seed, direction, lf)[0])
 
 
-def synthVertexValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", double=False):
+def synthVertexValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", double=False, lf=None):
     """Build extension: {total, points, normals} (double) or {points, 0, 0} - the mean loss over every clean validation mesh
     (records of _clean_vertex_meshes) at every noise level (_validation_loss).  R: rotation; rs draws the 500 + 500 rows."""
-    return _validation_loss(net, "double" if double else "points", valid, R, rs, noise_levels, seed, direction)
+    return _validation_loss(net, "double" if double else "points", valid, R, rs, noise_levels, seed, direction, lf)
 
 
 def _resume(net, network_path, net_name):
@@ -243,17 +267,24 @@ def _resume(net, network_path, net_name):
 
 
 def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
-             capture=False, validSet=None, noise_levels=None, noise_direction="random"):
+             capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None, lf_width=3.0,
+             lf_bumps=None):
     """train.py:380-632.  trainSet / validSet: dataClasses.TrainingSet.  Returns (net, lossArray [iters/50, 2]).
 
     noise_levels (build extension; None = the reference's loop, untouched): trainSet / validSet hold CLEAN meshes
     (TrainingSet.addCleanMesh, otherwise ValueError) and every iteration trains on fresh Gaussian vertex noise made on
     the GPU (FacetDenoiser.bind_clean): a level drawn from the list x the mesh's mean edge length, along
     noise_direction ("random" / "normal"), with the global iteration as the noise counter - a resumed run goes on with
-    new noise.  Validation: synthValidationLoss."""
+    new noise.  Validation: synthValidationLoss.
+
+    lf_levels (build extension; needs noise_levels, length 1 or that of noise_levels): low-frequency noise on top
+    (FacetDenoiser.bind_clean(lf=(lf_width, lf_bumps)), set_noise(step, level, lf_level)): level index k pairs
+    noise_levels[k] with lf_levels[k] - RMS displacements in mean edge lengths of bumps lf_width mean edge lengths wide,
+    lf_bumps per mesh (None: faces / 6).  The one draw that picks the level picks the pair."""
     form = "angular"
     levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
-    train_noise = None if levels is None else (seed, 0, noise_direction)
+    lf = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
+    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1])
     net = FacetDenoiser(device, seed=seed)
     F = net.trainer_form(form)
     ckpt = os.path.join(network_path, net_name) if network_path else None
@@ -269,12 +300,12 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
         if b != bound:       # the reference feeds a new patch through feed_dict; here every mesh stays bound in HBM
             _bind(F, b, meshes[b], train_noise)
             bound = b
-        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it)
+        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it, lf and lf[0])
         if valid and it % (evalStepNum * 2) == 0:
             # train.py:588-617: every 100 iterations the loss alone on every validation mesh, with this iteration's
             # rotation and fresh random rows, BEFORE the training step; the previous row of the CSV gets the mean of
             # this and the last value
-            valid_loss = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction)[0]
+            valid_loss = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf)[0]
             log("Iteration %d, validation loss %g" % (it, valid_loss))
             row = min(it // evalStepNum, len(lossArray) - 1)
             lossArray[row, 1] = valid_loss
@@ -301,7 +332,8 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
 
 
 def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
-                     capture=False, validSet=None, noise_levels=None, noise_direction="random"):
+                     capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None,
+                     lf_width=3.0, lf_bumps=None):
     """train.py:636-916: the multi-scale network trained through update_position_MS on the point-set loss fullLoss.
     trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT.  One iteration = a random mesh
     (meshes without ground-truth vertices are skipped), SAMP_NUM = 500 random rows of the vertices and of the
@@ -323,15 +355,16 @@ def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net"
     Gaussian vertex noise made on the GPU (FacetDenoiser.bind_clean_vertices): a level drawn from the list (after the
     rotation) x the mesh's mean edge length, along noise_direction, with the global iteration as the noise counter; the
     ground truth is the clean mesh.  Validation: synthVertexValidationLoss, every 20 iterations and - in this mode
-    only - at iteration 0 as well.
+    only - at iteration 0 as well.  lf_levels / lf_width / lf_bumps: low-frequency noise on top, as in trainNet.
 
     Returns (net, lossArray of the last block, per-iteration training losses [num_iterations])."""
     return _train_with_vertices("points", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
-                                validSet, noise_levels, noise_direction)
+                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps)
 
 
 def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
-                       capture=False, validSet=None, noise_levels=None, noise_direction="random"):
+                       capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None,
+                       lf_width=3.0, lf_bumps=None):
     """train.py:919-1268: the multi-scale network trained on the point-set loss fullLoss PLUS the dense face-normal loss
     faceNormalsLoss of head 0 against the rotated ground-truth face normals (customLoss = pointsLoss + normalsLoss,
     unweighted, train.py:1100-1102).  trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT
@@ -346,18 +379,20 @@ def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="ne
     1, the previous row's validation entry set to the mean of its two neighbours), and the block is appended to
     `<net_name>.csv` at every save.
 
-    noise_levels / noise_direction (build extension): as in trainAccuracyNet; the ground-truth normals are the clean ones.
+    noise_levels / noise_direction / lf_levels / lf_width / lf_bumps (build extension): as in trainAccuracyNet; the
+    ground-truth normals are the clean ones.
 
     Returns (net, lossArray of the last block, per-iteration {total, points, normals} [num_iterations, 3])."""
     return _train_with_vertices("double", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
-                                validSet, noise_levels, noise_direction)
+                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps)
 
 
 def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
-                         noise_levels=None, noise_direction="random"):
+                         noise_levels=None, noise_direction="random", lf_levels=None, lf_width=3.0, lf_bumps=None):
     """The loop of trainAccuracyNet (form "points") and trainDoubleLossNet ("double")."""
     levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
-    train_noise = None if levels is None else (seed, 0, noise_direction)
+    lf = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
+    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1])
     net = FacetDenoiser(device, multi_scale=True, seed=seed)
     F = net.trainer_form(form)
     ckpt = os.path.join(network_path, net_name) if network_path else None
@@ -379,10 +414,10 @@ def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name,
 
     for it in range(num_iterations):
         b = rs.randint(len(meshes))
-        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it)
+        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it, lf and lf[0])
         row = (it % block) // evalStepNum
         if valid and it % validStepNum == 0 and it >= first_valid:
-            vsum = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction)
+            vsum = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf)
             log(_VALID_LOG[F.outputs] % ((it,) + tuple(vsum[:F.outputs])))      # (the double loss with its points / normals split)
             lossArray[row, 1] = vsum[0]
             if row > 0:
@@ -591,6 +626,22 @@ def inferNetOld(inputMesh, net_or_checkpoint, device="cuda", update_vertices=Fal
     return out.cpu().numpy()
 
 
+def parse_lf_noise(text, n_levels):
+    """--lf-noise LEVELS[:WIDTH[:BUMPS]] -> the keywords lf_levels, lf_width, lf_bumps of the trainers; ValueError with
+    the reason otherwise."""
+    parts = text.split(":")
+    if not 1 <= len(parts) <= 3:
+        raise ValueError("at most LEVELS:WIDTH:BUMPS")
+    out = dict(lf_levels=tuple(float(t) for t in parts[0].split(",")), lf_width=3.0, lf_bumps=None)
+    if len(parts) > 1:
+        out["lf_width"] = float(parts[1])
+    if len(parts) > 2:
+        out["lf_bumps"] = int(parts[2])
+    lf, _ = _lf_inputs((0.0,) * n_levels, out["lf_levels"], out["lf_width"], out["lf_bumps"])
+    out["lf_levels"] = lf
+    return out
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description="Train the network on the pickles of `preprocess` (the reference's train()).")
     ap.add_argument("dump_dir", help="folder of trainingSet.pkl / validSet.pkl (or the ...WithVertices.pkl / ...Clean.pkl / "
@@ -611,6 +662,11 @@ def main(argv=None):
                     "(default %(const)s; the value is optional, so write the option BEHIND the two folders or as --synth-noise=LEVELS)")
     ap.add_argument("--noise-direction", choices=("random", "normal"), default="random",
                     help="with --synth-noise: displace along a random direction or along the vertex normal")
+    ap.add_argument("--lf-noise", default=None, metavar="LEVELS[:WIDTH[:BUMPS]]",
+                    help="with --synth-noise: low-frequency noise on top - LEVELS = comma-separated RMS displacements in mean "
+                    "edge lengths, one or one per --synth-noise level (level k pairs with lf level k); WIDTH = bump width "
+                    "in mean edge lengths (default 3); BUMPS per mesh (default faces / 6).  E.g. --synth-noise 0,0.1,0.2 "
+                    "--lf-noise 0.3,0.2,0.1:3")
     args = ap.parse_args(argv)
     if args.double_loss and not args.with_vertices:
         ap.error("--double-loss trains on the vertex data: it needs --with-vertices")
@@ -624,6 +680,14 @@ def main(argv=None):
             ap.error("--synth-noise takes comma-separated numbers, e.g. 0.1,0.2,0.3 (got %r)" % args.synth_noise)
         if not all(np.isfinite(l) and l >= 0 for l in levels):
             ap.error("--synth-noise levels must be >= 0 (got %r)" % args.synth_noise)
+    lf_extra = {}
+    if args.lf_noise is not None:
+        if levels is None:
+            ap.error("--lf-noise needs --synth-noise: pass --synth-noise 0 for bumps alone")
+        try:
+            lf_extra = parse_lf_noise(args.lf_noise, len(levels))
+        except ValueError as e:
+            ap.error("--lf-noise LEVELS[:WIDTH[:BUMPS]], e.g. 0.3,0.2,0.1:3 - %s (got %r)" % (e, args.lf_noise))
     names = (("trainingSetCleanWithVertices.pkl", "validSetCleanWithVertices.pkl") if args.with_vertices and levels is not None
              else ("trainingSetWithVertices.pkl", "validSetWithVertices.pkl") if args.with_vertices
              else ("trainingSetClean.pkl", "validSetClean.pkl") if levels is not None
@@ -643,7 +707,7 @@ def main(argv=None):
             valid_set = pickle.load(fp)
     os.makedirs(args.network_dir, exist_ok=True)
     trainer = (trainDoubleLossNet if args.double_loss else trainAccuracyNet) if args.with_vertices else trainNet
-    extra = dict(noise_levels=levels, noise_direction=args.noise_direction) if levels is not None else {}
+    extra = dict(noise_levels=levels, noise_direction=args.noise_direction, **lf_extra) if levels is not None else {}
     trainer(train_set, args.num_iterations, network_path=args.network_dir, net_name=args.net_name, seed=args.seed,
             capture=args.capture, validSet=valid_set, **extra)
     return trainer.__name__

@@ -60,8 +60,10 @@ extern "C" {
  * 112: fgc_point_sets_prepare (the two point sets of the point-set loss normalised together and rotated, on the device:
  * the vertex networks trained from clean meshes).
  * 113: fgc_mlp_forms (which kernel form a call of the MLP head takes, as text); fgc_mlp_fwd / fgc_mlp_bwd refuse a workspace
- * that is not 16-byte aligned (every kernel form reads its packed W1 in 16-byte pieces). */
-#define FGC_ABI_VERSION 113
+ * that is not 16-byte aligned (every kernel form reads its packed W1 in 16-byte pieces).
+ * 114: fgc_synth_noise_lf (+ fgc_synth_lf_scratch_floats): low-frequency noise, a field of Gaussian bumps on top of the
+ * per-vertex draw of fgc_synth_noise. */
+#define FGC_ABI_VERSION 114
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -844,6 +846,43 @@ int fgc_face_features_rows(const float* v, int32_t nv, const int32_t* faces_rows
 /* The raw generator of fgc_synth_noise, for known-answer tests: out [n,4] uint32 (device, 16-byte aligned),
  * out[i] = Philox4x32-10 of counter (first + i mod 2^32, step & 0xffffffff, step >> 32, stream_id) and key seed.  One launch. */
 int fgc_philox_words(uint32_t first, int32_t n, uint64_t step, uint64_t seed, uint32_t stream_id, uint32_t* out, void* stream);
+
+/* Low-frequency noise (BUILD EXTENSION; the reference's utils.addLFGaussianNoise, utils.py:2310-2319, is an unfinished stub
+ * of the same idea): fgc_synth_noise plus a smooth field, a sum of K = n_bumps Gaussian bumps centred on randomly chosen
+ * CLEAN vertices, evaluated with Euclidean distances on the clean mesh; every vertex moves by the field along its clean
+ * unit vertex normal.
+ *   bump k in [0, K): (x0, x1, x2, x3) = Philox4x32-10(counter = (k, step & 0xffffffff, step >> 32, stream_id | 0x80000000),
+ *                     key = seed);  c_k = (x0 * nv) >> 32 (the centre is clean vertex c_k; x1 is reserved);
+ *                     a_k = A z, z the first Gaussian of the pair (x2, x3) as defined above (z0 of u0 = x2, u1 = x3)
+ *   field             s_i = sum_k a_k exp(-|v_i - v_{c_k}|^2 / (2 w^2))           (fp32, clean vertices)
+ *   output            v_out_i = white_i + vnormals_i s_i
+ *   white_i is what fgc_synth_noise(v, white_normals, ...) writes for the same (ctl, seed, stream_id): with sigma 0 the
+ *   clean vertex.  The top bit of the stream word separates the bump counters from the per-vertex ones, so stream_id must
+ *   be below 2^31.  A >= 0: the amplitude, w > 0: the width, both in mesh units.  Centres are uniform over the VERTICES (not
+ *   over the area), and the distance is Euclidean, not geodesic: a bump reaches through a sheet thinner than w.
+ * lf_ctl (DEVICE, 4 x uint32, read by the kernels like ctl): {FGC_SYNTH_ON | float bits of A, float bits of w, 0, 0};
+ *   lf_ctl[0] = 0: bumps off - v_out and the scratch's bounding boxes get the bits fgc_synth_noise leaves.  ctl[2] = 0
+ *   switches everything off, as for fgc_synth_noise.
+ * vnormals [nv,3] is required (the bumps always go along it); white_normals is fgc_synth_noise's vnormals: NULL = the white
+ *   draw takes a random direction.
+ * Arithmetic: d2 = fma(dz, dz, fma(dy, dy, dx dx)); the exponential is the hardware exp2 of d2 * (-log2 e / (2 w w)) (about
+ *   1 ulp, on an argument rounded twice: the relative error of a term grows with its exponent); the terms are added in bump
+ *   order within a slice of K and the slices in slice order; the slicing depends on (nv, K) alone, and there are no
+ *   floating-point atomics: the same call gives the same bits, eager or replayed from a hipGraph.
+ * scratch (device floats, 16-byte aligned) >= fgc_synth_lf_scratch_floats(nv, n_bumps) (0 for arguments out of range): its
+ *   first fgc_synth_scratch_floats(nv) floats are the bounding boxes of the final v_out, as fgc_synth_noise leaves them for
+ *   fgc_face_features_rows / fgc_point_sets_prepare(have_bbox = 1); behind them, at the next multiple of 4 floats, the
+ *   bump table [n_bumps, 4] = {centre x, y, z, a_k} as the last ON call left it, then the slices' partial sums and one
+ *   arrival counter per vertex block.
+ * Two launches, enqueue-only, nothing allocated: the table (one thread per bump), then field + displacement (one vertex
+ *   per lane, the table wave-uniform through scalar loads; nv x K pairs, no spatial culling).  A NULL among v, vnormals, ctl,
+ *   lf_ctl, v_out, scratch, nv <= 0, v_out == v, n_bumps outside 1 ... FGC_SYNTH_LF_MAX_BUMPS, stream_id >= 2^31, a scratch
+ *   that is misaligned or too small: FGC_EINVAL, nothing launched. */
+#define FGC_SYNTH_LF_MAX_BUMPS (1 << 20)
+size_t fgc_synth_lf_scratch_floats(int32_t nv, int32_t n_bumps);
+int fgc_synth_noise_lf(const float* v, const float* vnormals, const float* white_normals, int32_t nv, const uint32_t* ctl,
+                       const uint32_t* lf_ctl, int32_t n_bumps, uint64_t seed, uint32_t stream_id, float* v_out,
+                       float* scratch, size_t scratch_floats, void* stream);
 
 /* The two point sets of the point-set loss (fgc_point_loss) from displaced vertices: what the host does with
  * normalizePointSets (utils.py:2077-2104) and two fgc_rotate_rows, in ONE launch per step.

@@ -15,7 +15,17 @@ per step of both and the synthesis kernels' own device time from the library's h
 The same for the vertex networks (FacetDenoiser.bind_clean_vertices): per mesh size the DEVICE time of
 fgc_point_sets_prepare (both point sets normalised by their union box and rotated, one launch) beside its bytes / 8 TB/s;
 and, for the largest size, the captured point-set step with the synthesis against the captured plain step (the same
-graph levels and host-made inputs of one noisy draw, bound with bind_vertices), alternating `rounds` times in this one process, with the launches per step of both."""
+graph levels and host-made inputs of one noisy draw, bound with bind_vertices), alternating `rounds` times in this one process, with the launches per step of both.
+
+    python tools/synth_probe.py --lf [--faces 20480 100000] [--steps 20] [--rounds 5] [--out FILE]
+
+The low-frequency noise (fgc_synth_noise_lf): per mesh size and for K = faces / 6 and K = vertices /
+16 bumps the DEVICE time of its two launches (bump table, field + displacement) beside the issue-rate floor of the field
+kernel - nv x K pairs x 8 VALU instructions over 256 CUs x 4 SIMDs, one wave64 instruction per SIMD every 4 cycles at 2.4
+GHz - and beside the same with the exponential counted as four slots (11 per pair: an estimate, not a bound - the measured
+slope between two bump counts is faster than it); and, for the largest size, the captured point-set step
+and the captured trainNet step with the bumps against the same steps with white noise alone, alternating `rounds` times in
+this one process."""
 import argparse
 import json
 import os
@@ -141,16 +151,118 @@ def points(args):
     return res
 
 
+LF_VALU_PER_PAIR = 8        # 3 v_sub, v_mul + 2 v_fma, v_mul, v_exp_f32, v_fma: the --save-temps ISA of lf_field_kernel
+LF_PAIRS_PER_S = 256 * 4 * 64 / (LF_VALU_PER_PAIR * 4) * 2.4e9      # the floor: one issue slot per instruction
+LF_PAIRS_PER_S_QUARTER = LF_PAIRS_PER_S * 8 / 11                    # the estimate with v_exp_f32 at a quarter of the rate
+
+
+def _device_us(L, fn, steps):
+    """{kernel name: device microseconds per launch} of `steps` calls of fn, from the library's hipEvent hooks."""
+    import ctypes as C
+    fn()
+    torch.cuda.synchronize()
+    L.fgc_profile_enable(1)
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    buf = C.create_string_buffer(1 << 16)
+    L.fgc_profile_collect(buf, len(buf))
+    L.fgc_profile_enable(0)
+    out = {}
+    for line in buf.value.decode().splitlines():
+        name, cnt, ms = line.rsplit(" ", 2)
+        out[name.split("/")[-1]] = float(ms) / int(cnt) * 1e3
+    return out
+
+
+def lf(args):
+    """--lf: the two launches of fgc_synth_noise_lf, and the captured steps with and without the bumps."""
+    from facet_graph_convolution_amd import ops, _lib
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    from facet_graph_convolution_amd.dataClasses import TrainingSet
+    from facet_graph_convolution_amd.utils import rand_rotation_matrix, areaWeightedVertexNormals, getAverageEdgeLength
+    L = _lib.lib()
+    dev = "cuda:0"
+    res = []
+    for nf in args.faces:
+        V, F = _clean_mesh(nf)
+        nv, edge = V.shape[0], float(getAverageEdgeLength(V, F)[0])
+        Vd = torch.as_tensor(V, device=dev)
+        nd = torch.as_tensor(areaWeightedVertexNormals(V, F).astype(np.float32), device=dev)
+        out_v = torch.empty_like(Vd)
+        row = dict(faces=int(F.shape[0]), vertices=int(nv), launches={})
+        for what, K in (("faces/6", -(-F.shape[0] // 6)), ("vertices/16", -(-nv // 16))):
+            _, width, area = ops.lf_plan(V, F, edge, 3.0, K)
+            amp = ops.lf_amplitude(0.3, edge, width, K, area)
+            scratch = torch.zeros(L.fgc_synth_lf_scratch_floats(nv, K), dtype=torch.float32, device=dev)
+            ctl = torch.from_numpy(ops.noise_words(3, 0.1 * edge).view(np.int32)).to(dev)
+            lf_ctl = torch.from_numpy(ops.lf_words(amp, width).view(np.int32)).to(dev)
+            call = lambda: ops.synth_noise_lf(Vd, nd, None, None, None, None, K, seed=1, out=out_v, scratch=scratch,  # noqa: E731
+                                              ctl=ctl, lf_ctl=lf_ctl)
+            us = _device_us(L, call, args.steps)
+            pairs = float(nv) * K
+            floor = pairs / LF_PAIRS_PER_S * 1e6
+            field = [t for k, t in us.items() if "lf_field_kernel" in k][0]
+            row["launches"][what] = dict(bumps=int(K), pairs=pairs, kernel_device_us=us, field_floor_us=floor,
+                                         field_over_floor=field / floor,
+                                         field_quarter_rate_exp_us=pairs / LF_PAIRS_PER_S_QUARTER * 1e6,
+                                         enqueued_back_to_back_us=timed(call, args.steps) * 1e3)
+        if nf == max(args.faces):
+            rs = np.random.RandomState(0)
+            Rm = rand_rotation_matrix(randnums=rs.uniform(size=3))
+            # the captured trainNet step
+            ds = TrainingSet()
+            ds.addCleanMesh(V, F, seed=0)
+            n0 = ds.in_list[0].shape[1]
+            net = FacetDenoiser(dev, seed=0)
+            net.bind_clean(0, ds.in_list[0], ds.adj_list[0], ds.gt_list[0], ds.clean_vertices[0], ds.clean_faces_rows[0],
+                           ds.clean_edge_len[0], lf=(3.0, None))
+            net.set_samples(rs.randint(n0, size=4000))
+            net.set_rotation(Rm)
+            step = lambda: net.forward_backward(rotate=True, capture=True)  # noqa: E731
+            times = {"bumps": [], "white": []}
+            for r in range(args.rounds):
+                for k in ("bumps", "white"):
+                    net.set_noise(r + 1, 0.1, 0.3 if k == "bumps" else None)
+                    times[k].append(timed(step, args.steps))
+            row["trainNet_captured_ms"] = times
+            row["trainNet_difference_us"] = (float(np.median(times["bumps"])) - float(np.median(times["white"]))) * 1e3
+            del net, ds
+            torch.cuda.empty_cache()
+            # the captured point-set step
+            dv = TrainingSet()
+            dv.addCleanMeshWithVertices(V, F, seed=0)
+            net = FacetDenoiser(dev, multi_scale=True, seed=0)
+            net.bind_clean_vertices(0, dv.in_list[0], dv.adj_list[0], dv.clean_vertices[0], dv.clean_faces_rows[0],
+                                    dv.v_faces_list[0], dv.clean_edge_len[0], lf=(3.0, None))
+            net.set_point_samples(rs.randint(nv, size=500), rs.randint(nv, size=500))
+            net.set_rotation(Rm)
+            step = lambda: net.pointset_forward_backward(rotate=True, capture=True)  # noqa: E731
+            times = {"bumps": [], "white": []}
+            for r in range(args.rounds):
+                for k in ("bumps", "white"):
+                    net.set_noise(r + 1, 0.1, 0.3 if k == "bumps" else None)
+                    times[k].append(timed(step, args.steps))
+            row["pointset_captured_ms"] = times
+            row["pointset_difference_us"] = (float(np.median(times["bumps"])) - float(np.median(times["white"]))) * 1e3
+            del net, dv
+        print(json.dumps(row), flush=True)
+        res.append(row)
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--faces", type=int, nargs="+", default=[20480, 100000])
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--points", action="store_true", help="the point sets of the vertex networks (fgc_point_sets_prepare)")
+    ap.add_argument("--lf", action="store_true", help="the low-frequency noise (fgc_synth_noise_lf)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
-    if args.points:
-        res = points(args)
+    if args.points or args.lf:
+        res = lf(args) if args.lf else points(args)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as fh:
