@@ -3,6 +3,7 @@
 
     python -m facet_graph_convolution_amd.bilateral NOISY_DIR RESULTS_DIR
            [--iterations 10] [--sigma-s 1.0] [--sigma-r 0.35] [--vertex-iterations 60] [--slices auto|N] [--overwrite]
+           [--guided]
 
 For each `name.obj`: face centres and areas of the noisy mesh (kept fixed), `--iterations` passes of the filter over
 the face normals (fgc_bilateral_filter; centres, areas and cells stay on the device between passes), then
@@ -15,6 +16,13 @@ range term).  --slices N (or X,Y,Z) is the filter's grid; 10 is the reference's.
 axis the largest count (1 .. 64) whose cell edge is still >= 4 sigma_s: everything outside a face's 3 x 3 x 3 window then
 carries a spatial weight below exp(-8) of a face at distance 0, the work per face does not grow with the mesh, and an
 axis of zero extent is one slice that holds every face (the reference's partition puts such a mesh in no cell).
+
+--guided (a build extension, not in the reference) turns every pass into guided normal filtering (Zhang et al. 2015): the
+range term reads a guidance normal G instead of the noisy normal, G_i being the area-weighted mean normal of the most
+consistent patch (a face and the faces that share a vertex with it) among the patches that contain face i
+(include/fgc.h: fgc_guided_normals).  The guidance is recomputed from the current normals before every pass, on the
+device.  It pays at high noise and loses to the plain filter at low noise (README); the other defaults stay as they are,
+and nobody has tuned --sigma-s, --sigma-r or --iterations for this mode either.
 """
 import argparse
 import os
@@ -34,11 +42,16 @@ def auto_slices(Fc, sigma_s):
     return tuple(int(min(BILATERAL_MAX_SLICES, max(1.0, np.floor(e / (4.0 * sigma_s))))) for e in extent)
 
 
-def denoise_mesh(V, faces, iterations=10, sigma_s=1.0, sigma_r=0.35, vertex_iterations=60, slices="auto", timings=None):
+def denoise_mesh(V, faces, iterations=10, sigma_s=1.0, sigma_r=0.35, vertex_iterations=60, slices="auto", timings=None,
+                 guided=False):
     """(V_out float32 [V,3], normals float32 [F,3]): `iterations` bilateral passes over the face normals of the mesh
     (sigma_s in mean edge lengths), then `vertex_iterations` iterations of update_position2.  slices: "auto", an int or
     a 3-tuple (module docstring).  Raises RuntimeError for a mesh with a vertex of more than MAX_EDGES edges.
-    timings (a dict, optional) receives the wall seconds of 'host', 'filter' and 'vertex'."""
+    guided: guided normal filtering (module docstring): the face rings and edge neighbours go to the device once, every
+    pass computes its guidance from the current normals there, nothing is read back between passes.  A ring of more than
+    utils.GUIDED_MAX_RING faces raises the same RuntimeError.
+    timings (a dict, optional) receives the wall seconds of 'host', 'filter' (all passes, guidance included) and 'vertex',
+    and 'guidance', the device time of the guidance launches alone (0 without guided)."""
     import torch
     from . import ops, utils
     from .settings import MAX_EDGES
@@ -70,17 +83,28 @@ def denoise_mesh(V, faces, iterations=10, sigma_s=1.0, sigma_r=0.35, vertex_iter
         return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
     c, a, n = put(utils.bilateral_device_centres(Fc), np.float32), put(Fa, np.float32), put(Fn, np.float32)
     order, ptr = put(order, np.int32), put(ptr, np.int32)
+    if guided:
+        ring, fe = put(utils.face_rings(faces)[0], np.int32), put(utils.face_edge_neighbours(faces, e_map), np.int32)
     torch.cuda.synchronize()
     t1 = time.time()
+    marks = []
     for _ in range(iterations):
-        n = ops.bilateral_filter(c, n, a, sig, sigma_r, order, ptr, grid)
+        if guided:
+            marks.append((torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)))
+            marks[-1][0].record()
+            g = ops.guidance_normals(n, a, ring, fe)
+            marks[-1][1].record()
+            n = ops.bilateral_filter(c, n, a, sig, sigma_r, order, ptr, grid, guide=g)
+        else:
+            n = ops.bilateral_filter(c, n, a, sig, sigma_r, order, ptr, grid)
     torch.cuda.synchronize()
     t2 = time.time()
+    guidance = sum(b.elapsed_time(e) for b, e in marks) / 1000.0
     pts = update_position2(put(V, np.float32).unsqueeze(0), n.unsqueeze(0), put(e_map, np.int32).unsqueeze(0),
                            put(v_e_map, np.int32).unsqueeze(0), iter_num=vertex_iterations, max_edges=MAX_EDGES)
     out = pts[0].cpu().numpy(), n.cpu().numpy()
     if timings is not None:
-        timings.update(host=t1 - t0, filter=t2 - t1, vertex=time.time() - t2, grid=grid)
+        timings.update(host=t1 - t0, filter=t2 - t1, vertex=time.time() - t2, grid=grid, guidance=guidance)
     return out
 
 
@@ -101,9 +125,9 @@ def denoise_file(noisy_dir, filename, results_dir, overwrite=False, log=print, *
             raise
         log("Skipping %s: %s" % (filename, e))
         return None
-    log("%s: %d faces, grid %s, host %.0f ms, filter %.0f ms, vertex update %.0f ms" %
+    log("%s: %d faces, grid %s, host %.0f ms, filter %.0f ms%s, vertex update %.0f ms" %
         (filename, faces.shape[0], "x".join(str(g) for g in tm["grid"]), 1000 * tm["host"], 1000 * tm["filter"],
-         1000 * tm["vertex"]))
+         " (guidance %.1f ms)" % (1000 * tm["guidance"]) if params.get("guided") else "", 1000 * tm["vertex"]))
     write_mesh(points, faces, out_path)
     return out_path
 
@@ -134,6 +158,8 @@ def main(argv=None):
                     help="the filter's grid: auto (cell edge >= 4 sigma_s), N or X,Y,Z (1 .. %d; 10 is the reference's)"
                     % BILATERAL_MAX_SLICES)
     ap.add_argument("--overwrite", action="store_true")
+    ap.add_argument("--guided", action="store_true",
+                    help="guided normal filtering: the range term reads a guidance normal (a build extension; untuned)")
     args = ap.parse_args(argv)
     if not args.sigma_s > 0:
         ap.error("--sigma-s must be > 0")
@@ -152,7 +178,7 @@ def main(argv=None):
             print("processing noisy file: " + f)
             denoise_file(args.noisy_dir, f, args.results_dir, args.overwrite, iterations=args.iterations,
                          sigma_s=args.sigma_s, sigma_r=args.sigma_r, vertex_iterations=args.vertex_iterations,
-                         slices=args.slices)
+                         slices=args.slices, guided=args.guided)
 
 
 if __name__ == "__main__":

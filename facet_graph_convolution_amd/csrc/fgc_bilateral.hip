@@ -19,6 +19,10 @@
 //
 // sigma_r = -1 ("no range term") runs as a zero factor: exp2(|dn|^2 * 0) = 1 exactly.
 //
+// The guided form (fgc_bilateral_filter_guided, a build extension; GUIDED = true in the templates below) takes the range term
+// on a guidance normal g instead of n: a third float4 plane (g, 0) behind the two, three more query registers, the same loop
+// in the same order; the unguided instantiations are the code they were.
+//
 // Device data is never trusted for addressing: ranges are clamped to [0, n], face indices are checked before a store.
 #include "fgc_common.h"
 
@@ -43,9 +47,11 @@ struct BlParams {
 
 __device__ __forceinline__ int bl_clamp(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
+// GUIDED: a third plane behind the two of every candidate, cand[2 (n + BL_CHUNK) + j] = (g, 0), the guidance normal
+template <bool GUIDED>
 __global__ __launch_bounds__(256) void bl_gather_kernel(const float* __restrict__ c, const float* __restrict__ nrm,
-                                                        const float* __restrict__ a, const int* __restrict__ order, int n,
-                                                        f32x4* __restrict__ cand) {
+                                                        const float* __restrict__ a, const float* __restrict__ guide,
+                                                        const int* __restrict__ order, int n, f32x4* __restrict__ cand) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= n + BL_CHUNK) return;
     const int f = j < n ? order[j] : -1;      // the last BL_CHUNK entries are padding: zero candidates
@@ -56,6 +62,11 @@ __global__ __launch_bounds__(256) void bl_gather_kernel(const float* __restrict_
     }
     cand[2 * (size_t)j] = v0;
     cand[2 * (size_t)j + 1] = v1;
+    if constexpr (GUIDED) {
+        f32x4 v2 = {0.f, 0.f, 0.f, 0.f};
+        if ((unsigned)f < (unsigned)n) v2 = f32x4{guide[3 * (size_t)f], guide[3 * (size_t)f + 1], guide[3 * (size_t)f + 2], 0.f};
+        cand[2 * ((size_t)n + BL_CHUNK) + j] = v2;
+    }
 }
 
 // tasks[t] = (cell, chunk) for every 64-query chunk of every occupied cell, in cell order; *ntasks = their number
@@ -89,12 +100,14 @@ __global__ __launch_bounds__(BL_TASK_THREADS) void bl_tasks_kernel(const int* __
     }
 }
 
-template <int S, int R>
-__device__ __forceinline__ void bl_visit(const float (&q)[6], float (&acc)[S * R][3], const BlParams& prm, f32x4 c0,
-                                         f32x4 c1) {
+// GUIDED: the range term is taken on the guidance normals (q[6 .. 8] against g), everything else is the same body
+template <int S, int R, bool GUIDED>
+__device__ __forceinline__ void bl_visit(const float (&q)[GUIDED ? 9 : 6], float (&acc)[S * R][3], const BlParams& prm,
+                                         f32x4 c0, f32x4 c1, f32x4 g) {
     const float dx = q[0] - c0.x, dy = q[1] - c0.y, dz = q[2] - c0.z;
     const float d2 = __builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx));
-    const float ex = q[3] - c1.x, ey = q[4] - c1.y, ez = q[5] - c1.z;
+    const float ex = q[GUIDED ? 6 : 3] - (GUIDED ? g.x : c1.x), ey = q[GUIDED ? 7 : 4] - (GUIDED ? g.y : c1.y),
+                ez = q[GUIDED ? 8 : 5] - (GUIDED ? g.z : c1.z);
     const float e2 = __builtin_fmaf(ez, ez, __builtin_fmaf(ey, ey, ex * ex));
     float ws[S], wr[R];
 #pragma unroll
@@ -112,7 +125,7 @@ __device__ __forceinline__ void bl_visit(const float (&q)[6], float (&acc)[S * R
         }
 }
 
-template <int S, int R>
+template <int S, int R, bool GUIDED>
 __global__ __launch_bounds__(BL_THREADS) void bl_filter_kernel(const f32x4* __restrict__ cand, const int* __restrict__ order,
                                                                const int* __restrict__ cell_ptr,
                                                                const int2* __restrict__ tasks,
@@ -128,10 +141,14 @@ __global__ __launch_bounds__(BL_THREADS) void bl_filter_kernel(const f32x4* __re
     const int qb = bl_clamp(cell_ptr[cell], 0, n), qe = bl_clamp(cell_ptr[cell + 1], qb, n);
     const int qi = qb + task.y * BL_Q + lane;
     const bool live = qi >= qb && qi < qe;
-    float q[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    float q[GUIDED ? 9 : 6] = {};
     if (live) {
         const f32x4 v0 = cand[2 * (size_t)qi], v1 = cand[2 * (size_t)qi + 1];
         q[0] = v0.x, q[1] = v0.y, q[2] = v0.z, q[3] = v1.x, q[4] = v1.y, q[5] = v1.z;
+        if constexpr (GUIDED) {
+            const f32x4 v2 = cand[2 * ((size_t)n + BL_CHUNK) + qi];
+            q[6] = v2.x, q[7] = v2.y, q[8] = v2.z;
+        }
     }
     // two levels: acc takes the candidates one by one and is added to sum (and cleared) every BL_FLUSH chunks, so that no
     // chain of additions is longer than 8 BL_FLUSH + (a wave's candidates) / (8 BL_FLUSH) whatever the window holds
@@ -149,16 +166,24 @@ __global__ __launch_bounds__(BL_THREADS) void bl_filter_kernel(const f32x4* __re
             for (int j = r0 + wave * BL_CHUNK; j < r1; j += BL_WAVES * BL_CHUNK) {
                 // wave-uniform: scalar loads.  Always a whole chunk (the buffer ends in BL_CHUNK zero entries); what lies past
                 // the range is replaced by a zero candidate (area 0: no weight) on the scalar unit
+                // (GUIDED: 12 dwords a candidate, so the chunk comes in two halves - a whole one would not fit the SGPRs)
                 const f32x4* cb = cand + 2 * (size_t)j;
                 const int m = r1 - j;
-                f32x4 c[2 * BL_CHUNK];
+                constexpr int SUB = GUIDED ? BL_CHUNK / 2 : BL_CHUNK;
 #pragma unroll
-                for (int t = 0; t < 2 * BL_CHUNK; ++t) c[t] = cb[t];
+                for (int h = 0; h < BL_CHUNK; h += SUB) {
+                    f32x4 c[2 * SUB], g[SUB];
 #pragma unroll
-                for (int t = 0; t < BL_CHUNK; ++t) {
-                    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                    bl_visit<S, R>(q, acc, prm, t < m ? c[2 * t] : zero, t < m ? c[2 * t + 1] : zero);
-                    if (P >= 6) __builtin_amdgcn_sched_barrier(0);   // many pairs: one candidate's weights live at a time
+                    for (int t = 0; t < 2 * SUB; ++t) c[t] = cb[2 * h + t];
+#pragma unroll
+                    for (int t = 0; t < SUB; ++t) g[t] = GUIDED ? cand[2 * ((size_t)n + BL_CHUNK) + j + h + t] : c[0];
+#pragma unroll
+                    for (int t = 0; t < SUB; ++t) {
+                        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+                        bl_visit<S, R, GUIDED>(q, acc, prm, h + t < m ? c[2 * t] : zero, h + t < m ? c[2 * t + 1] : zero,
+                                               h + t < m ? g[t] : zero);
+                        if (P >= 6) __builtin_amdgcn_sched_barrier(0);   // many pairs: one candidate's weights live at a time
+                    }
                 }
                 if (++since == BL_FLUSH) {
                     since = 0;
@@ -203,24 +228,25 @@ struct BlLayout {
     int max_tasks;
 };
 
-static BlLayout bl_layout(int n, long long cells) {
+// planes: float4 per candidate, 2 for the plain filter, 3 for the guided one (the tables follow the planes)
+static BlLayout bl_layout(int n, long long cells, int planes) {
     BlLayout L;
     L.max_tasks = (int)(n / BL_Q + (cells < n ? cells : (long long)n) + 1);
     L.cand = 0;
-    L.tasks = align_up(((size_t)n + BL_CHUNK) * 2 * sizeof(f32x4), 16);
+    L.tasks = align_up(((size_t)n + BL_CHUNK) * planes * sizeof(f32x4), 16);
     L.ntasks = L.tasks + align_up((size_t)L.max_tasks * sizeof(int2), 16);
     L.total = L.ntasks + 16;
     return L;
 }
 
-template <int S>
+template <int S, bool GUIDED>
 static void bl_launch_r(int R, hipStream_t st, int grid, const f32x4* cand, const int* order, const int* ptr,
                         const int2* tasks, const int* ntasks, int n, int sx, int sy, int sz, const BlParams& prm, float* out,
                         int ld) {
 #define BL_CASE(RR)                                                                                                    \
     case RR:                                                                                                           \
-        FGC_LAUNCH("bl_filter_kernel", st, (bl_filter_kernel<S, RR>), dim3(grid), dim3(BL_THREADS), 0, cand, order, ptr, \
-                   tasks, ntasks, n, sx, sy, sz, prm, out, ld);                                                        \
+        FGC_LAUNCH(GUIDED ? "bl_filter_guided_kernel" : "bl_filter_kernel", st, (bl_filter_kernel<S, RR, GUIDED>),     \
+                   dim3(grid), dim3(BL_THREADS), 0, cand, order, ptr, tasks, ntasks, n, sx, sy, sz, prm, out, ld);     \
         break;
     switch (R) {
         BL_CASE(1)
@@ -230,38 +256,31 @@ static void bl_launch_r(int R, hipStream_t st, int grid, const f32x4* cand, cons
 #undef BL_CASE
 }
 
-}  // namespace fgc
-
-using namespace fgc;
-
-extern "C" size_t fgc_bilateral_workspace_bytes(int32_t n, int32_t sx, int32_t sy, int32_t sz) {
-    if (n <= 0 || sx < 1 || sy < 1 || sz < 1 || sx > FGC_BILATERAL_MAX_SLICES || sy > FGC_BILATERAL_MAX_SLICES ||
-        sz > FGC_BILATERAL_MAX_SLICES)
-        return 0;
-    return bl_layout(n, (long long)sx * sy * sz).total;
-}
-
-extern "C" int fgc_bilateral_filter(const float* centres, const float* normals, const float* areas, int32_t n,
-                                    const int32_t* cell_order, const int32_t* cell_ptr, int32_t sx, int32_t sy, int32_t sz,
-                                    const float* sigma_s, int32_t S, const float* sigma_r, int32_t R, float* out,
-                                    void* workspace, size_t workspace_bytes, void* stream) {
-    FGC_CHECK_ARG(centres && normals && areas && cell_order && cell_ptr && sigma_s && sigma_r && out && workspace,
-                  "fgc_bilateral_filter: null pointer");
-    FGC_CHECK_ARG(n > 0, "fgc_bilateral_filter: n=%d (> 0)", n);
-    FGC_CHECK_ARG(S >= 1 && R >= 1 && (long long)S * R <= 65536, "fgc_bilateral_filter: S=%d R=%d (both >= 1)", S, R);
+// both entry points: guide == NULL is the plain filter (two planes, the launches and the arithmetic it always had)
+template <bool GUIDED>
+static int bl_run(const char* what, const float* centres, const float* normals, const float* areas, const float* guide,
+                  int32_t n, const int32_t* cell_order, const int32_t* cell_ptr, int32_t sx, int32_t sy, int32_t sz,
+                  const float* sigma_s, int32_t S, const float* sigma_r, int32_t R, float* out, void* workspace,
+                  size_t workspace_bytes, void* stream) {
+    FGC_CHECK_ARG(centres && normals && areas && cell_order && cell_ptr && sigma_s && sigma_r && out && workspace &&
+                      (guide || !GUIDED),
+                  "%s: null pointer", what);
+    FGC_CHECK_ARG(n > 0, "%s: n=%d (> 0)", what, n);
+    FGC_CHECK_ARG(S >= 1 && R >= 1 && (long long)S * R <= 65536, "%s: S=%d R=%d (both >= 1)", what, S, R);
     FGC_CHECK_ARG(sx >= 1 && sy >= 1 && sz >= 1 && sx <= FGC_BILATERAL_MAX_SLICES && sy <= FGC_BILATERAL_MAX_SLICES &&
                       sz <= FGC_BILATERAL_MAX_SLICES,
-                  "fgc_bilateral_filter: grid %d x %d x %d (1 .. %d per axis)", sx, sy, sz, FGC_BILATERAL_MAX_SLICES);
+                  "%s: grid %d x %d x %d (1 .. %d per axis)", what, sx, sy, sz, FGC_BILATERAL_MAX_SLICES);
     for (int s = 0; s < S; ++s)
-        FGC_CHECK_ARG(sigma_s[s] > 0.f && sigma_s[s] < __builtin_inff(), "fgc_bilateral_filter: sigma_s[%d]=%g (> 0)", s,
+        FGC_CHECK_ARG(sigma_s[s] > 0.f && sigma_s[s] < __builtin_inff(), "%s: sigma_s[%d]=%g (> 0)", what, s,
                       (double)sigma_s[s]);
     for (int r = 0; r < R; ++r)
         FGC_CHECK_ARG((sigma_r[r] > 0.f && sigma_r[r] < __builtin_inff()) || sigma_r[r] == -1.f,
-                      "fgc_bilateral_filter: sigma_r[%d]=%g (> 0, or -1 for no range term)", r, (double)sigma_r[r]);
-    const BlLayout L = bl_layout(n, (long long)sx * sy * sz);
-    FGC_CHECK_ARG(workspace_bytes >= L.total, "fgc_bilateral_filter: workspace too small (%zu < %zu bytes)", workspace_bytes,
-                  L.total);
-    FGC_CHECK_ARG((uintptr_t)workspace % 16 == 0, "fgc_bilateral_filter: workspace needs 16-byte alignment");
+                      "%s: sigma_r[%d]=%g (> 0, or -1 for no range term)", what, r, (double)sigma_r[r]);
+    const BlLayout L = bl_layout(n, (long long)sx * sy * sz, GUIDED ? 3 : 2);
+    // one size for both forms (fgc_bilateral_workspace_bytes): the plain one leaves the room of the third plane unused
+    const size_t need = bl_layout(n, (long long)sx * sy * sz, 3).total;
+    FGC_CHECK_ARG(workspace_bytes >= need, "%s: workspace too small (%zu < %zu bytes)", what, workspace_bytes, need);
+    FGC_CHECK_ARG((uintptr_t)workspace % 16 == 0, "%s: workspace needs 16-byte alignment", what);
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     f32x4* cand = (f32x4*)(ws + L.cand);
@@ -270,11 +289,11 @@ extern "C" int fgc_bilateral_filter(const float* centres, const float* normals, 
     const int ld = 3 * S * R;
     // rows of faces in no cell stay zero
     if (hipMemsetAsync(out, 0, (size_t)n * ld * sizeof(float), st) != hipSuccess) {
-        fgc::set_error("fgc_bilateral_filter: memset failed");
+        fgc::set_error("%s: memset failed", what);
         return FGC_EHIP;
     }
-    FGC_LAUNCH("bl_gather_kernel", st, bl_gather_kernel, dim3(cdiv(n + BL_CHUNK, 256)), dim3(256), 0, centres, normals, areas,
-               cell_order, n, cand);
+    FGC_LAUNCH("bl_gather_kernel", st, bl_gather_kernel<GUIDED>, dim3(cdiv(n + BL_CHUNK, 256)), dim3(256), 0, centres, normals,
+               areas, guide, cell_order, n, cand);
     FGC_LAUNCH("bl_tasks_kernel", st, bl_tasks_kernel, dim3(1), dim3(BL_TASK_THREADS), 0, cell_ptr, sx * sy * sz, n, tasks,
                L.max_tasks, ntasks);
     const double log2e = 1.4426950408889634;
@@ -291,12 +310,41 @@ extern "C" int fgc_bilateral_filter(const float* centres, const float* normals, 
                                 ? 0.f
                                 : (float)(-log2e / (2.0 * (double)sigma_r[r0 + r] * (double)sigma_r[r0 + r]));
             switch (ts) {
-                case 1: bl_launch_r<1>(tr, st, L.max_tasks, cand, cell_order, cell_ptr, tasks, ntasks, n, sx, sy, sz, prm, out, ld); break;
-                case 2: bl_launch_r<2>(tr, st, L.max_tasks, cand, cell_order, cell_ptr, tasks, ntasks, n, sx, sy, sz, prm, out, ld); break;
-                case 3: bl_launch_r<3>(tr, st, L.max_tasks, cand, cell_order, cell_ptr, tasks, ntasks, n, sx, sy, sz, prm, out, ld); break;
-                default: bl_launch_r<4>(tr, st, L.max_tasks, cand, cell_order, cell_ptr, tasks, ntasks, n, sx, sy, sz, prm, out, ld); break;
+                case 1: bl_launch_r<1, GUIDED>(tr, st, L.max_tasks, cand, cell_order, cell_ptr, tasks, ntasks, n, sx, sy, sz, prm, out, ld); break;
+                case 2: bl_launch_r<2, GUIDED>(tr, st, L.max_tasks, cand, cell_order, cell_ptr, tasks, ntasks, n, sx, sy, sz, prm, out, ld); break;
+                case 3: bl_launch_r<3, GUIDED>(tr, st, L.max_tasks, cand, cell_order, cell_ptr, tasks, ntasks, n, sx, sy, sz, prm, out, ld); break;
+                default: bl_launch_r<4, GUIDED>(tr, st, L.max_tasks, cand, cell_order, cell_ptr, tasks, ntasks, n, sx, sy, sz, prm, out, ld); break;
             }
         }
-    FGC_CHECK_LAUNCH("fgc_bilateral_filter");
+    FGC_CHECK_LAUNCH(what);
     return FGC_OK;
+}
+
+}  // namespace fgc
+
+using namespace fgc;
+
+// room for the guided form's third plane: one size serves both entry points
+extern "C" size_t fgc_bilateral_workspace_bytes(int32_t n, int32_t sx, int32_t sy, int32_t sz) {
+    if (n <= 0 || sx < 1 || sy < 1 || sz < 1 || sx > FGC_BILATERAL_MAX_SLICES || sy > FGC_BILATERAL_MAX_SLICES ||
+        sz > FGC_BILATERAL_MAX_SLICES)
+        return 0;
+    return bl_layout(n, (long long)sx * sy * sz, 3).total;
+}
+
+extern "C" int fgc_bilateral_filter(const float* centres, const float* normals, const float* areas, int32_t n,
+                                    const int32_t* cell_order, const int32_t* cell_ptr, int32_t sx, int32_t sy, int32_t sz,
+                                    const float* sigma_s, int32_t S, const float* sigma_r, int32_t R, float* out,
+                                    void* workspace, size_t workspace_bytes, void* stream) {
+    return bl_run<false>("fgc_bilateral_filter", centres, normals, areas, nullptr, n, cell_order, cell_ptr, sx, sy, sz, sigma_s,
+                         S, sigma_r, R, out, workspace, workspace_bytes, stream);
+}
+
+extern "C" int fgc_bilateral_filter_guided(const float* centres, const float* normals, const float* areas, int32_t n,
+                                           const int32_t* cell_order, const int32_t* cell_ptr, int32_t sx, int32_t sy,
+                                           int32_t sz, const float* sigma_s, int32_t S, const float* sigma_r, int32_t R,
+                                           const float* guide, float* out, void* workspace, size_t workspace_bytes,
+                                           void* stream) {
+    return bl_run<true>("fgc_bilateral_filter_guided", centres, normals, areas, guide, n, cell_order, cell_ptr, sx, sy, sz,
+                        sigma_s, S, sigma_r, R, out, workspace, workspace_bytes, stream);
 }

@@ -6,6 +6,7 @@ so every workload in BASELINE.json is synthetic:
 * ``icosphere(3)``        -> 642 vertices, 1 280 faces  (config C1)
 * ``torus(250, 200)``     -> 50 000 vertices, 100 000 faces (config C2, the bench workload)
 * ``torus(250, 100)``     -> 50 000 faces (C3), ``torus(1000, 500)`` -> 1M (C4), ``torus(500, 500)`` -> 500k (C5)
+* ``cube(n)``             -> 12 n^2 faces with sharp edges and corners (the guided-filter tests)
 
 All vertex valences are 6 (5 at the 12 icosahedron corners), which satisfies the
 hidden limits of the reference adjacency builder (utils.py:249-250).
@@ -57,6 +58,33 @@ def torus(nu, nv, R=1.0, r=0.4):
     v00, v10, v11, v01 = vid(i, j), vid(i + 1, j), vid(i + 1, j + 1), vid(i, j + 1)
     F = np.stack([np.stack([v00, v10, v11], -1), np.stack([v00, v11, v01], -1)], axis=2)
     return V, F.reshape(-1, 3).astype(np.uint32)
+
+
+def cube(n):
+    """Unit cube centred at the origin, every side an n x n grid of quads split in two: 12 n^2 faces, 6 n^2 + 2 vertices
+    (welded along the edges), outward orientation.  Sharp features for the filter tests: the corner vertices have valence 3
+    to 6, the rest 4 to 6."""
+    n = int(n)
+    if n < 1:
+        raise ValueError("cube(n): n >= 1")
+    i, j = (g.reshape(-1) for g in np.meshgrid(np.arange(n), np.arange(n), indexing="ij"))
+    tris = []
+    for a in range(3):
+        b, c = (a + 1) % 3, (a + 2) % 3
+        for side in (0, 1):
+            def corner(di, dj):
+                p = np.zeros((i.size, 3), dtype=np.int64)
+                p[:, a], p[:, b], p[:, c] = side * n, i + di, j + dj
+                return p
+            p00, p10, p11, p01 = corner(0, 0), corner(1, 0), corner(1, 1), corner(0, 1)
+            # (p10 - p00) x (p01 - p00) points along +a: outward on the far side, flipped on the near one
+            quads = ((p00, p10, p11), (p00, p11, p01)) if side else ((p00, p11, p10), (p00, p01, p11))
+            tris += [np.stack(t, axis=1) for t in quads]
+    T = np.concatenate(tris).reshape(-1, 3)
+    key = (T[:, 0] * (n + 1) + T[:, 1]) * (n + 1) + T[:, 2]
+    used, F = np.unique(key, return_inverse=True)
+    V = np.stack([used // ((n + 1) * (n + 1)), (used // (n + 1)) % (n + 1), used % (n + 1)], -1)
+    return (V / float(n) - 0.5).astype(np.float32), F.reshape(-1, 3).astype(np.uint32)
 
 
 def add_noise(V, F, sigma_rel=0.2, seed=1):

@@ -468,12 +468,37 @@ def nn_query(q, p, q_cell=None, p_cell=None):
     return dist, idx
 
 
-def bilateral_filter(centres, normals, areas, sigma_s, sigma_r, cell_order, cell_ptr, grid):
+def guidance_normals(normals, areas, ring, fe, want_pick=False, want_h=False):
+    """Guidance normals of guided normal filtering (include/fgc.h: fgc_guided_normals; a build extension) on GPU tensors:
+    normals [n,3] and areas [n] fp32, ring int32 [n, ld] (utils.face_rings), fe int32 [n,3] (utils.face_edge_neighbours).
+    Returns G [n,3], or (G, pick int32 [n] and / or H [n]) when asked for them."""
+    _req_cuda(normals, areas, ring, fe)
+    normals, areas = _f32c(normals.reshape(-1, 3)), _f32c(areas.reshape(-1))
+    n = normals.shape[0]
+    ring, fe = ring.to(torch.int32).contiguous(), fe.to(torch.int32).contiguous()
+    if areas.numel() != n or ring.dim() != 2 or ring.shape[0] != n or tuple(fe.shape) != (n, 3):
+        raise ValueError("normals [n,3], areas [n], ring [n, ld] and fe [n,3] must have one row per face")
+    ld = ring.shape[1]
+    guide = torch.empty(n, 3, dtype=torch.float32, device=normals.device)
+    pick = torch.empty(n, dtype=torch.int32, device=normals.device) if want_pick else None
+    h = torch.empty(n, dtype=torch.float32, device=normals.device) if want_h else None
+    nbytes = _lib.lib().fgc_guided_workspace_bytes(n, ld)
+    if nbytes == 0:
+        raise ValueError("ring [%d, %d]: at least one face, ld a multiple of 4 in 4 .. 64" % (n, ld))
+    ws = _workspace(nbytes, normals.device, "guided")
+    check(_lib.lib().fgc_guided_normals(ptr(normals), ptr(areas), n, ptr(ring), ld, ptr(fe), ptr(guide), ptr(pick), ptr(h),
+                                        ptr(ws), ws.numel(), stream_ptr()), "fgc_guided_normals")
+    extra = tuple(t for t in (pick, h) if t is not None)
+    return (guide,) + extra if extra else guide
+
+
+def bilateral_filter(centres, normals, areas, sigma_s, sigma_r, cell_order, cell_ptr, grid, guide=None):
     """Bilateral normal filter (include/fgc.h: fgc_bilateral_filter) on fp32 GPU tensors: centres [n,3], normals [n,3],
     areas [n]; sigma_s and sigma_r a number or a sequence each (sigma_r = -1: no range term); cell_order int32 [n] and
     cell_ptr int32 [sx sy sz + 1] the faces ordered by cell and the range table (utils.bilateral_order), grid =
     (sx, sy, sz).  Returns [n, 3 S R]: the filtered unit normal of every (sigma_s, sigma_r) pair, sigma_s-major, all
-    pairs from one pass over the candidates.  A face in no cell gets a zero row."""
+    pairs from one pass over the candidates.  A face in no cell gets a zero row.  guide [n,3] (optional): the range term
+    reads these normals instead of `normals` (fgc_bilateral_filter_guided; None: the plain filter, no other launch)."""
     from .utils import BILATERAL_MAX_SLICES
     _req_cuda(centres, normals, areas, cell_order, cell_ptr)
     centres, normals = _f32c(centres.reshape(-1, 3)), _f32c(normals.reshape(-1, 3))
@@ -493,6 +518,16 @@ def bilateral_filter(centres, normals, areas, sigma_s, sigma_r, cell_order, cell
     out = torch.empty(n, 3 * ss.size * sr.size, dtype=torch.float32, device=centres.device)
     nbytes = _lib.lib().fgc_bilateral_workspace_bytes(n, sx, sy, sz)
     ws = _workspace(nbytes, centres.device, "bilateral")
+    if guide is not None:
+        _req_cuda(guide)
+        guide = _f32c(guide.reshape(-1, 3))
+        if guide.shape[0] != n:
+            raise ValueError("guide must have one row per face")
+        check(_lib.lib().fgc_bilateral_filter_guided(ptr(centres), ptr(normals), ptr(areas), n, ptr(cell_order),
+                                                     ptr(cell_ptr), sx, sy, sz, ss.ctypes.data, ss.size, sr.ctypes.data,
+                                                     sr.size, ptr(guide), ptr(out), ptr(ws), ws.numel(), stream_ptr()),
+              "fgc_bilateral_filter_guided")
+        return out
     check(_lib.lib().fgc_bilateral_filter(ptr(centres), ptr(normals), ptr(areas), n, ptr(cell_order), ptr(cell_ptr), sx, sy,
                                           sz, ss.ctypes.data, ss.size, sr.ctypes.data, sr.size, ptr(out), ptr(ws),
                                           ws.numel(), stream_ptr()), "fgc_bilateral_filter")

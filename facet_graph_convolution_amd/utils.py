@@ -641,3 +641,74 @@ def bilateralFilter(Fc, Fn, Fa, sigma_s, sigma_r, slices=10):
     `slices` may also be a 3-tuple (not in the reference); at most BILATERAL_MAX_SLICES per axis, ValueError above.
     The sum runs on the GPU in float32 (fgc_bilateral_filter), the binning on the host."""
     return FND(Fc, Fn, Fa, [sigma_s], [sigma_r], slices=slices)
+
+
+# ---------------------------------------------------------------------------------------------------
+# guided normal filtering (BUILD EXTENSION: the reference stops at the bilateral filter; include/fgc.h: fgc_guided_normals)
+# ---------------------------------------------------------------------------------------------------
+GUIDED_MAX_RING = 64          # FGC_GUIDED_MAX_RING, include/fgc.h
+
+
+def face_rings(faces):
+    """(ring int32 [n, ld], ld): the patch of every face for fgc_guided_normals, zero-based and -1 padded: slot 0 the face
+    itself, then the faces that share at least one vertex with it, each once, in the order of getFacesLargeAdj's row (which
+    names an edge neighbour twice) with the repeats dropped.  ld is the longest ring rounded up to a multiple of 4.  A ring
+    that does not fit GUIDED_MAX_RING slots raises RuntimeError(bilateral.NO_EDGE_TABLES), the message of a mesh the
+    bilateral tool skips."""
+    from .bilateral import NO_EDGE_TABLES
+    adj = getFacesLargeAdj(faces, GUIDED_MAX_RING).astype(np.int64) - 1
+    if (adj[:, -1] >= 0).any():                       # a full row: the list was cut (or the next entry would have been)
+        raise RuntimeError(NO_EDGE_TABLES)
+    width = int((adj >= 0).sum(1).max())
+    adj = adj[:, :width]
+    bad = adj < 0
+    for j in range(1, width):
+        bad[:, j] |= (adj[:, :j] == adj[:, j:j + 1]).any(1)
+    order = np.argsort(bad, axis=1, kind="stable")    # the kept entries first, in their order
+    ring = np.where(np.take_along_axis(bad, order, 1), -1, np.take_along_axis(adj, order, 1))
+    ld = max(4, -(-int((ring >= 0).sum(1).max()) // 4) * 4)
+    out = np.full((adj.shape[0], ld), -1, dtype=np.int32)
+    out[:, :min(ld, width)] = ring[:, :ld]
+    return out, ld
+
+
+def face_edge_neighbours(faces, e_map=None):
+    """int32 [n,3]: the face across edge t = (corner t, corner t + 1) of every face, from getEdgeMap's table (e_map, computed
+    here with maxEdges = MAX_EDGES when not given), -1 at a border edge."""
+    F = np.asarray(faces).reshape(-1, 3).astype(np.int64)
+    if e_map is None:
+        from .settings import MAX_EDGES
+        e_map, _ = getEdgeMap(F, maxEdges=MAX_EDGES)
+    e_map = np.asarray(e_map, dtype=np.int64).reshape(-1, 4)
+    fe = np.full(F.shape, -1, dtype=np.int32)
+    e = e_map[e_map[:, 3] >= 0]
+    lo, hi = np.minimum(e[:, 0], e[:, 1]), np.maximum(e[:, 0], e[:, 1])
+    for mine, other in ((e[:, 2], e[:, 3]), (e[:, 3], e[:, 2])):
+        for t in range(3):
+            a, b = F[mine, t], F[mine, (t + 1) % 3]
+            hit = (np.minimum(a, b) == lo) & (np.maximum(a, b) == hi)
+            fe[mine[hit], t] = other[hit]
+    return fe
+
+
+def guidedFilter(Fc, Fn, Fa, faces, sigma_s, sigma_r, slices=10):
+    """One pass of guided normal filtering (Zhang et al. 2015; not in the reference): float32 [n,3], bilateralFilter with
+    the range term exp(-|G_i - G_j|^2 / (2 sigma_r^2)) on the guidance normals G of fgc_guided_normals (computed from Fn,
+    Fa and the face rings of `faces` on the GPU) instead of on Fn.  Window, `slices` and sigma_r = -1 as in
+    bilateralFilter."""
+    import torch
+    from . import ops
+    grid = bilateral_grid(slices)
+    Fc, Fn, Fa = np.asarray(Fc), np.asarray(Fn), np.asarray(Fa)
+    ring, _ = face_rings(faces)
+    fe = face_edge_neighbours(faces)
+    order, ptr = bilateral_order(bilateral_cells(Fc, grid), grid)
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def put(a, dt):
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+    n, a = put(Fn, np.float32), put(Fa.reshape(-1), np.float32)
+    guide = ops.guidance_normals(n, a, put(ring, np.int32), put(fe, np.int32))
+    out = ops.bilateral_filter(put(bilateral_device_centres(Fc), np.float32), n, a, sigma_s, sigma_r, put(order, np.int32),
+                               put(ptr, np.int32), grid, guide=guide)
+    return out.cpu().numpy()

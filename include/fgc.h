@@ -62,8 +62,10 @@ extern "C" {
  * 113: fgc_mlp_forms (which kernel form a call of the MLP head takes, as text); fgc_mlp_fwd / fgc_mlp_bwd refuse a workspace
  * that is not 16-byte aligned (every kernel form reads its packed W1 in 16-byte pieces).
  * 114: fgc_synth_noise_lf (+ fgc_synth_lf_scratch_floats): low-frequency noise, a field of Gaussian bumps on top of the
- * per-vertex draw of fgc_synth_noise. */
-#define FGC_ABI_VERSION 114
+ * per-vertex draw of fgc_synth_noise.
+ * 115: fgc_guided_normals / fgc_guided_workspace_bytes / fgc_bilateral_filter_guided (guided normal filtering);
+ * fgc_bilateral_workspace_bytes grows by one float4 per face, the guided form's third candidate plane (one size for both). */
+#define FGC_ABI_VERSION 115
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -800,7 +802,8 @@ int fgc_nn_query(const float* q, int32_t nq, const float* p, int32_t np, const i
  * fp32 throughout, exp through the hardware exp2 with a pre-scaled argument.  Deterministic: every row's sum has one fixed
  * order (no floating-point atomics), and a pair's result does not depend on which other pairs the call computes.
  * Entries of cell_order outside [0, n) and ranges of cell_ptr outside [0, n] are ignored, never dereferenced.
- * workspace (device, 16-byte aligned) >= fgc_bilateral_workspace_bytes(n, sx, sy, sz) (0 for arguments the filter refuses).
+ * workspace (device, 16-byte aligned) >= fgc_bilateral_workspace_bytes(n, sx, sy, sz) (0 for arguments the filter refuses;
+ * the size also covers fgc_bilateral_filter_guided).
  * A memset, two small launches, then one launch per 4 x 3 block of (sigma_s, sigma_r) on `stream`. */
 #define FGC_BILATERAL_MAX_SLICES 64
 size_t fgc_bilateral_workspace_bytes(int32_t n, int32_t sx, int32_t sy, int32_t sz);
@@ -808,6 +811,40 @@ int fgc_bilateral_filter(const float* centres, const float* normals, const float
                          const int32_t* cell_order, const int32_t* cell_ptr, int32_t sx, int32_t sy, int32_t sz,
                          const float* sigma_s, int32_t S, const float* sigma_r, int32_t R, float* out, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* Guided normal filtering (BUILD EXTENSION - the reference stops at the bilateral filter; Zhang, Deng, Zhang, Bouaziz, Liu:
+ * "Guided mesh normal filtering", 2015): the range term of the filter reads a guidance normal G instead of the noisy normal,
+ * and G_i is the area-weighted mean normal of the most consistent patch among the patches that contain face i.
+ * For n faces with unit normals N [n,3] and areas A [n] (float32, device):
+ *   ring [n, ld] (int32, device): zero-based, -1 padded; slot 0 is the face itself, then the faces that share at least one
+ *     vertex with it, each once (utils.face_rings: the row of getFacesLargeAdj with repeats dropped); ld a multiple of 4,
+ *     4 <= ld <= FGC_GUIDED_MAX_RING, rows 16-byte aligned.  P(k) = the faces of ring[k].
+ *   fe [n,3] (int32, device): the face across each edge of a face, -1 at a border (utils.face_edge_neighbours).
+ *     E(k) = the edges whose two faces both lie in P(k), each once: the pairs (a, t) with a in P(k), fe[a, t] in P(k) and
+ *     a < fe[a, t].
+ *   Phi(k) = max over a, b in P(k) of |N_a - N_b|;  phi(e) = |N_a - N_b| for e = (a, b) in E(k)
+ *   R(k)   = max_e phi(e) / (1e-9 + sum_e phi(e))  (0 when E(k) is empty);   H(k) = Phi(k) R(k)
+ *   M(k)   = sum over a in P(k) of A_a N_a, in slot order
+ *   pick(i)= the face k of ring[i] with the smallest H(k), the first such slot on a tie;  G_i = normalize(M(pick(i)))
+ *     (utils.normalize: x * (1 / (|x| + 1e-8)) twice; a zero sum stays zero)
+ * fgc_guided_normals writes guide_out [n,3] = G, and, where the pointers are not NULL, pick_out [n] (int32, -1 for a row
+ * without a valid slot) and h_out [n] = H.  Two launches on `stream`: gd_patch_kernel ({M, H} per face into the workspace,
+ * one row of 16 lanes per face) and gd_pick_kernel.  workspace (device, 16-byte aligned) >= fgc_guided_workspace_bytes(n, ld)
+ * (0 for arguments the call refuses); after the call it holds one float4 (M_x, M_y, M_z, H) per face.
+ * fgc_bilateral_filter_guided is fgc_bilateral_filter with exp(-|G_i - G_j|^2 / (2 sigma_r^2)) as its range term, guide
+ * [n,3] (float32, device) given by the caller; window, order of the sum, sigma_r = -1, the handling of indices and the
+ * workspace (fgc_bilateral_workspace_bytes) are those of fgc_bilateral_filter.
+ * fp32 throughout, deterministic (no floating-point atomics); entries of ring outside [0, n) are skipped and entries of fe
+ * are only compared, so no index outside [0, n) is ever dereferenced. */
+#define FGC_GUIDED_MAX_RING 64
+size_t fgc_guided_workspace_bytes(int32_t n, int32_t ld);
+int fgc_guided_normals(const float* normals, const float* areas, int32_t n, const int32_t* ring, int32_t ld, const int32_t* fe,
+                       float* guide_out, int32_t* pick_out, float* h_out, void* workspace, size_t workspace_bytes,
+                       void* stream);
+int fgc_bilateral_filter_guided(const float* centres, const float* normals, const float* areas, int32_t n,
+                                const int32_t* cell_order, const int32_t* cell_ptr, int32_t sx, int32_t sy, int32_t sz,
+                                const float* sigma_s, int32_t S, const float* sigma_r, int32_t R, const float* guide,
+                                float* out, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Noise synthesis: training from clean meshes (BUILD EXTENSION - the reference trains on noisy files prepared on the host)

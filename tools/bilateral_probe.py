@@ -12,6 +12,11 @@ csrc/fgc_bilateral.hip is 20 wave64 vector instructions per pair for P = 1 (--sa
 SIMD with two or more waves (profiles/r5_issue_rates.txt: 1.1 ns plain, 3.47 ns v_exp_f32, 1.91 ns packed) 64 pairs
 cost a SIMD 27.6 ns (105.1 ns for the 12 pairs), and the card has 256 CUs x 4 SIMDs.
     python tools/bilateral_probe.py [OUT.json]
+
+--guided: instead, for the same two meshes and both grids, the device-event times (median of 20) of the guidance launches
+(fgc_guided_normals: gd_patch_kernel + gd_pick_kernel), of one guided filter pass (fgc_bilateral_filter_guided) and of the
+plain pass of the same run, P = 1.
+    python tools/bilateral_probe.py --guided [OUT.json]
 """
 import json
 import os
@@ -70,6 +75,37 @@ def time_pass(V, F, slices, ss_list, sr_list, reps=20):
             "floor_ms_issued": floor_ms, "share_of_floor": floor_ms / ms}
 
 
+def time_guided(V, F, slices, reps=20):
+    Fc = utils.getTrianglesBarycenter(V, F, normalize=False).astype(np.float32)
+    Fa = utils.getTrianglesArea(V, F).astype(np.float32)
+    Fn = utils.computeFacesNormals(V, F)
+    el = float(utils.getAverageEdgeLength(V, F)[0])
+    auto = slices == "auto"
+    grid = bilateral.auto_slices(Fc, el) if auto else utils.bilateral_grid(slices)
+    order, ptr = utils.bilateral_order(utils.bilateral_cells(Fc, grid, flat_axis_one_cell=auto), grid)
+    ring, ld = utils.face_rings(F)
+    put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()  # noqa: E731
+    c, n, a, order, ptr, ring, fe = (put(x) for x in (Fc, Fn, Fa, order, ptr, ring, utils.face_edge_neighbours(F)))
+    g = ops.guidance_normals(n, a, ring, fe)
+    steps = {"guidance": lambda: ops.guidance_normals(n, a, ring, fe),
+             "guided_filter": lambda: ops.bilateral_filter(c, n, a, el, 0.35, order, ptr, grid, guide=g),
+             "plain_filter": lambda: ops.bilateral_filter(c, n, a, el, 0.35, order, ptr, grid)}
+    out = {"faces": int(F.shape[0]), "grid": list(grid), "ring_ld": int(ld)}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    times = {k: [] for k in steps}
+    for rep in range(reps + 3):                     # the three steps in turn, so that they share the clock they run at
+        for k, fn in steps.items():
+            ev[0].record()
+            fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            if rep >= 3:
+                times[k].append(ev[0].elapsed_time(ev[1]))
+    for k, t in times.items():
+        out[k + "_ms_median"], out[k + "_ms_min"] = float(np.median(t)), float(min(t))
+    return out
+
+
 def time_denoise(V, F):
     bilateral.denoise_mesh(V, F, iterations=1, vertex_iterations=1)          # warm-up
     tm = {}
@@ -81,18 +117,22 @@ def time_denoise(V, F):
 def main():
     meshes = {"ico5": icosphere(5), "torus100k": torus(250, 200)}
     out = {}
+    args = [a for a in sys.argv[1:] if a != "--guided"]
     for name, (V, F) in meshes.items():
         F = F.astype(np.int32)
         Vn = add_noise(V, F, sigma_rel=0.2, seed=3).astype(np.float32)
         for slices in (10, "auto"):
+            if "--guided" in sys.argv[1:]:
+                out["%s_slices_%s_guided" % (name, slices)] = time_guided(Vn, F, slices)
+                continue
             out["%s_slices_%s_P1" % (name, slices)] = time_pass(Vn, F, slices, [1.0], [0.35])
             out["%s_slices_%s_P12" % (name, slices)] = time_pass(Vn, F, slices, [0.5, 1.0, 1.5, 2.0], [0.2, 0.35, 0.5])
-        if name == "torus100k":
+        if name == "torus100k" and "--guided" not in sys.argv[1:]:
             out["denoise_mesh_torus100k"] = time_denoise(Vn, F)
     s = json.dumps(out)
     print(s)
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as fh:
+    if args:
+        with open(args[0], "w") as fh:
             fh.write(s + "\n")
 
 
