@@ -19,17 +19,14 @@ Design (MI355X-first, nothing traced or compiled at run time):
   * the whole forward+backward enqueue is capturable into a hipGraph (``capture=True``).
 """
 import collections
-import contextlib
 import ctypes as C
-import gc
 import os
-import warnings
 import types
 
 import numpy as np
 import torch
 
-from . import _lib, ops, require_graph_replay_safe
+from . import _lib, ops, require_graph_replay_safe, schedule, shard
 from ._lib import ConvDesc, ConvBwdIO, AG_LD, DL_LD, FGC_M
 from .graph import FacetGraph, as_graph
 
@@ -117,43 +114,6 @@ def _p(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
-_HIP = [None]
-
-
-def _graph_node_count(g):
-    """Nodes of a captured (not yet instantiated) torch.cuda.CUDAGraph(keep_graph=True), through hipGraphGetNodes.  Raises
-    when the runtime cannot say: whether a stretch of the schedule is a graph at all must not be a guess."""
-    if _HIP[0] is None:
-        _HIP[0] = C.CDLL("libamdhip64.so")
-    n = C.c_size_t(0)
-    rc = _HIP[0].hipGraphGetNodes(C.c_void_p(g.raw_cuda_graph()), None, C.byref(n))
-    if rc != 0:
-        raise RuntimeError("hipGraphGetNodes failed (%d): cannot tell whether a schedule segment has launches" % rc)
-    return int(n.value)
-
-
-@contextlib.contextmanager
-def _no_gc_while_capturing():
-    """A stream capture must not be interrupted by Python's cyclic garbage collector.  A dead reference cycle that still owns
-    device objects - the hipGraphs and pool tensors of an earlier network, say - is freed whenever the collector happens to
-    run, and it runs on allocation counts: in the middle of a capture its destructors call hipGraphDestroy / hipFree, which
-    a capturing stream refuses; torch raises from a destructor and the process ABORTS (the round-3 abort, caught in round 4
-    with its stack: `Garbage-collecting` under `_capture_segments`).  torch.cuda.graph stopped
-    collecting in its __enter__ (torch.compiler.config.force_cudagraph_gc, default off), so: collect once before the
-    capture, keep the collector off until it has ended.  FGC_NO_CAPTURE_GC_GUARD=1 (developer switch): no guard."""
-    if os.environ.get("FGC_NO_CAPTURE_GC_GUARD", "0") == "1":
-        yield
-        return
-    gc.collect()
-    was = gc.isenabled()
-    gc.disable()
-    try:
-        yield
-    finally:
-        if was:
-            gc.enable()
-
-
 # One conv of the trunk (in forward order, model.py:858-931): level, inputs, 4x upsampling shift, output, pooled output,
 # activation, width, and (per network) its first parameter slot
 _ConvLayer = collections.namedtuple("_ConvLayer", "name level x0 x1 shift y pool act cout pidx", defaults=(None,))
@@ -167,6 +127,11 @@ TRUNK = (
     _ConvLayer("upconv1", 0, "d2", None, 2, "u1", None, 0, 32),
     _ConvLayer("dconv1", 0, "u1", "h1", 0, "d1", None, 1, 32),
 )
+# What a layer's output feeds on OTHER ranks, as (level, tensor, parent rows) of schedule.rows: sent in one grouped exchange
+# right behind the layer; the consumer - the next layer - waits for it between its interior and its boundary tiles
+SEND_AFTER = {"conv1": ((0, "h1", False), (1, "p1", False)), "conv2": ((1, "h2", False), (2, "p2", False)),
+              "conv3": ((2, "h3", False),), "dconv3": ((1, "d3", True),), "upconv2": ((1, "u2", False),),
+              "dconv2": ((0, "d2", True),), "upconv1": ((0, "u1", False),)}
 
 
 def r_ld(cout, r_pad, bf16):
@@ -202,6 +167,9 @@ class FacetDenoiser:
             raise ValueError("dtype must be 'f32' or 'bf16' (storage of the activations; weights stay fp32)")
         self.dtype = dtype
         self.L = _lib.lib()
+        # entry points that differ between the fp32 and the bf16-storage network
+        self._mlp_fwd, self._mlp_bwd, self._pool4_bwd = (getattr(self.L, name + ("_bf16" if dtype == "bf16" else ""))
+                                                         for name in ("fgc_mlp_fwd", "fgc_mlp_bwd", "fgc_pool4_bwd"))
         # options: {name: value} of library options (fgc_option_name) that hold for THIS network's conv layers only - they
         # travel in every layer's descriptor (fgc_conv_desc.options), the process-level table (fgc_set_option) is not touched:
         # two networks in one process can run different kernel forms.  (The MLP entry points take no descriptor: their
@@ -217,6 +185,7 @@ class FacetDenoiser:
         self._mesh_cache = {}
         self.profile = False   # when True every enqueue is labelled for fgc_profile_collect
         self.comm = None       # exchange back end of a facet-sharded run (shard.DistComm)
+        self.segment_nodes = []     # the node count of every schedule segment captured so far (_capture_segments)
         # facet-sharded runs: compute the interior tiles of a layer while its halo rows travel (FGC_NO_OVERLAP=1: the
         # whole layer after a blocking exchange, for A/B timing)
         self.overlap = os.environ.get("FGC_NO_OVERLAP", "0") != "1"
@@ -311,8 +280,7 @@ class FacetDenoiser:
                 raise ValueError("the network needs exactly 3 adjacency levels (model.py:858-931)")
             nh, nhp, n_total, own_lo = [0, 0, 0], [0, 0], [g.n for g in graphs], 0
         else:
-            from .shard import LocalGraph
-            graphs = [LocalGraph(P, dev) for P in plan.levels]
+            graphs = [shard.LocalGraph(P, dev) for P in plan.levels]
             nh = [g.n_halo for g in graphs]
             # tail rows of the coarse tensors read 4x-upsampled by the level above: one per UNIQUE parent of that level's
             # halo nodes (shard.ShardPlan)
@@ -461,8 +429,7 @@ class FacetDenoiser:
                 # facet-sharded: the graph-dependent limits of the pair form on the GLOBAL pair graph - a rank-local test
                 # lets ranks disagree (one shard with a coarse row of 25 in-pairs), and the two forms exchange different
                 # tensors in the backward pass
-                from .shard import pair_form_allowed
-                use_pairs = pair_form_allowed(g.pair, W0.shape[1])
+                use_pairs = shard.pair_form_allowed(g.pair, W0.shape[1])
             if use_pairs:
                 # (facet-sharded: the level's LOCAL pair graph, whose columns address [owned coarse rows | unique halo parents])
                 pg = g.pairs() if plan is None else g.pair
@@ -765,27 +732,9 @@ class FacetDenoiser:
 
     # ------------------------------------------------------------------------------------------
     # enqueue helpers (no allocation, no sync).  The schedules are GENERATORS: they yield an exchange request
-    # wherever a facet-sharded run must talk to its peers; an unsharded run just drains them.
-    #   ("xchg", items, key)     ONE grouped exchange with every peer; items:
-    #        ("rows", level, tensor, parent)   halo rows of `tensor` (parent: rows of the coarse parents)
-    #        ("edges", level)                  d-logits of incoming cross-shard edges
-    #      key None: blocking.  Otherwise the kernels enqueued up to the matching ("wait", key) run while it travels
-    #   ("sum", tensor)          all-reduce
-    #   ("call", fn)             launches whose arguments change from step to step (a rank's own loss samples): run by
-    #                            an eager call, also between the hipGraphs of a captured schedule (_capture_segments)
-    # Per step: 7 exchanges forward (everything a layer produces that a peer gathers goes out in one message right
-    # behind it: conv1 -> {h1, p1}, conv2 -> {h2, p2}), 7 backward (a layer's s rows and cross-edge d-logits together),
-    # two scalar all-reduces for normalizeTensor and its gradient, one all-reduce of gradient + loss sum: 17.
+    # wherever a facet-sharded run must talk to its peers; an unsharded run just drains them.  The requests - Xchg, Wait,
+    # Sum, Call - and what serves, captures and replays them: schedule.py; a step's 17 collectives: shard.py.
     # ------------------------------------------------------------------------------------------
-    @property
-    def pair_split_min_tiles(self):
-        """The split threshold of a pair-form layer's backward exchange, in 32-row tiles of its COARSE rows: the same NUMBER as
-        `split_min_tiles`, i.e. four times stricter in rows.  Its boundary launch - a handful of workgroups of the data kernel -
-        costs that kernel's single-workgroup latency (~20 us at level 0 of a 100k-facet shard, measured: tools/
-        shard_latency_probe.py), so the split pays only where a collective's latency is well above that; at the default
-        threshold no pair layer of a 100k-facet shard splits (782 coarse tiles), at bench.py's tuning candidates 256 / 64 they do."""
-        return self.split_min_tiles
-
     def _option(self, name):
         """The value a library option has for THIS network: its own override (options=...) or the process-level value."""
         if self.option_overrides is not None:
@@ -798,22 +747,93 @@ class FacetDenoiser:
     def _st(self):
         return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
-    # entry points that differ between the fp32 and the bf16-storage network
-    @property
-    def _mlp_fwd(self):
-        return self.L.fgc_mlp_fwd_bf16 if self.dtype == "bf16" else self.L.fgc_mlp_fwd
-
-    @property
-    def _mlp_bwd(self):
-        return self.L.fgc_mlp_bwd_bf16 if self.dtype == "bf16" else self.L.fgc_mlp_bwd
-
-    @property
-    def _pool4_bwd(self):
-        return self.L.fgc_pool4_bwd_bf16 if self.dtype == "bf16" else self.L.fgc_pool4_bwd
-
     def _tag(self, name):
         if self.profile:
             self.L.fgc_profile_tag(name.encode())
+
+    def _conv_fwd(self, d, args, label, part=None):
+        """One fgc_conv_fwd call with the arguments `args` of the layer of descriptor d.  part = (tile_list, n_tiles, proj_row0,
+        proj_rows, flags): a PARTIAL call (include/fgc.h: partial forward calls) - the fields are set for this call and put
+        back to those of a full call behind it.  Nothing else writes them during a step: one left behind would make the
+        layer run a partial call in the next step."""
+        if part is None:
+            _lib.check(self.L.fgc_conv_fwd(*args), label)
+            return
+        full = d.flags
+        d.tile_list, d.n_tiles, d.proj_row0, d.proj_rows, d.flags = part
+        _lib.check(self.L.fgc_conv_fwd(*args), label)
+        d.tile_list, d.n_tiles, d.proj_row0, d.proj_rows, d.flags = None, 0, 0, 0, full
+
+    def _conv_bwd(self, d, io, lws, st, label, stages, flags, tiles=None, flags_after=None):
+        """One fgc_conv_bwd call of `stages` (0: all of them) under `flags`.  tiles = (tile list, count): the data kernel on
+        these tiles only; the list is taken back behind the call.  flags_after: what io.flags is left at - the grouped
+        reduction reads it - where that is not `flags`.  Nothing else writes these fields of an io during a step, but the
+        loop in front of fgc_conv_bwd_reduce."""
+        io.stages, io.flags = stages, flags
+        if tiles is not None:
+            io.data_tile_list, io.n_data_tiles = tiles[0].data_ptr(), tiles[1]
+        _lib.check(self.L.fgc_conv_bwd(C.byref(d), C.byref(io), _p(lws), lws.numel(), st), label)
+        if tiles is not None:
+            io.data_tile_list, io.n_data_tiles = None, 0
+        if flags_after is not None:
+            io.flags = flags_after
+
+    def _mlp_head_fwd(self, head, vals, xin, rows, out, partials, packed, ws, st):
+        """The MLP head `head` ("head0" / "head1" / "head2") on `rows` rows of xin: raw normals into `out`, the partial sums
+        of |out| (normalizeTensor's mean) into `partials`.  vals: self.params.values; packed: 0 or the step's FGC_MLP_PACKED
+        word, with the packed operands in `ws`."""
+        W1, b1, W2, b2 = vals[self.slot[head]:self.slot[head] + 4]
+        _lib.check(self._mlp_fwd(_p(xin), rows, xin.shape[1], HIDDEN, 3, _p(W1), _p(b1), _p(W2), _p(b2), LRELU_ALPHA,
+                                 _p(out), _p(partials), packed, _p(ws), ws.numel(), st), head)
+
+    def _mlp_head_bwd(self, head, vals, grads, xin, g_out, rows, g_in, packed, ws, st):
+        """Backward of _mlp_head_fwd: g_out (the gradient of the head's raw output) -> the head's parameter gradients and
+        g_in, the gradient of xin (written)."""
+        s = self.slot[head]
+        _lib.check(self._mlp_bwd(_p(xin), _p(g_out), rows, xin.shape[1], HIDDEN, 3, _p(vals[s]), _p(vals[s + 1]),
+                                 _p(vals[s + 2]), LRELU_ALPHA, _p(g_in), _p(grads[s]), _p(grads[s + 1]), _p(grads[s + 2]),
+                                 _p(grads[s + 3]), packed, _p(ws), ws.numel(), st), head + " bwd")
+
+    def _angular_head(self, k, samp, st, rotate=False, gt=None, normalize=False, backward=False, between=None):
+        """The angular loss of the head of level k ("" / "1" / "2": the buffers' suffix) on the sampled rows `samp`:
+        normalise (normalize), rotate the ground truth, loss, then (backward) the loss's gradient and (normalize) that of
+        normalizeTensor.  gt: ground-truth rows that ARE rotated already, instead of the level's own.  between(): run
+        between the loss and its gradient."""
+        B, L = self._mesh["B"], self.L
+        nk = self._mesh["ns"][int(k or 0)]
+        nc = B["nconv" + k]
+        if normalize:
+            self._drain(self._normalize_gen(k))
+        if gt is None:
+            gt = B["gt" + k]
+            if rotate:
+                _lib.check(L.fgc_rotate_rows(_p(gt), _p(B["gtr" + k]), nk, 1, _p(B["R"]), st), "rotate gt")
+                gt = B["gtr" + k]
+        if k:
+            # a coarse head: the fine head's sampled rows modulo the level's size (kept alive until the kernels have run)
+            samp = B["sample_ind" + k] = torch.remainder(samp, nk)
+        _lib.check(L.fgc_angular_loss_fwd(_p(nc), _p(gt), _p(samp), samp.numel(), _p(B["loss" + k]), st), "loss")
+        if between is not None:
+            between()
+        if backward:
+            _lib.check(L.fgc_angular_loss_bwd(_p(nc), _p(gt), _p(samp), samp.numel(), nk, _p(B["loss" + k]), 1.0,
+                                              _p(B["g_nconv" + k]), st), "loss bwd")
+            if normalize:
+                _lib.check(L.fgc_normalize_bwd(_p(B["y" + (k or "0")]), _p(B["g_nconv" + k]), nk, _p(B["g_y" + k]),
+                                               _p(B["norm_scratch" + k]), st), "normalize bwd")
+
+    def _normalize_gen(self, k):
+        """normalizeTensor on the head of level k ("" / "1" / "2": the buffers' suffix), y -> nconv, as a schedule: the mean |y| is
+        taken over the WHOLE tensor (utils.py:1705) - on a facet-sharded mesh by one scalar all-reduce, then the rows."""
+        M, B, st, level = self._mesh, self._mesh["B"], self._st(), int(k or 0)
+        y, part, sc, nc = B["y" + (k or "0")], B["abs_part" + k], B["norm_scratch" + k], B["nconv" + k]
+        if not self.sharded:
+            _lib.check(self.L.fgc_normalize_fwd(_p(y), M["ns"][level], _p(part), part.numel(), _p(nc), _p(sc), st), "normalize")
+            return
+        tot = part.sum().reshape(1)
+        yield schedule.sum_(tot)
+        sc[0:1] = tot / (3.0 * M["n_total"][level]) + 1e-5
+        _lib.check(self.L.fgc_normalize_apply(_p(y), M["ns"][level], _p(sc), _p(nc), st), "normalize")
 
     @property
     def grouped_dw_layers(self):
@@ -858,15 +878,6 @@ class FacetDenoiser:
                        "rotate")
         elif not rotate:
             B["xr"].copy_(B["x"])
-        # what a layer's output feeds on OTHER ranks: sent in one grouped exchange right behind the layer; the consumer
-        # waits for it between its interior and its boundary tiles
-        send_after = {"conv1": [("rows", 0, "h1", False), ("rows", 1, "p1", False)],
-                      "conv2": [("rows", 1, "h2", False), ("rows", 2, "p2", False)],
-                      "conv3": [("rows", 2, "h3", False)], "dconv3": [("rows", 1, "d3", True)],
-                      "upconv2": [("rows", 1, "u2", False)], "dconv2": [("rows", 0, "d2", True)],
-                      "upconv1": [("rows", 0, "u1", False)]}
-        wait_before = {"conv2": "conv1", "conv3": "conv2", "dconv3": "conv3", "upconv2": "dconv3", "dconv2": "upconv2",
-                       "upconv1": "dconv2", "dconv1": "upconv1"}
         split = self.sharded and self.overlap
         # A layer's output exchange is begun under a key only if its consumer launches something before it waits (interior
         # tiles, the transform of the owned coarse rows, a multi-scale head); otherwise it is served as ONE blocking call - a
@@ -875,12 +886,8 @@ class FacetDenoiser:
         in_flight = set()
 
         def consumer_overlaps(nxt):
-            if nxt is None or not split:
-                return False
-            dn = M["descs"][nxt.name]
-            if L.fgc_conv_uses_pairs(C.byref(dn)):
-                return True
-            return M["graphs"][nxt.level].tiles["tiles_int"][1] >= self.split_min_tiles
+            return nxt is not None and split and (L.fgc_conv_uses_pairs(C.byref(M["descs"][nxt.name])) or
+                                                  M["graphs"][nxt.level].tiles["tiles_int"][1] >= self.split_min_tiles)
         packed = 0
         table_done = False      # the first layer's logit table came with the housekeeping launch
         if self.batched:
@@ -923,124 +930,86 @@ class FacetDenoiser:
             d.flags = packed | lflags
             args = (C.byref(d), _p(B["ag_" + lay.name]), _p(B[lay.y]), _p(B[lay.pool]) if lay.pool else None, _p(lws),
                     lws.numel(), st)
-            need = wait_before.get(lay.name) if self.sharded else None
-            if need is not None and need not in in_flight:
-                need = None          # (its producer's exchange was a blocking call: the halo rows are there)
-            if self.sharded and need and L.fgc_conv_uses_pairs(C.byref(d)):
-                # pair form: the owned coarse rows are transformed while the halo parents travel; then the tail rows and
-                # every block (include/fgc.h: partial forward calls)
-                g = M["graphs"][lay.level]
-                own_src = d.n >> 2
-                self._tag("fwd:" + lay.name)
-                if split and need:
-                    d.tile_list, d.n_tiles = g.tiles["tiles_int"][0].data_ptr(), 0
-                    d.proj_row0, d.proj_rows = 0, own_src
-                    _lib.check(L.fgc_conv_fwd(*args), lay.name)
-                    yield ("wait", need)
-                    d.tile_list, d.n_tiles = None, 0
-                    d.proj_row0, d.proj_rows = own_src, (d.src_rows - own_src) or -1
-                    d.flags = _lib.CONV_PACKED | lflags
-                    _lib.check(L.fgc_conv_fwd(*args), lay.name)
-                    d.proj_row0, d.proj_rows, d.flags = 0, 0, packed | lflags
-                else:
-                    if need:
-                        yield ("wait", need)
-                    _lib.check(L.fgc_conv_fwd(*args), lay.name)
-            elif split and need and M["graphs"][lay.level].tiles["tiles_int"][1] >= self.split_min_tiles:
-                # interior tiles (they gather owned rows only) run while the halo rows travel; then the rest
-                g = M["graphs"][lay.level]
+            # a layer waits for the layer before it - if that one's exchange is in flight: after a blocking call the halo
+            # rows are there
+            need = self.layers[li - 1].name if li else None
+            if need not in in_flight:
+                need = None
+            pair = need is not None and L.fgc_conv_uses_pairs(C.byref(d))
+            if split and need and (pair or M["graphs"][lay.level].tiles["tiles_int"][1] >= self.split_min_tiles):
+                # the interior tiles (they gather owned rows only) and the logit rows of the owned sources run while the halo
+                # rows travel, then the rest.  Pair form: the owned coarse rows are transformed while the halo parents travel,
+                # then the tail rows and every block (include/fgc.h: partial forward calls)
+                ti, tb = M["graphs"][lay.level].tiles["tiles_int"], M["graphs"][lay.level].tiles["tiles_bnd"]
+                interior, boundary = (((ti[0].data_ptr(), 0), (None, 0)) if pair else
+                                      ((ti[0].data_ptr(), ti[1]), (tb[0].data_ptr(), tb[1])))
                 own_src = d.n >> d.shift
                 self._tag("fwd:" + lay.name)
-                d.tile_list, d.n_tiles = g.tiles["tiles_int"][0].data_ptr(), g.tiles["tiles_int"][1]
-                d.proj_row0, d.proj_rows = 0, own_src
-                _lib.check(L.fgc_conv_fwd(*args), lay.name)
-                yield ("wait", need)
-                d.tile_list, d.n_tiles = g.tiles["tiles_bnd"][0].data_ptr(), g.tiles["tiles_bnd"][1]
-                d.proj_row0, d.proj_rows = own_src, (d.src_rows - own_src) or -1
-                d.flags = _lib.CONV_PACKED | lflags
-                _lib.check(L.fgc_conv_fwd(*args), lay.name)
-                d.tile_list, d.n_tiles, d.proj_row0, d.proj_rows, d.flags = None, 0, 0, 0, packed | lflags
+                self._conv_fwd(d, args, lay.name, interior + (0, own_src, packed | lflags))
+                yield schedule.wait(need)
+                self._conv_fwd(d, args, lay.name, boundary + (own_src, (d.src_rows - own_src) or -1,
+                                                              _lib.CONV_PACKED | lflags))
             else:
+                # (the unpack behind a pair-form layer's wait has always been counted under that layer's tag)
+                if pair:
+                    self._tag("fwd:" + lay.name)
                 if need:
-                    yield ("wait", need)
-                self._tag("fwd:" + lay.name)
-                if lay.name == "conv1" and table_done:
-                    d.proj_rows = -1
-                _lib.check(L.fgc_conv_fwd(*args), lay.name)
-                if lay.name == "conv1" and table_done:
-                    d.proj_rows = 0
-            if self.sharded and lay.name in send_after:
-                items = [(k, lv, B[t], par) for k, lv, t, par in send_after[lay.name]]
+                    yield schedule.wait(need)
+                if not pair:
+                    self._tag("fwd:" + lay.name)
+                # (conv1's logit table may have come with the housekeeping launch: no projection then)
+                self._conv_fwd(d, args, lay.name,
+                               (None, 0, 0, -1, packed | lflags) if lay.name == "conv1" and table_done else None)
+            if self.sharded and lay.name in SEND_AFTER:
+                items = [schedule.rows(lv, B[t], par) for lv, t, par in SEND_AFTER[lay.name]]
                 nxt = self.layers[li + 1] if li + 1 < len(self.layers) else None
                 if consumer_overlaps(nxt) or (self.multi_scale and lay.name in ("dconv3", "dconv2")):
                     in_flight.add(lay.name)
-                    yield ("xchg", items, lay.name)
+                    yield schedule.xchg(items, lay.name)
                 else:
-                    yield ("xchg", items, None)
+                    yield schedule.xchg(items)
             if self.multi_scale and lay.name in ("dconv3", "dconv2"):
-                head, out = ("head2", "y2") if lay.name == "dconv3" else ("head1", "y1")
-                W1, b1, W2, b2 = vals[self.slot[head]:self.slot[head] + 4]
-                xin = B[lay.y]
-                nrows = M["ns"][lay.level]
-                _lib.check(self._mlp_fwd(_p(xin), nrows, xin.shape[1], HIDDEN, 3, _p(W1), _p(b1), _p(W2),
-                                         _p(b2), LRELU_ALPHA, _p(B[out]), _p(B["abs_part" + out[1]]), 0, _p(ws),
-                                         ws.numel(), st), head)
+                k = "2" if lay.name == "dconv3" else "1"
+                self._mlp_head_fwd("head" + k, vals, B[lay.y], M["ns"][lay.level], B["y" + k], B["abs_part" + k], 0, ws, st)
         self._tag("fwd:mlp")
-        W1, b1, W2, b2 = vals[self.slot["head0"]:self.slot["head0"] + 4]
-        wsm = B["ws_mlp_f"]
-        _lib.check(self._mlp_fwd(_p(B["d1"]), n0, 32, HIDDEN, 3, _p(W1), _p(b1), _p(W2), _p(b2), LRELU_ALPHA,
-                                 _p(B["y0"]), _p(B["abs_part"]), mlp_packed, _p(wsm), wsm.numel(), st), "head0")
+        self._mlp_head_fwd("head0", vals, B["d1"], n0, B["y0"], B["abs_part"], mlp_packed, B["ws_mlp_f"], st)
         self._tag("fwd:normalize")
         if defer_normalize and self.sharded:
             # training: the global mean |y| (utils.py:1705 takes it over the whole tensor) is all that is needed here -
             # one launch sums this rank's partials, one scalar all-reduce; the rows are normalised by fgc_loss_shard_rows
             LS = B["loss_sums"]
             _lib.check(L.fgc_loss_shard_abs_sum(_p(B["abs_part"]), B["abs_part"].numel(), _p(LS), st), "abs sum")
-            yield ("sum", LS[0:1])
-            return
-        if defer_normalize:
-            return
-        if not self.sharded:
-            _lib.check(L.fgc_normalize_fwd(_p(B["y0"]), n0, _p(B["abs_part"]), B["abs_part"].numel(),
-                                           _p(B["nconv"]), _p(B["norm_scratch"]), st), "normalize")
-        else:
-            # global mean |y| (utils.py:1705 takes it over the whole tensor): one scalar all-reduce
-            tot = B["abs_part"].sum().reshape(1)
-            yield ("sum", tot)
-            B["norm_scratch"][0:1] = tot / (3.0 * M["n_total"][0]) + 1e-5
-            _lib.check(L.fgc_normalize_apply(_p(B["y0"]), n0, _p(B["norm_scratch"]), _p(B["nconv"]), st),
-                       "normalize")
+            yield schedule.sum_(LS[0:1])
+        elif not defer_normalize:
+            yield from self._normalize_gen("")
 
     def _loss_backward_gen(self, rotate):
         M, L, st = self._mesh, self.L, self._st()
-        B, ws, ns = M["B"], M["B"]["ws"], M["ns"]
-        n0 = ns[0]
+        B, n0 = M["B"], M["ns"][0]
         gt = B["gt"]
         self._tag("bwd:loss")
-        fused = self._fused_loss_now()
+        fused = self.fused_loss
         if rotate and not fused:
             _lib.check(L.fgc_rotate_rows(_p(B["gt"]), _p(B["gtr"]), n0, 1, _p(B["R"]), st), "rotate gt")
             gt = B["gtr"]
 
+        def shard_loss_sum():
+            # loss = sum over ranks of (sum of angles) / (real rows among ALL samples).  The count is known to every
+            # rank (flags of the whole mesh were kept at bind time), so the backward pass can start at once; the sum
+            # of angles rides in the tail of the gradient all-reduce at the end of the step
+            ext = self.params.grad_ext
+            ext[-4:-3] = torch.nan_to_num(B["loss"][0:1] * B["loss"][1:2])
+            B["loss"][1:2] = B["real_flag"][B["sample_ind"].long()].sum().reshape(1)
+
         def loss_rows():
-            stl = self._st()
             samp = B["sample_ind_local"] if self.sharded else B["sample_ind"]
-            ns_samp = samp.numel()
-            if ns_samp:
-                _lib.check(L.fgc_angular_loss_fwd(_p(B["nconv"]), _p(gt), _p(samp), ns_samp, _p(B["loss"]), stl), "loss")
+            between = shard_loss_sum if self.sharded else None
+            if samp.numel():
+                self._angular_head("", samp, self._st(), gt=gt, backward=True, between=between)
             else:
                 B["loss"].zero_()
-            if self.sharded:
-                # loss = sum over ranks of (sum of angles) / (real rows among ALL samples).  The count is known to every
-                # rank (flags of the whole mesh were kept at bind time), so the backward pass can start at once; the sum
-                # of angles rides in the tail of the gradient all-reduce at the end of the step
-                ext = self.params.grad_ext
-                ext[-4:-3] = torch.nan_to_num(B["loss"][0:1] * B["loss"][1:2])
-                B["loss"][1:2] = B["real_flag"][B["sample_ind"].long()].sum().reshape(1)
-            if ns_samp:
-                _lib.check(L.fgc_angular_loss_bwd(_p(B["nconv"]), _p(gt), _p(samp), ns_samp, n0, _p(B["loss"]), 1.0,
-                                                  _p(B["g_nconv"]), stl), "loss bwd")
-            else:
+                if between is not None:
+                    between()
                 B["g_nconv"].zero_()
 
         if fused and self.sharded:
@@ -1057,8 +1026,8 @@ class FacetDenoiser:
                                                     _p(B["loss_gacc"]), _p(LS), self._st()), "loss samples")
             # (a rank's own samples are a list of another length - and another tensor - every step: a request of its own,
             #  served by an eager call also when the schedule is replayed from hipGraphs)
-            yield ("call", shard_samples)
-            yield ("sum", LS[4:])
+            yield schedule.call(shard_samples)
+            yield schedule.sum_(LS[4:])
             _lib.check(L.fgc_loss_shard_rows(_p(B["y0"]), n0, count, ns_total, _p(LS), _p(B["loss_gacc"]), _p(B["nconv"]),
                                              _p(B["g_y0"]), _p(B["loss"]), st), "loss rows")
         elif fused:
@@ -1072,65 +1041,38 @@ class FacetDenoiser:
         elif self.sharded:
             # a rank's own samples are a list of another length (and another tensor) every step: these few launches are
             # a request of their own, served by an eager call also when the schedule is replayed from hipGraphs
-            yield ("call", loss_rows)
-        else:
-            loss_rows()
-        if fused:
-            pass
-        elif not self.sharded:
-            _lib.check(L.fgc_normalize_bwd(_p(B["y0"]), _p(B["g_nconv"]), n0, _p(B["g_y0"]), _p(B["norm_scratch"]),
-                                           st), "normalize bwd")
-        else:
+            yield schedule.call(loss_rows)
             sc = B["norm_scratch"]
             _lib.check(L.fgc_normalize_bwd_partial(_p(B["y0"]), _p(B["g_nconv"]), n0, _p(sc), _p(B["g_y0"]),
                                                    C.c_void_p(sc.data_ptr() + 8), st), "normalize bwd 1")
             tot = sc[2:].sum().reshape(1)
-            yield ("sum", tot)
+            yield schedule.sum_(tot)
             sc[1:2] = -tot / (sc[0:1] * sc[0:1])
             _lib.check(L.fgc_normalize_bwd_apply(_p(B["y0"]), n0, 3.0 * M["n_total"][0], _p(sc), _p(B["g_y0"]), st),
                        "normalize bwd 2")
-        vals, grads = self.params.values, self.params.grads
+        else:
+            loss_rows()
+            _lib.check(L.fgc_normalize_bwd(_p(B["y0"]), _p(B["g_nconv"]), n0, _p(B["g_y0"]), _p(B["norm_scratch"]),
+                                           st), "normalize bwd")
         if self.multi_scale:
             if self.sharded or self.dtype != "f32":
                 raise NotImplementedError("training the multi-scale heads: unsharded fp32 network only")
             # Build extension: the reference trains the coarse heads through a point-set loss on the vertex update
             # (trainAccuracyNet: pointset_step below).  Here every head gets the angular loss of the fine head
             # (train.py:1272-1294) against the pooled ground truth, on the same sampled rows modulo the level's size.
-            for k, name, head in (("2", "dconv3", "head2"), ("1", "dconv2", "head1")):
-                lvl = int(k)
-                nk = ns[lvl]
-                y, nc, part, sc = B["y" + k], B["nconv" + k], B["abs_part" + k], B["norm_scratch" + k]
+            for k in ("2", "1"):
                 self._tag("bwd:head" + k)
-                _lib.check(L.fgc_normalize_fwd(_p(y), nk, _p(part), part.numel(), _p(nc), _p(sc), st), "normalize")
-                gtk = B["gt" + k]
-                if rotate:
-                    _lib.check(L.fgc_rotate_rows(_p(gtk), _p(B["gtr" + k]), nk, 1, _p(B["R"]), st), "rotate gt")
-                    gtk = B["gtr" + k]
-                sk = torch.remainder(B["sample_ind"], nk)
-                B["sample_ind" + k] = sk        # (kept alive until the kernels have run)
-                _lib.check(L.fgc_angular_loss_fwd(_p(nc), _p(gtk), _p(sk), sk.numel(), _p(B["loss" + k]), st), "loss")
-                _lib.check(L.fgc_angular_loss_bwd(_p(nc), _p(gtk), _p(sk), sk.numel(), nk, _p(B["loss" + k]), 1.0,
-                                                  _p(B["g_nconv" + k]), st), "loss bwd")
-                _lib.check(L.fgc_normalize_bwd(_p(y), _p(B["g_nconv" + k]), nk, _p(B["g_y" + k]), _p(sc), st),
-                           "normalize bwd")
+                self._angular_head(k, B["sample_ind"], st, rotate=rotate, normalize=True, backward=True)
                 self._coarse_head_bwd(k)
         yield from self._params_backward_gen(fused)
 
     def _coarse_head_bwd(self, k):
         """g_y<k> (the gradient of coarse head k's raw output) -> the head's parameter gradients and g_d3 / g_d2 (written:
-        the up-convolution adds its own later)."""
-        M, L, st = self._mesh, self.L, self._st()
-        B, ws = M["B"], M["B"]["ws"]
-        vals, grads = self.params.values, self.params.grads
-        name, head = {"2": ("dconv3", "head2"), "1": ("dconv2", "head1")}[k]
-        nk = M["ns"][int(k)]
-        lay = next(l for l in self.layers if l.name == name)
-        xin = B[lay.y]
-        hs = self.slot[head]
-        _lib.check(L.fgc_mlp_bwd(_p(xin), _p(B["g_y" + k]), nk, xin.shape[1], HIDDEN, 3, _p(vals[hs]),
-                                 _p(vals[hs + 1]), _p(vals[hs + 2]), LRELU_ALPHA, _p(B["g_" + lay.y]),
-                                 _p(grads[hs]), _p(grads[hs + 1]), _p(grads[hs + 2]), _p(grads[hs + 3]), 0, _p(ws),
-                                 ws.numel(), st), head + " bwd")
+        the up-convolution adds its own later).  (The coarse heads train on the fp32 network only.)"""
+        B = self._mesh["B"]
+        y = {"2": "d3", "1": "d2"}[k]
+        self._mlp_head_bwd("head" + k, self.params.values, self.params.grads, B[y], B["g_y" + k], self._mesh["ns"][int(k)],
+                           B["g_" + y], 0, B["ws"], self._st())
 
     def _params_backward_gen(self, fused):
         """g_y0 (and, multi-scale, the coarse heads' contributions to g_d3 / g_d2, already written) -> every parameter
@@ -1139,13 +1081,9 @@ class FacetDenoiser:
         M, L, st = self._mesh, self.L, self._st()
         B, ws, ns = M["B"], M["B"]["ws"], M["ns"]
         n0 = ns[0]
-        vals, grads = self.params.values, self.params.grads
-        s = self.slot["head0"]
         self._tag("bwd:mlp")
-        _lib.check(self._mlp_bwd(_p(B["d1"]), _p(B["g_y0"]), n0, 32, HIDDEN, 3, _p(vals[s]), _p(vals[s + 1]),
-                                 _p(vals[s + 2]), LRELU_ALPHA, _p(B["g_d1"]), _p(grads[s]), _p(grads[s + 1]),
-                                 _p(grads[s + 2]), _p(grads[s + 3]), M.get("mlp_packed", 0), _p(ws), ws.numel(), st),
-                   "head0 bwd")
+        self._mlp_head_bwd("head0", self.params.values, self.params.grads, B["d1"], B["g_y0"], n0, B["g_d1"],
+                           M.get("mlp_packed", 0), ws, st)
         # (the stride of r - padded to whole 128-byte lines unless FGC_NO_R_PAD=1 - is stated in every io's r_ld at bind time:
         #  the staged calls below may reset io.flags freely)
         # Facet-sharded: a layer's weight-gradient stage (8: the GEMM over its r rows and inputs, the partial sums) depends on
@@ -1154,104 +1092,88 @@ class FacetDenoiser:
         # rows) and its wait - where it hides 20 - 55 us of a collective's latency that nothing else in a strictly sequential
         # backward pass can hide (tools/shard_latency_probe.py; FGC_NO_DW_IN_WINDOW=1: right behind its own data kernel).
         # Same launches, same arithmetic, another order.
-        pending_dw = [None]
+        pending_dw = []      # (at most one weight-gradient stage: (layer, descriptor, io, workspace, flags))
 
         def flush_dw():
-            if pending_dw[0] is not None:
-                pending_dw[0]()
-                pending_dw[0] = None
-
-        def defer_dw(name, d, io, lws, flags):
-            def run():
+            if pending_dw:
+                name, d, io, lws, flags = pending_dw.pop()
                 self._tag("bwd:" + name)
-                io.stages, io.flags = 8, flags
-                io.data_tile_list, io.n_data_tiles = None, 0
-                _lib.check(L.fgc_conv_bwd(C.byref(d), C.byref(io), _p(lws), lws.numel(), st), name + " bwd/weights")
-                io.flags = 0
-            pending_dw[0] = run
-            if not self.dw_in_window:
-                flush_dw()
+                self._conv_bwd(d, io, lws, st, name + " bwd/weights", 8, flags, flags_after=0)
 
-        for name in ["dconv1", "upconv1", "dconv2", "upconv2", "dconv3", "conv3", "conv2", "conv1"]:
+        for lay in reversed(self.layers):
+            name = lay.name
             self._tag("bwd:" + name)
             # (g_h2 += d pool2 and g_h1 += d pool1 are folded into stage 1 of conv2 / conv1: fgc_conv_bwd_io.pool_y / pool_dy;
             #  FGC_NO_FUSED_POOL=1: by launches of their own)
-            if name == "conv2" and not self.fused_pool:
-                _lib.check(self._pool4_bwd(_p(B["h2"]), _p(B["p2"]), _p(B["g_p2"]), _p(B["g_h2"]), ns[2], 64, 1, st),
-                           "pool2 bwd")
-            if name == "conv1" and not self.fused_pool:
-                _lib.check(self._pool4_bwd(_p(B["h1"]), _p(B["p1"]), _p(B["g_p1"]), _p(B["g_h1"]), ns[1], 32, 1, st),
-                           "pool1 bwd")
+            if lay.pool and not self.fused_pool:
+                _lib.check(self._pool4_bwd(_p(B[lay.y]), _p(B[lay.pool]), _p(B["g_" + lay.pool]), _p(B["g_" + lay.y]),
+                                           ns[lay.level + 1], lay.cout, 1, st), "pool" + lay.pool[1:] + " bwd")
             d, io = M["descs"][name], M["ios"][name]
             lws = B["wsb_" + name]
             base = (_lib.CONV_PACKED | _lib.CONV_DEFER_REDUCE) if self.batched else 0
             if self.batched and name in M["grouped_dw_layers"]:
                 base |= _lib.CONV_DEFER_DW
             if not self.sharded:
-                io.stages, io.flags = 0, base
-                _lib.check(L.fgc_conv_bwd(C.byref(d), C.byref(io), _p(lws), lws.numel(), st), name + " bwd")
+                self._conv_bwd(d, io, lws, st, name + " bwd", 0, base)
                 continue
-            lay = next(l for l in self.layers if l.name == name)
             cout = d.cout
             nloc = ns[lay.level] + M["nh"][lay.level]
             g = M["graphs"][lay.level]
-            call = lambda what: _lib.check(L.fgc_conv_bwd(C.byref(d), C.byref(io), _p(lws), lws.numel(), st),
-                                           name + " bwd/" + what)
-            io.flags = base
             if not L.fgc_conv_bwd_needs_exchange(C.byref(d), C.byref(io)):
                 # first layer over a narrow input: its parameter gradients are sums over owned nodes, nothing to
                 # exchange (the flat-gradient all-reduce adds the ranks)
                 flush_dw()
                 self._tag("bwd:" + name)
-                io.stages = 1 | 2 | 8
-                call("params")
+                self._conv_bwd(d, io, lws, st, name + " bwd/params", 1 | 2 | 8, base)
                 continue
             pair = L.fgc_conv_uses_pairs(C.byref(d))
-            io.stages = 1 | 2
-            call("pair logits" if pair else "logits")
+            self._conv_bwd(d, io, lws, st, name + (" bwd/pair logits" if pair else " bwd/logits"), 1 | 2, base)
+            packed_base = base | _lib.CONV_PACKED      # (the logits call packed the operands of the data and weight stages)
             if pair:
                 # pair form: dt and the d-logits of the owned pairs; the rows of the pairs whose parent a peer owns travel to it
                 # (ONE grouped exchange, no rows of s), then the data kernel over the owned coarse rows and the weight gradients
                 pg = g.pair
                 npl = pg.n_pairs + pg.n_cross_in
-                items = [("pedges", lay.level, B["dt"][:npl * cout].view(npl, cout)),
-                         ("pedges", lay.level, B["dl"][:npl * DL_LD].view(npl, DL_LD))]
-                tiles, min_tiles, what = pg.tiles, self.pair_split_min_tiles, "pair data"
+                items = [schedule.pedges(lay.level, B["dt"][:npl * cout].view(npl, cout)),
+                         schedule.pedges(lay.level, B["dl"][:npl * DL_LD].view(npl, DL_LD))]
+                tiles, what = pg.tiles, name + " bwd/pair data"
             else:
                 # s = dy * lrelu'(y) / deg on owned rows and the d-logits of owned edges came in one call (the deep d-logits
                 # kernel computes s in its prologue; packs the operands of stages 2 and 4 when the network did not).  ONE
                 # grouped exchange per layer: the halo rows of s (their owners') and the d-logits of incoming cross-shard
                 # edges, both first read by the data kernel
                 ds_rows = (B["ds"].view(torch.bfloat16) if self.dtype == "bf16" else B["ds"])[:nloc * cout].view(nloc, cout)
-                items = [("rows", lay.level, ds_rows, False), ("edges", lay.level)]
-                tiles, min_tiles, what = g.tiles, self.split_min_tiles, "data"
-            if self.overlap and tiles["ttiles_int"][1] >= min_tiles:
+                items = [schedule.rows(lay.level, ds_rows), schedule.edges(lay.level)]
+                tiles, what = g.tiles, name + " bwd/data"
+            # The split threshold of a pair-form layer's backward exchange counts 32-row tiles of its COARSE rows: the same
+            # NUMBER as for the other layers, i.e. four times stricter in rows.  Its boundary launch - a handful of workgroups
+            # of the data kernel - costs that kernel's single-workgroup latency (~20 us at level 0 of a 100k-facet shard,
+            # measured: tools/shard_latency_probe.py), so the split pays only where a collective's latency is well above that;
+            # at the default threshold no pair layer of a 100k-facet shard splits (782 coarse tiles), at bench.py's tuning
+            # candidates 256 / 64 they do.
+            if self.overlap and tiles["ttiles_int"][1] >= self.split_min_tiles:
                 # ... it travels under the data kernel of the interior tiles (all in-edges from owned rows; pair form: all
                 # in-pairs with owned parents); the boundary tiles and the weight gradients follow (round 6: the pair layers'
                 # backward exchange used to block - tools/shard_latency_probe.py)
-                yield ("xchg", items, "bwd")
+                yield schedule.xchg(items, "bwd")
                 flush_dw()
                 self._tag("bwd:" + name)
-                io.stages, io.flags = 4, base | _lib.CONV_PACKED
-                io.data_tile_list, io.n_data_tiles = tiles["ttiles_int"][0].data_ptr(), tiles["ttiles_int"][1]
-                call(what + "/interior")
-                yield ("wait", "bwd")
-                io.data_tile_list, io.n_data_tiles = tiles["ttiles_bnd"][0].data_ptr(), tiles["ttiles_bnd"][1]
-                call(what + "/boundary")
-                io.data_tile_list, io.n_data_tiles, io.flags = None, 0, 0
+                self._conv_bwd(d, io, lws, st, what + "/interior", 4, packed_base, tiles["ttiles_int"])
+                yield schedule.wait("bwd")
+                self._conv_bwd(d, io, lws, st, what + "/boundary", 4, packed_base, tiles["ttiles_bnd"], flags_after=0)
             else:
                 # (nothing to put under it - no weight-gradient stage pending -: ONE blocking call, a synchronous collective on
                 #  the compute stream, without the cross-stream dependencies of an asynchronous one)
-                key = "bwd" if pending_dw[0] is not None else None
-                yield ("xchg", items, key)
+                key = "bwd" if pending_dw else None
+                yield schedule.xchg(items, key)
                 flush_dw()
                 if key:
-                    yield ("wait", key)
+                    yield schedule.wait(key)
                 self._tag("bwd:" + name)
-                io.stages, io.flags = 4, base | _lib.CONV_PACKED
-                call(what)
-                io.flags = 0
-            defer_dw(name, d, io, lws, base | _lib.CONV_PACKED)
+                self._conv_bwd(d, io, lws, st, what, 4, packed_base, flags_after=0)
+            pending_dw.append((name, d, io, lws, packed_base))
+            if not self.dw_in_window:
+                flush_dw()
         flush_dw()
         if self.batched:
             A = M["arrays"]
@@ -1261,120 +1183,40 @@ class FacetDenoiser:
             _lib.check(L.fgc_conv_bwd_reduce(A["descs"], A["ios"], A["wsb"], A["count"], st), "reduce")
         if self.sharded:
             # every rank summed its own facets: one flat all-reduce (gradient + the loss sum in the tail)
-            yield ("sum", self.params.grad_ext)
+            yield schedule.sum_(self.params.grad_ext)
             if not fused:
                 B["loss"][0:1] = self.params.grad_ext[-4:-3] / B["loss"][1:2]
 
-    # ---- exchange items -> (send buffer, send counts, receive view, receive counts) ------------------------
-    def _block(self, item):
-        """One block of a grouped exchange (shard.PackedExchange): (src rows, send index, send counts, halo tail, recv
-        counts)."""
-        M = self._mesh
-        g = M["graphs"][item[1]]
-        if item[0] == "rows":
-            t, parent = item[2], item[3]
-            if t.dtype == torch.bfloat16:
-                # a row of C bf16 channels travels as C / 2 dwords (every exchanged width is even): the copies and the
-                # collective only move bytes
-                t = t.view(torch.float32)
-            if parent:
-                # a coarse tensor read 4x-upsampled by this level: its tail holds the unique parents of the level's halo nodes
-                pg = g.pair
-                return (t, pg.send_rows, pg.send_counts, t[t.shape[0] - pg.n_halo:], pg.recv_counts)
-            tail = t.shape[0] - g.n_halo
-            return (t, g.send_rows, g.send_counts, t[tail:], g.recv_counts)
-        if item[0] == "pedges":
-            # per-pair rows (dt, d-logits) of the pairs whose parent another rank owns: they land behind the owned pairs
-            t, pg = item[2], g.pair
-            if t.dtype == torch.bfloat16:
-                t = t.view(torch.float32)
-            return (t, pg.send_edges, pg.cross_send_counts, t[pg.n_pairs:], pg.cross_recv_counts)
-        if item[0] == "edges":
-            dl = M["B"]["dl"][:(g.nnz + g.n_cross_in) * DL_LD].view(-1, DL_LD)
-            return (dl, g.send_edges, g.cross_send_counts, dl[g.nnz:], g.cross_recv_counts)
-        raise ValueError(item[0])
-
     def _packed(self, req):
-        """The PackedExchange of an ("xchg", items, key) request; built at its first use, the same every step."""
-        from .shard import PackedExchange
+        """The PackedExchange of a schedule.Xchg request; built at its first use, the same every step."""
         cache = self._mesh.setdefault("packed", {})
-        key = tuple((it[0], it[1]) + ((it[2].data_ptr(), tuple(it[2].shape), bool(it[3])) if it[0] == "rows" else
-                                      ((it[2].data_ptr(), tuple(it[2].shape)) if it[0] == "pedges" else ()))
-                    for it in req[1])
+        key = tuple(tuple((f.data_ptr(), tuple(f.shape)) if isinstance(f, torch.Tensor) else f for f in it) for it in req.items)
         px = cache.get(key)
         if px is None:
             world = len(self._mesh["graphs"][0].send_counts)
-            px = cache[key] = PackedExchange([self._block(it) for it in req[1]], world)
+            px = cache[key] = shard.PackedExchange([shard.exchange_block(self._mesh, it) for it in req.items], world)
         return px
 
-    def _serve(self, req, pending):
-        """One request of a schedule through self.comm (exchange now / begin / await, or an all-reduce)."""
-        if req[0] == "wait":
-            self.comm.finish(pending.pop(req[1]))
-        elif req[0] == "call":
-            req[1]()
-        elif req[0] == "sum":
-            self.comm.all_reduce_sum(req[1])
-        else:
-            px = self._packed(req)
-            if req[2] is None:
-                self.comm.exchange(px)
-            else:
-                pending[req[2]] = self.comm.exchange_begin(px)
-
     def _drain(self, gen):
-        """Run a schedule on this rank: no-op exchanges when unsharded, collectives through self.comm otherwise."""
-        pending = {}
-        for req in gen:
-            self._serve(req, pending)
+        """Run a schedule on this rank: nothing to serve when unsharded, collectives through self.comm otherwise."""
+        schedule.drain(gen, self.comm, self._packed)
 
     def _capture_segments(self, make_gen):
-        """A facet-sharded schedule as a list of (hipGraph, request): the launches between two exchanges are captured
-        into one graph each; the exchanges themselves (row gather + grouped point-to-point, all-reduces) stay eager
-        calls between the replays - a collective is not a graph node here.  The schedule is static (same buffers, same
-        tile lists, same message sizes every step), so the requests recorded with the graphs are replayed as they are."""
-        # (one collection in front of the first capture, the collector off until the last one has ended: a full collection
-        #  per segment - thirty a step and shard - made the capture of an 8-shard step take seconds)
-        with _no_gc_while_capturing():
-            gen = make_gen()
-            segs = []
-            self.segment_nodes = getattr(self, "segment_nodes", [])
-            while True:
-                g = torch.cuda.CUDAGraph(keep_graph=True)
-                # (thread_local: the collective back end's watchdog thread may query its events while this thread captures)
-                # Whether a stretch has launches is only known once it has been captured - library launches and torch
-                # operations alike become nodes, and nothing else sees both - so a stretch of two requests back to back IS
-                # captured; torch's "The CUDA Graph is empty" warning about it is expected here and silenced for exactly
-                # these captures (the graph is dropped below: never instantiated, never replayed).
-                with warnings.catch_warnings():
-                    warnings.filterwarnings("ignore", message="The CUDA Graph is empty")
-                    with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                        try:
-                            req = next(gen)
-                        except StopIteration:
-                            req = None
-                # a stretch WITHOUT launches (two requests back to back, or nothing behind the last one) is no graph at all:
-                # an empty hipGraph is never instantiated or replayed (segment_nodes keeps the counts for the tests)
-                nodes = _graph_node_count(g)
-                if nodes == 0:
-                    g = None
-                else:
-                    g.instantiate()
-                self.segment_nodes.append(nodes)
-                segs.append((g, req))
-                if req is None:
-                    return segs
+        """The schedule make_gen() as hipGraph segments (schedule.capture_segments); their node counts join segment_nodes."""
+        segs, counts = schedule.capture_segments(make_gen)
+        self.segment_nodes += counts
+        return segs
 
     def _replay_segments(self, segs):
-        pending = {}
-        for g, req in segs:
-            if g is not None:
-                g.replay()
-            if req is not None:
-                self._serve(req, pending)
+        self._drain(schedule.replay(segs))
 
-    def _fused_loss_now(self):
-        return self.fused_loss
+    def _capture_angular_segments(self, rotate):
+        """The angular step of a facet-sharded mesh as hipGraph segments, kept as captured["angular"] = ((forward segments,
+        backward segments), rotate).  Run one step eagerly first: lazy one-time set-up inside the library must not happen
+        under capture."""
+        self._own_step_inputs()
+        self._graph_fb = ((self._capture_segments(lambda: self._forward_gen(rotate, self.fused_loss)),
+                           self._capture_segments(lambda: self._loss_backward_gen(rotate))), rotate)
 
     # ------------------------------------------------------------------------------------------
     # public API
@@ -1510,25 +1352,13 @@ class FacetDenoiser:
         """The multi-scale forward as a schedule: the network, then normalizeTensor on the two coarse heads (on a
         facet-sharded run one scalar all-reduce each: utils.py:1705 takes the mean over the whole tensor)."""
         yield from self._forward_gen(rotate)
-        if not self.sharded:
-            self._normalize_coarse_heads()
-            return
-        M, B = self._mesh, self._mesh["B"]
-        for k, level in (("1", 1), ("2", 2)):
-            y, part, sc = B["y" + k], B["abs_part" + k], B["norm_scratch" + k]
-            tot = part.sum().reshape(1)
-            yield ("sum", tot)
-            sc[0:1] = tot / (3.0 * M["n_total"][level]) + 1e-5
-            _lib.check(self.L.fgc_normalize_apply(_p(y), M["ns"][level], _p(sc), _p(B["nconv" + k]), self._st()),
-                       "normalize")
+        for k in ("1", "2"):
+            yield from self._normalize_gen(k)
 
     def _normalize_coarse_heads(self):
         """normalizeTensor on the coarse heads 1 and 2 of an unsharded mesh: y1 / y2 -> nconv1 / nconv2, one launch each."""
-        B, ns = self._mesh["B"], self._mesh["ns"]
         for k in ("1", "2"):
-            y, part, sc = B["y" + k], B["abs_part" + k], B["norm_scratch" + k]
-            _lib.check(self.L.fgc_normalize_fwd(_p(y), ns[int(k)], _p(part), part.numel(), _p(B["nconv" + k]), _p(sc),
-                                                self._st()), "normalize head" + k)
+            self._drain(self._normalize_gen(k))
 
     def forward_multi_scale(self, rotate=False):
         """The multi-scale denoising forward of inferNet (train.py:188-193): the three heads, each through
@@ -1590,7 +1420,7 @@ class FacetDenoiser:
                 "bytes_sent_per_step": stats["bytes"] // steps, "per_collective": each}
 
     def _angular_step(self, rotate):
-        self._drain(self._forward_gen(rotate, defer_normalize=self._fused_loss_now()))
+        self._drain(self._forward_gen(rotate, defer_normalize=self.fused_loss))
         self._drain(self._loss_backward_gen(rotate))
 
     def _run_step(self, form, rotate, capture, enqueue):
@@ -1608,7 +1438,7 @@ class FacetDenoiser:
                 enqueue()
             torch.cuda.current_stream().wait_stream(s)
             graph = torch.cuda.CUDAGraph()
-            with _no_gc_while_capturing(), torch.cuda.graph(graph):
+            with schedule._no_gc_while_capturing(), torch.cuda.graph(graph):
                 enqueue()
             self._mesh["captured"][form] = g = (graph, rotate)
         g[0].replay()
@@ -1627,8 +1457,7 @@ class FacetDenoiser:
             self._own_step_inputs()
             self._angular_step(rotate)
             torch.cuda.synchronize()
-            self._graph_fb = ((self._capture_segments(lambda: self._forward_gen(rotate, self._fused_loss_now())),
-                               self._capture_segments(lambda: self._loss_backward_gen(rotate))), rotate)
+            self._capture_angular_segments(rotate)
         else:
             for segs in g[0]:
                 self._replay_segments(segs)
@@ -1641,13 +1470,7 @@ class FacetDenoiser:
 
     def _angular_loss(self, rotate):
         self._drain(self._forward_gen(rotate))
-        B, L, st = self._mesh["B"], self.L, self._st()
-        gt = B["gt"]
-        if rotate:
-            _lib.check(L.fgc_rotate_rows(_p(B["gt"]), _p(B["gtr"]), self._mesh["ns"][0], 1, _p(B["R"]), st), "rotate gt")
-            gt = B["gtr"]
-        samp = B["sample_ind"]
-        _lib.check(L.fgc_angular_loss_fwd(_p(B["nconv"]), _p(gt), _p(samp), samp.numel(), _p(B["loss"]), st), "loss")
+        self._angular_head("", self._mesh["B"]["sample_ind"], self._st(), rotate=rotate)
 
     def eval_loss(self, rotate=True):
         """Forward + sampled angular loss, no gradients: the validation pass of trainNet (train.py:588-617 runs

@@ -25,6 +25,8 @@ import time
 import numpy as np
 import torch
 
+from . import schedule
+
 
 def _owner_ranges(n2, world):
     """Contiguous split of the coarsest level; level l ranges are these times 4^(2-l)."""
@@ -344,6 +346,30 @@ class PackedExchange:
         self._run(self._row_jobs()[1], "halo unpack")
 
 
+def exchange_block(M, item):
+    """One block of a grouped exchange (PackedExchange) on the bound mesh state M of a shard network, for the item
+    (schedule.Rows / PEdges / Edges) of a request: (src rows, send index, send counts, halo tail, recv counts)."""
+    from ._lib import DL_LD
+    g = M["graphs"][item.level]
+    if item.kind == "edges":
+        dl = M["B"]["dl"][:(g.nnz + g.n_cross_in) * DL_LD].view(-1, DL_LD)
+        return (dl, g.send_edges, g.cross_send_counts, dl[g.nnz:], g.cross_recv_counts)
+    t = item.tensor
+    if t.dtype == torch.bfloat16:
+        # a row of C bf16 channels travels as C / 2 dwords (every exchanged width is even): the copies and the
+        # collective only move bytes
+        t = t.view(torch.float32)
+    if item.kind == "rows":
+        # (parent: a coarse tensor read 4x-upsampled by this level - its tail holds the unique parents of the level's halo nodes)
+        src = g.pair if item.parent else g
+        return (t, src.send_rows, src.send_counts, t[t.shape[0] - src.n_halo:], src.recv_counts)
+    if item.kind == "pedges":
+        # per-pair rows (dt, d-logits) of the pairs whose parent another rank owns: they land behind the owned pairs
+        pg = g.pair
+        return (t, pg.send_edges, pg.cross_send_counts, t[pg.n_pairs:], pg.cross_recv_counts)
+    raise ValueError(item.kind)
+
+
 # ---------------------------------------------------------------------------------------------------
 # exchange back ends
 # ---------------------------------------------------------------------------------------------------
@@ -527,13 +553,13 @@ class SimLatency:
 
 
 def sim_run(nets, make_gen, poison=True, latency=None):
-    """Advance the schedules of all shards; every yielded exchange / all-reduce request is served among them.
+    """Advance the schedules of all shards; every yielded exchange / all-reduce request (schedule.py) is served among them.
 
-    Exchanges and sums are COLLECTIVE: all shards must arrive at them in the same order.  A ("wait", key) is
+    Exchanges and sums are COLLECTIVE: all shards must arrive at them in the same order.  A Wait(key) is
     rank-local (one shard may overlap an exchange with its interior tiles while a peer with a small interior blocks), so
     every generator is advanced to its next collective request on its own.  An overlapped exchange is modelled the way
     the hardware may behave at worst: the rows are packed when it begins, but they only land in the halo tails at the
-    shard's ("wait", key) - and until then the tails hold NaN (`poison`), so a kernel of the overlapped stretch that
+    shard's Wait(key) - and until then the tails hold NaN (`poison`), so a kernel of the overlapped stretch that
     lets a halo row reach a result fails the parity tests instead of reading last step's values."""
     gens = [make_gen(n) for n in nets]
     pending = [dict() for _ in nets]
@@ -546,14 +572,14 @@ def sim_run(nets, make_gen, poison=True, latency=None):
                     clocks[i][key] = latency.start(i)
         while True:
             try:
-                r = next(gens[i])
+                r = schedule.named(next(gens[i]))
             except StopIteration:
                 assert not pending[i], "a begun exchange was never awaited"
                 return None
-            if r[0] == "wait":
-                px = pending[i].pop(r[1])
+            if r.kind == "wait":
+                px = pending[i].pop(r.key)
                 if latency is not None:
-                    torch.cuda.current_stream().wait_event(clocks[i].pop(r[1]))
+                    torch.cuda.current_stream().wait_event(clocks[i].pop(r.key))
                 if getattr(px, "_sim_late", None) is not None:
                     px.recv_buf.copy_(px._sim_late)
                     px._sim_late = None
@@ -566,17 +592,17 @@ def sim_run(nets, make_gen, poison=True, latency=None):
         if all(r is None for r in reqs):
             return
         assert all(r is not None for r in reqs), "shards disagree on the exchange schedule"
-        assert len({r[0] for r in reqs}) == 1, "shards disagree on the exchange schedule"
-        if reqs[0][0] == "call":       # launches a shard makes outside its captured graphs (see net._loss_backward_gen)
+        assert len({r.kind for r in reqs}) == 1, "shards disagree on the exchange schedule"
+        if reqs[0].kind == "call":       # launches a shard makes outside its captured graphs (see net._loss_backward_gen)
             for r in reqs:
-                r[1]()
+                r.fn()
             continue
-        if reqs[0][0] == "sum":
-            tot = reqs[0][1].clone()
+        if reqs[0].kind == "sum":
+            tot = reqs[0].tensor.clone()
             for r in reqs[1:]:
-                tot += r[1]
+                tot += r.tensor
             for i, r in enumerate(reqs):
-                r[1].copy_(tot)
+                r.tensor.copy_(tot)
                 if latency is not None:
                     latency.stall(i)     # (an all-reduce blocks every rank: one stall per shard on the shared stream)
             continue
@@ -587,7 +613,7 @@ def sim_run(nets, make_gen, poison=True, latency=None):
             ro = np.cumsum([0] + pd.recv_splits)
             # an overlapped exchange that receives straight into a halo tail (PackedExchange.direct) is held back in a
             # staging buffer until the shard's wait, like the unpack of the others
-            late = pd.direct and reqs[dst][2] is not None
+            late = pd.direct and reqs[dst].key is not None
             target = torch.empty_like(pd.recv_buf) if late else pd.recv_buf
             for src, ps in enumerate(pxs):
                 if src == dst or not pd.recv_splits[src]:
@@ -597,19 +623,19 @@ def sim_run(nets, make_gen, poison=True, latency=None):
                 target[ro[src]:ro[src + 1]].copy_(ps.send_buf[so[dst]:so[dst + 1]])
             pd._sim_late = target if late else None
         for i, (px, r) in enumerate(zip(pxs, reqs)):
-            if r[2] is None:
+            if r.key is None:
                 if latency is not None:
                     latency.stall(i)
                 px.unpack()
             else:
-                assert r[2] not in pending[i], "two exchanges in flight under one key"
-                pending[i][r[2]] = px
+                assert r.key not in pending[i], "two exchanges in flight under one key"
+                pending[i][r.key] = px
                 if poison:
                     px.poison_tails()
 
 
 def sim_forward_backward(nets, rotate=True, latency=None):
-    sim_run(nets, lambda n: n._forward_gen(rotate, n._fused_loss_now()), latency=latency)
+    sim_run(nets, lambda n: n._forward_gen(rotate, n.fused_loss), latency=latency)
     sim_run(nets, lambda n: n._loss_backward_gen(rotate), latency=latency)
 
 
@@ -619,22 +645,11 @@ def sim_forward_multi_scale(nets, rotate=False):
 
 def sim_forward_backward_captured(nets, rotate=True, latency=None):
     """The step of sim_forward_backward with every shard's launches replayed from its hipGraph segments (one graph per
-    stretch between two exchanges, net._capture_segments), the requests served between the replays - what
+    stretch between two exchanges, schedule.capture_segments), the requests served between the replays - what
     `forward_backward(capture=True)` does on a sharded rank, with the simulated exchange in place of the communicator.
     Run one eager step first: one-time set-up inside the library must not happen under capture."""
     for n in nets:
         if n._graph_fb is None:
-            n._own_step_inputs()
-            n._graph_fb = ((n._capture_segments(lambda: n._forward_gen(rotate, n._fused_loss_now())),
-                            n._capture_segments(lambda: n._loss_backward_gen(rotate))), rotate)
-
-    def replay(segs):
-        for g, req in segs:
-            if g is not None:        # (a stretch without launches is no graph: net._capture_segments)
-                g.replay()
-            if req is not None:
-                yield req
-
-    sim_run(nets, lambda n: replay(n._graph_fb[0][0]), latency=latency)
-    sim_run(nets, lambda n: replay(n._graph_fb[0][1]), latency=latency)
-
+            n._capture_angular_segments(rotate)
+    sim_run(nets, lambda n: schedule.replay(n._graph_fb[0][0]), latency=latency)
+    sim_run(nets, lambda n: schedule.replay(n._graph_fb[0][1]), latency=latency)

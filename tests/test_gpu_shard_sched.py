@@ -273,7 +273,7 @@ def test_no_schedule_segment_is_an_empty_graph_and_back_to_back_requests_run(gol
     loss end issues ("call", samples) and ("sum", table) back to back, and nothing follows the last all-reduce - is
     recorded as no graph at all, and every graph that IS instantiated and replayed holds at least one node.  The schedule
     with those back-to-back requests then replays twice, bit-identical to eager."""
-    from facet_graph_convolution_amd import net as netmod
+    from facet_graph_convolution_amd import schedule as netmod
     monkeypatch.setenv("FGC_SPLIT_MIN_TILES", "0")
     x, adjs, gt = _prep(golden_dir, "ico3")
     z = np.load(os.path.join(golden_dir, "net_ico3.npz"))
@@ -295,6 +295,45 @@ def test_no_schedule_segment_is_an_empty_graph_and_back_to_back_requests_run(gol
         assert bwd[-1][1] is None and bwd[-1][0] is None, "nothing is launched behind the last all-reduce"
 
 
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_a_step_leaves_no_partial_call_behind(golden_dir, dtype, monkeypatch):
+    """Every split layer runs partial calls: tile lists and projection ranges in its descriptor, data tile lists and staged
+    flags in its backward io.  A field left behind would make the layer run a partial call in the NEXT step.  With every
+    layer forced to split (threshold 0), after an eager step and after a step captured into and replayed from hipGraph
+    segments: the descriptors' tile_list / n_tiles / proj_row0 / proj_rows and the ios' data_tile_list / n_data_tiles are
+    None / 0 as they were bound, every io's flags are what the first step left, and the second step - same inputs -
+    gives the first one's gradient bit for bit."""
+    from facet_graph_convolution_amd.shard import make_sim_shards, sim_forward_backward, sim_forward_backward_captured
+    monkeypatch.setenv("FGC_SPLIT_MIN_TILES", "0")
+    x, adjs, gt = _prep(golden_dir, "ico3")
+    z = np.load(os.path.join(golden_dir, "net_ico3.npz"))
+    nets = make_sim_shards(x, adjs, gt, 2, "cuda:0", 0, dtype=dtype)
+    for n in nets:
+        n.set_rotation(z["R"])
+        n.set_samples(z["sample_ind"])
+    assert _took_the_split_branch(nets) == (7, 7)
+
+    def fields(n):
+        M = n._mesh
+        return ({k: (d.tile_list, d.n_tiles, d.proj_row0, d.proj_rows) for k, d in M["descs"].items()},
+                {k: (io.data_tile_list, io.n_data_tiles) for k, io in M["ios"].items()},
+                {k: io.flags for k, io in M["ios"].items()})
+    bound = [fields(n) for n in nets]
+    for descs, tiles, _ in bound:
+        assert set(descs.values()) == {(None, 0, 0, 0)} and set(tiles.values()) == {(None, 0)}
+    sim_forward_backward(nets, rotate=True)
+    torch.cuda.synchronize()
+    first = [(fields(n), n.params.grad.clone()) for n in nets]
+    sim_forward_backward_captured(nets, rotate=True)
+    torch.cuda.synchronize()
+    for n, b, (f, grad) in zip(nets, bound, first):
+        for descs, tiles, flags in (f, fields(n)):
+            assert descs == b[0] and tiles == b[1], "a step left a partial call behind"
+            assert flags == f[2], "the second step left other io.flags behind than the first"
+        assert np.isfinite(grad.cpu().numpy()).all()
+        assert torch.equal(n.params.grad, grad), "the second step's gradient differs from the first's"
+
+
 def test_capture_is_not_interrupted_by_the_garbage_collector():
     """The round-3 abort, as the stack of its round-4 recurrence shows it: Python's cyclic collector ran inside a segment
     capture (`Garbage-collecting` under net._capture_segments) and freed a dead cycle that owned an earlier network's
@@ -309,7 +348,7 @@ def test_capture_is_not_interrupted_by_the_garbage_collector():
     assert out.returncode == 0 and "probe ok (guard)" in out.stdout, out.stdout[-1500:] + out.stderr[-3000:]
     # in-process: the collector is off inside the guard and back on after it
     import gc
-    from facet_graph_convolution_amd.net import _no_gc_while_capturing
+    from facet_graph_convolution_amd.schedule import _no_gc_while_capturing
     assert gc.isenabled()
     with _no_gc_while_capturing():
         assert not gc.isenabled()

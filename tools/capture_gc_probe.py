@@ -4,7 +4,7 @@ stack shows it: a dead cycle [network -> its captured segm
 net._capture_segments; its destructors call hipGraphExecDestroy / hipGraphDestroy / hipFree while the stream captures.
 
 usage: python tools/capture_gc_probe.py [guard|noguard]
-  guard    (default) the capture runs under net._no_gc_while_capturing: must print "probe ok"
+  guard    (default) the capture runs under schedule._no_gc_while_capturing: must print "probe ok"
   noguard  FGC_NO_CAPTURE_GC_GUARD=1: the collector is forced to run inside the capture (gc.set_threshold(1))"""
 import gc, os, sys
 mode = sys.argv[1] if len(sys.argv) > 1 else "guard"
@@ -46,7 +46,7 @@ nets = shards()
 gc.set_threshold(10 ** 9, 10 ** 9, 10 ** 9)
 gc.enable()
 # 2. the collector "fires" at the first schedule tag INSIDE a capture - if it is enabled there, as an allocation-count trigger
-#    would find it (net._no_gc_while_capturing turns it off for the capture and has collected before it)
+#    would find it (schedule._no_gc_while_capturing turns it off for the capture and has collected before it)
 from facet_graph_convolution_amd.net import FacetDenoiser
 fired = []
 orig_tag = FacetDenoiser._tag

@@ -43,7 +43,8 @@ def main():
     ap.add_argument("--double-loss", action="store_true")
     args = ap.parse_args()
     from facet_graph_convolution_amd import ops
-    from facet_graph_convolution_amd.net import FacetDenoiser, _graph_node_count
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    from facet_graph_convolution_amd.schedule import _graph_node_count
     from facet_graph_convolution_amd.dataClasses import TrainingSet
     from facet_graph_convolution_amd.meshgen import torus, add_noise
     from facet_graph_convolution_amd.utils import rand_rotation_matrix
