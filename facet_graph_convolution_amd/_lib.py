@@ -12,7 +12,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("FGC_LIB", os.path.join(_HERE, "csrc", "libfgc.so"))  # FGC_LIB: developer A/B builds
 
-ABI_VERSION = 115  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
+ABI_VERSION = 116  # FGC_ABI_VERSION of the include/fgc.h this binding was written against
 FGC_M = 9
 AG_LD = 24
 DL_LD = 12
@@ -137,6 +137,10 @@ _SIGS = {
     "fgc_edge_map": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "fgc_vertex_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                     C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p]),
+    "fgc_vertex_update_dir_workspace_floats": (C.c_size_t, [C.c_int32]),
+    "fgc_vertex_update_dir": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p,
+                                        C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                        C.c_int32, C.c_float, C.c_void_p]),
     "fgc_metis_one_level": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                       C.c_int32, C.c_void_p, C.c_void_p]),
     "fgc_hierarchy_build": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,

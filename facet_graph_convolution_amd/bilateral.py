@@ -3,7 +3,7 @@
 
     python -m facet_graph_convolution_amd.bilateral NOISY_DIR RESULTS_DIR
            [--iterations 10] [--sigma-s 1.0] [--sigma-r 0.35] [--vertex-iterations 60] [--slices auto|N] [--overwrite]
-           [--guided]
+           [--guided] [--view-dir X,Y,Z | --camera X,Y,Z]
 
 For each `name.obj`: face centres and areas of the noisy mesh (kept fixed), `--iterations` passes of the filter over
 the face normals (fgc_bilateral_filter; centres, areas and cells stay on the device between passes), then
@@ -23,6 +23,10 @@ consistent patch (a face and the faces that share a vertex with it) among the pa
 (include/fgc.h: fgc_guided_normals).  The guidance is recomputed from the current normals before every pass, on the
 device.  It pays at high noise and loses to the plain filter at low noise (README); the other defaults stay as they are,
 and nobody has tuned --sigma-s, --sigma-r or --iterations for this mode either.
+
+--view-dir / --camera (depth-scan mode, README "Depth scans"): the mesh is a depth scan seen along one direction, or from a
+camera position given in the mesh's raw units.  The viewing rays are built from the NOISY input's vertices
+(utils.view_rays) and the vertex iterations become update_position_with_depth's: every vertex moves along its ray only.
 """
 import argparse
 import os
@@ -43,7 +47,7 @@ def auto_slices(Fc, sigma_s):
 
 
 def denoise_mesh(V, faces, iterations=10, sigma_s=1.0, sigma_r=0.35, vertex_iterations=60, slices="auto", timings=None,
-                 guided=False):
+                 guided=False, depth_dir=None):
     """(V_out float32 [V,3], normals float32 [F,3]): `iterations` bilateral passes over the face normals of the mesh
     (sigma_s in mean edge lengths), then `vertex_iterations` iterations of update_position2.  slices: "auto", an int or
     a 3-tuple (module docstring).  Raises RuntimeError for a mesh with a vertex of more than MAX_EDGES edges.
@@ -51,11 +55,13 @@ def denoise_mesh(V, faces, iterations=10, sigma_s=1.0, sigma_r=0.35, vertex_iter
     pass computes its guidance from the current normals there, nothing is read back between passes.  A ring of more than
     utils.GUIDED_MAX_RING faces raises the same RuntimeError.
     timings (a dict, optional) receives the wall seconds of 'host', 'filter' (all passes, guidance included) and 'vertex',
-    and 'guidance', the device time of the guidance launches alone (0 without guided)."""
+    and 'guidance', the device time of the guidance launches alone (0 without guided).
+    depth_dir ([V,3] or [1,3] viewing rays, utils.view_rays): the vertex iterations are update_position_with_depth's, every
+    vertex moves along its ray only."""
     import torch
     from . import ops, utils
     from .settings import MAX_EDGES
-    from .train import update_position2
+    from .train import update_position2, depth_update
     if iterations < 0 or vertex_iterations < 0:
         raise ValueError("iterations and vertex_iterations must be >= 0")
     if not sigma_s > 0 or not (sigma_r > 0 or sigma_r == -1):
@@ -100,16 +106,21 @@ def denoise_mesh(V, faces, iterations=10, sigma_s=1.0, sigma_r=0.35, vertex_iter
     torch.cuda.synchronize()
     t2 = time.time()
     guidance = sum(b.elapsed_time(e) for b, e in marks) / 1000.0
-    pts = update_position2(put(V, np.float32).unsqueeze(0), n.unsqueeze(0), put(e_map, np.int32).unsqueeze(0),
-                           put(v_e_map, np.int32).unsqueeze(0), iter_num=vertex_iterations, max_edges=MAX_EDGES)
+    if depth_dir is not None:
+        pts = depth_update(put(V, np.float32), n, put(e_map, np.int32).unsqueeze(0), put(v_e_map, np.int32).unsqueeze(0),
+                           depth_dir, vertex_iterations).unsqueeze(0)
+    else:
+        pts = update_position2(put(V, np.float32).unsqueeze(0), n.unsqueeze(0), put(e_map, np.int32).unsqueeze(0),
+                               put(v_e_map, np.int32).unsqueeze(0), iter_num=vertex_iterations, max_edges=MAX_EDGES)
     out = pts[0].cpu().numpy(), n.cpu().numpy()
     if timings is not None:
         timings.update(host=t1 - t0, filter=t2 - t1, vertex=time.time() - t2, grid=grid, guidance=guidance)
     return out
 
 
-def denoise_file(noisy_dir, filename, results_dir, overwrite=False, log=print, **params):
-    from .utils import load_mesh, write_mesh
+def denoise_file(noisy_dir, filename, results_dir, overwrite=False, log=print, view=None, **params):
+    """view: {} / None, or the keywords of utils.view_rays ({'view_dir': xyz} or {'camera': xyz}): depth-scan mode."""
+    from .utils import load_mesh, write_mesh, view_rays
     out_name = filename[:-4] + "_denoised.obj"
     out_path = os.path.join(results_dir, out_name)
     if os.path.isfile(out_path) and not overwrite:
@@ -118,6 +129,8 @@ def denoise_file(noisy_dir, filename, results_dir, overwrite=False, log=print, *
     V, _, _, faces, _ = load_mesh(noisy_dir, filename, 0, False)
     faces = np.array(faces).astype(np.int32)
     tm = {}
+    if view:
+        params["depth_dir"] = view_rays(V, **view)
     try:
         points, _ = denoise_mesh(V, faces, timings=tm, **params)
     except RuntimeError as e:
@@ -145,7 +158,7 @@ def _slices_arg(text):
 
 
 def main(argv=None):
-    from .utils import BILATERAL_MAX_SLICES, bilateral_grid
+    from .utils import BILATERAL_MAX_SLICES, bilateral_grid, view_options, view_spec
     ap = argparse.ArgumentParser(prog="python -m facet_graph_convolution_amd.bilateral",
                                  description=__doc__.split("\n")[0])
     ap.add_argument("noisy_dir")
@@ -160,7 +173,9 @@ def main(argv=None):
     ap.add_argument("--overwrite", action="store_true")
     ap.add_argument("--guided", action="store_true",
                     help="guided normal filtering: the range term reads a guidance normal (a build extension; untuned)")
+    view_options(ap)
     args = ap.parse_args(argv)
+    view = view_spec(ap, args)
     if not args.sigma_s > 0:
         ap.error("--sigma-s must be > 0")
     if not (args.sigma_r > 0 or args.sigma_r == -1):
@@ -178,7 +193,7 @@ def main(argv=None):
             print("processing noisy file: " + f)
             denoise_file(args.noisy_dir, f, args.results_dir, args.overwrite, iterations=args.iterations,
                          sigma_s=args.sigma_s, sigma_r=args.sigma_r, vertex_iterations=args.vertex_iterations,
-                         slices=args.slices, guided=args.guided)
+                         slices=args.slices, guided=args.guided, view=view)
 
 
 if __name__ == "__main__":

@@ -51,6 +51,60 @@ __global__ __launch_bounds__(256) void vertex_update_kernel(const float* __restr
     xo[3 * (size_t)i + 2] = xi2 + lambda * a2;
 }
 
+// The same walk with every contribution projected onto the vertex' own direction d_i (update_position_with_depth,
+// train.py:1561-1665: a vertex of a depth scan moves along its viewing ray only).  The state of a vertex is ONE scalar,
+// t_i = the signed step along d_i accumulated so far: t_i += lambda * sum_s (u_s . d_i) in slot order, and the position is
+// always rebuilt from the INPUT position, x_i = fma(t_i, d_i, x0_i) - never previous iterate + step, so a vertex stays
+// within one rounding of its ray whatever the iteration count.  d is used as given (unit or not): sum (u . d) d.
+// x: the previous iterate (x0 itself in the first iteration, `first`: t is not read then); t is private to its thread and
+// updated in place; dstride: 3, or 0 for one direction shared by every vertex.
+__global__ __launch_bounds__(256) void vertex_update_dir_kernel(const float* __restrict__ x0, const float* __restrict__ x,
+                                                                float* __restrict__ xo, float* __restrict__ t,
+                                                                float* __restrict__ t_out, int nv,
+                                                                const float* __restrict__ nrm, int nf,
+                                                                const int4* __restrict__ emap, int ne,
+                                                                const int* __restrict__ vemap, int max_edges,
+                                                                const float* __restrict__ dirs, int dstride, float lambda,
+                                                                int first) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    const float xi0 = x[3 * (size_t)i], xi1 = x[3 * (size_t)i + 1], xi2 = x[3 * (size_t)i + 2];
+    const float* dir = dirs + (size_t)i * dstride;
+    const float e0 = dir[0], e1 = dir[1], e2 = dir[2];
+    float acc = 0.f;
+    const int* slots = vemap + (size_t)i * max_edges;
+    for (int s = 0; s < max_edges; ++s) {
+        const int e = slots[s];
+        if (e < 0 || e >= ne) continue;           // unused slot, as in vertex_update_kernel
+        const int4 em = emap[e];
+        const int j = em.x == i ? em.y : em.x;    // the endpoint that is i itself contributes zero
+        if (j < 0 || j >= nv) continue;
+        const float d0 = x[3 * (size_t)j] - xi0, d1 = x[3 * (size_t)j + 1] - xi1, d2 = x[3 * (size_t)j + 2] - xi2;
+        float u0 = 0.f, u1 = 0.f, u2 = 0.f;
+        if (em.z >= 0 && em.z < nf) {
+            const float n0 = nrm[3 * (size_t)em.z], n1 = nrm[3 * (size_t)em.z + 1], n2 = nrm[3 * (size_t)em.z + 2];
+            const float dp = (d0 * n0 + d1 * n1) + d2 * n2;
+            u0 = n0 * dp;
+            u1 = n1 * dp;
+            u2 = n2 * dp;
+        }
+        if (em.w >= 0 && em.w < nf) {              // a boundary edge has f2 = -1
+            const float n0 = nrm[3 * (size_t)em.w], n1 = nrm[3 * (size_t)em.w + 1], n2 = nrm[3 * (size_t)em.w + 2];
+            const float dp = (d0 * n0 + d1 * n1) + d2 * n2;
+            u0 += n0 * dp;
+            u1 += n1 * dp;
+            u2 += n2 * dp;
+        }
+        acc += (u0 * e0 + u1 * e1) + u2 * e2;
+    }
+    const float ti = (first ? 0.f : t[i]) + lambda * acc;
+    t[i] = ti;
+    if (t_out) t_out[i] = ti;
+    xo[3 * (size_t)i] = fmaf(ti, e0, x0[3 * (size_t)i]);
+    xo[3 * (size_t)i + 1] = fmaf(ti, e1, x0[3 * (size_t)i + 1]);
+    xo[3 * (size_t)i + 2] = fmaf(ti, e2, x0[3 * (size_t)i + 2]);
+}
+
 // ---------------------------------------------------------------------------------------------
 // multi-scale vertex update (update_position_MS, train.py:1668-1798)
 // ---------------------------------------------------------------------------------------------
@@ -384,6 +438,51 @@ extern "C" int fgc_vertex_update(const float* x, float* x_out, float* tmp, int32
         src = dst;
     }
     FGC_CHECK_LAUNCH("fgc_vertex_update");
+    return FGC_OK;
+}
+
+extern "C" size_t fgc_vertex_update_dir_workspace_floats(int32_t nv) {
+    return nv > 0 ? 4 * (size_t)nv : 0;      // one ping-pong position buffer [nv,3] and t [nv]
+}
+
+extern "C" int fgc_vertex_update_dir(const float* x, float* x_out, float* t_out, float* ws, size_t ws_floats, int32_t nv,
+                                     const float* normals, int32_t nf, const int32_t* e_map, int32_t ne,
+                                     const int32_t* v_e_map, int32_t max_edges, const float* dirs, int32_t n_dirs,
+                                     int32_t iters, float lambda, void* stream) {
+    FGC_CHECK_ARG(x && x_out && ws && normals && v_e_map && dirs && (e_map || ne == 0),
+                  "fgc_vertex_update_dir: null pointer");
+    FGC_CHECK_ARG(nv > 0 && nf > 0 && ne >= 0 && max_edges > 0 && iters >= 0,
+                  "fgc_vertex_update_dir: nv=%d nf=%d ne=%d max_edges=%d iters=%d", nv, nf, ne, max_edges, iters);
+    FGC_CHECK_ARG(n_dirs == 1 || n_dirs == nv, "fgc_vertex_update_dir: n_dirs=%d (1, or nv=%d)", n_dirs, nv);
+    const size_t need = fgc_vertex_update_dir_workspace_floats(nv);
+    FGC_CHECK_ARG(ws_floats >= need, "fgc_vertex_update_dir: workspace too small (%zu < %zu floats)", ws_floats, need);
+    FGC_CHECK_ARG(x != x_out && (x + 3 * (size_t)nv <= ws || x >= ws + need) &&
+                      (x_out + 3 * (size_t)nv <= ws || x_out >= ws + need),
+                  "fgc_vertex_update_dir: x, x_out and the workspace must be distinct");
+    FGC_CHECK_ARG(!t_out || (t_out != x && t_out != x_out && (t_out + nv <= ws || t_out >= ws + need)),
+                  "fgc_vertex_update_dir: t_out must be a buffer of its own");
+    FGC_CHECK_ARG((uintptr_t)e_map % 16 == 0, "fgc_vertex_update_dir: e_map needs 16-byte alignment");
+    hipStream_t st = (hipStream_t)stream;
+    if (iters == 0) {
+        if (hipMemcpyAsync(x_out, x, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+            (t_out && hipMemsetAsync(t_out, 0, (size_t)nv * 4, st) != hipSuccess)) {
+            fgc::set_error("fgc_vertex_update_dir: copy failed");
+            return FGC_EHIP;
+        }
+        return FGC_OK;
+    }
+    float* tmp = ws;
+    float* t = ws + 3 * (size_t)nv;
+    const float* src = x;
+    for (int it = 0; it < iters; ++it) {
+        const bool last = it == iters - 1;
+        float* dst = ((iters - 1 - it) & 1) ? tmp : x_out;   // the last iteration lands in x_out
+        FGC_LAUNCH("vertex_update_dir_kernel", st, vertex_update_dir_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, x, src, dst,
+                   t, last ? t_out : (float*)nullptr, nv, normals, nf, reinterpret_cast<const int4*>(e_map), ne, v_e_map,
+                   max_edges, dirs, n_dirs == 1 ? 0 : 3, lambda, it == 0 ? 1 : 0);
+        src = dst;
+    }
+    FGC_CHECK_LAUNCH("fgc_vertex_update_dir");
     return FGC_OK;
 }
 

@@ -1,6 +1,6 @@
 """Denoise every OBJ of a folder (the reference's infer.py:40-100 for the face-normal network, withVerts = False):
 
-    python -m facet_graph_convolution_amd.infer NOISY_DIR RESULTS_DIR NETWORK.pt
+    python -m facet_graph_convolution_amd.infer NOISY_DIR RESULTS_DIR NETWORK.pt [--view-dir X,Y,Z | --camera X,Y,Z]
 
 For each `name.obj`: preprocess (native adjacency + coarsening), predict the facet normals, move the vertices with 60
 iterations of update_position2, write `name_denoised.obj` (same faces) and, like the reference,
@@ -10,6 +10,11 @@ Existing results are skipped unless --overwrite (B_OVERWRITE_RESULT, settings.py
 With --with-vertices (the reference's withVerts branch) the network is the multi-scale one (trainAccuracyNet's): inferNet
 moves the vertices with update_position_MS and writes `name_denoised.obj`, `name_d_mid.obj` and `name_d_coarse.obj`
 (the positions after the fine, the middle and the coarse stage).
+
+--view-dir / --camera (depth-scan mode, README "Depth scans"): the mesh is a depth scan seen along one direction, or from a
+camera position given in the mesh's raw units.  The viewing rays are built from the NOISY input's vertices
+(utils.view_rays) and the 60 iterations are update_position_with_depth's: every vertex moves along its ray only.  Not with
+--with-vertices: the multi-scale update has no ray-constrained form (nor has the reference).
 """
 import argparse
 import os
@@ -18,10 +23,11 @@ import time
 import numpy as np
 
 
-def denoise_file(net, noisy_dir, filename, results_dir, overwrite=False, log=print):
+def denoise_file(net, noisy_dir, filename, results_dir, overwrite=False, log=print, view=None):
+    """view: {} / None, or the keywords of utils.view_rays ({'view_dir': xyz} or {'camera': xyz}): depth-scan mode."""
     from .dataClasses import InferenceMesh
     from .train import inferNetOld
-    from .utils import write_mesh
+    from .utils import write_mesh, view_rays
     out_name = filename[:-4] + "_denoised.obj"
     out_path = os.path.join(results_dir, out_name)
     if os.path.isfile(out_path) and not overwrite:
@@ -32,7 +38,8 @@ def denoise_file(net, noisy_dir, filename, results_dir, overwrite=False, log=pri
     mesh.addMesh(noisy_dir, filename)
     log("mesh added (%.0f ms): %d faces" % (1000 * (time.time() - t0), mesh.faces.shape[0]))
     t0 = time.time()
-    points, normals = inferNetOld(mesh, net, update_vertices=True)
+    rays = view_rays(np.asarray(mesh.vertices).reshape(-1, 3), **view) if view else None
+    points, normals = inferNetOld(mesh, net, update_vertices=True, depth_dir=rays)
     log("Inference complete (%.0f ms)" % (1000 * (time.time() - t0)))
     write_mesh(points, mesh.faces, out_path)
     np.savetxt(os.path.join(results_dir, filename[:-4] + "_normals.txt"), normals, fmt="%.6f")
@@ -69,7 +76,13 @@ def main(argv=None):
     ap.add_argument("--overwrite", action="store_true")
     ap.add_argument("--with-vertices", action="store_true",
                     help="multi-scale network + update_position_MS (a network trained by trainAccuracyNet)")
+    from .utils import view_options, view_spec
+    view_options(ap)
     args = ap.parse_args(argv)
+    view = view_spec(ap, args)
+    if view and args.with_vertices:
+        ap.error("--view-dir / --camera go with the single-scale vertex update: the multi-scale update of --with-vertices "
+                 "has no ray-constrained form")
     from .net import FacetDenoiser
     from .train import load_checkpoint
     net = FacetDenoiser("cuda:0", multi_scale=args.with_vertices)
@@ -79,7 +92,7 @@ def main(argv=None):
     for f in sorted(os.listdir(args.noisy_dir)):
         if f.endswith(".obj"):
             print("processing noisy file: " + f)
-            run(net, args.noisy_dir, f, args.results_dir, args.overwrite)
+            run(net, args.noisy_dir, f, args.results_dir, args.overwrite, **({"view": view} if view else {}))
 
 
 if __name__ == "__main__":

@@ -2,7 +2,8 @@
 downloads that ship their noisy meshes):
 
     python -m facet_graph_convolution_amd.makeNoisy CLEAN_DIR OUT_DIR [--levels 0.1,0.2,0.3] [--seed S]
-        [--direction random|normal] [--lf-levels 0.3,0.2,0.1] [--lf-width 3] [--lf-bumps K] [--overwrite]
+        [--direction random|normal|ray] [--view-dir X,Y,Z | --camera X,Y,Z]
+        [--lf-levels 0.3,0.2,0.1] [--lf-width 3] [--lf-bumps K] [--overwrite]
 
 For every `name.obj` of CLEAN_DIR (sorted) and level k = 1, 2, ... the file `name_n<k>.obj` with the input's faces and
 its vertices displaced by Gaussian noise of standard deviation level x mean edge length - the names getGTFilename,
@@ -12,6 +13,10 @@ meshes trainNet(noise_levels=...) validates on when the same folder was preproce
 --lf-levels (one value, or one per level; level 0 in --levels gives bumps alone) adds the low-frequency field of
 ops.synth_noise_lf (include/fgc.h: fgc_synth_noise_lf): file `_n<k>` is the pair (level k, lf level k), what
 trainNet(noise_levels=..., lf_levels=...) validates on.  Existing files are skipped unless --overwrite.
+--direction ray (with --view-dir or --camera; README "Depth scans") displaces every vertex along its viewing ray, the
+noise of a depth sensor.  The rays are built from the CLEAN vertices (utils.view_rays), as `train --noise-direction ray`
+builds them, so the files stay the validation meshes of a training run with the same seed and view.  The low-frequency
+bumps keep going along the clean vertex normals.
 """
 import argparse
 import os
@@ -26,27 +31,33 @@ def make_noisy(V, faces, level, seed=0, stream=0, step=0, direction="random", de
     """The vertices V [V,3] of a clean mesh displaced at `level` x its mean edge length: float32 numpy [V,3].  lf_level
     (None: white noise only): plus the low-frequency field of RMS lf_level mean edge lengths, bumps of width lf_width mean
     edge lengths, lf_bumps of them (None: ceil(faces / 6)) - what FacetDenoiser.set_noise(step, level, lf_level) makes on
-    a mesh bound with lf=(lf_width, lf_bumps)."""
+    a mesh bound with lf=(lf_width, lf_bumps).  direction: "random", "normal" (the area-weighted vertex normals) or a
+    [V,3] array of unit rows, e.g. the viewing rays of utils.view_rays (finite, every norm within 1e-3 of 1): the white
+    noise goes along them.  The low-frequency bumps go along the clean vertex normals whatever the white direction."""
     import torch
     from . import ops
-    from .utils import getAverageEdgeLength, areaWeightedVertexNormals
+    from .utils import getAverageEdgeLength, areaWeightedVertexNormals, check_directions
     V = np.ascontiguousarray(np.asarray(V, dtype=np.float32))
-    if direction not in ("random", "normal"):
-        raise ValueError("direction must be 'random' or 'normal'")
+    rays = None
+    if not isinstance(direction, str):
+        rays = torch.as_tensor(check_directions(direction, V.reshape(-1, 3).shape[0]), device=device)
+    elif direction not in ("random", "normal"):
+        raise ValueError("direction must be 'random', 'normal' or a [V,3] array of unit rows")
     edge_len = getAverageEdgeLength(V, faces)[0]
     sigma = np.float32(level) * np.float32(edge_len)
     normals = None
-    if direction == "normal" or lf_level is not None:
+    if (rays is None and direction == "normal") or lf_level is not None:
         normals = torch.as_tensor(areaWeightedVertexNormals(V, faces).astype(np.float32), device=device)
     Vd = torch.as_tensor(V, device=device)
     if lf_level is None:
-        out = ops.synth_noise(Vd, sigma, step, seed=seed, stream=stream, normals=normals)
+        out = ops.synth_noise(Vd, sigma, step, seed=seed, stream=stream, normals=normals if rays is None else rays)
     else:
         if not (np.isfinite(lf_level) and lf_level >= 0):
             raise ValueError("lf_level must be finite and >= 0 (got %r)" % (lf_level,))
         K, width, area = ops.lf_plan(V, faces, edge_len, lf_width, lf_bumps)
         out = ops.synth_noise_lf(Vd, normals, sigma, step, ops.lf_amplitude(lf_level, edge_len, width, K, area), width, K,
-                                 seed=seed, stream=stream, white_normals=normals if direction == "normal" else None)
+                                 seed=seed, stream=stream,
+                                 white_normals=rays if rays is not None else normals if direction == "normal" else None)
     return out.cpu().numpy()
 
 
@@ -68,13 +79,19 @@ def main(argv=None):
     ap.add_argument("--levels", default=",".join(str(l) for l in DEFAULT_LEVELS),
                     help="comma-separated multiples of the mean edge length, at most 9 (default %(default)s)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--direction", choices=("random", "normal"), default="random")
+    ap.add_argument("--direction", choices=("random", "normal", "ray"), default="random",
+                    help="ray: along the viewing rays of --view-dir / --camera, built from the clean vertices")
+    from .utils import view_options, view_spec, view_rays
+    view_options(ap)
     ap.add_argument("--lf-levels", default=None, help="low-frequency noise on top: comma-separated RMS levels in mean "
                     "edge lengths, one or one per --levels entry (pair k = level k with lf level k)")
     ap.add_argument("--lf-width", type=float, default=3.0, help="bump width in mean edge lengths (default %(default)s)")
     ap.add_argument("--lf-bumps", type=int, default=None, help="bumps per mesh (default: faces / 6, rounded up)")
     ap.add_argument("--overwrite", action="store_true")
     args = ap.parse_args(argv)
+    view = view_spec(ap, args)
+    if (args.direction == "ray") != bool(view):
+        ap.error("--direction ray needs --view-dir or --camera, and the two go with --direction ray only")
     try:
         levels = [float(t) for t in args.levels.split(",")]
     except ValueError:
@@ -98,12 +115,15 @@ def main(argv=None):
     written = []
     for i, f in enumerate(sorted(n for n in os.listdir(args.clean_dir) if n.endswith(".obj"))):
         V, _, _, faces, _ = load_mesh(args.clean_dir, f, 0, False)
+        direction = args.direction
+        if view:        # (one ray per vertex: the synthesis kernel reads a [V,3] table)
+            direction = np.ascontiguousarray(np.broadcast_to(view_rays(V, **view), np.asarray(V).shape))
         for k, level in enumerate(levels):
             out = os.path.join(args.out_dir, "%s_n%d.obj" % (f[:-4], k + 1))
             if os.path.isfile(out) and not args.overwrite:
                 print("Skipping %s. File already exists." % os.path.basename(out))
                 continue
-            write_mesh(make_noisy(V, faces, level, args.seed, 1 + i, k, args.direction, lf_level=lf_levels[k],
+            write_mesh(make_noisy(V, faces, level, args.seed, 1 + i, k, direction, lf_level=lf_levels[k],
                                   lf_width=args.lf_width, lf_bumps=args.lf_bumps), faces, out)
             written.append(out)
     return written

@@ -29,6 +29,7 @@ import torch
 from . import _lib, ops, require_graph_replay_safe, schedule, shard
 from ._lib import ConvDesc, ConvBwdIO, AG_LD, DL_LD, FGC_M
 from .graph import FacetGraph, as_graph
+from .utils import check_directions, direction_key
 
 LRELU_ALPHA = 0.1      # model.py:846
 STD_W, STD_B = 0.05, 0.01  # model.py:17-18
@@ -588,11 +589,14 @@ class FacetDenoiser:
         state kept with the mesh: the clean vertices verts [V,3], faces_rows int [N0,3] (the faces in node order, -1 rows
         = fake nodes: TrainingSet.addCleanMesh's clean_faces_rows), the mean edge length edge_len (a noise level is a
         multiple of it), the Philox key `seed` and `stream` id (training 0, validation mesh i 1 + i) and the
-        direction - "random", or "normal": along the clean mesh's area-weighted vertex normals.  x: the clean mesh's own
+        direction - "random", "normal": along the clean mesh's area-weighted vertex normals, or a [V,3] array of unit rows
+        (finite, every norm within 1e-3 of 1), e.g. the viewing rays of utils.view_rays for the noise of a depth scan: the
+        white noise goes along them; binds are compared by a digest of the rows.  x: the clean mesh's own
         rows (what the steps read until set_noise switches the synthesis on); gt: the clean normals.  Unsharded only.
         lf = (width_rel, bumps) (None: white noise only): low-frequency noise on top (include/fgc.h: fgc_synth_noise_lf),
         a field of `bumps` Gaussian bumps (None: ceil(real faces / 6), the count of the reference's addLFGaussianNoise
-        stub) of width width_rel mean edge lengths along the clean vertex normals, switched on per step by
+        stub) of width width_rel mean edge lengths along the clean vertex normals (whatever the white direction, a table of
+        rays included), switched on per step by
         set_noise(step, level, lf_level).  Centres are uniform over the vertices, distances Euclidean."""
         self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf), False,
                          lambda: self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt)))
@@ -611,7 +615,11 @@ class FacetDenoiser:
             if points and not M["mode"].synth_points:
                 raise ValueError("mesh %r is bound under this key without synthesised point sets" % (key,))
             S = M["synth"]
-            if (S["seed"], S["stream"], S["direction"]) != (int(synth_args[4]), int(synth_args[5]), synth_args[6]):
+            d = synth_args[6]
+            # (a training loop rebinds every step: the very table this mesh was bound with, read-only, needs no digest)
+            same = (isinstance(d, np.ndarray) and d is S["direction_src"] and not d.flags.writeable) or \
+                S["direction"] == direction_key(d)
+            if (S["seed"], S["stream"]) != (int(synth_args[4]), int(synth_args[5])) or not same:
                 raise ValueError("mesh %r is bound with another seed / stream / direction" % (key,))
             if S["lf_key"] != self._lf_key(synth_args[7]):
                 raise ValueError("mesh %r is bound with another lf setting (%r)" % (key, S["lf_key"]))
@@ -635,8 +643,11 @@ class FacetDenoiser:
 
     def _synth_state(self, x, verts, faces_rows, edge_len, seed, stream, direction, lf=None):
         """The checked arguments of bind_clean / bind_clean_vertices as the synthesis state kept with the mesh."""
-        if direction not in ("random", "normal"):
-            raise ValueError("direction must be 'random' or 'normal'")
+        rays = None
+        if not isinstance(direction, str):
+            rays = check_directions(direction, np.asarray(verts).reshape(-1, 3).shape[0])
+        elif direction not in ("random", "normal"):
+            raise ValueError("direction must be 'random', 'normal' or a [V,3] array of unit rows")
         lf_key = self._lf_key(lf)
         if lf_key is not None:
             if not 0 <= int(stream) < 1 << 31:
@@ -653,13 +664,16 @@ class FacetDenoiser:
             raise ValueError("edge_len must be a positive length")
         dev = self.device
         S = dict(v=torch.as_tensor(vx, device=dev), faces=torch.as_tensor(fr, device=dev), vn=None,
-                 edge_len=float(edge_len), seed=int(seed), stream=int(stream), direction=direction, lf_key=lf_key, lf=None)
+                 edge_len=float(edge_len), seed=int(seed), stream=int(stream),
+                 direction=direction_key(direction if rays is None else rays), direction_src=direction, lf_key=lf_key, lf=None)
         real = fr[fr[:, 0] >= 0]
-        if direction == "normal" or lf_key is not None:
+        if (rays is None and direction == "normal") or lf_key is not None:
             from .utils import areaWeightedVertexNormals
             vn = torch.as_tensor(areaWeightedVertexNormals(vx, real).astype(np.float32), device=dev)
-            if direction == "normal":
+            if rays is None and direction == "normal":
                 S["vn"] = vn
+        if rays is not None:
+            S["vn"] = torch.as_tensor(rays, device=dev)      # (where the vertex normals land: the kernel reads rows as given)
         S["v_out"] = S["v"].clone()
         need = self.L.fgc_synth_scratch_floats(vx.shape[0])
         if lf_key is not None:

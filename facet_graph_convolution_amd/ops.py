@@ -392,6 +392,30 @@ def vertex_update(x, normals, e_map, v_e_map, iters, lmbd=1.0 / 18):
     return out
 
 
+def vertex_update_dir(x, normals, e_map, v_e_map, dirs, iters, lmbd=1.0 / 18, return_t=False):
+    """update_position_with_depth (train.py:1561-1665) on [V,3] positions: vertex_update with every contribution projected
+    onto the vertex' direction, dirs [V,3] or [1,3] (used as given, nothing is normalised; include/fgc.h:
+    fgc_vertex_update_dir).  Returns the positions [V,3]; return_t: (positions, t [V]), t the signed step along the
+    direction, positions = fma(t, dirs, x)."""
+    _req_cuda(x, normals, e_map, v_e_map, dirs)
+    x, normals, dirs = _f32c(x), _f32c(normals), _f32c(dirs.reshape(-1, 3))
+    e_map = e_map.to(torch.int32).reshape(-1, 4).contiguous()
+    v_e_map = v_e_map.to(torch.int32).contiguous()
+    nv = x.shape[0]
+    if dirs.shape[0] not in (1, nv):
+        raise ValueError("dirs has %d rows: one row, or one per vertex (%d)" % (dirs.shape[0], nv))
+    if x.dim() != 2 or x.shape[1] != 3 or v_e_map.dim() != 2 or v_e_map.shape[0] != nv or normals.shape[-1] != 3:
+        raise ValueError("x [V,3], normals [F,3], v_e_map [V,slots] with one row per vertex (%d)" % nv)
+    L = _lib.lib()
+    out = torch.empty_like(x)
+    t = torch.empty(nv, dtype=torch.float32, device=x.device) if return_t else None
+    ws = torch.empty(max(L.fgc_vertex_update_dir_workspace_floats(nv), 1), dtype=torch.float32, device=x.device)
+    check(L.fgc_vertex_update_dir(ptr(x), ptr(out), ptr(t), ptr(ws), ws.numel(), nv, ptr(normals), normals.shape[0],
+                                  ptr(e_map), e_map.shape[0], ptr(v_e_map), v_e_map.shape[1], ptr(dirs), dirs.shape[0],
+                                  int(iters), float(lmbd), stream_ptr()), "fgc_vertex_update_dir")
+    return (out, t) if return_t else out
+
+
 def pool4_avg_iz(x):
     """custom_binary_tree_pooling(x, steps=2, 'avg_ignore_zeros') (model.py:792-814) on [n, c] rows."""
     _req_cuda(x)

@@ -12,7 +12,8 @@ Training command (the reference's ``train(withVerts)``, train.py:1894-1921):
 
     python -m facet_graph_convolution_amd.train DUMP_DIR NETWORK_DIR [--num-iterations N] [--net-name NAME]
         [--with-vertices] [--double-loss] [--capture] [--seed S]
-        [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal] [--lf-noise 0.3,0.2,0.1[:WIDTH[:BUMPS]]]
+        [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal|ray] [--view-dir X,Y,Z | --camera X,Y,Z]
+        [--lf-noise 0.3,0.2,0.1[:WIDTH[:BUMPS]]]
 
 loads the pickles `preprocess` wrote and runs trainNet, trainAccuracyNet (--with-vertices) or trainDoubleLossNet
 (--with-vertices --double-loss).  --synth-noise (build extension) loads the CLEAN pickles of `preprocess --clean`
@@ -115,7 +116,8 @@ DEFAULT_NOISE_LEVELS = (0.1, 0.2, 0.3)      # --synth-noise without a value: a c
 
 # One mesh of a trainer's input: `args` follow the key in the bind call, `gt_normals` go with them (a keyword) for the
 # double loss only, rows = the number of rows each sample set of a step is drawn from: (N0,), or (V, Vgt).
-_Mesh = collections.namedtuple("_Mesh", "args gt_normals rows")
+# verts: the raw clean vertices of a clean mesh, what the viewing rays of a depth-scan noise direction are built from.
+_Mesh = collections.namedtuple("_Mesh", "args gt_normals rows verts", defaults=(None,))
 _VALID_LOG = {1: "Iteration %d, validation loss %g", 3: "Iteration %d, validation loss = %g (points %g, normals %g)"}
 
 
@@ -134,7 +136,8 @@ def _clean_meshes(ds, what):
     if not (hasattr(ds, "is_clean") and ds.is_clean()):
         raise ValueError("noise_levels needs a %s of clean meshes (TrainingSet.addCleanMesh, preprocess --clean)" % what)
     return [_Mesh((ds.in_list[i], ds.adj_list[i], ds.gt_list[i], ds.clean_vertices[i], ds.clean_faces_rows[i],
-                   ds.clean_edge_len[i]), None, (np.asarray(ds.in_list[i]).shape[1],)) for i in range(len(ds.in_list))]
+                   ds.clean_edge_len[i]), None, (np.asarray(ds.in_list[i]).shape[1],), ds.clean_vertices[i])
+            for i in range(len(ds.in_list))]
 
 
 def _vertex_meshes(ds, double):
@@ -160,7 +163,8 @@ def _clean_vertex_meshes(ds, what):
         raise ValueError("noise_levels needs a %s of clean meshes with their vertex data (TrainingSet."
                          "addCleanMeshWithVertices, preprocess --clean --with-vertices)" % what)
     return [_Mesh((ds.in_list[i], ds.adj_list[i], ds.clean_vertices[i], ds.clean_faces_rows[i], ds.v_faces_list[i],
-                   ds.clean_edge_len[i]), ds.gt_list[i], (_rows(ds.clean_vertices[i]),) * 2) for i in range(n)]
+                   ds.clean_edge_len[i]), ds.gt_list[i], (_rows(ds.clean_vertices[i]),) * 2, ds.clean_vertices[i])
+            for i in range(n)]
 
 
 def _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction):
@@ -174,8 +178,12 @@ def _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction):
     levels = tuple(float(l) for l in noise_levels)
     if not levels or not all(np.isfinite(l) and l >= 0 for l in levels):
         raise ValueError("noise_levels: a non-empty list of levels >= 0")
-    if noise_direction not in ("random", "normal"):
-        raise ValueError("noise_direction must be 'random' or 'normal'")
+    if isinstance(noise_direction, dict):
+        if len(noise_direction) != 1 or next(iter(noise_direction)) not in ("camera", "view_dir"):
+            raise ValueError("noise_direction: a view is {'camera': xyz} or {'view_dir': xyz}")
+    elif isinstance(noise_direction, str) and noise_direction not in ("random", "normal"):
+        raise ValueError("noise_direction must be 'random' or 'normal', a [V,3] array of unit rows or a view "
+                         "({'camera': xyz} / {'view_dir': xyz})")
     clean = _clean_meshes if form == "angular" else _clean_vertex_meshes
     return levels, clean(trainSet, "training set"), clean(validSet, "validation set") if validSet is not None else []
 
@@ -195,13 +203,32 @@ def _lf_inputs(levels, lf_levels, lf_width, lf_bumps):
     return lf, (float(lf_width), None if lf_bumps is None else int(lf_bumps))
 
 
+def _mesh_direction(direction, m):
+    """The noise direction of mesh record m: a mode name or a [V,3] array as given, a view ({'camera': xyz} / {'view_dir':
+    xyz}) as the viewing rays of the mesh's CLEAN vertices - one row per vertex, what makeNoisy --direction ray makes."""
+    if not isinstance(direction, dict):
+        return direction
+    from .utils import view_rays
+    key = (id(m.verts), tuple(sorted((k, tuple(v)) for k, v in direction.items())))
+    hit = _RAYS.get(key)
+    if hit is None or hit[0] is not m.verts:        # (built once per mesh and view: a loop binds its meshes every step)
+        v = np.asarray(m.verts, dtype=np.float32).reshape(-1, 3)
+        rays = np.ascontiguousarray(np.broadcast_to(view_rays(v, **direction), v.shape))
+        rays.setflags(write=False)
+        hit = _RAYS[key] = (m.verts, rays)
+    return hit[1]
+
+
+_RAYS = {}
+
+
 def _bind(F, key, m, noise=None):
     """Bind mesh record m under `key` through F = net.trainer_form(form): plain, or - noise = (seed, stream, direction
     [, lf = (width, bumps)]) - clean for noise synthesis.  (A cached mesh returns at once; the bind methods reshape the
     [1, ...] arrays.)"""
     kw = {"gt_normals": m.gt_normals} if F.gt_normals else {}
     if noise is not None:
-        kw.update(seed=noise[0], stream=noise[1], direction=noise[2])
+        kw.update(seed=noise[0], stream=noise[1], direction=_mesh_direction(noise[2], m))
         if len(noise) > 3 and noise[3] is not None:
             kw.update(lf=noise[3])
     (F.bind if noise is None else F.bind_clean)(key, *m.args, **kw)
@@ -274,7 +301,9 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
     noise_levels (build extension; None = the reference's loop, untouched): trainSet / validSet hold CLEAN meshes
     (TrainingSet.addCleanMesh, otherwise ValueError) and every iteration trains on fresh Gaussian vertex noise made on
     the GPU (FacetDenoiser.bind_clean): a level drawn from the list x the mesh's mean edge length, along
-    noise_direction ("random" / "normal"), with the global iteration as the noise counter - a resumed run goes on with
+    noise_direction ("random" / "normal"; or a [V,3] array of unit rows for every mesh, or a view {'camera': xyz} /
+    {'view_dir': xyz}: along the viewing rays of each mesh's clean vertices, the noise of a depth scan - the low-frequency
+    bumps keep going along the clean vertex normals), with the global iteration as the noise counter - a resumed run goes on with
     new noise.  Validation: synthValidationLoss.
 
     lf_levels (build extension; needs noise_levels, length 1 or that of noise_levels): low-frequency noise on top
@@ -456,6 +485,31 @@ def update_position2(x, face_normals, edge_map, v_edges, iter_num=20, max_edges=
     return out.unsqueeze(0)
 
 
+def update_position_with_depth(x, face_normals, edge_map, v_edges, depth_dir, iter_num=20):
+    """train.py:1561-1665, same argument layout on torch GPU tensors: update_position2 with every contribution projected
+    onto a per-vertex direction, so that a vertex of a depth scan moves along its viewing ray only.  x [1,V,3],
+    face_normals [1,F,3], edge_map int [1,E,4], v_edges int [1,V,slots] (-1 = unused; any width - the reference hard-codes
+    50), depth_dir [1,3] or [V,3] (the reference's reshape(depth_dir, [1,-1,1,1,3]); used as given, not normalised).
+    Returns the reference's pair (x [1,V,3], x - x_init [1,V,3]).  lambda = 1/18 (:1563).  The positions are fma(t,
+    depth_dir, x_init) of the accumulated step t (include/fgc.h: fgc_vertex_update_dir), not a chain of additions."""
+    x = x.reshape(-1, 3)
+    out = ops.vertex_update_dir(x, face_normals.reshape(-1, 3), edge_map.reshape(-1, 4),
+                                v_edges.reshape(x.shape[0], -1), depth_dir.reshape(-1, 3), iter_num)
+    return out.unsqueeze(0), (out - x.float()).unsqueeze(0)
+
+
+def depth_update(V, normals, e_map, v_e_map, depth_dir, iters):
+    """What the single-scale drivers (inferNetOld, bilateral.denoise_mesh) run in the place of update_position2 when they are
+    given viewing rays: update_position_with_depth on device tensors V [V,3], normals [F,3], e_map [1,E,4], v_e_map
+    [1,V,slots] and depth_dir [V,3] / [1,3] (array-like or tensor).  Returns the positions [V,3]."""
+    if not isinstance(depth_dir, torch.Tensor):
+        depth_dir = torch.from_numpy(np.ascontiguousarray(np.asarray(depth_dir, dtype=np.float32)))
+    d = depth_dir.to(V.device).reshape(-1, 3)
+    if d.shape[0] not in (1, V.shape[0]):
+        raise ValueError("depth_dir has %d rows: one row, or one per vertex (%d)" % (d.shape[0], V.shape[0]))
+    return update_position_with_depth(V.unsqueeze(0), normals.unsqueeze(0), e_map, v_e_map, d, iter_num=iters)[0][0]
+
+
 def updateFacesCenter(vertices, faces, coarsening_steps):
     """train.py:1768-1798: node centres of the three levels, [fpos0 [1,N0,3], fpos1 [1,N0/4,3], fpos2 [1,N0/16,3]]."""
     if coarsening_steps != 2:
@@ -584,10 +638,12 @@ def _normalize_rows_like_reference(t):
     return normalizeTensor(t.unsqueeze(0))[0]
 
 
-def inferNetOld(inputMesh, net_or_checkpoint, device="cuda", update_vertices=False):
+def inferNetOld(inputMesh, net_or_checkpoint, device="cuda", update_vertices=False, depth_dir=None):
     """train.py:29-144.  inputMesh: dataClasses.InferenceMesh.  Returns the predicted unit normals [F, 3] (numpy, face
     order); with update_vertices=True the reference's full return value (outPoints [V,3], predicted_normals): the
-    vertex positions after 60 iterations of update_position2 on those normals (train.py:129-139)."""
+    vertex positions after 60 iterations of update_position2 on those normals (train.py:129-139).  depth_dir ([V,3] or
+    [1,3] viewing rays, utils.view_rays): the 60 iterations are update_position_with_depth's instead, every vertex moves
+    along its ray only (the commented call at train.py:131)."""
     if isinstance(net_or_checkpoint, FacetDenoiser):
         net = net_or_checkpoint
     else:
@@ -617,6 +673,11 @@ def inferNetOld(inputMesh, net_or_checkpoint, device="cuda", update_vertices=Fal
             raise RuntimeError("the mesh has a vertex with more than MAX_EDGES edges: no edge tables, no vertex update")
         dev = out.device
         xp = torch.as_tensor(inputMesh.vertices, dtype=torch.float32, device=dev)
+        if depth_dir is not None:
+            pts = depth_update(xp.reshape(-1, 3), out, torch.as_tensor(inputMesh.edge_map, device=dev),
+                               torch.as_tensor(inputMesh.v_e_map, device=dev), depth_dir, 60)
+            torch.cuda.synchronize()
+            return pts.cpu().numpy(), out.cpu().numpy()
         pts = update_position2(xp, out.unsqueeze(0), torch.as_tensor(inputMesh.edge_map, device=dev),
                                torch.as_tensor(inputMesh.v_e_map, device=dev), iter_num=60,
                                max_edges=inputMesh.v_e_map.shape[2])
@@ -660,14 +721,22 @@ def main(argv=None):
                     "--with-vertices: of `preprocess --clean --with-vertices`), Gaussian "
                     "vertex noise made on the GPU every step; LEVELS = comma-separated multiples of the mean edge length "
                     "(default %(const)s; the value is optional, so write the option BEHIND the two folders or as --synth-noise=LEVELS)")
-    ap.add_argument("--noise-direction", choices=("random", "normal"), default="random",
-                    help="with --synth-noise: displace along a random direction or along the vertex normal")
+    ap.add_argument("--noise-direction", choices=("random", "normal", "ray"), default="random",
+                    help="with --synth-noise: displace along a random direction, along the vertex normal, or (ray) along the "
+                    "viewing rays of --view-dir / --camera, built from each mesh's clean vertices (depth scans)")
+    from .utils import view_options, view_spec
+    view_options(ap)
     ap.add_argument("--lf-noise", default=None, metavar="LEVELS[:WIDTH[:BUMPS]]",
                     help="with --synth-noise: low-frequency noise on top - LEVELS = comma-separated RMS displacements in mean "
                     "edge lengths, one or one per --synth-noise level (level k pairs with lf level k); WIDTH = bump width "
                     "in mean edge lengths (default 3); BUMPS per mesh (default faces / 6).  E.g. --synth-noise 0,0.1,0.2 "
                     "--lf-noise 0.3,0.2,0.1:3")
     args = ap.parse_args(argv)
+    view = view_spec(ap, args)
+    if (args.noise_direction == "ray") != bool(view):
+        ap.error("--noise-direction ray needs --view-dir or --camera, and the two go with --noise-direction ray only")
+    if view and args.synth_noise is None:
+        ap.error("--noise-direction ray needs --synth-noise")
     if args.double_loss and not args.with_vertices:
         ap.error("--double-loss trains on the vertex data: it needs --with-vertices")
     if args.num_iterations < 0:
@@ -707,7 +776,7 @@ def main(argv=None):
             valid_set = pickle.load(fp)
     os.makedirs(args.network_dir, exist_ok=True)
     trainer = (trainDoubleLossNet if args.double_loss else trainAccuracyNet) if args.with_vertices else trainNet
-    extra = dict(noise_levels=levels, noise_direction=args.noise_direction, **lf_extra) if levels is not None else {}
+    extra = dict(noise_levels=levels, noise_direction=view or args.noise_direction, **lf_extra) if levels is not None else {}
     trainer(train_set, args.num_iterations, network_path=args.network_dir, net_name=args.net_name, seed=args.seed,
             capture=args.capture, validSet=valid_set, **extra)
     return trainer.__name__

@@ -312,6 +312,85 @@ def areaWeightedVertexNormals(verts, faces):
     return np.where(nrm > 0, out / np.where(nrm > 0, nrm, 1.0), 0.0)
 
 
+def view_rays(V, camera=None, view_dir=None):
+    """Viewing rays of a depth scan (build extension), float32 unit rows.  camera: a point in the mesh's raw units, the
+    rows are normalize(V - camera), [V,3]; view_dir: one direction for every vertex (an orthographic sensor), normalised,
+    [1,3].  Exactly one of the two.  Computed in float64 and rounded once, so a second call gives the same bits; a vertex
+    at the camera has no ray: ValueError."""
+    if (camera is None) == (view_dir is None):
+        raise ValueError("view_rays takes exactly one of camera and view_dir")
+    if view_dir is not None:
+        d = np.asarray(view_dir, dtype=np.float64).reshape(-1)
+        if d.shape != (3,) or not np.isfinite(d).all() or not np.linalg.norm(d) > 0:
+            raise ValueError("view_dir must be three finite numbers, not all zero (got %r)" % (view_dir,))
+        return (d / np.linalg.norm(d)).astype(np.float32).reshape(1, 3)
+    c = np.asarray(camera, dtype=np.float64).reshape(-1)
+    if c.shape != (3,) or not np.isfinite(c).all():
+        raise ValueError("camera must be three finite numbers (got %r)" % (camera,))
+    r = np.asarray(V, dtype=np.float64).reshape(-1, 3) - c
+    n = np.sqrt((r * r).sum(1, keepdims=True))
+    if not (n > 0).all():
+        raise ValueError("vertex %d lies at the camera: it has no viewing ray" % int(np.argmin(n)))
+    return (r / n).astype(np.float32)
+
+
+def parse_xyz(text):
+    """'X,Y,Z' of --view-dir / --camera as three floats; ValueError otherwise."""
+    vals = [float(t) for t in text.split(",")]
+    if len(vals) != 3 or not np.isfinite(vals).all():
+        raise ValueError("X,Y,Z: three finite numbers")
+    return tuple(vals)
+
+
+def view_options(ap):
+    """The options --view-dir / --camera every depth-scan CLI has (mutually exclusive)."""
+    g = ap.add_mutually_exclusive_group()
+    g.add_argument("--view-dir", default=None, metavar="X,Y,Z",
+                   help="depth-scan mode: one viewing direction for every vertex (an orthographic sensor)")
+    g.add_argument("--camera", default=None, metavar="X,Y,Z",
+                   help="depth-scan mode: the camera position in the mesh's raw units; the rays run from it to the vertices")
+
+
+def view_spec(ap, args):
+    """The parsed pair of view_options as keywords of view_rays: {}, {'view_dir': xyz} or {'camera': xyz}."""
+    out = {}
+    for name in ("view_dir", "camera"):
+        text = getattr(args, name)
+        if text is not None:
+            try:
+                out[name] = parse_xyz(text)
+            except ValueError as e:
+                ap.error("--%s: %s (got %r)" % (name.replace("_", "-"), e, text))
+    if "view_dir" in out and not np.linalg.norm(out["view_dir"]) > 0:
+        ap.error("--view-dir must not be the zero vector")
+    return out
+
+
+def check_directions(direction, nv):
+    """A [V,3] table of unit noise directions (rays) as a contiguous float32 copy (the caller's may be read-only): nv rows,
+    finite, every row norm within 1e-3 of 1; ValueError otherwise."""
+    d = np.asarray(direction)
+    if d.ndim != 2 or d.shape != (nv, 3):
+        raise ValueError("direction: an array must be [V,3] with one row per vertex (%d), got shape %r" % (nv, d.shape))
+    d = np.array(d, dtype=np.float32, order="C")
+    if not np.isfinite(d).all():
+        raise ValueError("direction: the rows must be finite")
+    n = np.sqrt((d.astype(np.float64) ** 2).sum(1))
+    if np.abs(n - 1.0).max() > 1e-3:
+        raise ValueError("direction: the rows must be unit vectors (row %d has norm %g)"
+                         % (int(np.argmax(np.abs(n - 1.0))), n[int(np.argmax(np.abs(n - 1.0)))]))
+    return d
+
+
+def direction_key(direction):
+    """What two binds compare a noise direction by: the mode name, or ('rays', digest of the rows) for an array."""
+    if isinstance(direction, str):
+        return direction
+    import hashlib
+    d = np.ascontiguousarray(direction, dtype=np.float32)
+    return ("rays", hashlib.sha1(d.tobytes()).hexdigest())
+
+
 def write_mesh(vl, fl, strFileName):
     """utils.py:659-697: 'v x y z' (6 decimals, extra per-vertex columns such as colours written as they are), then
     'f a b c' one-indexed; a face (0,0,..) ends the list and a face (-1,-1,..) is skipped, as in the reference."""

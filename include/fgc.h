@@ -64,8 +64,9 @@ extern "C" {
  * 114: fgc_synth_noise_lf (+ fgc_synth_lf_scratch_floats): low-frequency noise, a field of Gaussian bumps on top of the
  * per-vertex draw of fgc_synth_noise.
  * 115: fgc_guided_normals / fgc_guided_workspace_bytes / fgc_bilateral_filter_guided (guided normal filtering);
- * fgc_bilateral_workspace_bytes grows by one float4 per face, the guided form's third candidate plane (one size for both). */
-#define FGC_ABI_VERSION 115
+ * fgc_bilateral_workspace_bytes grows by one float4 per face, the guided form's third candidate plane (one size for both).
+ * 116: fgc_vertex_update_dir (+ _workspace_floats): the vertex update along a per-vertex direction, for depth scans. */
+#define FGC_ABI_VERSION 116
 
 const char* fgc_last_error(void);
 int fgc_version(void);
@@ -680,6 +681,25 @@ int fgc_copy_rows_jobs(const fgc_row_job* jobs, int32_t njobs, void* stream);
 int fgc_vertex_update(const float* x, float* x_out, float* tmp, int32_t nv, const float* normals, int32_t nf,
                       const int32_t* e_map, int32_t ne, const int32_t* v_e_map, int32_t max_edges, int32_t iters,
                       float lambda, void* stream);
+
+/* Vertex update along a per-vertex direction = update_position_with_depth (train.py:1561-1665): fgc_vertex_update with
+ * every contribution projected onto the direction d_i of its vertex (a vertex of a depth scan is a sample along a viewing
+ * ray and may move along that ray only).  dirs [n_dirs,3]: d_i is row i when n_dirs == nv, the one row when n_dirs == 1;
+ * any other n_dirs is FGC_EINVAL.  d is used as given - unit or not, nothing is normalised: the rule is sum (u . d) d.
+ * Per Jacobi iteration and vertex, with u_s = n_f1 (n_f1 . (x_j - x_i)) + n_f2 (n_f2 . (x_j - x_i)) of edge slot s (slot
+ * handling exactly as in fgc_vertex_update: an unused or out-of-range slot, the endpoint that is i itself and a missing
+ * face add nothing):
+ *   t_i += lambda * sum_s (u_s . d_i)   (slot order),      x_i = fma(t_i, d_i, x0_i)   per coordinate, x0 = the INPUT x.
+ * The position is always rebuilt from the input position and the accumulated scalar, never by adding a step to the
+ * previous iterate: in exact arithmetic the reference's rule, and a vertex stays within one rounding of its ray whatever
+ * the iteration count.  x_out [nv,3]; t_out [nv] (may be NULL) receives t, the signed correction along the ray (in
+ * units of |d|).  iters == 0: x_out = x bit for bit, t_out = 0.  ws: at least fgc_vertex_update_dir_workspace_floats(nv)
+ * floats; x may alias neither x_out nor ws; e_map may be NULL when ne == 0.  Only enqueues: one launch per iteration, one
+ * thread per vertex, ping-ponging between x_out and ws; allocates nothing. */
+size_t fgc_vertex_update_dir_workspace_floats(int32_t nv);
+int fgc_vertex_update_dir(const float* x, float* x_out, float* t_out, float* ws, size_t ws_floats, int32_t nv,
+                          const float* normals, int32_t nf, const int32_t* e_map, int32_t ne, const int32_t* v_e_map,
+                          int32_t max_edges, const float* dirs, int32_t n_dirs, int32_t iters, float lambda, void* stream);
 
 /* 4:1 "average ignoring zero rows" pooling = custom_binary_tree_pooling(x, steps=2, 'avg_ignore_zeros')
  * (model.py:792-814): two rounds of pairwise means in which a row that is zero in every channel is replaced by its
