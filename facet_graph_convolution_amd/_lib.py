@@ -239,6 +239,19 @@ _SIGS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgc_vertex_update_ms_dir_scratch_floats": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "fgc_vertex_update_ms_dir": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgc_vertex_update_ms_dir_traj": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                                C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgc_vertex_update_ms_dir_bwd_workspace_floats": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "fgc_vertex_update_ms_dir_bwd": (C.c_int, [C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.c_void_p]),
     "fgc_point_loss_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
     "fgc_point_loss": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                  C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
@@ -290,7 +303,13 @@ def lib():
         for name, (res, args) in _SIGS.items():
             if os.environ.get("FGC_DEV_PARTIAL") and not hasattr(L, name):
                 continue  # developer-only: library under construction
-            fn = getattr(L, name)  # AttributeError if the symbol is missing
+            try:
+                fn = getattr(L, name)
+            except AttributeError:
+                # (entry points are also added without a new ABI number: an older build of the same number lacks them)
+                raise RuntimeError("libfgc.so (%s, ABI %d) has no entry point %s: it was built from an older include/fgc.h - "
+                                   "rebuild it (`make -C facet_graph_convolution_amd/csrc`)"
+                                   % (LIB_PATH, L.fgc_version() if hasattr(L, "fgc_version") else -1, name)) from None
             fn.restype = res
             fn.argtypes = args
         # a library built from another header would take the arguments below in another order: refuse it here

@@ -288,20 +288,13 @@ __global__ __launch_bounds__(256) void pool4_avg_iz_bwd_kernel(const float* __re
     }
 }
 
-// one thread per vertex: the direct term over the vertex' own slots, then the barycentre adjoint over its face incidence
-__global__ __launch_bounds__(256) void vertex_ms_bwd_vertex_kernel(const float* __restrict__ g, int nv,
-                                                                   const float* __restrict__ lam,
-                                                                   const int* __restrict__ vfaces, int k_v, int shift,
-                                                                   const float* __restrict__ nrm, int nnodes,
-                                                                   const int* __restrict__ inc_ptr,
-                                                                   const int* __restrict__ inc_face,
-                                                                   const float* __restrict__ gfp0,
-                                                                   float* __restrict__ go) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= nv) return;
-    const float l = lam[v];
-    const float g0 = g[3 * (size_t)v], g1 = g[3 * (size_t)v + 1], g2 = g[3 * (size_t)v + 2];
-    const float a0 = l * g0, a1 = l * g1, a2 = l * g2;
+// one vertex of the adjoint: the direct term over the vertex' own slots on a = lam_v x (the gradient as it enters the step),
+// then the barycentre adjoint over its face incidence; the identity term is g itself
+__device__ __forceinline__ void ms_bwd_vertex_row(int v, float g0, float g1, float g2, float a0, float a1, float a2,
+                                                  const int* __restrict__ vfaces, int k_v, int shift,
+                                                  const float* __restrict__ nrm, int nnodes,
+                                                  const int* __restrict__ inc_ptr, const int* __restrict__ inc_face,
+                                                  const float* __restrict__ gfp0, float* __restrict__ go) {
     float d0 = 0.f, d1 = 0.f, d2 = 0.f;
     for (int k = 0; k < k_v; ++k) {
         const int f = vfaces[(size_t)v * k_v + k];
@@ -327,9 +320,101 @@ __global__ __launch_bounds__(256) void vertex_ms_bwd_vertex_kernel(const float* 
     go[3 * (size_t)v + 2] = (g2 - d2) + b2 / 3.0f;
 }
 
+// one thread per vertex: the direct term over the vertex' own slots, then the barycentre adjoint over its face incidence
+__global__ __launch_bounds__(256) void vertex_ms_bwd_vertex_kernel(const float* __restrict__ g, int nv,
+                                                                   const float* __restrict__ lam,
+                                                                   const int* __restrict__ vfaces, int k_v, int shift,
+                                                                   const float* __restrict__ nrm, int nnodes,
+                                                                   const int* __restrict__ inc_ptr,
+                                                                   const int* __restrict__ inc_face,
+                                                                   const float* __restrict__ gfp0,
+                                                                   float* __restrict__ go) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const float l = lam[v];
+    const float g0 = g[3 * (size_t)v], g1 = g[3 * (size_t)v + 1], g2 = g[3 * (size_t)v + 2];
+    ms_bwd_vertex_row(v, g0, g1, g2, l * g0, l * g1, l * g2, vfaces, k_v, shift, nrm, nnodes, inc_ptr, inc_face, gfp0, go);
+}
+
 __global__ void sub3_kernel(const float* a, const float* b, int n, float* o) {   // o may alias b
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) o[i] = a[i] - b[i];
+}
+
+// ---------------------------------------------------------------------------------------------
+// the multi-scale update along a per-vertex direction (a build extension: the reference constrains the single-scale
+// update only) and its adjoint
+// ---------------------------------------------------------------------------------------------
+// vertex_update_ms_kernel's walk, the step delta_v = lam_v sum_k n (n . (c - x_v)) projected onto the vertex' own direction
+// d_v.  As in vertex_update_dir_kernel the state of a vertex is ONE scalar, t_v += delta_v . d_v, private to its thread
+// and zeroed by the host before the first iteration, and the position is rebuilt from the INPUT position x0, x_v = fma(t_v,
+// d_v, x0_v).  x: the previous iterate (where the centres came from); dstride: 3, or 0 for one direction shared by all.
+__global__ __launch_bounds__(256) void vertex_update_ms_dir_kernel(const float* __restrict__ x0,
+                                                                   const float* __restrict__ x, float* __restrict__ xo,
+                                                                   float* __restrict__ t, int nv,
+                                                                   const int* __restrict__ vfaces, int k_v, int shift,
+                                                                   const float* __restrict__ nrm,
+                                                                   const float* __restrict__ fpos, int nnodes,
+                                                                   const float* __restrict__ dirs, int dstride) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const float p0 = x[3 * (size_t)v], p1 = x[3 * (size_t)v + 1], p2 = x[3 * (size_t)v + 2];   // the current iterate
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    int numf = 0;
+    for (int k = 0; k < k_v; ++k) {
+        const int f = vfaces[(size_t)v * k_v + k];
+        if (f < 0) continue;                      // slot handling exactly as in vertex_update_ms_kernel
+        ++numf;
+        const int node = f >> shift;
+        if (node >= nnodes) continue;
+        const float n0 = nrm[3 * (size_t)node], n1 = nrm[3 * (size_t)node + 1], n2 = nrm[3 * (size_t)node + 2];
+        const float e0 = fpos[3 * (size_t)node] - p0, e1 = fpos[3 * (size_t)node + 1] - p1,
+                    e2 = fpos[3 * (size_t)node + 2] - p2;
+        const float w = (n0 * e0 + n1 * e1) + n2 * e2;
+        a0 += w * n0;
+        a1 += w * n1;
+        a2 += w * n2;
+    }
+    const float lm = numf > 0 ? 1.0f / (float)numf : 0.f;      // a vertex without faces: t stays where it is
+    const float* dir = dirs + (size_t)v * dstride;
+    const float d0 = dir[0], d1 = dir[1], d2 = dir[2];
+    const float tv = t[v] + (((lm * a0) * d0 + (lm * a1) * d1) + (lm * a2) * d2);
+    t[v] = tv;
+    xo[3 * (size_t)v] = fmaf(tv, d0, x0[3 * (size_t)v]);
+    xo[3 * (size_t)v + 1] = fmaf(tv, d1, x0[3 * (size_t)v + 1]);
+    xo[3 * (size_t)v + 2] = fmaf(tv, d2, x0[3 * (size_t)v + 2]);
+}
+
+// gp_v = d_v (d_v . g_v): the incoming gradient as the projected step sees it
+__global__ __launch_bounds__(256) void project_rows_kernel(const float* __restrict__ g, int nv,
+                                                           const float* __restrict__ dirs, int dstride,
+                                                           float* __restrict__ gp) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const float* dir = dirs + (size_t)v * dstride;
+    const float d0 = dir[0], d1 = dir[1], d2 = dir[2];
+    const float s = (d0 * g[3 * (size_t)v] + d1 * g[3 * (size_t)v + 1]) + d2 * g[3 * (size_t)v + 2];
+    gp[3 * (size_t)v] = s * d0;
+    gp[3 * (size_t)v + 1] = s * d1;
+    gp[3 * (size_t)v + 2] = s * d2;
+}
+
+// vertex_ms_bwd_vertex_kernel with the projected gradient gp in the direct term; the identity term keeps g itself
+__global__ __launch_bounds__(256) void vertex_ms_dir_bwd_vertex_kernel(const float* __restrict__ g,
+                                                                       const float* __restrict__ gp, int nv,
+                                                                       const float* __restrict__ lam,
+                                                                       const int* __restrict__ vfaces, int k_v, int shift,
+                                                                       const float* __restrict__ nrm, int nnodes,
+                                                                       const int* __restrict__ inc_ptr,
+                                                                       const int* __restrict__ inc_face,
+                                                                       const float* __restrict__ gfp0,
+                                                                       float* __restrict__ go) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const float l = lam[v];
+    ms_bwd_vertex_row(v, g[3 * (size_t)v], g[3 * (size_t)v + 1], g[3 * (size_t)v + 2], l * gp[3 * (size_t)v],
+                      l * gp[3 * (size_t)v + 1], l * gp[3 * (size_t)v + 2], vfaces, k_v, shift, nrm, nnodes, inc_ptr, inc_face,
+                      gfp0, go);
 }
 
 }  // namespace fgc
@@ -543,32 +628,192 @@ extern "C" size_t fgc_vertex_update_ms_bwd_workspace_floats(int32_t nv, int32_t 
     return (size_t)nv * 7 + 6 * nodes;      // lam, two gradient buffers; centres and their gradients of the three levels
 }
 
-extern "C" int fgc_vertex_update_ms_bwd(const float* traj, size_t traj_floats, int32_t nv, const int32_t* faces, int32_t n0,
-                                        const int32_t* v_faces, int32_t k_v, const float* normals0,
-                                        const float* normals1, const float* normals2, const int32_t* iters,
-                                        const int32_t* slot_ptr, const int32_t* slot_vert, const int32_t* inc_ptr,
-                                        const int32_t* inc_face, const float* g_out, float* g_x, float* g_n0,
-                                        float* g_n1, float* g_n2, float* workspace, size_t workspace_floats,
-                                        void* stream) {
+// ---------------------------------------------------------------------------------------------
+// the multi-scale update along a per-vertex direction: host side
+// ---------------------------------------------------------------------------------------------
+static bool ms_dir_apart(const float* p, size_t n, const float* q, size_t m) {   // [p, p+n) and [q, q+m) do not meet
+    return p + n <= q || q + m <= p;
+}
+
+extern "C" size_t fgc_vertex_update_ms_dir_scratch_floats(int32_t nv, int32_t n0) {
+    if (nv <= 0 || n0 <= 0) return 0;
+    // t [nv], the node centres of the three levels, two ping-pong position buffers (the trajectory form: the first two)
+    return (size_t)nv * 7 + 3 * ((size_t)n0 + n0 / 4 + n0 / 16);
+}
+
+// one constrained iteration at `scale`: the centre launches of fgc_vertex_update_ms, then the projected vertex kernel
+static void ms_dir_iteration(hipStream_t st, const float* x0, const float* cur, float* nxt, float* t, int nv,
+                             const int32_t* faces, int n0, const int32_t* v_faces, int k_v, int scale,
+                             const float* const* nrm, float* const* fps, const int* nn, const float* dirs, int dstride) {
+    FGC_LAUNCH("face_centers_kernel", st, face_centers_kernel, dim3(cdiv(n0, 256)), dim3(256), 0, cur, nv, faces, n0, fps[0]);
+    if (scale >= 1)
+        FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(nn[1] * 3, 256)), dim3(256), 0, fps[0], nn[1], 3,
+                   fps[1]);
+    if (scale >= 2)
+        FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(nn[2] * 3, 256)), dim3(256), 0, fps[1], nn[2], 3,
+                   fps[2]);
+    FGC_LAUNCH("vertex_update_ms_dir_kernel", st, vertex_update_ms_dir_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, x0, cur,
+               nxt, t, nv, v_faces, k_v, 2 * scale, nrm[scale], fps[scale], nn[scale], dirs, dstride);
+}
+
+extern "C" int fgc_vertex_update_ms_dir(const float* x, float* x_out, int32_t nv, const int32_t* faces, int32_t n0,
+                                        const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
+                                        const float* normals2, const int32_t* iters, const float* dirs, int32_t n_dirs,
+                                        float* t_out, float* dx_out, float* scratch, size_t scratch_floats, void* stream) {
+    FGC_CHECK_ARG(x && x_out && faces && v_faces && normals0 && normals1 && normals2 && iters && dirs && scratch,
+                  "fgc_vertex_update_ms_dir: null pointer");
+    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0,
+                  "fgc_vertex_update_ms_dir: nv=%d n0=%d (multiple of 16) k_v=%d", nv, n0, k_v);
+    FGC_CHECK_ARG(n_dirs == 1 || n_dirs == nv, "fgc_vertex_update_ms_dir: n_dirs=%d (1, or nv=%d)", n_dirs, nv);
+    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0, "fgc_vertex_update_ms_dir: negative iteration count");
+    const size_t need = fgc_vertex_update_ms_dir_scratch_floats(nv, n0);
+    FGC_CHECK_ARG(scratch_floats >= need, "fgc_vertex_update_ms_dir: scratch too small (%zu < %zu floats)", scratch_floats,
+                  need);
+    const size_t nx = 3 * (size_t)nv;
+    FGC_CHECK_ARG(ms_dir_apart(x, nx, x_out, nx) && ms_dir_apart(x, nx, scratch, need) &&
+                      ms_dir_apart(x_out, nx, scratch, need),
+                  "fgc_vertex_update_ms_dir: x, x_out and the scratch must be distinct");
+    FGC_CHECK_ARG(!dx_out || (ms_dir_apart(dx_out, 3 * nx, x, nx) && ms_dir_apart(dx_out, 3 * nx, x_out, nx) &&
+                              ms_dir_apart(dx_out, 3 * nx, scratch, need) &&
+                              (!t_out || ms_dir_apart(dx_out, 3 * nx, t_out, nv))),
+                  "fgc_vertex_update_ms_dir: dx_out must be a buffer of its own");
+    FGC_CHECK_ARG(!t_out || (ms_dir_apart(t_out, nv, x, nx) && ms_dir_apart(t_out, nv, x_out, nx) &&
+                             ms_dir_apart(t_out, nv, scratch, need)),
+                  "fgc_vertex_update_ms_dir: t_out must be a buffer of its own");
+    const int n1 = n0 / 4, n2 = n0 / 16;
+    hipStream_t st = (hipStream_t)stream;
+    float* t = scratch;
+    float* fp0 = t + nv;
+    float* fp1 = fp0 + 3 * (size_t)n0;
+    float* fp2 = fp1 + 3 * (size_t)n1;
+    float* xa = fp2 + 3 * (size_t)n2;
+    float* xb = xa + nx;
+    const float* nrm[3] = {normals0, normals1, normals2};
+    float* fps[3] = {fp0, fp1, fp2};
+    const int nn[3] = {n0, n1, n2};
+    if (hipMemsetAsync(t, 0, (size_t)nv * 4, st) != hipSuccess) {
+        fgc::set_error("fgc_vertex_update_ms_dir: memset failed");
+        return FGC_EHIP;
+    }
+    const float* cur = x;      // x0 is the caller's x through all three stages: the first iteration reads it in place
+    float* nxt = xa;
+    for (int stage = 0; stage < 3; ++stage) {
+        const int scale = 2 - stage;                 // coarse to fine
+        float* start = nullptr;
+        if (dx_out) {
+            start = dx_out + (size_t)stage * nx;
+            if (hipMemcpyAsync(start, cur, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+                fgc::set_error("fgc_vertex_update_ms_dir: copy failed");
+                return FGC_EHIP;
+            }
+        }
+        for (int it = 0; it < iters[stage]; ++it) {
+            ms_dir_iteration(st, x, cur, nxt, t, nv, faces, n0, v_faces, k_v, scale, nrm, fps, nn, dirs,
+                             n_dirs == 1 ? 0 : 3);
+            cur = nxt;
+            nxt = nxt == xa ? xb : xa;
+        }
+        if (dx_out)
+            FGC_LAUNCH("sub3_kernel", st, sub3_kernel, dim3(cdiv(nv * 3, 256)), dim3(256), 0, cur, start, nv * 3, start);
+    }
+    if (hipMemcpyAsync(x_out, cur, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+        (t_out && hipMemcpyAsync(t_out, t, (size_t)nv * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)) {
+        fgc::set_error("fgc_vertex_update_ms_dir: copy failed");
+        return FGC_EHIP;
+    }
+    FGC_CHECK_LAUNCH("fgc_vertex_update_ms_dir");
+    return FGC_OK;
+}
+
+// the trajectory form: the same launches with the same arguments, every iteration writing its own slot of traj
+extern "C" int fgc_vertex_update_ms_dir_traj(const float* x, int32_t nv, const int32_t* faces, int32_t n0,
+                                             const int32_t* v_faces, int32_t k_v, const float* normals0,
+                                             const float* normals1, const float* normals2, const int32_t* iters,
+                                             const float* dirs, int32_t n_dirs, float* traj, size_t traj_floats,
+                                             float* t_out, float* scratch, size_t scratch_floats, void* stream) {
+    FGC_CHECK_ARG(x && faces && v_faces && normals0 && normals1 && normals2 && iters && dirs && traj && scratch,
+                  "fgc_vertex_update_ms_dir_traj: null pointer");
+    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0,
+                  "fgc_vertex_update_ms_dir_traj: nv=%d n0=%d (multiple of 16) k_v=%d", nv, n0, k_v);
+    FGC_CHECK_ARG(n_dirs == 1 || n_dirs == nv, "fgc_vertex_update_ms_dir_traj: n_dirs=%d (1, or nv=%d)", n_dirs, nv);
+    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0,
+                  "fgc_vertex_update_ms_dir_traj: negative iteration count");
+    const int n1 = n0 / 4, n2 = n0 / 16;
+    const size_t nx = 3 * (size_t)nv;
+    const size_t T = (size_t)iters[0] + iters[1] + iters[2];
+    const size_t need_traj = (T + 1) * nx;
+    FGC_CHECK_ARG(traj_floats >= need_traj, "fgc_vertex_update_ms_dir_traj: traj too small (%zu < %zu floats)", traj_floats,
+                  need_traj);
+    const size_t need = (size_t)nv + 3 * ((size_t)n0 + n1 + n2);
+    FGC_CHECK_ARG(scratch_floats >= need, "fgc_vertex_update_ms_dir_traj: scratch too small (%zu < %zu floats)",
+                  scratch_floats, need);
+    FGC_CHECK_ARG(ms_dir_apart(x, nx, traj, need_traj) && ms_dir_apart(x, nx, scratch, need) &&
+                      ms_dir_apart(traj, need_traj, scratch, need),
+                  "fgc_vertex_update_ms_dir_traj: x, traj and the scratch must be distinct");
+    FGC_CHECK_ARG(!t_out || (ms_dir_apart(t_out, nv, x, nx) && ms_dir_apart(t_out, nv, traj, need_traj) &&
+                             ms_dir_apart(t_out, nv, scratch, need)),
+                  "fgc_vertex_update_ms_dir_traj: t_out must be a buffer of its own");
+    hipStream_t st = (hipStream_t)stream;
+    float* t = scratch;
+    float* fp0 = t + nv;
+    float* fp1 = fp0 + 3 * (size_t)n0;
+    float* fp2 = fp1 + 3 * (size_t)n1;
+    const float* nrm[3] = {normals0, normals1, normals2};
+    float* fps[3] = {fp0, fp1, fp2};
+    const int nn[3] = {n0, n1, n2};
+    if (hipMemsetAsync(t, 0, (size_t)nv * 4, st) != hipSuccess ||
+        hipMemcpyAsync(traj, x, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        fgc::set_error("fgc_vertex_update_ms_dir_traj: copy failed");
+        return FGC_EHIP;
+    }
+    size_t k = 0;
+    for (int stage = 0; stage < 3; ++stage)
+        for (int it = 0; it < iters[stage]; ++it, ++k)
+            ms_dir_iteration(st, x, traj + k * nx, traj + (k + 1) * nx, t, nv, faces, n0, v_faces, k_v, 2 - stage, nrm, fps,
+                             nn, dirs, n_dirs == 1 ? 0 : 3);
+    if (t_out && hipMemcpyAsync(t_out, t, (size_t)nv * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        fgc::set_error("fgc_vertex_update_ms_dir_traj: copy failed");
+        return FGC_EHIP;
+    }
+    FGC_CHECK_LAUNCH("fgc_vertex_update_ms_dir_traj");
+    return FGC_OK;
+}
+
+extern "C" size_t fgc_vertex_update_ms_dir_bwd_workspace_floats(int32_t nv, int32_t n0) {
+    if (nv <= 0 || n0 <= 0) return 0;
+    return fgc_vertex_update_ms_bwd_workspace_floats(nv, n0) + 3 * (size_t)nv;      // and the projected gradient
+}
+
+// The adjoint of the multi-scale update, free (dirs == NULL: fgc_vertex_update_ms_bwd) or along dirs
+// (fgc_vertex_update_ms_dir_bwd): one body, so the two cannot drift apart.  Along dirs every iteration first writes the
+// projected gradient gp (3 nv more workspace floats, behind the two gradient buffers); the node kernel then reads gp in the
+// place of g, and the vertex kernel takes both.  fn: the entry point's name, for the messages.
+static int ms_bwd_impl(const char* fn, const float* traj, size_t traj_floats, int32_t nv, const int32_t* faces, int32_t n0,
+                       const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
+                       const float* normals2, const int32_t* iters, const float* dirs, int32_t n_dirs,
+                       const int32_t* slot_ptr, const int32_t* slot_vert, const int32_t* inc_ptr, const int32_t* inc_face,
+                       const float* g_out, float* g_x, float* g_n0, float* g_n1, float* g_n2, float* workspace,
+                       size_t workspace_floats, void* stream) {
     FGC_CHECK_ARG(traj && faces && v_faces && normals0 && normals1 && normals2 && iters && slot_ptr && slot_vert &&
                       inc_ptr && inc_face && g_out && g_x && g_n0 && g_n1 && g_n2 && workspace,
-                  "fgc_vertex_update_ms_bwd: null pointer");
-    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0,
-                  "fgc_vertex_update_ms_bwd: nv=%d n0=%d (multiple of 16) k_v=%d", nv, n0, k_v);
-    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0, "fgc_vertex_update_ms_bwd: negative iteration count");
-    const size_t need = fgc_vertex_update_ms_bwd_workspace_floats(nv, n0);
-    FGC_CHECK_ARG(workspace_floats >= need, "fgc_vertex_update_ms_bwd: workspace too small (%zu < %zu floats)",
-                  workspace_floats, need);
+                  "%s: null pointer", fn);
+    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0, "%s: nv=%d n0=%d (multiple of 16) k_v=%d", fn, nv, n0, k_v);
+    FGC_CHECK_ARG(!dirs || n_dirs == 1 || n_dirs == nv, "%s: n_dirs=%d (1, or nv=%d)", fn, n_dirs, nv);
+    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0, "%s: negative iteration count", fn);
+    const size_t need = dirs ? fgc_vertex_update_ms_dir_bwd_workspace_floats(nv, n0)
+                             : fgc_vertex_update_ms_bwd_workspace_floats(nv, n0);
+    FGC_CHECK_ARG(workspace_floats >= need, "%s: workspace too small (%zu < %zu floats)", fn, workspace_floats, need);
     const size_t need_traj = ((size_t)iters[0] + iters[1] + iters[2] + 1) * 3 * (size_t)nv;
-    FGC_CHECK_ARG(traj_floats >= need_traj, "fgc_vertex_update_ms_bwd: traj too small (%zu < %zu floats)", traj_floats,
-                  need_traj);
-    FGC_CHECK_ARG(g_out != g_x, "fgc_vertex_update_ms_bwd: g_out and g_x must be distinct");
+    FGC_CHECK_ARG(traj_floats >= need_traj, "%s: traj too small (%zu < %zu floats)", fn, traj_floats, need_traj);
+    FGC_CHECK_ARG(g_out != g_x, "%s: g_out and g_x must be distinct", fn);
     const int n1 = n0 / 4, n2 = n0 / 16;
+    const int dstride = n_dirs == 1 ? 0 : 3;
     hipStream_t st = (hipStream_t)stream;
     float* lam = workspace;
     float* ga = lam + nv;
     float* gb = ga + 3 * (size_t)nv;
-    float* fp0 = gb + 3 * (size_t)nv;
+    float* gp = gb + 3 * (size_t)nv;                      // (along dirs only)
+    float* fp0 = dirs ? gp + 3 * (size_t)nv : gp;
     float* fp1 = fp0 + 3 * (size_t)n0;
     float* fp2 = fp1 + 3 * (size_t)n1;
     float* gc0 = fp2 + 3 * (size_t)n2;
@@ -581,11 +826,11 @@ extern "C" int fgc_vertex_update_ms_bwd(const float* traj, size_t traj_floats, i
     const int nn[3] = {n0, n1, n2};
     for (int s = 0; s < 3; ++s)
         if (hipMemsetAsync(gns[s], 0, (size_t)nn[s] * 12, st) != hipSuccess) {
-            fgc::set_error("fgc_vertex_update_ms_bwd: memset failed");
+            fgc::set_error("%s: memset failed", fn);
             return FGC_EHIP;
         }
     if (hipMemcpyAsync(ga, g_out, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        fgc::set_error("fgc_vertex_update_ms_bwd: copy failed");
+        fgc::set_error("%s: copy failed", fn);
         return FGC_EHIP;
     }
     FGC_LAUNCH("vertex_lambda_kernel", st, vertex_lambda_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, v_faces, k_v, nv, lam);
@@ -603,22 +848,56 @@ extern "C" int fgc_vertex_update_ms_bwd(const float* traj, size_t traj_floats, i
                 FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n1 * 3, 256)), dim3(256), 0, fp0, n1, 3, fp1);
             if (scale >= 2)
                 FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n2 * 3, 256)), dim3(256), 0, fp1, n2, 3, fp2);
+            if (dirs)
+                FGC_LAUNCH("project_rows_kernel", st, project_rows_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, cur, nv, dirs,
+                           dstride, gp);
             FGC_LAUNCH("vertex_ms_bwd_node_kernel", st, vertex_ms_bwd_node_kernel, dim3(cdiv(nn[scale], 256)), dim3(256), 0,
-                       cur, xt, lam, slot_ptr, slot_vert, 2 * scale, nn[scale], nrm[scale], fps[scale], gcs[scale], gns[scale]);
+                       dirs ? gp : cur, xt, lam, slot_ptr, slot_vert, 2 * scale, nn[scale], nrm[scale], fps[scale], gcs[scale],
+                       gns[scale]);
             for (int l = scale; l >= 1; --l)
                 FGC_LAUNCH("pool4_avg_iz_bwd_kernel", st, pool4_avg_iz_bwd_kernel, dim3(cdiv(nn[l], 256)), dim3(256), 0,
                            fps[l - 1], nn[l], gcs[l], gcs[l - 1]);
-            FGC_LAUNCH("vertex_ms_bwd_vertex_kernel", st, vertex_ms_bwd_vertex_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, cur,
-                       nv, lam, v_faces, k_v, 2 * scale, nrm[scale], nn[scale], inc_ptr, inc_face, gc0, nxt);
+            if (dirs)
+                FGC_LAUNCH("vertex_ms_dir_bwd_vertex_kernel", st, vertex_ms_dir_bwd_vertex_kernel, dim3(cdiv(nv, 256)),
+                           dim3(256), 0, cur, gp, nv, lam, v_faces, k_v, 2 * scale, nrm[scale], nn[scale], inc_ptr, inc_face, gc0,
+                           nxt);
+            else
+                FGC_LAUNCH("vertex_ms_bwd_vertex_kernel", st, vertex_ms_bwd_vertex_kernel, dim3(cdiv(nv, 256)), dim3(256), 0,
+                           cur, nv, lam, v_faces, k_v, 2 * scale, nrm[scale], nn[scale], inc_ptr, inc_face, gc0, nxt);
             float* tmp = cur;
             cur = nxt;
             nxt = tmp;
         }
     }
     if (hipMemcpyAsync(g_x, cur, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        fgc::set_error("fgc_vertex_update_ms_bwd: copy failed");
+        fgc::set_error("%s: copy failed", fn);
         return FGC_EHIP;
     }
-    FGC_CHECK_LAUNCH("fgc_vertex_update_ms_bwd");
+    FGC_CHECK_LAUNCH(fn);
     return FGC_OK;
+}
+
+extern "C" int fgc_vertex_update_ms_bwd(const float* traj, size_t traj_floats, int32_t nv, const int32_t* faces, int32_t n0,
+                                        const int32_t* v_faces, int32_t k_v, const float* normals0,
+                                        const float* normals1, const float* normals2, const int32_t* iters,
+                                        const int32_t* slot_ptr, const int32_t* slot_vert, const int32_t* inc_ptr,
+                                        const int32_t* inc_face, const float* g_out, float* g_x, float* g_n0,
+                                        float* g_n1, float* g_n2, float* workspace, size_t workspace_floats,
+                                        void* stream) {
+    return ms_bwd_impl("fgc_vertex_update_ms_bwd", traj, traj_floats, nv, faces, n0, v_faces, k_v, normals0, normals1,
+                       normals2, iters, nullptr, 0, slot_ptr, slot_vert, inc_ptr, inc_face, g_out, g_x, g_n0, g_n1, g_n2,
+                       workspace, workspace_floats, stream);
+}
+
+extern "C" int fgc_vertex_update_ms_dir_bwd(const float* traj, size_t traj_floats, int32_t nv, const int32_t* faces,
+                                            int32_t n0, const int32_t* v_faces, int32_t k_v, const float* normals0,
+                                            const float* normals1, const float* normals2, const int32_t* iters,
+                                            const float* dirs, int32_t n_dirs, const int32_t* slot_ptr,
+                                            const int32_t* slot_vert, const int32_t* inc_ptr, const int32_t* inc_face,
+                                            const float* g_out, float* g_x, float* g_n0, float* g_n1, float* g_n2,
+                                            float* workspace, size_t workspace_floats, void* stream) {
+    FGC_CHECK_ARG(dirs, "fgc_vertex_update_ms_dir_bwd: null pointer");
+    return ms_bwd_impl("fgc_vertex_update_ms_dir_bwd", traj, traj_floats, nv, faces, n0, v_faces, k_v, normals0, normals1,
+                       normals2, iters, dirs, n_dirs, slot_ptr, slot_vert, inc_ptr, inc_face, g_out, g_x, g_n0, g_n1, g_n2,
+                       workspace, workspace_floats, stream);
 }

@@ -1,6 +1,7 @@
 """Denoise every OBJ of a folder (the reference's infer.py:40-100 for the face-normal network, withVerts = False):
 
     python -m facet_graph_convolution_amd.infer NOISY_DIR RESULTS_DIR NETWORK.pt [--view-dir X,Y,Z | --camera X,Y,Z]
+        [--with-vertices [--ray-update]]
 
 For each `name.obj`: preprocess (native adjacency + coarsening), predict the facet normals, move the vertices with 60
 iterations of update_position2, write `name_denoised.obj` (same faces) and, like the reference,
@@ -13,8 +14,11 @@ moves the vertices with update_position_MS and writes `name_denoised.obj`, `name
 
 --view-dir / --camera (depth-scan mode, README "Depth scans"): the mesh is a depth scan seen along one direction, or from a
 camera position given in the mesh's raw units.  The viewing rays are built from the NOISY input's vertices
-(utils.view_rays) and the 60 iterations are update_position_with_depth's: every vertex moves along its ray only.  Not with
---with-vertices: the multi-scale update has no ray-constrained form (nor has the reference).
+(utils.view_rays) and the 60 iterations are update_position_with_depth's: every vertex moves along its ray only.  With
+--with-vertices the two options need --ray-update (as `train --ray-update`; without it they are refused as before: the
+multi-scale update of the reference has no ray-constrained form): the 80 / 20 / 20 iterations of update_position_MS are then
+the ray-constrained ones (a build extension, include/fgc.h: fgc_vertex_update_ms_dir), the vertices of all three files lie
+on their rays.
 """
 import argparse
 import os
@@ -46,11 +50,12 @@ def denoise_file(net, noisy_dir, filename, results_dir, overwrite=False, log=pri
     return out_path
 
 
-def denoise_file_with_vertices(net, noisy_dir, filename, results_dir, overwrite=False, log=print):
-    """infer.py:82-101 withVerts: the three vertex sets of inferNet as OBJ files with the input's faces."""
+def denoise_file_with_vertices(net, noisy_dir, filename, results_dir, overwrite=False, log=print, view=None):
+    """infer.py:82-101 withVerts: the three vertex sets of inferNet as OBJ files with the input's faces.  view: as in
+    denoise_file - the rays of the noisy input's raw vertices go to inferNet(depth_dir=)."""
     from .dataClasses import InferenceMesh
     from .train import inferNet
-    from .utils import write_mesh
+    from .utils import write_mesh, view_rays
     out_path = os.path.join(results_dir, filename[:-4] + "_denoised.obj")
     if os.path.isfile(out_path) and not overwrite:
         log("Skipping %s. File already exists." % os.path.basename(out_path))
@@ -60,7 +65,8 @@ def denoise_file_with_vertices(net, noisy_dir, filename, results_dir, overwrite=
     mesh.addMeshWithVertices(noisy_dir, filename)
     log("mesh added (%.0f ms): %d faces" % (1000 * (time.time() - t0), mesh.faces.shape[0]))
     t0 = time.time()
-    res = inferNet(mesh, net)
+    rays = view_rays(np.asarray(mesh.vertices).reshape(-1, 3), **view) if view else None
+    res = inferNet(mesh, net, depth_dir=rays)
     log("Inference complete (%.0f ms)" % (1000 * (time.time() - t0)))
     write_mesh(res[0], mesh.faces, out_path)
     write_mesh(res[1], mesh.faces, os.path.join(results_dir, filename[:-4] + "_d_mid.obj"))
@@ -78,11 +84,17 @@ def main(argv=None):
                     help="multi-scale network + update_position_MS (a network trained by trainAccuracyNet)")
     from .utils import view_options, view_spec
     view_options(ap)
+    ap.add_argument("--ray-update", action="store_true",
+                    help="with --with-vertices and --view-dir / --camera: update_position_MS moves every vertex along its "
+                    "viewing ray only (a build extension)")
     args = ap.parse_args(argv)
     view = view_spec(ap, args)
-    if view and args.with_vertices:
+    if view and args.with_vertices and not args.ray_update:
         ap.error("--view-dir / --camera go with the single-scale vertex update: the multi-scale update of --with-vertices "
-                 "has no ray-constrained form")
+                 "has no ray-constrained form unless --ray-update asks for this build's (fgc_vertex_update_ms_dir)")
+    if args.ray_update and not (view and args.with_vertices):
+        ap.error("--ray-update constrains the multi-scale vertex update to the viewing rays: it needs --with-vertices and "
+                 "--view-dir or --camera")
     from .net import FacetDenoiser
     from .train import load_checkpoint
     net = FacetDenoiser("cuda:0", multi_scale=args.with_vertices)

@@ -713,7 +713,7 @@ class FacetDenoiser:
         return self._require_synth()["v_out"]
 
     def bind_clean_vertices(self, key, x, adjs, verts, faces_rows, v_faces, edge_len, gt_normals=None, iters=VERTEX_ITERS,
-                            seed=0, stream=0, direction="random", lf=None):
+                            seed=0, stream=0, direction="random", lf=None, ray_update=False):
         """Build extension: bind a CLEAN mesh for the point-set and double-loss steps on noise synthesised per step -
         bind_vertices plus bind_clean's synthesis state, kept with the mesh under `key`.  verts [V,3]: the RAW clean
         vertices (TrainingSet.addCleanMeshWithVertices' clean_vertices), which are also the ground-truth vertices;
@@ -724,15 +724,24 @@ class FacetDenoiser:
         and rotates both, straight into the buffers the vertex update and fgc_point_loss read - in the place of the two
         fgc_rotate_rows launches of a mesh bound by bind_vertices.  The last launch has no control word: while the noise
         words are zero (right after binding, or set_noise(step, None)) a step runs on the vertices the last
-        synthesising step left; right after binding these are the clean ones."""
+        synthesising step left; right after binding these are the clean ones.
+        ray_update: the vertex update of every step is the ray-constrained one (bind_vertices(depth_dir=)) along the table
+        of rays the noise goes along - `direction`, built from the clean vertices - so the network is trained on what a depth
+        scan asks of it; refused unless `direction` is such a table."""
+        if ray_update and isinstance(direction, str):
+            raise ValueError("ray_update moves the vertices along the noise's rays: direction must be a [V,3] table of rays")
+
         def bind():
             # (the plain vertex state holds the clean mesh normalised by its own box; the steps read xr / gtr instead)
             from .utils import normalizePointSets
             vx = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
             vn = normalizePointSets(vx, vx)[0]
-            self.bind_vertices(key, x, adjs, vn, faces_rows, v_faces, vn, iters=iters)
+            self.bind_vertices(key, x, adjs, vn, faces_rows, v_faces, vn, iters=iters,
+                               depth_dir=direction if ray_update else None)
             return self._mesh
         M, fresh = self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf), True, bind)
+        if bool(ray_update) != (M["verts"]["dirs"] is not None):      # (the direction itself: compared by _bind_synth)
+            raise ValueError("mesh %r is bound %s ray_update" % (key, "without" if ray_update else "with"))
         if fresh:
             S = M["synth"]
             nv, sc = S["v"].shape[0], S["scratch"]
@@ -1494,13 +1503,23 @@ class FacetDenoiser:
     # ------------------------------------------------------------------------------------------
     # point-set training (trainAccuracyNet, train.py:636-916): network -> update_position_MS -> fullLoss
     # ------------------------------------------------------------------------------------------
-    def bind_vertices(self, key, x, adjs, verts, faces, v_faces, gt_verts, iters=VERTEX_ITERS, gt_normals=None):
+    def bind_vertices(self, key, x, adjs, verts, faces, v_faces, gt_verts, iters=VERTEX_ITERS, gt_normals=None,
+                      depth_dir=None):
         """Bind a mesh for the point-set step: its graph (bind_cached under `key`) together with its vertex data - the
         normalised vertices [V,3], the faces in node order [N0,3] (-1 rows = fake nodes), v_faces [V,K], the
         ground-truth vertices [Vgt,3] and the two inverse tables of the vertex-update adjoint (ops.vertex_ms_tables) -
         all cached with the graph, like bind_cached.  gt_normals: the ground-truth face normals [N0,3] in node order
-        (gt_list), for the double-loss step; uploaded into the cached vertex state (the first time they are given)."""
+        (gt_list), for the double-loss step; uploaded into the cached vertex state (the first time they are given).
+        depth_dir (build extension): [V,3] or [1,3] viewing rays (utils.view_rays; used as given, rows longer than 1 can
+        diverge), kept with the cached vertex state - the steps then run the ray-constrained update and its adjoint
+        (include/fgc.h: fgc_vertex_update_ms_dir_traj / _bwd), with the rays rotated like the vertices.  A key is bound
+        with its rays or without for good: a later bind that differs is refused."""
         self._require_vertex_network()
+        if depth_dir is not None:      # (before anything is bound under the key)
+            shape = tuple(depth_dir.shape) if hasattr(depth_dir, "shape") else np.shape(depth_dir)
+            nv = np.asarray(verts).reshape(-1, 3).shape[0]
+            if shape[-1:] != (3,) or int(np.prod(shape[:-1])) not in (1, nv):
+                raise ValueError("depth_dir: [V,3] or [1,3] rows for %d vertices, got shape %r" % (nv, shape))
 
         def bind():
             # the backward buffers of the heads come with a ground truth; the point-set step never reads its values
@@ -1534,10 +1553,45 @@ class FacetDenoiser:
             V["loss_ws"] = torch.empty(self.L.fgc_point_loss_workspace_bytes(nv, gv.shape[0], POINT_SAMPLES, POINT_SAMPLES)
                                        + 256, dtype=torch.uint8, device=dev)
             V["threshold"] = POINT_LOSS_THRESHOLD
+            V["dirs"] = None
+            if depth_dir is not None:
+                self._attach_rays(V, depth_dir, n0)
             M["verts"] = V
             M["mode"].verts = True
+        elif not self._same_rays(M["verts"], depth_dir):
+            raise ValueError("mesh %r is bound with other rays, or without (depth_dir)" % (key,))
         self._attach_gt_normals(M, gt_normals)
         return self
+
+    def _attach_rays(self, V, depth_dir, n0):
+        """The ray table of the constrained vertex update and its buffers into the vertex state V."""
+        nv = V["x"].shape[0]
+        if isinstance(depth_dir, torch.Tensor):
+            depth_dir = depth_dir.detach().cpu().numpy()
+        d = np.array(depth_dir, dtype=np.float32, order="C").reshape(-1, 3)
+        if d.shape[0] not in (1, nv) or not np.isfinite(d).all():
+            raise ValueError("depth_dir: finite rows, one or one per vertex (%d), got %d" % (nv, d.shape[0]))
+        f = dict(dtype=torch.float32, device=self.device)
+        V["dirs"], V["dirs_key"] = torch.as_tensor(d, device=self.device), direction_key(d)
+        V["dirs_r"] = torch.empty_like(V["dirs"])
+        V["dir_scratch"] = torch.empty(self.L.fgc_vertex_update_ms_dir_scratch_floats(nv, n0), **f)
+        V["dir_bwd_ws"] = torch.empty(self.L.fgc_vertex_update_ms_dir_bwd_workspace_floats(nv, n0), **f)
+
+    @staticmethod
+    def _same_rays(V, depth_dir):
+        """Whether depth_dir is what the vertex state V was bound with (None: without rays): by the digest of the rows."""
+        if depth_dir is None or V["dirs"] is None:
+            return depth_dir is None and V["dirs"] is None
+        if isinstance(depth_dir, torch.Tensor):
+            depth_dir = depth_dir.detach().cpu().numpy()
+        return direction_key(np.asarray(depth_dir, dtype=np.float32).reshape(-1, 3)) == V["dirs_key"]
+
+    def _step_rays(self, rotate):
+        """The ray table a step of the bound mesh runs along (None: the free update): rotated steps read the rotated copy."""
+        V = self._mesh["verts"]
+        if V["dirs"] is None:
+            return None
+        return V["dirs_r"] if rotate else V["dirs"]
 
     def _require_vertex_network(self):
         if not self.multi_scale or self.dtype != "f32":      # (bind_cached binds unsharded)
@@ -1603,10 +1657,21 @@ class FacetDenoiser:
             x, gt = V["xr"], V["gtr"]
         self._tag("pts:vertex_fwd")
         it = (C.c_int32 * 3)(*V["iters"])
-        _lib.check(L.fgc_vertex_update_ms_traj(_p(x), nv, _p(V["faces"]), n0, _p(V["v_faces"]), V["v_faces"].shape[1],
-                                               _p(heads[0]), _p(heads[1]), _p(heads[2]), it, _p(V["traj"]),
-                                               V["traj"].numel(), _p(V["centres"]), V["centres"].numel(), st),
-                   "vertex update")
+        rays = self._step_rays(rotate)
+        if rays is not None:
+            # along rays: the rays turn with the vertices (fgc_point_sets_prepare scales uniformly: they stay valid there)
+            if rotate:
+                _lib.check(L.fgc_rotate_rows(_p(V["dirs"]), _p(rays), rays.shape[0], 1, _p(B["R"]), st), "rotate rays")
+            sc = V["dir_scratch"]
+            _lib.check(L.fgc_vertex_update_ms_dir_traj(_p(x), nv, _p(V["faces"]), n0, _p(V["v_faces"]),
+                                                       V["v_faces"].shape[1], _p(heads[0]), _p(heads[1]), _p(heads[2]), it,
+                                                       _p(rays), rays.shape[0], _p(V["traj"]), V["traj"].numel(), None,
+                                                       _p(sc), sc.numel(), st), "vertex update along rays")
+        else:
+            _lib.check(L.fgc_vertex_update_ms_traj(_p(x), nv, _p(V["faces"]), n0, _p(V["v_faces"]), V["v_faces"].shape[1],
+                                                   _p(heads[0]), _p(heads[1]), _p(heads[2]), it, _p(V["traj"]),
+                                                   V["traj"].numel(), _p(V["centres"]), V["centres"].numel(), st),
+                       "vertex update")
         self._tag("pts:loss")
         T = sum(V["iters"])
         refined = C.c_void_p(V["traj"].data_ptr() + T * nv * 12)
@@ -1635,11 +1700,21 @@ class FacetDenoiser:
         # dL/d normals: head 0 into g_nconv (then through normalizeTensor), the raw coarse heads straight into g_y1 / g_y2
         # (double: the normalised coarse heads into g_nconv1 / g_nconv2, then through their own normalizeTensor)
         heads, g_heads = self._vertex_heads(double)
-        _lib.check(L.fgc_vertex_update_ms_bwd(_p(V["traj"]), V["traj"].numel(), nv, _p(V["faces"]), n0, _p(V["v_faces"]),
-                                              V["v_faces"].shape[1], _p(heads[0]), _p(heads[1]), _p(heads[2]), it,
-                                              _p(sp), _p(sv), _p(ip), _p(fi), _p(V["g_p"]), _p(V["g_x"]),
-                                              _p(g_heads[0]), _p(g_heads[1]), _p(g_heads[2]), _p(wsv), wsv.numel(), st),
-                   "vertex update bwd")
+        rays = self._step_rays(rotate)      # (rotated by the forward)
+        if rays is not None:
+            wsv = V["dir_bwd_ws"]
+            _lib.check(L.fgc_vertex_update_ms_dir_bwd(_p(V["traj"]), V["traj"].numel(), nv, _p(V["faces"]), n0,
+                                                      _p(V["v_faces"]), V["v_faces"].shape[1], _p(heads[0]), _p(heads[1]),
+                                                      _p(heads[2]), it, _p(rays), rays.shape[0], _p(sp), _p(sv), _p(ip),
+                                                      _p(fi), _p(V["g_p"]), _p(V["g_x"]), _p(g_heads[0]), _p(g_heads[1]),
+                                                      _p(g_heads[2]), _p(wsv), wsv.numel(), st),
+                       "vertex update along rays bwd")
+        else:
+            _lib.check(L.fgc_vertex_update_ms_bwd(_p(V["traj"]), V["traj"].numel(), nv, _p(V["faces"]), n0, _p(V["v_faces"]),
+                                                  V["v_faces"].shape[1], _p(heads[0]), _p(heads[1]), _p(heads[2]), it,
+                                                  _p(sp), _p(sv), _p(ip), _p(fi), _p(V["g_p"]), _p(V["g_x"]),
+                                                  _p(g_heads[0]), _p(g_heads[1]), _p(g_heads[2]), _p(wsv), wsv.numel(), st),
+                       "vertex update bwd")
         if double:
             self._tag("dl:bwd")      # (added to what the vertex adjoint has just written)
             sc = V["dl_scratch"]

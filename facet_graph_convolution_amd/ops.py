@@ -637,6 +637,84 @@ def vertex_update_ms_bwd(traj, normals, faces, v_faces, g_out, iters=(80, 20, 20
     return g_x, g_n
 
 
+def _ms_dirs(dirs, nv, device):
+    """dirs ([V,3] or [1,3]; tensor or array-like) as the contiguous fp32 device rows of the *_ms_dir entry points."""
+    if not isinstance(dirs, torch.Tensor):
+        dirs = torch.from_numpy(np.ascontiguousarray(np.asarray(dirs, dtype=np.float32)))
+    dirs = dirs.to(device)
+    _req_cuda(dirs)
+    dirs = _f32c(dirs.reshape(-1, 3))
+    if dirs.shape[0] not in (1, nv):
+        raise ValueError("dirs has %d rows: one row, or one per vertex (%d)" % (dirs.shape[0], nv))
+    return dirs
+
+
+def vertex_update_ms_dir(x, normals, faces, v_faces, dirs, iters=(80, 20, 20), return_t=False):
+    """vertex_update_ms with every iteration's step projected onto the vertex' direction, dirs [V,3] or [1,3] (used as
+    given; rows longer than 1 can diverge) - a build extension, include/fgc.h: fgc_vertex_update_ms_dir.  Returns
+    (x_out [V,3], dx [3,V,3]); return_t: (x_out, dx, t [V]), t the signed step along the direction, x_out = fma(t, dirs,
+    x)."""
+    x, (n0, n1, n2), faces, v_faces = _ms_args(x, normals, faces, v_faces)
+    nv, N0 = x.shape[0], faces.shape[0]
+    dirs = _ms_dirs(dirs, nv, x.device)
+    L = _lib.lib()
+    out = torch.empty_like(x)
+    dx = torch.empty(3, nv, 3, dtype=torch.float32, device=x.device)
+    t = torch.empty(nv, dtype=torch.float32, device=x.device) if return_t else None
+    scr = torch.empty(L.fgc_vertex_update_ms_dir_scratch_floats(nv, N0), dtype=torch.float32, device=x.device)
+    it = (C.c_int32 * 3)(*[int(i) for i in iters])
+    check(L.fgc_vertex_update_ms_dir(ptr(x), ptr(out), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0), ptr(n1),
+                                     ptr(n2), it, ptr(dirs), dirs.shape[0], ptr(t), ptr(dx), ptr(scr), scr.numel(),
+                                     stream_ptr()), "fgc_vertex_update_ms_dir")
+    return (out, dx, t) if return_t else (out, dx)
+
+
+def vertex_update_ms_dir_traj(x, normals, faces, v_faces, dirs, iters=(80, 20, 20), return_t=False):
+    """vertex_update_ms_dir keeping every iterate: traj [T+1, V, 3] (traj[0] = x, traj[-1] = vertex_update_ms_dir's x_out,
+    bit for bit; include/fgc.h: fgc_vertex_update_ms_dir_traj); return_t: (traj, t [V])."""
+    x, (n0, n1, n2), faces, v_faces = _ms_args(x, normals, faces, v_faces)
+    nv, N0 = x.shape[0], faces.shape[0]
+    dirs = _ms_dirs(dirs, nv, x.device)
+    L = _lib.lib()
+    T = sum(int(i) for i in iters)
+    traj = torch.empty(T + 1, nv, 3, dtype=torch.float32, device=x.device)
+    t = torch.empty(nv, dtype=torch.float32, device=x.device) if return_t else None
+    scr = torch.empty(L.fgc_vertex_update_ms_dir_scratch_floats(nv, N0), dtype=torch.float32, device=x.device)
+    it = (C.c_int32 * 3)(*[int(i) for i in iters])
+    check(L.fgc_vertex_update_ms_dir_traj(ptr(x), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0), ptr(n1),
+                                          ptr(n2), it, ptr(dirs), dirs.shape[0], ptr(traj), traj.numel(), ptr(t), ptr(scr),
+                                          scr.numel(), stream_ptr()), "fgc_vertex_update_ms_dir_traj")
+    return (traj, t) if return_t else traj
+
+
+def vertex_update_ms_dir_bwd(traj, normals, faces, v_faces, dirs, g_out, iters=(80, 20, 20), tables=None):
+    """Adjoint of vertex_update_ms_dir (include/fgc.h: fgc_vertex_update_ms_dir_bwd): given the trajectory of
+    vertex_update_ms_dir_traj and g_out = dL/dx_out [V,3], returns (dL/dx [V,3], [dL/dn0, dL/dn1, dL/dn2]); no gradient
+    with respect to dirs.  tables: the device tensors of vertex_ms_tables (built here when None)."""
+    nv = traj.shape[1]
+    if traj.dtype != torch.float32 or not traj.is_contiguous():
+        raise ValueError("traj must be the contiguous float32 [T+1, V, 3] of vertex_update_ms_dir_traj")
+    _, (n0, n1, n2), faces, v_faces = _ms_args(traj[0], normals, faces, v_faces)
+    dirs = _ms_dirs(dirs, nv, traj.device)
+    _req_cuda(g_out)
+    g_out = _f32c(g_out.reshape(nv, 3))
+    N0 = faces.shape[0]
+    if tables is None:
+        tables = [torch.as_tensor(t, device=traj.device)
+                  for t in vertex_ms_tables(faces.cpu().numpy(), v_faces.cpu().numpy(), nv)]
+    sp, sv, ip, fi = tables
+    g_x = torch.empty(nv, 3, dtype=torch.float32, device=traj.device)
+    g_n = [torch.empty_like(t) for t in (n0, n1, n2)]
+    L = _lib.lib()
+    ws = _workspace(L.fgc_vertex_update_ms_dir_bwd_workspace_floats(nv, N0) * 4, traj.device, "vms_dir_bwd")
+    it = (C.c_int32 * 3)(*[int(i) for i in iters])
+    check(L.fgc_vertex_update_ms_dir_bwd(ptr(traj), traj.numel(), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1],
+                                         ptr(n0), ptr(n1), ptr(n2), it, ptr(dirs), dirs.shape[0], ptr(sp), ptr(sv), ptr(ip),
+                                         ptr(fi), ptr(g_out), ptr(g_x), ptr(g_n[0]), ptr(g_n[1]), ptr(g_n[2]), ptr(ws),
+                                         ws.numel() // 4, stream_ptr()), "fgc_vertex_update_ms_dir_bwd")
+    return g_x, g_n
+
+
 def point_loss(p0, p1, sample_ind0, sample_ind1, threshold=5000.0, want_grad=True):
     """fullLoss (train.py:1373-1424; include/fgc.h: fgc_point_loss) of the points p0 [n0,3] against p1 [n1,3] on the
     sampled rows: (loss [1], dloss/dp0 [n0,3] or None)."""

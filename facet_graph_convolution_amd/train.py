@@ -12,7 +12,7 @@ Training command (the reference's ``train(withVerts)``, train.py:1894-1921):
 
     python -m facet_graph_convolution_amd.train DUMP_DIR NETWORK_DIR [--num-iterations N] [--net-name NAME]
         [--with-vertices] [--double-loss] [--capture] [--seed S]
-        [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal|ray] [--view-dir X,Y,Z | --camera X,Y,Z]
+        [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal|ray] [--view-dir X,Y,Z | --camera X,Y,Z] [--ray-update]
         [--lf-noise 0.3,0.2,0.1[:WIDTH[:BUMPS]]]
 
 loads the pickles `preprocess` wrote and runs trainNet, trainAccuracyNet (--with-vertices) or trainDoubleLossNet
@@ -224,13 +224,15 @@ _RAYS = {}
 
 def _bind(F, key, m, noise=None):
     """Bind mesh record m under `key` through F = net.trainer_form(form): plain, or - noise = (seed, stream, direction
-    [, lf = (width, bumps)]) - clean for noise synthesis.  (A cached mesh returns at once; the bind methods reshape the
-    [1, ...] arrays.)"""
+    [, lf = (width, bumps)[, ray_update]]) - clean for noise synthesis.  (A cached mesh returns at once; the bind methods
+    reshape the [1, ...] arrays.)"""
     kw = {"gt_normals": m.gt_normals} if F.gt_normals else {}
     if noise is not None:
         kw.update(seed=noise[0], stream=noise[1], direction=_mesh_direction(noise[2], m))
         if len(noise) > 3 and noise[3] is not None:
             kw.update(lf=noise[3])
+        if len(noise) > 4 and noise[4]:
+            kw.update(ray_update=True)      # (the vertex trainers only: bind_clean_vertices)
     (F.bind if noise is None else F.bind_clean)(key, *m.args, **kw)
 
 
@@ -250,15 +252,15 @@ def _draw_step(rs, F, m, levels, counter, lf_levels=None):
     return samples, R, (counter, levels[k]) if lf_levels is None else (counter, levels[k], lf_levels[k])
 
 
-def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="random", lf=None):
+def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="random", lf=None, ray_update=False):
     """The mean {total, points, normals} (entries a form does not have stay 0) of the loss alone over the validation mesh
     records, with rotation R and fresh rows from rs: one pass per mesh, or - levels given - per clean mesh and noise level
     with stream = 1 + mesh index and step = level index: the SAME noisy meshes at every call (and what makeNoisy writes for
     the same seed), so the validation curve is comparable along a run.  lf = (lf levels, (width, bumps)) of _lf_inputs:
-    level k goes with lf level k."""
+    level k goes with lf level k.  ray_update: the vertex update along the noise's rays, as in training."""
     F, vsum = net.trainer_form(form), np.zeros(3)
     for vbm, m in enumerate(valid):
-        _bind(F, ("valid", vbm), m, None if levels is None else (seed, 1 + vbm, direction, lf and lf[1]))
+        _bind(F, ("valid", vbm), m, None if levels is None else (seed, 1 + vbm, direction, lf and lf[1], ray_update))
         for k, level in enumerate((None,) if levels is None else levels):
             F.set_samples(*_draw_samples(rs, F, m))
             net.set_rotation(R)
@@ -274,10 +276,12 @@ def synthValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="rand
     return float(_validation_loss(net, "angular", valid, R, rs, noise_levels, seed, direction, lf)[0])
 
 
-def synthVertexValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", double=False, lf=None):
+def synthVertexValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", double=False, lf=None,
+                              ray_update=False):
     """Build extension: {total, points, normals} (double) or {points, 0, 0} - the mean loss over every clean validation mesh
     (records of _clean_vertex_meshes) at every noise level (_validation_loss).  R: rotation; rs draws the 500 + 500 rows."""
-    return _validation_loss(net, "double" if double else "points", valid, R, rs, noise_levels, seed, direction, lf)
+    return _validation_loss(net, "double" if double else "points", valid, R, rs, noise_levels, seed, direction, lf,
+                            ray_update)
 
 
 def _resume(net, network_path, net_name):
@@ -362,7 +366,7 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
 
 def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
                      capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None,
-                     lf_width=3.0, lf_bumps=None):
+                     lf_width=3.0, lf_bumps=None, ray_update=False):
     """train.py:636-916: the multi-scale network trained through update_position_MS on the point-set loss fullLoss.
     trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT.  One iteration = a random mesh
     (meshes without ground-truth vertices are skipped), SAMP_NUM = 500 random rows of the vertices and of the
@@ -385,15 +389,19 @@ def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net"
     rotation) x the mesh's mean edge length, along noise_direction, with the global iteration as the noise counter; the
     ground truth is the clean mesh.  Validation: synthVertexValidationLoss, every 20 iterations and - in this mode
     only - at iteration 0 as well.  lf_levels / lf_width / lf_bumps: low-frequency noise on top, as in trainNet.
+    ray_update (with noise_levels and a noise_direction of rays - a view or a [V,3] table; otherwise ValueError): the
+    vertex update of every training and validation step is the ray-constrained one along those rays
+    (update_position_MS(depth_dir=), FacetDenoiser.bind_clean_vertices(ray_update=True)): the network learns what
+    `infer --with-vertices --camera / --view-dir` will ask of it.  False: the free update, as before.
 
     Returns (net, lossArray of the last block, per-iteration training losses [num_iterations])."""
     return _train_with_vertices("points", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
-                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps)
+                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update)
 
 
 def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
                        capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None,
-                       lf_width=3.0, lf_bumps=None):
+                       lf_width=3.0, lf_bumps=None, ray_update=False):
     """train.py:919-1268: the multi-scale network trained on the point-set loss fullLoss PLUS the dense face-normal loss
     faceNormalsLoss of head 0 against the rotated ground-truth face normals (customLoss = pointsLoss + normalsLoss,
     unweighted, train.py:1100-1102).  trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT
@@ -408,20 +416,25 @@ def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="ne
     1, the previous row's validation entry set to the mean of its two neighbours), and the block is appended to
     `<net_name>.csv` at every save.
 
-    noise_levels / noise_direction / lf_levels / lf_width / lf_bumps (build extension): as in trainAccuracyNet; the
-    ground-truth normals are the clean ones.
+    noise_levels / noise_direction / lf_levels / lf_width / lf_bumps / ray_update (build extension): as in
+    trainAccuracyNet; the ground-truth normals are the clean ones.
 
     Returns (net, lossArray of the last block, per-iteration {total, points, normals} [num_iterations, 3])."""
     return _train_with_vertices("double", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
-                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps)
+                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update)
 
 
 def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
-                         noise_levels=None, noise_direction="random", lf_levels=None, lf_width=3.0, lf_bumps=None):
+                         noise_levels=None, noise_direction="random", lf_levels=None, lf_width=3.0, lf_bumps=None,
+                         ray_update=False):
     """The loop of trainAccuracyNet (form "points") and trainDoubleLossNet ("double")."""
     levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
     lf = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
-    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1])
+    ray_update = bool(ray_update)
+    if ray_update and (levels is None or isinstance(noise_direction, str)):
+        raise ValueError("ray_update moves the vertices along the noise's rays: it needs noise_levels and a noise_direction "
+                         "of rays (a view {'camera': xyz} / {'view_dir': xyz} or a [V,3] table)")
+    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1], ray_update)
     net = FacetDenoiser(device, multi_scale=True, seed=seed)
     F = net.trainer_form(form)
     ckpt = os.path.join(network_path, net_name) if network_path else None
@@ -446,7 +459,7 @@ def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name,
         samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it, lf and lf[0])
         row = (it % block) // evalStepNum
         if valid and it % validStepNum == 0 and it >= first_valid:
-            vsum = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf)
+            vsum = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf, ray_update)
             log(_VALID_LOG[F.outputs] % ((it,) + tuple(vsum[:F.outputs])))      # (the double loss with its points / normals split)
             lossArray[row, 1] = vsum[0]
             if row > 0:
@@ -542,7 +555,39 @@ class _UpdatePositionMSFn(torch.autograd.Function):
         return g_x, g_n[0], g_n[1], g_n[2], None, None, None, None
 
 
-def update_position_MS(x, face_normals_list, faces, v_faces0, coarsening_steps, iter_num_list=[80, 20, 20], tables=None):
+class _UpdatePositionMSDirFn(torch.autograd.Function):
+    """_UpdatePositionMSFn along the rays `dirs` (no gradient with respect to them)."""
+    @staticmethod
+    def forward(ctx, x, n0, n1, n2, faces, v_faces, dirs, iters, tables):
+        traj = ops.vertex_update_ms_dir_traj(x, [n0, n1, n2], faces, v_faces, dirs, iters)
+        ctx.save_for_backward(traj, n0, n1, n2, faces, v_faces, dirs)
+        ctx.iters, ctx.tables = iters, tables
+        ctx.set_materialize_grads(False)
+        T0, T1 = iters[0], iters[0] + iters[1]
+        return traj[-1].clone(), traj[T0] - traj[0], traj[T1] - traj[T0], traj[-1] - traj[T1]
+
+    @staticmethod
+    def backward(ctx, g_out, g_dx0, g_dx1, g_dx2):
+        traj, n0, n1, n2, faces, v_faces, dirs = ctx.saved_tensors
+        if g_out is None or any(g is not None for g in (g_dx0, g_dx1, g_dx2)):
+            raise NotImplementedError("update_position_MS differentiates its positions, not the stage displacements")
+        g_x, g_n = ops.vertex_update_ms_dir_bwd(traj, [n0, n1, n2], faces, v_faces, dirs, g_out, ctx.iters,
+                                                tables=ctx.tables)
+        return g_x, g_n[0], g_n[1], g_n[2], None, None, None, None, None
+
+
+def _depth_rows(depth_dir, nv, device):
+    """depth_dir ([V,3] or [1,3]; array-like or tensor) as fp32 device rows, one row or one per vertex."""
+    if not isinstance(depth_dir, torch.Tensor):
+        depth_dir = torch.from_numpy(np.ascontiguousarray(np.asarray(depth_dir, dtype=np.float32)))
+    d = depth_dir.to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
+    if d.shape[0] not in (1, nv):
+        raise ValueError("depth_dir has %d rows: one row, or one per vertex (%d)" % (d.shape[0], nv))
+    return d
+
+
+def update_position_MS(x, face_normals_list, faces, v_faces0, coarsening_steps, iter_num_list=[80, 20, 20], tables=None,
+                       depth_dir=None):
     """train.py:1668-1764, same arguments on torch GPU tensors: x [1,V,3], face_normals_list = [n0 [1,N0,3],
     n1 [1,N0/4,3], n2 [1,N0/16,3]], faces int [1,N0,3] (fake nodes = -1 rows), v_faces0 int [1,V,K].  Returns
     (x [1,V,3], [dx of the coarse, the middle and the fine stage, each [V,3]]).  Differentiable with respect to x and
@@ -550,9 +595,25 @@ def update_position_MS(x, face_normals_list, faces, v_faces0, coarsening_steps, 
     forward keeps its trajectory, 12 bytes per vertex and iteration); the values are the same bits either way.
     tables: the mesh's inverse tables (ops.vertex_ms_tables, as device tensors) for the backward; without them every
     backward copies faces and v_faces to the host and rebuilds them there (a host synchronisation per call) - pass them
-    when the same mesh is differentiated repeatedly.  (FacetDenoiser.pointset_step keeps them per bound mesh.)"""
+    when the same mesh is differentiated repeatedly.  (FacetDenoiser.pointset_step keeps them per bound mesh.)
+    depth_dir (build extension; [V,3] or [1,3] viewing rays, utils.view_rays; None: the free update above): every
+    iteration's step is projected onto the vertex' ray (include/fgc.h: fgc_vertex_update_ms_dir), a vertex moves along
+    its ray only; differentiable in the same arguments, not in the rays.  Rows are used as given: longer than 1 can
+    diverge."""
     if coarsening_steps != 2 or len(face_normals_list) != 3:
         raise NotImplementedError("three levels pooled 4:1, as the network has them (settings.py:31-32)")
+    if depth_dir is not None:
+        xr = x.reshape(-1, 3)
+        nv = xr.shape[0]
+        d = _depth_rows(depth_dir, nv, xr.device)
+        ns = [t.reshape(-1, 3) for t in face_normals_list]
+        it = tuple(int(i) for i in iter_num_list)
+        if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in face_normals_list)):
+            out, d0, d1, d2 = _UpdatePositionMSDirFn.apply(xr, *ns, faces.reshape(-1, 3), v_faces0.reshape(nv, -1), d, it,
+                                                           tables)
+            return out.unsqueeze(0), [d0, d1, d2]
+        out, dx = ops.vertex_update_ms_dir(xr, ns, faces.reshape(-1, 3), v_faces0.reshape(nv, -1), d, it)
+        return out.unsqueeze(0), [dx[0], dx[1], dx[2]]
     if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in face_normals_list)):
         nv = x.reshape(-1, 3).shape[0]
         out, d0, d1, d2 = _UpdatePositionMSFn.apply(x.reshape(-1, 3), *[t.reshape(-1, 3) for t in face_normals_list],
@@ -564,13 +625,17 @@ def update_position_MS(x, face_normals_list, faces, v_faces0, coarsening_steps, 
     return out.unsqueeze(0), [dx[0], dx[1], dx[2]]
 
 
-def inferNet(inputMesh, net_or_checkpoint, device="cuda"):
+def inferNet(inputMesh, net_or_checkpoint, device="cuda", depth_dir=None):
     """train.py:147-376: the multi-scale network (three heads), its three normal fields normalised, update_position_MS
     with [80, 20, 20] iterations - on the whole mesh, or patch by patch when addMeshWithVertices cut it (maxSize).
     inputMesh: InferenceMesh filled by addMeshWithVertices; the network must have been built with multi_scale=True.
     Returns the reference's 9-tuple
     (points, points_mid, points_coarse, fine / mid / coarse normals [F,3] in face order, fine / mid / coarse positions
-    [F,3]; as in the reference the three position arrays are the input barycentre channels)."""
+    [F,3]; as in the reference the three position arrays are the input barycentre channels).
+    depth_dir (build extension): [V,3] or [1,3] viewing rays of the WHOLE mesh (utils.view_rays of the raw vertices: the
+    vertices divided by the bounding-box diagonal have the same rays) - the update is the ray-constrained one
+    (update_position_MS(depth_dir=)), every vertex of the three sets lies on its ray; a patch takes its rows through
+    vOldInd_list."""
     if isinstance(net_or_checkpoint, FacetDenoiser):
         net = net_or_checkpoint
     else:
@@ -583,6 +648,9 @@ def inferNet(inputMesh, net_or_checkpoint, device="cuda"):
     dev = net.device
     c = lambda t: t.cpu().numpy()
     n_patches = len(inputMesh.in_list)
+    rays = None
+    if depth_dir is not None:
+        rays = _depth_rows(depth_dir, inputMesh.vNum, dev)
     if n_patches > 1:
         # train.py:255-330: the vertex positions of the patches are averaged over the patches that hold a vertex, the
         # normals of a face are those of the last patch that holds it, and (as in the reference) the three position
@@ -592,6 +660,8 @@ def inferNet(inputMesh, net_or_checkpoint, device="cuda"):
         weights = torch.zeros(vnum, 3, dtype=torch.float32, device=dev)
         normals = [torch.zeros(fnum, 3, dtype=torch.float32, device=dev) for _ in range(3)]
         pos = None
+        if rays is not None:      # (the input positions, patch by patch)
+            x0_all = torch.zeros(vnum, 3, dtype=torch.float32, device=dev)
     for i in range(n_patches):
         x, adjs = inputMesh.in_list[i], inputMesh.adj_list[i]
         net.bind_mesh(x, adjs)
@@ -603,7 +673,13 @@ def inferNet(inputMesh, net_or_checkpoint, device="cuda"):
         xp = torch.as_tensor(inputMesh.v_list[i][0], dtype=torch.float32, device=dev)
         faces = torch.as_tensor(np.asarray(inputMesh.faces_list[i][0]).astype(np.int32), device=dev)
         vf = torch.as_tensor(np.asarray(inputMesh.v_faces_list[i][0]).astype(np.int32), device=dev)
-        pts, dx = ops.vertex_update_ms(xp, [n0, n1, n2], faces, vf, (80, 20, 20))
+        if rays is None:
+            pts, dx = ops.vertex_update_ms(xp, [n0, n1, n2], faces, vf, (80, 20, 20))
+        else:
+            d = rays
+            if len(inputMesh.vOldInd_list[i]) and rays.shape[0] > 1:      # a patch: the rows of its own vertices
+                d = rays[torch.as_tensor(np.asarray(inputMesh.vOldInd_list[i]).astype(np.int64), device=dev)]
+            pts, dx = ops.vertex_update_ms_dir(xp, [n0, n1, n2], faces, vf, d, (80, 20, 20))
         pts_mid = pts - dx[2]                                        # train.py:249-250
         pts_coarse = pts_mid - dx[1]
         perm = torch.as_tensor(np.asarray(inputMesh.permutations[i]).astype(np.int64), device=dev)
@@ -620,13 +696,24 @@ def inferNet(inputMesh, net_or_checkpoint, device="cuda"):
             return c(pts), c(pts_mid), c(pts_coarse), c(fine), c(mid), c(coarse), c(pos), c(pos), c(pos)
         vold = torch.as_tensor(np.asarray(inputMesh.vOldInd_list[i]).astype(np.int64), device=dev)
         fold = torch.as_tensor(np.asarray(inputMesh.fOldInd_list[i]).astype(np.int64), device=dev)
-        for a, p_ in zip(acc, (pts, pts_mid, pts_coarse)):
-            a.index_add_(0, vold, p_)
+        if rays is not None:
+            # along rays the patches are averaged in the ray's own coordinate, s = d . (p - x0) / d . d, and the vertex is
+            # rebuilt from the input position: the mean lies on the ray as every patch's vertex does
+            x0_all[vold] = xp
+            dd = (d * d).sum(1, keepdim=True)
+            for a, p_ in zip(acc, (pts, pts_mid, pts_coarse)):
+                a.index_add_(0, vold, (((p_ - xp) * d).sum(1, keepdim=True) / dd).expand(-1, 3).contiguous())
+        else:
+            for a, p_ in zip(acc, (pts, pts_mid, pts_coarse)):
+                a.index_add_(0, vold, p_)
         weights.index_add_(0, vold, torch.ones_like(pts))
         for nrm, v in zip(normals, (fine, mid, coarse)):
             nrm[fold] = v
         pos = pos_nodes
     w = torch.clamp(weights, min=1.0)
+    if rays is not None:
+        acc = [x0_all + (a / w) * rays for a in acc]
+        w = torch.ones_like(w)
     torch.cuda.synchronize()
     return (c(acc[0] / w), c(acc[1] / w), c(acc[2] / w), c(normals[0]), c(normals[1]), c(normals[2]), c(pos), c(pos),
             c(pos))
@@ -726,6 +813,9 @@ def main(argv=None):
                     "viewing rays of --view-dir / --camera, built from each mesh's clean vertices (depth scans)")
     from .utils import view_options, view_spec
     view_options(ap)
+    ap.add_argument("--ray-update", action="store_true",
+                    help="with --with-vertices --noise-direction ray: the vertex update of every step moves the vertices along "
+                    "the same viewing rays only (what `infer --with-vertices --view-dir / --camera` runs)")
     ap.add_argument("--lf-noise", default=None, metavar="LEVELS[:WIDTH[:BUMPS]]",
                     help="with --synth-noise: low-frequency noise on top - LEVELS = comma-separated RMS displacements in mean "
                     "edge lengths, one or one per --synth-noise level (level k pairs with lf level k); WIDTH = bump width "
@@ -739,6 +829,9 @@ def main(argv=None):
         ap.error("--noise-direction ray needs --synth-noise")
     if args.double_loss and not args.with_vertices:
         ap.error("--double-loss trains on the vertex data: it needs --with-vertices")
+    if args.ray_update and not (view and args.with_vertices):
+        ap.error("--ray-update constrains the multi-scale vertex update to the noise's rays: it needs --with-vertices and "
+                 "--noise-direction ray with --view-dir or --camera")
     if args.num_iterations < 0:
         ap.error("--num-iterations must be >= 0")
     levels = None
@@ -777,6 +870,8 @@ def main(argv=None):
     os.makedirs(args.network_dir, exist_ok=True)
     trainer = (trainDoubleLossNet if args.double_loss else trainAccuracyNet) if args.with_vertices else trainNet
     extra = dict(noise_levels=levels, noise_direction=view or args.noise_direction, **lf_extra) if levels is not None else {}
+    if args.ray_update:
+        extra["ray_update"] = True
     trainer(train_set, args.num_iterations, network_path=args.network_dir, net_name=args.net_name, seed=args.seed,
             capture=args.capture, validSet=valid_set, **extra)
     return trainer.__name__

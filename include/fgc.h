@@ -65,7 +65,11 @@ extern "C" {
  * per-vertex draw of fgc_synth_noise.
  * 115: fgc_guided_normals / fgc_guided_workspace_bytes / fgc_bilateral_filter_guided (guided normal filtering);
  * fgc_bilateral_workspace_bytes grows by one float4 per face, the guided form's third candidate plane (one size for both).
- * 116: fgc_vertex_update_dir (+ _workspace_floats): the vertex update along a per-vertex direction, for depth scans. */
+ * 116: fgc_vertex_update_dir (+ _workspace_floats): the vertex update along a per-vertex direction, for depth scans.
+ * Added under 116, the number unchanged (new entry points only: nothing a 116 binding calls has moved, and a binding that
+ * declares them finds out at load time whether the library has them): fgc_vertex_update_ms_dir / _traj / _bwd
+ * (+ _scratch_floats, _bwd_workspace_floats), the multi-scale vertex update along a per-vertex direction and its adjoint,
+ * depth scans for the vertex networks. */
 #define FGC_ABI_VERSION 116
 
 const char* fgc_last_error(void);
@@ -755,6 +759,49 @@ int fgc_vertex_update_ms_bwd(const float* traj, size_t traj_floats, int32_t nv, 
                              const int32_t* inc_ptr, const int32_t* inc_face, const float* g_out, float* g_x,
                              float* g_n0, float* g_n1, float* g_n2, float* workspace, size_t workspace_floats,
                              void* stream);
+
+/* The multi-scale vertex update along a per-vertex direction (a build extension: the reference constrains the
+ * single-scale update only, update_position_with_depth) - fgc_vertex_update_ms with the step of every iteration
+ * projected onto the direction d_v of its vertex, for the vertices of a depth scan, which may move along their viewing
+ * rays only.  dirs [n_dirs,3] as in fgc_vertex_update_dir: row v when n_dirs == nv, the one row when n_dirs == 1, any
+ * other n_dirs is FGC_EINVAL; d is used as given, nothing is normalised.  With delta_v = (1 / #faces(v)) sum_k n (n . (c -
+ * x_v)) of fgc_vertex_update_ms (same slot handling, same centre launches per iteration), one iteration is
+ *   t_v += delta_v . d_v,      x_v = fma(t_v, d_v, x0_v)   per coordinate, x0 = the INPUT x through all three stages:
+ * in exact arithmetic x' = x + d (d . delta(x)).  t starts at 0 and accumulates across the stages; a vertex stays within
+ * one rounding of its ray whatever the iteration counts.  The gain of a step is |d|^2: rows longer than 1 can diverge
+ * (norms up to 2 reached 1e2 after 80 + 20 + 20 iterations on a 642-vertex sphere); unit rows, or shorter ones, are safe.
+ * x_out [nv,3]; t_out [nv] (may be NULL) the signed step along d; dx_out (may be NULL) [3][nv,3] end minus start of each
+ * stage, as in fgc_vertex_update_ms.  iters = {0,0,0}: x_out = x bit for bit, t_out = 0.  A vertex without faces does
+ * not move.  scratch: at least fgc_vertex_update_ms_dir_scratch_floats(nv, n0) floats; x, x_out, t_out, dx_out and the
+ * scratch are buffers of their own (no two may overlap).  Only enqueues (t is zeroed by an enqueued memset), allocates nothing. */
+size_t fgc_vertex_update_ms_dir_scratch_floats(int32_t nv, int32_t n0);
+int fgc_vertex_update_ms_dir(const float* x, float* x_out, int32_t nv, const int32_t* faces, int32_t n0,
+                             const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
+                             const float* normals2, const int32_t* iters, const float* dirs, int32_t n_dirs, float* t_out,
+                             float* dx_out, float* scratch, size_t scratch_floats, void* stream);
+
+/* Trajectory form of fgc_vertex_update_ms_dir (the same launches, the same arithmetic: slot T is bit-identical to its
+ * x_out): traj [T+1][nv,3], slot 0 = x, slot k + 1 = the positions after iteration k.  scratch: the size above serves (t
+ * and the node centres, nv + 3*(n0 + n0/4 + n0/16) floats, are used).  x, traj, t_out (may be NULL) and the scratch are
+ * buffers of their own. */
+int fgc_vertex_update_ms_dir_traj(const float* x, int32_t nv, const int32_t* faces, int32_t n0, const int32_t* v_faces,
+                                  int32_t k_v, const float* normals0, const float* normals1, const float* normals2,
+                                  const int32_t* iters, const float* dirs, int32_t n_dirs, float* traj, size_t traj_floats,
+                                  float* t_out, float* scratch, size_t scratch_floats, void* stream);
+
+/* Adjoint of fgc_vertex_update_ms_dir on the trajectory fgc_vertex_update_ms_dir_traj wrote: fgc_vertex_update_ms_bwd
+ * (same tables, same outputs, no atomics, the same bits from run to run) with the incoming gradient of every iteration
+ * projected where it enters delta, gp_v = d_v (d_v . g_v):
+ *   dL/dx_v = g_v - sum_k n_j (n_j . a_v) + (barycentre and pooling adjoints of dL/dc),   a_v = gp_v / #faces(v),
+ * and A_j, S_j, dL/dc_j, dL/dn_j of fgc_vertex_update_ms_bwd on that a_v; the identity term keeps the unprojected g_v.
+ * No gradient with respect to dirs.  workspace: at least fgc_vertex_update_ms_dir_bwd_workspace_floats(nv, n0) floats. */
+size_t fgc_vertex_update_ms_dir_bwd_workspace_floats(int32_t nv, int32_t n0);
+int fgc_vertex_update_ms_dir_bwd(const float* traj, size_t traj_floats, int32_t nv, const int32_t* faces, int32_t n0,
+                                 const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
+                                 const float* normals2, const int32_t* iters, const float* dirs, int32_t n_dirs,
+                                 const int32_t* slot_ptr, const int32_t* slot_vert, const int32_t* inc_ptr,
+                                 const int32_t* inc_face, const float* g_out, float* g_x, float* g_n0, float* g_n1,
+                                 float* g_n2, float* workspace, size_t workspace_floats, void* stream);
 
 /* Point-set loss fullLoss (train.py:1373-1424) and its gradient.  p0 [np0,3] refined vertices, p1 [np1,3] ground-truth
  * vertices, i0 [ns0] rows of p0 and i1 [ns1] rows of p1 (repeats allowed):
