@@ -279,6 +279,9 @@ _SIGS = {
     "fgc_synth_lf_scratch_floats": (C.c_size_t, [C.c_int32, C.c_int32]),
     "fgc_synth_noise_lf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgc_ray_cast_workspace_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "fgc_ray_cast": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                               C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "fgc_philox_words": (C.c_int, [C.c_uint32, C.c_int32, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "fgc_face_features_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                          C.c_void_p, C.c_size_t, C.c_void_p]),

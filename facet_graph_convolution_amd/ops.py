@@ -416,6 +416,32 @@ def vertex_update_dir(x, normals, e_map, v_e_map, dirs, iters, lmbd=1.0 / 18, re
     return (out, t) if return_t else out
 
 
+def ray_cast(verts, faces, origins, dirs, t_min=0.0, want_bary=False):
+    """First hit of every ray against a triangle list (include/fgc.h: fgc_ray_cast; a build extension) on GPU tensors:
+    verts [V,3] fp32, faces int32 [F,3] (a row with an id outside [0, V) is skipped), origins [1,3] (a camera) or [Q,3],
+    dirs [Q,3] used as given, never normalised: t is in units of |d|.  Returns (t [Q] fp32, face [Q] int32) - a miss is
+    (+inf, -1) - and with want_bary also bary [Q,2] = (u, v) of the hit, the point being (1 - u - v) a + u b + v c."""
+    _req_cuda(verts, faces, origins, dirs)
+    verts, origins, dirs = _f32c(verts.reshape(-1, 3)), _f32c(origins.reshape(-1, 3)), _f32c(dirs.reshape(-1, 3))
+    faces = faces.to(torch.int32).reshape(-1, 3).contiguous()
+    nv, nf, nq = verts.shape[0], faces.shape[0], dirs.shape[0]
+    if origins.shape[0] not in (1, nq):
+        raise ValueError("origins has %d rows: one row, or one per ray (%d)" % (origins.shape[0], nq))
+    if not (np.isfinite(t_min) and t_min >= 0):
+        raise ValueError("t_min must be finite and >= 0 (got %r)" % (t_min,))
+    L = _lib.lib()
+    nbytes = L.fgc_ray_cast_workspace_bytes(nf, nq)
+    if nbytes == 0 or nv == 0:
+        raise ValueError("ray_cast needs at least one vertex, one face and one ray (got %d, %d, %d)" % (nv, nf, nq))
+    t = torch.empty(nq, dtype=torch.float32, device=verts.device)
+    face = torch.empty(nq, dtype=torch.int32, device=verts.device)
+    bary = torch.empty(nq, 2, dtype=torch.float32, device=verts.device) if want_bary else None
+    ws = _workspace(nbytes, verts.device, "ray_cast")
+    check(L.fgc_ray_cast(ptr(verts), nv, ptr(faces), nf, ptr(origins), origins.shape[0], ptr(dirs), nq, float(t_min), ptr(t),
+                         ptr(face), ptr(bary), ptr(ws), ws.numel(), stream_ptr()), "fgc_ray_cast")
+    return (t, face, bary) if want_bary else (t, face)
+
+
 def pool4_avg_iz(x):
     """custom_binary_tree_pooling(x, steps=2, 'avg_ignore_zeros') (model.py:792-814) on [n, c] rows."""
     _req_cuda(x)

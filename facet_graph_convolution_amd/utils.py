@@ -391,14 +391,168 @@ def direction_key(direction):
     return ("rays", hashlib.sha1(d.tobytes()).hexdigest())
 
 
-def write_mesh(vl, fl, strFileName):
+# ---------------------------------------------------------------------------------------------------
+# virtual depth scans (build extension; README "Depth scans"): what one sensor sees of a clean mesh.  The ray casting is
+# ops.ray_cast (include/fgc.h: fgc_ray_cast); everything around it is host code, numpy in and out.
+# ---------------------------------------------------------------------------------------------------
+def _ray_cast_host(V, faces, origins, dirs, t_min=0.0):
+    """ops.ray_cast on host arrays: (t float32 [Q], face int32 [Q])."""
+    import torch
+    from . import ops
+    dev = torch.device("cuda", torch.cuda.current_device())
+    put = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
+    t, face = ops.ray_cast(put(V, np.float32), put(np.asarray(faces).astype(np.int64), np.int32), put(origins, np.float32),
+                           put(dirs, np.float32), t_min)
+    return t.cpu().numpy(), face.cpu().numpy()
+
+
+def _bbox_diagonal(V):
+    V = np.asarray(V, dtype=np.float64).reshape(-1, 3)
+    return float(np.linalg.norm(V.max(0) - V.min(0)))
+
+
+def visible_vertices(V, faces, camera=None, view_dir=None, eps=1e-3):
+    """Which vertices of a mesh one sensor sees: bool [V].  Exactly one of camera (a point, perspective) and view_dir (one
+    direction for every vertex, orthographic), checked as view_rays checks them.  One ray per vertex, built so that the
+    vertex itself sits at t = 1: from the camera, origin = camera and d = v - camera (unnormalised); along a direction,
+    origin = v - L dhat and d = L dhat with L twice the bounding-box diagonal, so that every origin lies outside the mesh.
+    A vertex is visible iff the first hit of its ray (ops.ray_cast over ALL faces, its own included - they are hit at t
+    close to 1) has t >= 1 - eps; a ray that hits nothing counts as visible.  Rays x faces pairs, no spatial culling."""
+    view_rays(V, camera=camera, view_dir=view_dir)          # (the checks: exactly one view, finite, no vertex at the camera)
+    if not (np.isfinite(eps) and 0 <= eps < 1):
+        raise ValueError("eps must lie in [0, 1) (got %r)" % (eps,))
+    V64 = np.asarray(V, dtype=np.float64).reshape(-1, 3)
+    if camera is not None:
+        c = np.asarray(camera, dtype=np.float64).reshape(1, 3)
+        origins, dirs = c, V64 - c
+    else:
+        d = np.asarray(view_dir, dtype=np.float64).reshape(1, 3)
+        step = d / np.linalg.norm(d) * (2.0 * _bbox_diagonal(V64))
+        origins, dirs = V64 - step, np.broadcast_to(step, V64.shape)
+    t, _ = _ray_cast_host(V64, faces, origins, dirs)
+    return t >= np.float32(1.0 - eps)
+
+
+def scan_cut(V, faces, camera=None, view_dir=None, eps=1e-3, max_angle=80.0):
+    """The part of a mesh one sensor sees, as an open mesh: (V_cut float32 [v,3], faces_cut int32 [f,3], vertex_ids int64
+    [v]).  A face stays iff its three vertices are visible (visible_vertices) and it is turned towards the sensor by less
+    than max_angle degrees: -n . r >= cos(max_angle), n the unit face normal and r the unit ray to the face centre (from
+    the camera, or view_dir), both in float64 on the host.  The vertices are those of the kept faces in their old order,
+    vertex_ids maps them to the old ones; the faces keep their order and are re-indexed.  Nothing left: ValueError.
+    max_angle = 80 is this build's choice (a sensor returns little from a surface it grazes); nobody has tuned it."""
+    if not (np.isfinite(max_angle) and 0 < max_angle <= 180):
+        raise ValueError("max_angle must lie in (0, 180] degrees (got %r)" % (max_angle,))
+    vis = visible_vertices(V, faces, camera=camera, view_dir=view_dir, eps=eps)
+    V = np.asarray(V)
+    F = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    T = V.astype(np.float64).reshape(-1, 3)[F]
+    n = np.cross(T[:, 1] - T[:, 0], T[:, 2] - T[:, 0])
+    nn = np.sqrt((n * n).sum(1, keepdims=True))
+    n = np.where(nn > 0, n / np.where(nn > 0, nn, 1.0), 0.0)
+    if camera is not None:
+        r = T.mean(1) - np.asarray(camera, dtype=np.float64).reshape(1, 3)
+        r = r / np.sqrt((r * r).sum(1, keepdims=True))
+    else:
+        r = np.asarray(view_dir, dtype=np.float64).reshape(1, 3)
+        r = r / np.linalg.norm(r)
+    keep = vis[F].all(1) & (-(n * r).sum(1) >= math.cos(math.radians(max_angle)))
+    if not keep.any():
+        raise ValueError("scan_cut: the view sees no face of the mesh")
+    Fk = F[keep]
+    ids = np.unique(Fk)
+    new = np.full(V.reshape(-1, 3).shape[0], -1, dtype=np.int64)
+    new[ids] = np.arange(ids.size)
+    return np.ascontiguousarray(V.reshape(-1, 3)[ids], dtype=np.float32), new[Fk].astype(np.int32), ids
+
+
+def pixel_rays(camera, look_at, size, fov=40.0, up=(0, 0, 1)):
+    """Unit pixel-centre rays of a pinhole camera, float32 [H,W,3] (built in float64, rounded once).  The camera sits at
+    `camera` and looks at `look_at`; fov is the HORIZONTAL field of view in degrees, size = (W, H), square pixels; row 0 is
+    the top of the image, column 0 its left.  up falls back to (0, 1, 0) when the view is within |f . up| > 0.99 of it."""
+    W, H = (int(s) for s in size)
+    if W < 1 or H < 1:
+        raise ValueError("size = (W, H), both >= 1 (got %r)" % (size,))
+    if not (np.isfinite(fov) and 0 < fov < 180):
+        raise ValueError("fov must lie in (0, 180) degrees (got %r)" % (fov,))
+    c = np.asarray(camera, dtype=np.float64).reshape(-1)
+    f = np.asarray(look_at, dtype=np.float64).reshape(-1) - c
+    if c.shape != (3,) or f.shape != (3,) or not np.isfinite(c).all() or not np.isfinite(f).all() or not np.linalg.norm(f) > 0:
+        raise ValueError("camera and look_at must be two different finite points")
+    f = f / np.linalg.norm(f)
+    u = np.asarray(up, dtype=np.float64).reshape(-1)
+    if u.shape != (3,) or not np.isfinite(u).all() or not np.linalg.norm(u) > 0:
+        raise ValueError("up must be three finite numbers, not all zero (got %r)" % (up,))
+    u = u / np.linalg.norm(u)
+    if abs(f @ u) > 0.99:
+        u = np.array([0.0, 1.0, 0.0])
+    right = np.cross(f, u)
+    right = right / np.linalg.norm(right)
+    top = np.cross(right, f)
+    half = math.tan(math.radians(fov) / 2.0)
+    x = (2.0 * (np.arange(W) + 0.5) / W - 1.0) * half
+    y = (1.0 - 2.0 * (np.arange(H) + 0.5) / H) * half * H / W
+    r = f[None, None] + x[None, :, None] * right[None, None] + y[:, None, None] * top[None, None]
+    return (r / np.sqrt((r * r).sum(-1, keepdims=True))).astype(np.float32)
+
+
+def depth_image(V, faces, camera, size=(640, 480), fov=40.0, look_at=None, up=(0, 0, 1)):
+    """A depth image of a mesh: (depth float32 [H,W], face int32 [H,W], rays float32 [H,W,3]).  A pinhole at `camera`
+    looking at look_at (default: the centre of the bounding box), the rays of pixel_rays; depth is the distance t along the
+    unit ray to the first hit (ops.ray_cast), +inf for background, face the triangle hit or -1.  fov = 40 degrees is this
+    build's choice; nobody has tuned it.  W x H x faces pairs, no spatial culling."""
+    V64 = np.asarray(V, dtype=np.float64).reshape(-1, 3)
+    if look_at is None:
+        look_at = 0.5 * (V64.min(0) + V64.max(0))
+    rays = pixel_rays(camera, look_at, size, fov, up)
+    H, W = rays.shape[:2]
+    t, face = _ray_cast_host(V64, faces, np.asarray(camera, dtype=np.float64).reshape(1, 3), rays.reshape(-1, 3))
+    return t.reshape(H, W), face.reshape(H, W), rays
+
+
+def range_mesh(depth, rays, camera, jump=0.05, return_pixels=False):
+    """The mesh a sensor driver would make of a depth image: (V float32 [v,3], faces int32 [f,3]).  One vertex
+    camera + t r per pixel (float64, rounded once); every 2 x 2 block of pixels p[row][col] gives the two triangles
+    (p00, p10, p01) and (p10, p11, p01), p10 the pixel below p00 and p01 the one to its right, which are oriented towards
+    the camera; a block is kept only if its four depths are finite and max - min <= jump x min (a larger step is a
+    silhouette, not a surface).  Pixels no triangle uses are dropped; the vertices are in row-major order.
+    utils.view_rays(V, camera=camera) then gives the pixel rays back to one rounding.  Nothing left: ValueError.
+    return_pixels: also the flat pixel index row * W + col of every vertex, int64 [v].
+    jump = 0.05 is this build's choice; nobody has tuned it."""
+    depth = np.asarray(depth, dtype=np.float64)
+    rays = np.asarray(rays, dtype=np.float64)
+    if depth.ndim != 2 or rays.shape != depth.shape + (3,):
+        raise ValueError("depth [H,W] and rays [H,W,3] (got %r and %r)" % (depth.shape, rays.shape))
+    if not (np.isfinite(jump) and jump >= 0):
+        raise ValueError("jump must be finite and >= 0 (got %r)" % (jump,))
+    H, W = depth.shape
+    c = np.asarray(camera, dtype=np.float64).reshape(1, 1, 3)
+    d = np.stack([depth[:-1, :-1], depth[1:, :-1], depth[:-1, 1:], depth[1:, 1:]])          # p00, p10, p01, p11
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(d).all(0) & (d.max(0) - d.min(0) <= jump * d.min(0))
+    idx = np.arange(H * W).reshape(H, W)
+    p00, p10, p01, p11 = idx[:-1, :-1][ok], idx[1:, :-1][ok], idx[:-1, 1:][ok], idx[1:, 1:][ok]
+    faces = np.stack([np.stack([p00, p10, p01], 1), np.stack([p10, p11, p01], 1)], 1).reshape(-1, 3)
+    if faces.shape[0] == 0:
+        raise ValueError("range_mesh: no 2 x 2 block of the image holds a surface")
+    ids = np.unique(faces)
+    new = np.full(H * W, -1, dtype=np.int64)
+    new[ids] = np.arange(ids.size)
+    t = depth.reshape(-1)[ids]
+    P = c.reshape(1, 3) + t[:, None] * rays.reshape(-1, 3)[ids]
+    out = (P.astype(np.float32), new[faces].astype(np.int32))
+    return out + (ids,) if return_pixels else out
+
+
+def write_mesh(vl, fl, strFileName, fmt="%.6f"):
     """utils.py:659-697: 'v x y z' (6 decimals, extra per-vertex columns such as colours written as they are), then
-    'f a b c' one-indexed; a face (0,0,..) ends the list and a face (-1,-1,..) is skipped, as in the reference."""
+    'f a b c' one-indexed; a face (0,0,..) ends the list and a face (-1,-1,..) is skipped, as in the reference.
+    fmt (build extension): the format of a coordinate; "%.9g" keeps every float32 bit (the scan tool: a range mesh's
+    vertices lie on their pixel rays to one rounding, which six decimals would undo)."""
     vl = np.asarray(vl)
     fl = np.asarray(fl).astype(np.int64) + 1
     with open(strFileName, "w") as fh:
         for row in vl:
-            fh.write("v " + " ".join("%.6f" % x for x in row) + " \n")
+            fh.write("v " + " ".join(fmt % x for x in row) + " \n")
         for row in fl:
             if row[0] == 1 and row[1] == 1:
                 break

@@ -69,7 +69,8 @@ extern "C" {
  * Added under 116, the number unchanged (new entry points only: nothing a 116 binding calls has moved, and a binding that
  * declares them finds out at load time whether the library has them): fgc_vertex_update_ms_dir / _traj / _bwd
  * (+ _scratch_floats, _bwd_workspace_floats), the multi-scale vertex update along a per-vertex direction and its adjoint,
- * depth scans for the vertex networks. */
+ * depth scans for the vertex networks; fgc_ray_cast (+ _workspace_bytes), rays against a triangle list: virtual depth
+ * scans of a clean mesh. */
 #define FGC_ABI_VERSION 116
 
 const char* fgc_last_error(void);
@@ -1010,6 +1011,43 @@ int fgc_synth_noise_lf(const float* v, const float* vnormals, const float* white
 int fgc_point_sets_prepare(const float* v, int32_t nv, const float* gt, int32_t ngt, const float* gt_box, const float* R,
                            int32_t have_bbox, float* v_out, float* gt_out, float* scratch, size_t scratch_floats,
                            void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Ray casting: virtual depth scans (BUILD EXTENSION - the reference has no such primitive; its scans are downloads)
+ * ---------------------------------------------------------------------------------- */
+
+/* For every ray q in [0, nq) the first triangle of a list that it meets, brute force over rays x triangles (no spatial
+ * culling: the cost grows with nq x nf).  Made for preparation time - which vertices a camera sees (utils.visible_vertices),
+ * a depth image (utils.depth_image) - not for a training step.
+ *   Ray q: o_q + t d_q.  o_q = row q of origins [n_origins,3], the one row when n_origins == 1 (a camera); d_q = row q of
+ *     dirs [nq,3], used as given and never normalised: t is in units of |d_q|.
+ *   Triangle f = (a, b, c) = faces[f] on verts [nv,3] takes part only if all three ids lie in [0, nv); other rows are
+ *     skipped and never dereferenced.
+ *   Intersection (Moeller-Trumbore, two-sided), with x . y = fma(x_z, y_z, fma(x_y, y_y, x_x y_x)) and
+ *     (x x y)_i = fma(x_j, y_k, -(x_k y_j)) for (i, j, k) a cyclic shift of (x, y, z):
+ *       e1 = b - a, e2 = c - a, p = d x e2, det = e1 . p            (det == 0: the triangle is skipped)
+ *       s = o - a, u = (s . p) / det, qv = s x e1, v = (d . qv) / det, t = (e2 . qv) / det
+ *     a hit iff u >= 0, v >= 0, u + v <= 1, t > t_min and t is finite.  fp32 throughout, IEEE divisions, no contraction:
+ *     every fused operation is one of the fma above.  (det == 0 makes t an infinity or a NaN, which is no hit.)
+ *   Result: the smallest t over the hits, among equal t the smallest face index; t_out [nq], face_out [nq], bary_out [nq,2]
+ *     = (u, v) of the winner (may be NULL).  A miss: t_out = +inf, face_out = -1, bary_out = (0, 0).
+ * The minimum over (t, face) is exact - each workgroup's result goes into a 64-bit integer atomic min on
+ *   (float bits of t) << 32 | face, and t > t_min >= 0 orders like its bits - so the result does not depend on how the launch
+ *   splits rays and triangles, and is the same bits eager or replayed from a hipGraph.  No floating-point atomics.
+ * A call with n_origins == 1 gives the bits of the same call with that row repeated nq times (the same kernel).
+ * workspace (device, 16-byte aligned) >= fgc_ray_cast_workspace_bytes(nf, nq) (0 for arguments out of range): one record of
+ *   three float4 per triangle, (a, 0), (e1, 0), (e2, 0), nf rounded up to a multiple of 4 (an invalid row and the padding
+ *   are zero records: det = 0), then one 64-bit key per ray.
+ * Three launches, enqueue-only, nothing allocated: the records (and the keys' initial value), rays x triangles (64 rays per
+ *   workgroup, the records wave-uniform through scalar loads, the triangle list split over blockIdx.y when the rays alone
+ *   do not fill the device), keys -> outputs.  A NULL among verts, faces, origins, dirs, t_out, face_out, workspace;
+ *   nv, nf or nq <= 0; nf > FGC_RAY_CAST_MAX_FACES; n_origins neither 1 nor nq; t_min negative, infinite or a NaN; a
+ *   workspace that is misaligned or too small: FGC_EINVAL, nothing launched. */
+#define FGC_RAY_CAST_MAX_FACES (1 << 30)
+size_t fgc_ray_cast_workspace_bytes(int32_t nf, int32_t nq);
+int fgc_ray_cast(const float* verts, int32_t nv, const int32_t* faces, int32_t nf, const float* origins, int32_t n_origins,
+                 const float* dirs, int32_t nq, float t_min, float* t_out, int32_t* face_out, float* bary_out,
+                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Checkpoint files (CPU; HOST pointers)
