@@ -16,7 +16,7 @@
 //   rc_finish_kernel  one thread per ray: key -> t_out, face_out, and (u, v) of the winner evaluated again by the same
 //                     function on the same record (the same bits the cast kernel compared).
 //
-// Per pair (rc_uvt below): p = d x e2 (3 v_mul + 3 v_fma), det (v_mul + 2 v_fma), s = o - a (3 v_sub), s . p (v_mul + 2
+// Per pair (rc_uvt, fgc_raycast.h): p = d x e2 (3 v_mul + 3 v_fma), det (v_mul + 2 v_fma), s = o - a (3 v_sub), s . p (v_mul + 2
 // v_fma), u = (s . p) / det (the IEEE division: 11 instructions, one of them v_rcp_f32), the test of u (two v_cmp and a
 // v_mov): 29 vector instructions in the gfx950 ISA.  A hit needs 0 <= u <= 1 (u + v <= 1 with v >= 0 implies it in rounded
 // arithmetic too: rounding is monotonic), so everything else - qv = s x e1, v, t, two more divisions, 39 more instructions -
@@ -27,7 +27,7 @@
 //
 // Contraction is off, every FMA is written out.  Device data is never trusted for addressing: vertex ids are checked
 // before a load, the face of a key before the record is read.
-#include "fgc_common.h"
+#include "fgc_raycast.h"
 
 #pragma clang fp contract(off)
 
@@ -36,7 +36,6 @@ namespace fgc {
 constexpr int RC_THREADS = 256;
 constexpr int RC_WAVES = RC_THREADS / 64;
 constexpr int RC_Q = 64;               // rays per workgroup: one per lane, the same in every wave
-constexpr int RC_CHUNK = 4;            // records per scalar-load chunk: 48 dwords of SGPRs
 constexpr int RC_TARGET_WGS = 2048;    // workgroups that fill the device: 256 CUs x 8 of 256 threads
 constexpr int RC_MIN_SLAB = 1024;      // records a slab has at least (a slab costs one atomic per ray)
 constexpr unsigned long long RC_MISS = 0x7F800000FFFFFFFFull;      // (+inf, face -1)
@@ -80,28 +79,6 @@ __global__ __launch_bounds__(256) void rc_gather_kernel(const float* __restrict_
     rec[3 * (size_t)j] = r0;
     rec[3 * (size_t)j + 1] = r1;
     rec[3 * (size_t)j + 2] = r2;
-}
-
-// a . b = fma(a_z, b_z, fma(a_y, b_y, a_x b_x))
-__device__ __forceinline__ float rc_dot(float ax, float ay, float az, float bx, float by, float bz) {
-    return __builtin_fmaf(az, bz, __builtin_fmaf(ay, by, ax * bx));
-}
-// one component of a x b: fma(a1, b2, -(a2 b1))
-__device__ __forceinline__ float rc_det2(float a1, float b2, float a2, float b1) { return __builtin_fmaf(a1, b2, -(a2 * b1)); }
-
-// Moeller-Trumbore as include/fgc.h spells it.  Returns whether (u, v, t) is a hit of a ray with t > t_min; u, v, t are
-// written only as far as they were needed (all three when the result is true).
-__device__ __forceinline__ bool rc_uvt(const float (&o)[3], const float (&d)[3], f32x4 a, f32x4 e1, f32x4 e2, float t_min,
-                                       float& u, float& v, float& t) {
-    const float px = rc_det2(d[1], e2.z, d[2], e2.y), py = rc_det2(d[2], e2.x, d[0], e2.z), pz = rc_det2(d[0], e2.y, d[1], e2.x);
-    const float det = rc_dot(e1.x, e1.y, e1.z, px, py, pz);
-    const float sx = o[0] - a.x, sy = o[1] - a.y, sz = o[2] - a.z;
-    u = rc_dot(sx, sy, sz, px, py, pz) / det;
-    if (!(u >= 0.f && u <= 1.f)) return false;      // (det == 0: u is an infinity or a NaN)
-    const float qx = rc_det2(sy, e1.z, sz, e1.y), qy = rc_det2(sz, e1.x, sx, e1.z), qz = rc_det2(sx, e1.y, sy, e1.x);
-    v = rc_dot(d[0], d[1], d[2], qx, qy, qz) / det;
-    t = rc_dot(e2.x, e2.y, e2.z, qx, qy, qz) / det;
-    return v >= 0.f && u + v <= 1.f && t > t_min && t < __builtin_inff();
 }
 
 // grid (ceil(nq / 64), slabs)

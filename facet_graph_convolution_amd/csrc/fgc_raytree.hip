@@ -1,0 +1,334 @@
+// Ray casting through a bounding-box tree (build extension; include/fgc.h: fgc_ray_tree_build, fgc_ray_cast_tree): the first
+// triangle every ray meets, as fgc_ray_cast finds it, at a cost that does not grow with rays x faces.  The per-pair
+// arithmetic is rc_uvt of fgc_raycast.h, the function the brute-force kernel runs: what the tree finds is bit for bit what the
+// full search finds, as long as the boxes do not cull the winner (DESIGN.md 8e.1 has the argument).
+//
+// The tree is implicit: a caller-given order of the triangles, cut into chunks of RC_CHUNK records (the leaves), and above
+// them levels of fan-out 8.  Nothing in the buffer is a pointer or an index that addresses memory:
+//   records   nrec x 3 float4, record j = (a, 0), (e1, 0), (e2, 0) of face order[j] (what rc_gather_kernel makes of it)
+//   face_of   nrec x int32, order[j] (-1 behind nf)
+//   nodes     node (L, k), L = 1 .. depth, k < n[L]: the boxes of its 8 children, 8 x (lo.xyz, hi.xyz) = 48 dwords, three
+//             16-dword scalar loads like a chunk of records.  The children of (1, k) are the leaves 8k .. 8k + 7, those of
+//             (L, k) the nodes (L - 1, 8k .. 8k + 7); a missing child is the empty box (+inf, -inf).  n[0] = leaves,
+//             n[L] = ceil(n[L - 1] / 8), depth = the first L with n[L] = 1; level L starts at node noff[L].
+//
+// rt_leaf_kernel   one thread per leaf box (padding included): its four records, their face ids, and the exact min / max over
+//                  the ORIGINAL vertices of its valid, finite faces.
+// rt_level_kernel  one launch per level above, one thread per box: the union of its 8 children (min / max: exact).
+// rt_cast_kernel   one wave of 64 rays per workgroup, one ray per lane.  The walk is the wave's: a stack of (node, ballot of
+//                  the lanes that met it) in the wave's LDS row, popped into SGPRs, so node boxes and records come through
+//                  scalar loads and no memory access diverges.  A lane takes part in a node only if ITS ray met that node and
+//                  every node above it, tests a leaf's records only if its ray meets the leaf's box within [t_min, best_t]
+//                  at that moment, and keeps the smallest (t, face_of) in full key order.  Children go in index order, so
+//                  the leaves a lane tests, and in which order, are what its own ray would visit walking alone: the result
+//                  of a ray does not depend on its neighbours, the launch or the order of the rays.
+// No loop ends on device data: the walk pops at most `nodes` times (a host-side count; each node is pushed at most once),
+// the stack holds at most 7 entries per level + 1, and every popped id is bounded before it addresses anything.
+#include "fgc_raycast.h"
+
+#pragma clang fp contract(off)
+
+namespace fgc {
+
+constexpr int RT_FAN = 8;                            // children per node
+constexpr int RT_MAX_LEVELS = 10;                    // node levels of 2^30 faces
+constexpr int RT_STACK = 7 * RT_MAX_LEVELS + 1;
+constexpr int RT_NODE_F4 = RT_FAN * 6 / 4;           // a node as float4: 12
+constexpr float RT_SLACK = 0x1p-21f;                 // 4 units in the last place, relative
+constexpr float RT_TINY = 0x1p-125f;                 // ... and absolute, for a product that underflowed
+
+struct RtShape {
+    int depth, nleaf;
+    int n[RT_MAX_LEVELS + 1];                // boxes of level L (n[0] = nleaf)
+    unsigned noff[RT_MAX_LEVELS + 1];        // first node of level L (L >= 1) in the node array
+};
+
+struct RtLayout {
+    RtShape s;
+    int nrec;
+    unsigned nodes;
+    size_t face_of, boxes, total;            // byte offsets
+};
+
+static RtLayout rt_layout(int nf) {
+    RtLayout l = {};
+    l.nrec = cdiv(nf, RC_CHUNK) * RC_CHUNK;
+    l.s.nleaf = l.s.n[0] = l.nrec / RC_CHUNK;
+    int L = 0;
+    unsigned off = 0;
+    do {
+        ++L;
+        l.s.n[L] = cdiv(l.s.n[L - 1], RT_FAN);
+        l.s.noff[L] = off;
+        off += (unsigned)l.s.n[L];
+    } while (l.s.n[L] > 1);
+    l.s.depth = L;
+    l.nodes = off;
+    l.face_of = (size_t)l.nrec * 3 * sizeof(f32x4);
+    l.boxes = l.face_of + (size_t)l.nrec * sizeof(int);          // (nrec is a multiple of 4: 16-byte aligned)
+    l.total = l.boxes + (size_t)l.nodes * RT_NODE_F4 * sizeof(f32x4);
+    return l;
+}
+
+__device__ __forceinline__ bool rt_finite3(const float* p) {
+    return fabsf(p[0]) < __builtin_inff() && fabsf(p[1]) < __builtin_inff() && fabsf(p[2]) < __builtin_inff();
+}
+
+// one thread per box of level 0, padding included (nbox = 8 n[1])
+__global__ __launch_bounds__(256) void rt_leaf_kernel(const float* __restrict__ verts, int nv, const int* __restrict__ faces,
+                                                      int nf, const int* __restrict__ order, int nleaf, int nbox,
+                                                      f32x4* __restrict__ rec, int* __restrict__ face_of,
+                                                      float* __restrict__ box) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nbox) return;
+    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    if (i < nleaf) {
+#pragma unroll
+        for (int k = 0; k < RC_CHUNK; ++k) {
+            const int j = RC_CHUNK * i + k;
+            const int f = j < nf ? order[j] : -1;
+            f32x4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = r0, r2 = r0;
+            if ((unsigned)f < (unsigned)nf) {
+                const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
+                if ((unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv) {
+                    const float* pa = verts + 3 * (size_t)a;
+                    const float* pb = verts + 3 * (size_t)b;
+                    const float* pc = verts + 3 * (size_t)c;
+                    r0 = f32x4{pa[0], pa[1], pa[2], 0.f};
+                    r1 = f32x4{pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2], 0.f};
+                    r2 = f32x4{pc[0] - pa[0], pc[1] - pa[1], pc[2] - pa[2], 0.f};
+                    if (rt_finite3(pa) && rt_finite3(pb) && rt_finite3(pc)) {
+#pragma unroll
+                        for (int x = 0; x < 3; ++x) {
+                            lo[x] = fminf(lo[x], fminf(pa[x], fminf(pb[x], pc[x])));
+                            hi[x] = fmaxf(hi[x], fmaxf(pa[x], fmaxf(pb[x], pc[x])));
+                        }
+                    }
+                }
+            }
+            rec[3 * (size_t)j] = r0;
+            rec[3 * (size_t)j + 1] = r1;
+            rec[3 * (size_t)j + 2] = r2;
+            face_of[j] = f;
+        }
+    }
+    float* b = box + 6 * (size_t)i;
+    b[0] = lo[0], b[1] = lo[1], b[2] = lo[2], b[3] = hi[0], b[4] = hi[1], b[5] = hi[2];
+}
+
+// one thread per box of a level above the leaves, padding included: the union of children 8i .. 8i + 7 (all stored: the
+// level below is padded to whole nodes)
+__global__ __launch_bounds__(256) void rt_level_kernel(const float* __restrict__ child, int n, int nbox, float* __restrict__ box) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nbox) return;
+    float lo[3] = {__builtin_inff(), __builtin_inff(), __builtin_inff()};
+    float hi[3] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
+    if (i < n) {
+        const float* c = child + 6 * (size_t)RT_FAN * i;
+#pragma unroll
+        for (int k = 0; k < RT_FAN; ++k)
+#pragma unroll
+            for (int x = 0; x < 3; ++x) lo[x] = fminf(lo[x], c[6 * k + x]), hi[x] = fmaxf(hi[x], c[6 * k + 3 + x]);
+    }
+    float* b = box + 6 * (size_t)i;
+    b[0] = lo[0], b[1] = lo[1], b[2] = lo[2], b[3] = hi[0], b[4] = hi[1], b[5] = hi[2];
+}
+
+// The slab test (include/fgc.h has the argument).  Per axis t1 = (lo - o) inv, t2 = (hi - o) inv, inv = 1 / d in IEEE; the
+// nearer of the two is chosen by the sign of inv, never by comparing them, so a NaN (0 x inf: the ray lies in that plane)
+// stays on its own side and fmaxf / fminf, which return the operand that is no NaN, drop it: that plane does not constrain.
+// Returns the widened near end of the interval if [near', far'] is not empty and reaches t_min, a NaN otherwise; the lane
+// meets the box iff that value <= best_t (false for a NaN).
+__device__ __forceinline__ float rt_entry(const float (&o)[3], const float (&inv)[3], const bool (&neg)[3], const float* lo,
+                                          const float* hi, float t_min) {
+    float tn[3], tf[3];
+#pragma unroll
+    for (int x = 0; x < 3; ++x) {
+        const float t1 = (lo[x] - o[x]) * inv[x], t2 = (hi[x] - o[x]) * inv[x];
+        tn[x] = neg[x] ? t2 : t1;
+        tf[x] = neg[x] ? t1 : t2;
+    }
+    const float near = fmaxf(fmaxf(tn[0], tn[1]), tn[2]);
+    const float far = fminf(fminf(tf[0], tf[1]), tf[2]);
+    const float nw = near - __builtin_fmaf(fabsf(near), RT_SLACK, RT_TINY);
+    const float fw = far + __builtin_fmaf(fabsf(far), RT_SLACK, RT_TINY);
+    return (nw <= fw && fw >= t_min) ? nw : __builtin_nanf("");
+}
+
+// grid ceil(nq / 64), 64 threads: one wave.  COUNT: the probe-only build (-DFGC_RT_COUNT) also writes, per ray, the pairs
+// its lane tested and the boxes it tested.
+template <bool COUNT>
+__global__ __launch_bounds__(64) void rt_cast_kernel(const f32x4* __restrict__ rec, const int* __restrict__ face_of,
+                                                     const f32x4* __restrict__ boxes, const RtShape S, unsigned nodes,
+                                                     const float* __restrict__ origins, int n_origins,
+                                                     const float* __restrict__ dirs, int nq, float t_min,
+                                                     float* __restrict__ t_out, int* __restrict__ face_out,
+                                                     float* __restrict__ bary_out, unsigned* __restrict__ count_out) {
+    __shared__ unsigned st_id[RT_STACK];                    // (L << 28) | k
+    __shared__ unsigned long long st_mask[RT_STACK];        // the lanes whose ray met that node
+    __shared__ float ent[RT_FAN][64];                       // a leaf node's entry values, one row per child
+    const int lane = threadIdx.x;
+    const int q = blockIdx.x * 64 + lane;
+    const bool live = q < nq;
+    float o[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
+    if (live) {
+        const size_t oo = n_origins == 1 ? 0 : 3 * (size_t)q;
+        o[0] = origins[oo], o[1] = origins[oo + 1], o[2] = origins[oo + 2];
+        d[0] = dirs[3 * (size_t)q], d[1] = dirs[3 * (size_t)q + 1], d[2] = dirs[3 * (size_t)q + 2];
+    }
+    const float inv[3] = {1.f / d[0], 1.f / d[1], 1.f / d[2]};
+    const bool neg[3] = {inv[0] < 0.f, inv[1] < 0.f, inv[2] < 0.f};
+    float best_t = __builtin_inff(), best_u = 0.f, best_v = 0.f;
+    int best_f = -1;
+    unsigned n_pairs = 0, n_boxes = 0;
+    const int depth = min(max(S.depth, 1), RT_MAX_LEVELS);
+
+    int sp = 1;
+    st_id[0] = (unsigned)depth << 28;
+    st_mask[0] = __ballot(live);          // a dead lane takes part in no ballot
+    for (unsigned it = 0; it < nodes && sp > 0; ++it) {
+        --sp;
+        const unsigned long long mask_v = st_mask[sp];
+        const unsigned id = __builtin_amdgcn_readfirstlane(st_id[sp]);
+        const unsigned long long mask = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(mask_v >> 32)) << 32) |
+                                        __builtin_amdgcn_readfirstlane((unsigned)mask_v);
+        const int L = (int)(id >> 28), k = (int)(id & 0x0FFFFFFFu);
+        if (L < 1 || L > depth || k >= S.n[L]) continue;          // the wave's own ids; bounded all the same
+        const f32x4* nb = boxes + (size_t)(S.noff[L] + (unsigned)k) * RT_NODE_F4;      // wave-uniform: scalar loads
+        f32x4 b4[RT_NODE_F4];
+#pragma unroll
+        for (int x = 0; x < RT_NODE_F4; ++x) b4[x] = nb[x];
+        float bx[RT_FAN * 6];
+#pragma unroll
+        for (int x = 0; x < RT_NODE_F4; ++x) bx[4 * x] = b4[x].x, bx[4 * x + 1] = b4[x].y, bx[4 * x + 2] = b4[x].z, bx[4 * x + 3] = b4[x].w;
+        const bool active = (mask >> lane) & 1ull;
+        float en[RT_FAN];
+#pragma unroll
+        for (int c = 0; c < RT_FAN; ++c) en[c] = active ? rt_entry(o, inv, neg, bx + 6 * c, bx + 6 * c + 3, t_min) : __builtin_nanf("");
+        if (COUNT && active) n_boxes += RT_FAN;
+        if (L > 1) {
+            // push in falling order: child 0 is popped first
+#pragma unroll
+            for (int c = RT_FAN - 1; c >= 0; --c) {
+                const unsigned long long m = __ballot(en[c] <= best_t);
+                if (m != 0 && sp < RT_STACK) {
+                    st_id[sp] = ((unsigned)(L - 1) << 28) | (unsigned)(RT_FAN * k + c);
+                    st_mask[sp] = m;
+                    ++sp;
+                }
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < RT_FAN; ++c) ent[c][lane] = en[c];
+#pragma unroll 1
+            for (int c = 0; c < RT_FAN; ++c) {
+                const int leaf = RT_FAN * k + c;
+                if (leaf >= S.nleaf) break;
+                const bool meet = ent[c][lane] <= best_t;          // best_t as it is NOW: earlier leaves have shrunk it
+                if (__ballot(meet) == 0) continue;
+                const f32x4* rb = rec + 3 * (size_t)RC_CHUNK * leaf;      // wave-uniform: scalar loads
+                const int* fb = face_of + (size_t)RC_CHUNK * leaf;
+                f32x4 r[3 * RC_CHUNK];
+                int fid[RC_CHUNK];
+#pragma unroll
+                for (int x = 0; x < 3 * RC_CHUNK; ++x) r[x] = rb[x];
+#pragma unroll
+                for (int x = 0; x < RC_CHUNK; ++x) fid[x] = fb[x];
+                if (meet) {
+                    if (COUNT) n_pairs += RC_CHUNK;
+#pragma unroll
+                    for (int x = 0; x < RC_CHUNK; ++x) {
+                        float u, v, t;
+                        if (rc_uvt(o, d, r[3 * x], r[3 * x + 1], r[3 * x + 2], t_min, u, v, t) &&
+                            (t < best_t || (t == best_t && fid[x] < best_f)))
+                            best_t = t, best_f = fid[x], best_u = u, best_v = v;
+                    }
+                }
+            }
+        }
+    }
+    if (!live) return;
+    t_out[q] = best_t;
+    face_out[q] = best_f;
+    if (bary_out) bary_out[2 * (size_t)q] = best_u, bary_out[2 * (size_t)q + 1] = best_v;
+    if (COUNT && count_out) count_out[2 * (size_t)q] = n_pairs, count_out[2 * (size_t)q + 1] = n_boxes;
+}
+
+static int rt_cast(const char* what, const void* tree, size_t tree_bytes, int32_t nf, const float* origins, int32_t n_origins,
+                   const float* dirs, int32_t nq, float t_min, float* t_out, int32_t* face_out, float* bary_out,
+                   unsigned* count_out, void* stream) {
+    FGC_CHECK_ARG(tree && origins && dirs && t_out && face_out, "%s: null pointer", what);
+    FGC_CHECK_ARG(nf > 0 && nq > 0, "%s: nf=%d nq=%d (both > 0)", what, nf, nq);
+    FGC_CHECK_ARG(nf <= FGC_RAY_CAST_MAX_FACES, "%s: nf=%d (at most %d)", what, nf, FGC_RAY_CAST_MAX_FACES);
+    FGC_CHECK_ARG(n_origins == 1 || n_origins == nq, "%s: n_origins=%d (1 or nq=%d)", what, n_origins, nq);
+    FGC_CHECK_ARG(t_min >= 0.f && t_min < __builtin_inff(), "%s: t_min=%g (>= 0 and finite)", what, (double)t_min);
+    FGC_CHECK_ARG((uintptr_t)tree % 16 == 0, "%s: tree needs 16-byte alignment", what);
+    const RtLayout T = rt_layout(nf);
+    FGC_CHECK_ARG(tree_bytes >= T.total, "%s: tree too small (%zu < %zu bytes)", what, tree_bytes, T.total);
+    hipStream_t st = (hipStream_t)stream;
+    const char* base = (const char*)tree;
+#ifdef FGC_RT_COUNT
+    if (count_out)
+        FGC_LAUNCH("rt_cast_kernel", st, rt_cast_kernel<true>, dim3(cdiv(nq, 64)), dim3(64), 0, (const f32x4*)base,
+                   (const int*)(base + T.face_of), (const f32x4*)(base + T.boxes), T.s, T.nodes, origins, n_origins, dirs, nq,
+                   t_min, t_out, face_out, bary_out, count_out);
+    else
+#endif
+        FGC_LAUNCH("rt_cast_kernel", st, rt_cast_kernel<false>, dim3(cdiv(nq, 64)), dim3(64), 0, (const f32x4*)base,
+                   (const int*)(base + T.face_of), (const f32x4*)(base + T.boxes), T.s, T.nodes, origins, n_origins, dirs, nq,
+                   t_min, t_out, face_out, bary_out, (unsigned*)nullptr);
+    FGC_CHECK_LAUNCH(what);
+    return FGC_OK;
+}
+
+}  // namespace fgc
+
+using namespace fgc;
+
+extern "C" size_t fgc_ray_tree_bytes(int32_t nf) {
+    if (nf <= 0 || nf > FGC_RAY_CAST_MAX_FACES) return 0;
+    return rt_layout(nf).total;
+}
+
+extern "C" int fgc_ray_tree_build(const float* verts, int32_t nv, const int32_t* faces, int32_t nf, const int32_t* order,
+                                  void* tree, size_t tree_bytes, void* stream) {
+    FGC_CHECK_ARG(verts && faces && order && tree, "fgc_ray_tree_build: null pointer");
+    FGC_CHECK_ARG(nv > 0 && nf > 0, "fgc_ray_tree_build: nv=%d nf=%d (both > 0)", nv, nf);
+    FGC_CHECK_ARG(nf <= FGC_RAY_CAST_MAX_FACES, "fgc_ray_tree_build: nf=%d (at most %d)", nf, FGC_RAY_CAST_MAX_FACES);
+    FGC_CHECK_ARG((uintptr_t)tree % 16 == 0, "fgc_ray_tree_build: tree needs 16-byte alignment");
+    const RtLayout T = rt_layout(nf);
+    FGC_CHECK_ARG(tree_bytes >= T.total, "fgc_ray_tree_build: tree too small (%zu < %zu bytes)", tree_bytes, T.total);
+    hipStream_t st = (hipStream_t)stream;
+    char* base = (char*)tree;
+    float* boxes = (float*)(base + T.boxes);
+    auto level = [&](int L) { return boxes + (size_t)T.s.noff[L + 1] * RT_FAN * 6; };      // the boxes of level L: the nodes of L + 1
+    const int nbox0 = RT_FAN * T.s.n[1];
+    FGC_LAUNCH("rt_leaf_kernel", st, rt_leaf_kernel, dim3(cdiv(nbox0, 256)), dim3(256), 0, verts, nv, faces, nf, order, T.s.nleaf,
+               nbox0, (f32x4*)base, (int*)(base + T.face_of), level(0));
+    for (int L = 1; L < T.s.depth; ++L) {
+        const int nbox = RT_FAN * T.s.n[L + 1];
+        FGC_LAUNCH("rt_level_kernel", st, rt_level_kernel, dim3(cdiv(nbox, 256)), dim3(256), 0, (const float*)level(L - 1),
+                   T.s.n[L], nbox, level(L));
+    }
+    FGC_CHECK_LAUNCH("fgc_ray_tree_build");
+    return FGC_OK;
+}
+
+extern "C" int fgc_ray_cast_tree(const void* tree, size_t tree_bytes, int32_t nf, const float* origins, int32_t n_origins,
+                                 const float* dirs, int32_t nq, float t_min, float* t_out, int32_t* face_out, float* bary_out,
+                                 void* stream) {
+    return rt_cast("fgc_ray_cast_tree", tree, tree_bytes, nf, origins, n_origins, dirs, nq, t_min, t_out, face_out, bary_out,
+                   nullptr, stream);
+}
+
+#ifdef FGC_RT_COUNT
+// probe-only build (tools/ray_cast_probe.py --tree): the same cast, plus count_out [nq,2] = (pairs, boxes) each ray's lane tested
+extern "C" int fgc_ray_cast_tree_count(const void* tree, size_t tree_bytes, int32_t nf, const float* origins, int32_t n_origins,
+                                       const float* dirs, int32_t nq, float t_min, float* t_out, int32_t* face_out,
+                                       float* bary_out, uint32_t* count_out, void* stream) {
+    FGC_CHECK_ARG(count_out, "fgc_ray_cast_tree_count: null pointer");
+    return rt_cast("fgc_ray_cast_tree_count", tree, tree_bytes, nf, origins, n_origins, dirs, nq, t_min, t_out, face_out,
+                   bary_out, count_out, stream);
+}
+#endif

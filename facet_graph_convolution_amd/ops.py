@@ -442,6 +442,110 @@ def ray_cast(verts, faces, origins, dirs, t_min=0.0, want_bary=False):
     return (t, face, bary) if want_bary else (t, face)
 
 
+def _morton30(p, ok=None):
+    """30-bit Morton code of the rows of p [N,3] over the bounding box of the rows marked ok (default: the finite ones):
+    int64 [N], 10 bits per axis, x the lowest of each triple; a row that is not ok gets 2^30, behind every code.  Plain
+    torch on the tensor's device - plumbing that decides the ORDER of work only, never a result."""
+    p = p.reshape(-1, 3).to(torch.float32)
+    fin = torch.isfinite(p).all(1)
+    ok = fin if ok is None else (ok & fin)
+    code = torch.full((p.shape[0],), 1 << 30, dtype=torch.int64, device=p.device)
+    if not bool(ok.any()):
+        return code
+    pk = p[ok].double()
+    lo, hi = pk.min(0).values, pk.max(0).values
+    ext = torch.where(hi > lo, hi - lo, torch.ones_like(lo))
+    cell = ((pk - lo) / ext * 1024.0).floor().clamp_(0, 1023).to(torch.int64)
+    c = torch.zeros(pk.shape[0], dtype=torch.int64, device=p.device)
+    for bit in range(10):
+        for axis in range(3):
+            c |= ((cell[:, axis] >> bit) & 1) << (3 * bit + axis)
+    code[ok] = c
+    return code
+
+
+def ray_tree_order(verts, faces):
+    """The default order of ray_tree: int32 [F], a permutation of 0 .. F-1 - the faces sorted (stably) by the 30-bit Morton
+    code of their centroids over the centroids' bounding box; a face with a vertex id outside [0, V) or a non-finite
+    coordinate goes last.  Plain torch, on the tensors' device (CPU tensors are fine here)."""
+    verts = verts.reshape(-1, 3).to(torch.float32)
+    faces = faces.reshape(-1, 3).to(torch.int64)
+    valid = ((faces >= 0) & (faces < verts.shape[0])).all(1)
+    tri = verts[faces.clamp(0, max(verts.shape[0] - 1, 0))]                      # [F,3,3]
+    valid = valid & torch.isfinite(tri).all(2).all(1)
+    cen = tri.double().mean(1).to(torch.float32)
+    return torch.sort(_morton30(cen, valid), stable=True).indices.to(torch.int32)
+
+
+class RayTree:
+    """What ray_tree returns: the device buffer of fgc_ray_tree_build and the sizes it was built for."""
+
+    def __init__(self, tree, nf, nv):
+        self.tree, self.nf, self.nv = tree, int(nf), int(nv)
+
+    def __repr__(self):
+        return "RayTree(nf=%d, nv=%d, %d bytes on %s)" % (self.nf, self.nv, self.tree.numel(), self.tree.device)
+
+
+def ray_tree(verts, faces, order=None):
+    """The bounding-box tree of a triangle list for ray_cast_tree (include/fgc.h: fgc_ray_tree_build; a build extension) on
+    GPU tensors: verts [V,3] fp32, faces int [F,3].  order: int [F], a permutation of 0 .. F-1 that says which faces share
+    a leaf (four in a row) and a node; ANY permutation gives the same results, only the speed depends on it.  None: the
+    Morton order of ray_tree_order.  The tree is built once per mesh and serves any number of casts."""
+    _req_cuda(verts, faces, order)
+    verts = _f32c(verts.reshape(-1, 3))
+    faces = faces.to(torch.int32).reshape(-1, 3).contiguous()
+    nv, nf = verts.shape[0], faces.shape[0]
+    L = _lib.lib()
+    nbytes = L.fgc_ray_tree_bytes(nf)
+    if nbytes == 0 or nv == 0:
+        raise ValueError("ray_tree needs at least one vertex and one face (got %d, %d)" % (nv, nf))
+    order = ray_tree_order(verts, faces) if order is None else order.to(torch.int32).reshape(-1).contiguous()
+    if order.shape[0] != nf:
+        raise ValueError("order has %d entries: one per face (%d)" % (order.shape[0], nf))
+    tree = torch.empty(nbytes, dtype=torch.uint8, device=verts.device)
+    check(L.fgc_ray_tree_build(ptr(verts), nv, ptr(faces), nf, ptr(order), ptr(tree), tree.numel(), stream_ptr()),
+          "fgc_ray_tree_build")
+    return RayTree(tree, nf, nv)
+
+
+def ray_cast_tree(tree, origins, dirs, t_min=0.0, want_bary=False, sort_rays=True):
+    """ray_cast through a RayTree (include/fgc.h: fgc_ray_cast_tree): the same arguments and the same returns, the mesh
+    being the one the tree was built of.  sort_rays: cast the rays in the (stable) Morton order of their unit directions
+    (one origin) or of their origins, and scatter the results back - neighbours in a wave then walk the same nodes.  A ray's
+    result does not depend on its neighbours, so this changes the time and not one bit of the result."""
+    if not isinstance(tree, RayTree):
+        raise TypeError("ray_cast_tree needs the RayTree that ray_tree returns (got %s)" % type(tree).__name__)
+    _req_cuda(tree.tree, origins, dirs)
+    origins, dirs = _f32c(origins.reshape(-1, 3)), _f32c(dirs.reshape(-1, 3))
+    nq = dirs.shape[0]
+    if origins.shape[0] not in (1, nq):
+        raise ValueError("origins has %d rows: one row, or one per ray (%d)" % (origins.shape[0], nq))
+    if not (np.isfinite(t_min) and t_min >= 0):
+        raise ValueError("t_min must be finite and >= 0 (got %r)" % (t_min,))
+    if nq == 0:
+        raise ValueError("ray_cast_tree needs at least one ray")
+    perm = None
+    if sort_rays and nq > 1:
+        key = dirs / dirs.norm(dim=1, keepdim=True) if origins.shape[0] == 1 else origins
+        perm = torch.sort(_morton30(key), stable=True).indices
+        dirs = dirs[perm].contiguous()
+        if origins.shape[0] != 1:
+            origins = origins[perm].contiguous()
+    dev = dirs.device
+    t = torch.empty(nq, dtype=torch.float32, device=dev)
+    face = torch.empty(nq, dtype=torch.int32, device=dev)
+    bary = torch.empty(nq, 2, dtype=torch.float32, device=dev) if want_bary else None
+    check(_lib.lib().fgc_ray_cast_tree(ptr(tree.tree), tree.tree.numel(), tree.nf, ptr(origins), origins.shape[0], ptr(dirs),
+                                       nq, float(t_min), ptr(t), ptr(face), ptr(bary), stream_ptr()), "fgc_ray_cast_tree")
+    if perm is not None:
+        t = torch.empty_like(t).index_copy_(0, perm, t)
+        face = torch.empty_like(face).index_copy_(0, perm, face)
+        if want_bary:
+            bary = torch.empty_like(bary).index_copy_(0, perm, bary)
+    return (t, face, bary) if want_bary else (t, face)
+
+
 def pool4_avg_iz(x):
     """custom_binary_tree_pooling(x, steps=2, 'avg_ignore_zeros') (model.py:792-814) on [n, c] rows."""
     _req_cuda(x)

@@ -1,7 +1,7 @@
 """Virtual depth scans of a folder of clean OBJ files (build extension; README "Depth scans"):
 
     python -m facet_graph_convolution_amd.scan CLEAN_DIR SCAN_DIR (--camera X,Y,Z | --view-dir X,Y,Z)
-        [--image W,H [--fov DEG] [--jump R]] [--max-angle DEG] [--eps E] [--overwrite]
+        [--image W,H [--fov DEG] [--jump R]] [--max-angle DEG] [--eps E] [--accel none|tree] [--overwrite]
 
 For every `name.obj` of CLEAN_DIR (sorted) the file `SCAN_DIR/name.obj`: the part of the mesh that ONE sensor sees, an
 open sheet that ends at silhouettes and occlusions.  Without --image it is the visible cut of the mesh itself
@@ -13,7 +13,9 @@ folder of everything downstream (makeNoisy --direction ray, preprocess --clean, 
 computeMetrics) with the same --camera / --view-dir.  Existing files are skipped unless --overwrite; a mesh of which the
 view sees nothing is reported and skipped.
 
-The visibility test is ops.ray_cast (include/fgc.h: fgc_ray_cast): rays x faces pairs, brute force, once per mesh.
+The visibility test is ops.ray_cast (include/fgc.h: fgc_ray_cast): rays x faces pairs, brute force, once per mesh; with
+--accel tree it is ops.ray_cast_tree through a bounding-box tree built once per mesh (fgc_ray_cast_tree), whose cost does
+not grow with rays x faces.
 --max-angle 80, --fov 40 and --jump 0.05 are this build's choices; nobody has tuned them.
 """
 import argparse
@@ -22,17 +24,17 @@ import os
 import numpy as np
 
 
-def scan_mesh(V, faces, camera=None, view_dir=None, image=None, fov=40.0, jump=0.05, max_angle=80.0, eps=1e-3):
+def scan_mesh(V, faces, camera=None, view_dir=None, image=None, fov=40.0, jump=0.05, max_angle=80.0, eps=1e-3, accel="none"):
     """One virtual scan of a mesh: (V float32 [v,3], faces int32 [f,3]).  image=None: utils.scan_cut (camera or view_dir);
     image=(W, H): utils.range_mesh of utils.depth_image (camera only; the camera looks at the centre of the bounding box).
-    ValueError when the view sees nothing."""
+    accel: "none", "tree" or a handle of utils.ray_tree, as in utils.visible_vertices.  ValueError when the view sees nothing."""
     from . import utils
     if image is None:
-        Vc, Fc, _ = utils.scan_cut(V, faces, camera=camera, view_dir=view_dir, eps=eps, max_angle=max_angle)
+        Vc, Fc, _ = utils.scan_cut(V, faces, camera=camera, view_dir=view_dir, eps=eps, max_angle=max_angle, accel=accel)
         return Vc, Fc
     if camera is None or view_dir is not None:
         raise ValueError("a depth image needs a camera (and takes no view_dir)")
-    depth, _, rays = utils.depth_image(V, faces, camera, size=image, fov=fov)
+    depth, _, rays = utils.depth_image(V, faces, camera, size=image, fov=fov, accel=accel)
     return utils.range_mesh(depth, rays, camera, jump=jump)
 
 
@@ -50,6 +52,8 @@ def main(argv=None):
                     help="the cut: drop faces turned away from the sensor by more than this many degrees (default %(default)s)")
     ap.add_argument("--eps", type=float, default=1e-3,
                     help="the cut: a vertex is visible when nothing is hit before t = 1 - eps on its ray (default %(default)s)")
+    ap.add_argument("--accel", choices=("none", "tree"), default="none",
+                    help="none: every ray against every face; tree: through a bounding-box tree built per mesh (default %(default)s)")
     ap.add_argument("--overwrite", action="store_true")
     args = ap.parse_args(argv)
     view = view_spec(ap, args)
@@ -85,7 +89,7 @@ def main(argv=None):
         V, _, _, faces, _ = load_mesh(args.clean_dir, f, 0, False)
         try:
             Vs, Fs = scan_mesh(V, faces, image=image, fov=args.fov, jump=args.jump, max_angle=args.max_angle, eps=args.eps,
-                               **view)
+                               accel=args.accel, **view)
         except ValueError as e:
             print("Skipping %s. %s" % (f, e))
             continue

@@ -393,16 +393,42 @@ def direction_key(direction):
 
 # ---------------------------------------------------------------------------------------------------
 # virtual depth scans (build extension; README "Depth scans"): what one sensor sees of a clean mesh.  The ray casting is
-# ops.ray_cast (include/fgc.h: fgc_ray_cast); everything around it is host code, numpy in and out.
+# ops.ray_cast (include/fgc.h: fgc_ray_cast) or, with accel=, ops.ray_cast_tree; everything around it is host code, numpy
+# in and out.
 # ---------------------------------------------------------------------------------------------------
-def _ray_cast_host(V, faces, origins, dirs, t_min=0.0):
-    """ops.ray_cast on host arrays: (t float32 [Q], face int32 [Q])."""
+def _put(a, dt):
     import torch
-    from . import ops
     dev = torch.device("cuda", torch.cuda.current_device())
-    put = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)  # noqa: E731
-    t, face = ops.ray_cast(put(V, np.float32), put(np.asarray(faces).astype(np.int64), np.int32), put(origins, np.float32),
-                           put(dirs, np.float32), t_min)
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)
+
+
+def ray_tree(V, faces):
+    """The bounding-box tree of a mesh on the current GPU (ops.ray_tree, include/fgc.h: fgc_ray_tree_build), numpy in, a
+    handle out: pass it as accel= to visible_vertices, scan_cut and depth_image so that several views of ONE mesh share a
+    build (the handle remembers the sizes of the mesh, not the mesh: give it the arrays it was built of)."""
+    from . import ops
+    return ops.ray_tree(_put(np.array(V, dtype=np.float32).reshape(-1, 3), np.float32),
+                        _put(np.asarray(faces).astype(np.int64).reshape(-1, 3), np.int32))
+
+
+def _ray_cast_host(V, faces, origins, dirs, t_min=0.0, accel="none"):
+    """ops.ray_cast on host arrays: (t float32 [Q], face int32 [Q]).  accel: "none" - rays x faces, brute force; "tree" -
+    build a bounding-box tree for this call and cast through it (ops.ray_cast_tree); a handle of utils.ray_tree - cast
+    through that tree."""
+    from . import ops
+    if isinstance(accel, str) and accel == "none":
+        t, face = ops.ray_cast(_put(V, np.float32), _put(np.asarray(faces).astype(np.int64), np.int32),
+                               _put(origins, np.float32), _put(dirs, np.float32), t_min)
+        return t.cpu().numpy(), face.cpu().numpy()
+    if isinstance(accel, str) and accel == "tree":
+        accel = ray_tree(V, faces)
+    elif not isinstance(accel, ops.RayTree):
+        raise ValueError('accel must be "none", "tree" or a handle of utils.ray_tree (got %r)' % (accel,))
+    nv, nf = np.asarray(V).reshape(-1, 3).shape[0], np.asarray(faces).reshape(-1, 3).shape[0]
+    if (accel.nv, accel.nf) != (nv, nf):
+        raise ValueError("the tree was built of a mesh of %d vertices and %d faces, this one has %d and %d"
+                         % (accel.nv, accel.nf, nv, nf))
+    t, face = ops.ray_cast_tree(accel, _put(origins, np.float32), _put(dirs, np.float32), t_min)
     return t.cpu().numpy(), face.cpu().numpy()
 
 
@@ -411,13 +437,14 @@ def _bbox_diagonal(V):
     return float(np.linalg.norm(V.max(0) - V.min(0)))
 
 
-def visible_vertices(V, faces, camera=None, view_dir=None, eps=1e-3):
+def visible_vertices(V, faces, camera=None, view_dir=None, eps=1e-3, accel="none"):
     """Which vertices of a mesh one sensor sees: bool [V].  Exactly one of camera (a point, perspective) and view_dir (one
     direction for every vertex, orthographic), checked as view_rays checks them.  One ray per vertex, built so that the
     vertex itself sits at t = 1: from the camera, origin = camera and d = v - camera (unnormalised); along a direction,
     origin = v - L dhat and d = L dhat with L twice the bounding-box diagonal, so that every origin lies outside the mesh.
     A vertex is visible iff the first hit of its ray (ops.ray_cast over ALL faces, its own included - they are hit at t
-    close to 1) has t >= 1 - eps; a ray that hits nothing counts as visible.  Rays x faces pairs, no spatial culling."""
+    close to 1) has t >= 1 - eps; a ray that hits nothing counts as visible.  accel="none": rays x faces pairs, no spatial
+    culling; "tree" or a handle of utils.ray_tree: through a bounding-box tree (_ray_cast_host)."""
     view_rays(V, camera=camera, view_dir=view_dir)          # (the checks: exactly one view, finite, no vertex at the camera)
     if not (np.isfinite(eps) and 0 <= eps < 1):
         raise ValueError("eps must lie in [0, 1) (got %r)" % (eps,))
@@ -429,20 +456,21 @@ def visible_vertices(V, faces, camera=None, view_dir=None, eps=1e-3):
         d = np.asarray(view_dir, dtype=np.float64).reshape(1, 3)
         step = d / np.linalg.norm(d) * (2.0 * _bbox_diagonal(V64))
         origins, dirs = V64 - step, np.broadcast_to(step, V64.shape)
-    t, _ = _ray_cast_host(V64, faces, origins, dirs)
+    t, _ = _ray_cast_host(V64, faces, origins, dirs, accel=accel)
     return t >= np.float32(1.0 - eps)
 
 
-def scan_cut(V, faces, camera=None, view_dir=None, eps=1e-3, max_angle=80.0):
+def scan_cut(V, faces, camera=None, view_dir=None, eps=1e-3, max_angle=80.0, accel="none"):
     """The part of a mesh one sensor sees, as an open mesh: (V_cut float32 [v,3], faces_cut int32 [f,3], vertex_ids int64
     [v]).  A face stays iff its three vertices are visible (visible_vertices) and it is turned towards the sensor by less
     than max_angle degrees: -n . r >= cos(max_angle), n the unit face normal and r the unit ray to the face centre (from
     the camera, or view_dir), both in float64 on the host.  The vertices are those of the kept faces in their old order,
     vertex_ids maps them to the old ones; the faces keep their order and are re-indexed.  Nothing left: ValueError.
-    max_angle = 80 is this build's choice (a sensor returns little from a surface it grazes); nobody has tuned it."""
+    max_angle = 80 is this build's choice (a sensor returns little from a surface it grazes); nobody has tuned it.
+    accel: as in visible_vertices."""
     if not (np.isfinite(max_angle) and 0 < max_angle <= 180):
         raise ValueError("max_angle must lie in (0, 180] degrees (got %r)" % (max_angle,))
-    vis = visible_vertices(V, faces, camera=camera, view_dir=view_dir, eps=eps)
+    vis = visible_vertices(V, faces, camera=camera, view_dir=view_dir, eps=eps, accel=accel)
     V = np.asarray(V)
     F = np.asarray(faces).astype(np.int64).reshape(-1, 3)
     T = V.astype(np.float64).reshape(-1, 3)[F]
@@ -495,17 +523,18 @@ def pixel_rays(camera, look_at, size, fov=40.0, up=(0, 0, 1)):
     return (r / np.sqrt((r * r).sum(-1, keepdims=True))).astype(np.float32)
 
 
-def depth_image(V, faces, camera, size=(640, 480), fov=40.0, look_at=None, up=(0, 0, 1)):
+def depth_image(V, faces, camera, size=(640, 480), fov=40.0, look_at=None, up=(0, 0, 1), accel="none"):
     """A depth image of a mesh: (depth float32 [H,W], face int32 [H,W], rays float32 [H,W,3]).  A pinhole at `camera`
     looking at look_at (default: the centre of the bounding box), the rays of pixel_rays; depth is the distance t along the
     unit ray to the first hit (ops.ray_cast), +inf for background, face the triangle hit or -1.  fov = 40 degrees is this
-    build's choice; nobody has tuned it.  W x H x faces pairs, no spatial culling."""
+    build's choice; nobody has tuned it.  accel="none": W x H x faces pairs, no spatial culling; "tree" or a handle of
+    utils.ray_tree: through a bounding-box tree (_ray_cast_host)."""
     V64 = np.asarray(V, dtype=np.float64).reshape(-1, 3)
     if look_at is None:
         look_at = 0.5 * (V64.min(0) + V64.max(0))
     rays = pixel_rays(camera, look_at, size, fov, up)
     H, W = rays.shape[:2]
-    t, face = _ray_cast_host(V64, faces, np.asarray(camera, dtype=np.float64).reshape(1, 3), rays.reshape(-1, 3))
+    t, face = _ray_cast_host(V64, faces, np.asarray(camera, dtype=np.float64).reshape(1, 3), rays.reshape(-1, 3), accel=accel)
     return t.reshape(H, W), face.reshape(H, W), rays
 
 

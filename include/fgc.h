@@ -70,7 +70,8 @@ extern "C" {
  * declares them finds out at load time whether the library has them): fgc_vertex_update_ms_dir / _traj / _bwd
  * (+ _scratch_floats, _bwd_workspace_floats), the multi-scale vertex update along a per-vertex direction and its adjoint,
  * depth scans for the vertex networks; fgc_ray_cast (+ _workspace_bytes), rays against a triangle list: virtual depth
- * scans of a clean mesh. */
+ * scans of a clean mesh; fgc_ray_tree_bytes / fgc_ray_tree_build / fgc_ray_cast_tree, the same cast through a bounding-box
+ * tree: scans of large meshes. */
 #define FGC_ABI_VERSION 116
 
 const char* fgc_last_error(void);
@@ -1048,6 +1049,76 @@ size_t fgc_ray_cast_workspace_bytes(int32_t nf, int32_t nq);
 int fgc_ray_cast(const float* verts, int32_t nv, const int32_t* faces, int32_t nf, const float* origins, int32_t n_origins,
                  const float* dirs, int32_t nq, float t_min, float* t_out, int32_t* face_out, float* bary_out,
                  void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same cast through a bounding-box tree, at a cost that does not grow with nq x nf.  Two steps: fgc_ray_tree_build once
+ * per mesh, fgc_ray_cast_tree once per set of rays (any number of views share a build).
+ *
+ * THE TREE is implicit: no topology is stored, it is defined by an order of the triangles alone.
+ *   order [nf] int32: a permutation of 0 .. nf-1, device memory.  Nothing about it is checked on the host; on the device an
+ *     entry outside [0, nf) yields a zero record.  ANY permutation gives a valid tree with the same results; only the speed
+ *     depends on it (ops.ray_tree sorts the faces along a Morton curve of their centroids).
+ *   Records: record j = the record fgc_ray_cast makes of face order[j] - (a, 0), (e1, 0), (e2, 0), 48 bytes, a zero record
+ *     for a row with a vertex id outside [0, nv) - with face_of[j] = order[j] beside it; nf is rounded up to whole chunks of
+ *     4 with zero records.
+ *   Leaves: leaf i = the chunk of records 4i .. 4i + 3.  Its box is the exact min / max over the ORIGINAL three vertices
+ *     verts[a], verts[b], verts[c] (not a + e1) of those of its faces that are valid and whose nine coordinates are finite; a
+ *     face with a bad id or a non-finite coordinate contributes nothing (fgc_ray_cast never reports a hit on a NaN either),
+ *     and a leaf without such a face has the empty box lo = +inf, hi = -inf.
+ *   Nodes: a node is 8 children, stored as their 8 boxes of 6 floats (lo.xyz, hi.xyz): 48 dwords, three 16-dword scalar
+ *     loads, the size of a chunk of records.  n[0] = leaves, n[L] = ceil(n[L-1] / 8); node k of level L >= 1 holds the boxes
+ *     of children 8k .. 8k + 7 of level L - 1 (leaves for L = 1), a missing child is the empty box; the level whose n is 1
+ *     is the root (10 levels for 2^30 faces).  A box above the leaves is the union of its children, min / max again: exact.
+ *   tree (device, 16-byte aligned) >= fgc_ray_tree_bytes(nf) bytes (0 for nf <= 0 or nf > FGC_RAY_CAST_MAX_FACES; it never
+ *     decreases with nf): the records, face_of, then the nodes level by level from the bottom.  It holds no pointer and no
+ *     index that is used to address memory.
+ *   fgc_ray_tree_build: one launch for the leaves (one thread per box: records, face_of, box) and one per level above (one
+ *     thread per box).  Enqueue-only, capturable, nothing allocated.  A NULL among verts, faces, order, tree; nv or nf <= 0;
+ *     nf > FGC_RAY_CAST_MAX_FACES; a tree that is misaligned or too small: FGC_EINVAL, nothing launched.
+ *
+ * THE CAST.  Arguments and outputs mean what they mean in fgc_ray_cast (nf is the nf of the build); a miss is
+ *   (+inf, -1, (0, 0)), the barycentrics are those rc_uvt gave for the winner.  The per-pair arithmetic is the ONE function
+ *   fgc_ray_cast runs, on the same record, so a pair tested by both gives the same bits; the tree tests a subset of the pairs.
+ *   Hence on every ray the tree's (t, face) is never smaller in key order than fgc_ray_cast's, and it is equal wherever the
+ *   boxes do not cull the winner.  fp32 Moeller-Trumbore is not watertight: it can report a hit on a grazed triangle whose box
+ *   the exact ray misses, and the tree may cull that one.
+ *   Traversal by packet: a wave holds 64 rays, one per lane; its stack of (node, ballot) entries is wave-uniform, the boxes of
+ *   a node and the records of a leaf arrive through scalar loads.  A lane takes part in a node only if its own ray met that
+ *   node and every node above it; it tests the four records of a leaf only if its ray meets the leaf's box in
+ *   [t_min, best_t] with the best_t it has at that moment; it keeps the smallest (t, face_of) in FULL key order
+ *   (t < best_t, or t == best_t and face < best_face: records are not in rising face order).  Children are visited in index
+ *   order.  So the leaves a lane tests, and the best_t it tests each with, are those of its ray walking the tree alone: a
+ *   ray's result is a function of the tree and that ray - not of its neighbours in the wave, the launch geometry, the order
+ *   of the rays, eager or replayed.  A lane beyond nq takes part in no ballot.
+ *   THE SLAB TEST of a lane's ray against a box (lo, hi), inv = (1 / d_x, 1 / d_y, 1 / d_z) in IEEE (a zero component gives
+ *   an infinity): per axis t1 = (lo - o) inv, t2 = (hi - o) inv (one subtraction, one multiplication), tn = t1 and tf = t2
+ *   if inv >= 0, swapped otherwise; near = max(tn_x, tn_y, tn_z), far = min(tf_x, tf_y, tf_z) with min / max that return the
+ *   operand that is no NaN; near' = near - (|near| 2^-21 + 2^-125), far' = far + (|far| 2^-21 + 2^-125).  The lane meets the
+ *   box iff near' <= far', far' >= t_min and near' <= best_t, all non-strict (an equal t on a lower face index behind a box
+ *   entered at exactly best_t is still found).
+ *   Why it never rejects a box the exact ray passes through (for 1 / d finite or d == 0, and t within the range of fp32):
+ *   the exact parameters of the two planes are (lo - o) / d and (hi - o) / d.  The subtraction, the reciprocal and the
+ *   product each round once, so a computed t is the exact one times (1 + e)^3, |e| <= 2^-24: off by less than 2 units in
+ *   the last place and never of the wrong sign; a product that underflows is off by less than 2^-126.  near' and far' move
+ *   each end outward by 4 units and 2^-125, more than that error, and rounding is monotonic, so near' <= exact near and
+ *   far' >= exact far: if the exact interval is not empty and meets [t_min, best_t], the computed one does.  Which of t1, t2
+ *   is the near one is decided by the sign of inv, not by comparing them, so with d == 0 on an axis: an origin strictly
+ *   inside the slab gives tn = -inf, tf = +inf (no constraint); outside it, tn = +inf or tf = -inf (rejected, rightly: the
+ *   ray never enters); ON a plane, 0 x inf = NaN on that side, which max / min drop: the plane does not constrain, the ray
+ *   counts as inside.  An empty box gives near = +inf or far = -inf on every axis and is never met; so is any box for a ray
+ *   with a NaN, which can hit nothing.  (Ize, "Robust BVH Ray Traversal", JCGT 2013, is the usual statement of this test.)
+ *   NO LOOP ENDS ON DEVICE DATA: each node is pushed at most once, so the walk pops at most (number of nodes) times, a count
+ *   made on the host from nf; the stack holds at most 7 entries per level + 1; every popped id is bounded before it addresses
+ *   anything.  A corrupt tree gives wrong answers, not a hang and no access outside the buffer.
+ *   No per-call workspace, no key buffer, no atomics: each ray is owned by one lane.  One launch, enqueue-only, capturable.
+ *   A NULL among tree, origins, dirs, t_out, face_out; nf or nq <= 0; nf > FGC_RAY_CAST_MAX_FACES; n_origins neither 1 nor nq;
+ *   t_min negative, infinite or a NaN; a tree that is misaligned or below fgc_ray_tree_bytes(nf): FGC_EINVAL, nothing
+ *   launched. */
+size_t fgc_ray_tree_bytes(int32_t nf);
+int fgc_ray_tree_build(const float* verts, int32_t nv, const int32_t* faces, int32_t nf, const int32_t* order, void* tree,
+                       size_t tree_bytes, void* stream);
+int fgc_ray_cast_tree(const void* tree, size_t tree_bytes, int32_t nf, const float* origins, int32_t n_origins,
+                      const float* dirs, int32_t nq, float t_min, float* t_out, int32_t* face_out, float* bary_out,
+                      void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Checkpoint files (CPU; HOST pointers)
