@@ -276,6 +276,8 @@ _SIGS = {
     "fgc_synth_scratch_floats": (C.c_size_t, [C.c_int32]),
     "fgc_synth_noise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p,
                                   C.c_void_p, C.c_size_t, C.c_void_p]),
+    "fgc_synth_noise_sensor": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "fgc_synth_lf_scratch_floats": (C.c_size_t, [C.c_int32, C.c_int32]),
     "fgc_synth_noise_lf": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                      C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),

@@ -64,6 +64,46 @@ FGC_HD void synth_displace(uint32_t i, uint32_t step_lo, uint32_t step_hi, uint3
     for (int t = 0; t < 3; ++t) out[t] = sigma == 0.0f ? v[t] : v[t] + d[t] * len;
 }
 
+// The depth-sensor model of fgc_synth_noise_sensor (include/fgc.h has the definition): vertex i displaced along its viewing
+// ray d by a Gaussian whose sigma grows with the range r = |v - cam| (power 0, 1, 2 of r / r_ref), then - q > 0 - put on the
+// lattice of a sensor that reports r = 1 / (k q).  z3 is synth_displace's: the same counter, key and pair of words.
+// power 0 with q == 0 is synth_displace(along_normal) bit for bit; q == 0 with sigma == 0 returns the vertex itself.
+// Every operation is one rounded IEEE operation (the file compiles with contraction off; / and sqrtf are the accurate
+// ones): the fmaf below are the definition's.
+FGC_HD void synth_displace_sensor(uint32_t i, uint32_t step_lo, uint32_t step_hi, uint32_t stream_id, uint32_t seed_lo,
+                                  uint32_t seed_hi, float sigma, uint32_t power, float r_ref, float q, const float cam[3],
+                                  const float v[3], const float d[3], float out[3]) {
+    uint32_t c[4] = {i, step_lo, step_hi, stream_id};
+    philox4x32_10(c, seed_lo, seed_hi);
+    float z2, z3;
+    box_muller(c[2], c[3], &z2, &z3);
+    const float w[3] = {v[0] - cam[0], v[1] - cam[1], v[2] - cam[2]};
+    const float r = sqrtf(fmaf(w[2], w[2], fmaf(w[1], w[1], w[0] * w[0])));
+    const float rho = r / r_ref;
+    float s = sigma;
+    if (power >= 1) s = sigma * rho;
+    if (power == 2) s = s * rho;
+    float len = s * z3;
+    bool keep = sigma == 0.0f;
+    if (q > 0.0f) {
+        float rt = r + len;
+        if (!(rt > 0.0f)) rt = r;      // the noise carried the sample through the sensor (or r itself is 0)
+        const float k = fminf(fmaxf(rintf(1.0f / (rt * q)), 1.0f), 16777216.0f);
+        len = 1.0f / (k * q) - r;
+        keep = false;
+    }
+    for (int t = 0; t < 3; ++t) out[t] = keep ? v[t] : v[t] + d[t] * len;
+}
+
+// What a sensor_ctl of fgc_synth_noise_sensor must hold to be ON: the on flag, power 0 ... 2, r_ref a positive normal
+// float, q zero or a positive normal float.  Anything else is OFF - plain noise along the rays - never a non-finite vertex.
+FGC_HD bool sensor_words_valid(uint32_t w0, float r_ref, float q) {
+    const bool on = (w0 & 0x80000000u) != 0 && (w0 & 0x7FFFFFFFu) <= 2u;
+    const bool ref_ok = r_ref >= 0x1p-126f && r_ref <= 3.402823466e+38f;
+    const bool q_ok = q == 0.0f || (q >= 0x1p-126f && q <= 3.402823466e+38f);
+    return on && ref_ok && q_ok;
+}
+
 // ---- what the noise launches share (fgc_synth.hip, fgc_synth_lf.hip): launch shape and the workgroup's bounding box ----
 constexpr int SY_THREADS = 256;
 constexpr int SY_MAX_BLOCKS = 1024;      // vertex blocks of a launch = bounding-box partials the feature kernel re-reduces

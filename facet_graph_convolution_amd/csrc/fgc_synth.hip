@@ -8,6 +8,7 @@
 // The features must carry the host routine's roundings: no fused multiply-add anywhere in this file but the explicit
 // fmaf of rot3 (fgc_pack.h), which are the rotation's definition.
 #include <algorithm>
+#include <cmath>
 
 #include "fgc_common.h"
 #include "fgc_pack.h"
@@ -46,6 +47,50 @@ __global__ __launch_bounds__(SY_THREADS) void synth_noise_kernel(const float* __
             v_out[o + t] = q[t];
             mn[t] = fminf(mn[t], q[t]);
             mx[t] = fmaxf(mx[t], q[t]);
+        }
+    }
+    block_minmax(mn, mx, red);
+    if (threadIdx.x == 0) store_box(partials + 6 * (size_t)blockIdx.x, mn, mx);
+}
+
+// synth_noise_kernel's launch for the depth-sensor model (fgc_synth.h: synth_displace_sensor): the same vertex sets per
+// workgroup, so the same bounding-box partials layout.  sensor_ctl (device): {FGC_SYNTH_ON | power, float bits of r_ref,
+// float bits of q, 0}; words that are off or out of range (sensor_words_valid) give plain noise along dirs, the bits of
+// synth_noise_kernel(vn = dirs).  The camera comes by value: it is fixed per bound mesh, and a captured launch keeps it.
+__global__ __launch_bounds__(SY_THREADS) void synth_noise_sensor_kernel(const float* __restrict__ v,
+                                                                        const float* __restrict__ dirs, int nv,
+                                                                        const uint32_t* __restrict__ ctl,
+                                                                        const uint32_t* __restrict__ sensor_ctl, float cx,
+                                                                        float cy, float cz, uint32_t seed_lo, uint32_t seed_hi,
+                                                                        uint32_t stream_id, float* __restrict__ v_out,
+                                                                        float* __restrict__ partials) {
+    __shared__ float red[SY_THREADS / 64][6];
+    const uint32_t word = ctl[2];
+    if (word == 0) return;      // (uniform over the launch)
+    const float sigma = __uint_as_float(word & 0x7FFFFFFFu);
+    const uint32_t step_lo = ctl[0], step_hi = ctl[1];
+    const uint32_t w0 = sensor_ctl[0];
+    float r_ref = __uint_as_float(sensor_ctl[1]), q = __uint_as_float(sensor_ctl[2]);
+    uint32_t power = w0 & 0x7FFFFFFFu;
+    if (!sensor_words_valid(w0, r_ref, q)) {
+        power = 0;
+        r_ref = 1.0f;
+        q = 0.0f;
+    }
+    const float cam[3] = {cx, cy, cz};
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    for (int i = blockIdx.x * SY_THREADS + threadIdx.x; i < nv; i += gridDim.x * SY_THREADS) {
+        const size_t o = 3 * (size_t)i;
+        const float p[3] = {v[o], v[o + 1], v[o + 2]};
+        const float d[3] = {dirs[o], dirs[o + 1], dirs[o + 2]};
+        float out[3];
+        synth_displace_sensor((uint32_t)i, step_lo, step_hi, stream_id, seed_lo, seed_hi, sigma, power, r_ref, q, cam, p, d,
+                              out);
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            v_out[o + t] = out[t];
+            mn[t] = fminf(mn[t], out[t]);
+            mx[t] = fmaxf(mx[t], out[t]);
         }
     }
     block_minmax(mn, mx, red);
@@ -224,6 +269,26 @@ extern "C" int fgc_synth_noise(const float* v, const float* vnormals, int32_t nv
     FGC_LAUNCH("synth_noise_kernel", st, synth_noise_kernel, dim3(synth_blocks(nv)), dim3(SY_THREADS), 0, v, vnormals, nv,
                ctl, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), stream_id, v_out, scratch);
     FGC_CHECK_LAUNCH("fgc_synth_noise");
+    return FGC_OK;
+}
+
+extern "C" int fgc_synth_noise_sensor(const float* v, const float* dirs, int32_t nv, const uint32_t* ctl,
+                                      const uint32_t* sensor_ctl, const float* camera, uint64_t seed, uint32_t stream_id,
+                                      float* v_out, float* scratch, size_t scratch_floats, void* stream) {
+    FGC_CHECK_ARG(v && dirs && ctl && sensor_ctl && camera && v_out && scratch,
+                  "fgc_synth_noise_sensor: null pointer (the model needs the table of rays and the camera)");
+    FGC_CHECK_ARG(nv > 0, "fgc_synth_noise_sensor: nv=%d (> 0)", nv);
+    FGC_CHECK_ARG(v_out != v, "fgc_synth_noise_sensor: v_out and v must be distinct (the clean vertices are kept)");
+    FGC_CHECK_ARG(std::isfinite(camera[0]) && std::isfinite(camera[1]) && std::isfinite(camera[2]),
+                  "fgc_synth_noise_sensor: the camera must be three finite numbers");
+    const size_t need = fgc_synth_scratch_floats(nv);
+    FGC_CHECK_ARG(scratch_floats >= need, "fgc_synth_noise_sensor: scratch too small (%zu < %zu floats)", scratch_floats,
+                  need);
+    hipStream_t st = (hipStream_t)stream;
+    FGC_LAUNCH("synth_noise_sensor_kernel", st, synth_noise_sensor_kernel, dim3(synth_blocks(nv)), dim3(SY_THREADS), 0, v,
+               dirs, nv, ctl, sensor_ctl, camera[0], camera[1], camera[2], (uint32_t)(seed & 0xFFFFFFFFu),
+               (uint32_t)(seed >> 32), stream_id, v_out, scratch);
+    FGC_CHECK_LAUNCH("fgc_synth_noise_sensor");
     return FGC_OK;
 }
 

@@ -3,7 +3,7 @@ downloads that ship their noisy meshes):
 
     python -m facet_graph_convolution_amd.makeNoisy CLEAN_DIR OUT_DIR [--levels 0.1,0.2,0.3] [--seed S]
         [--direction random|normal|ray] [--view-dir X,Y,Z | --camera X,Y,Z]
-        [--lf-levels 0.3,0.2,0.1] [--lf-width 3] [--lf-bumps K] [--overwrite]
+        [--lf-levels 0.3,0.2,0.1] [--lf-width 3] [--lf-bumps K] [--sensor POWER[:QUANT]] [--overwrite]
 
 For every `name.obj` of CLEAN_DIR (sorted) and level k = 1, 2, ... the file `name_n<k>.obj` with the input's faces and
 its vertices displaced by Gaussian noise of standard deviation level x mean edge length - the names getGTFilename,
@@ -17,6 +17,10 @@ trainNet(noise_levels=..., lf_levels=...) validates on.  Existing files are skip
 noise of a depth sensor.  The rays are built from the CLEAN vertices (utils.view_rays), as `train --noise-direction ray`
 builds them, so the files stay the validation meshes of a training run with the same seed and view.  The low-frequency
 bumps keep going along the clean vertex normals.
+--sensor POWER[:QUANT] (with --direction ray --camera; not with --view-dir or --lf-levels) makes that noise the one of a
+triangulating depth sensor (utils.sensor_model, include/fgc.h: fgc_synth_noise_sensor): a level is the sigma at the
+camera's distance to the mesh's centre and grows with range^POWER; QUANT > 0 quantises the depth in disparity, QUANT mean
+edge lengths per step at that distance - the validation meshes of `train --sensor POWER:QUANT` with the same seed and camera.
 """
 import argparse
 import os
@@ -27,13 +31,16 @@ DEFAULT_LEVELS = (0.1, 0.2, 0.3)
 
 
 def make_noisy(V, faces, level, seed=0, stream=0, step=0, direction="random", device="cuda", lf_level=None, lf_width=3.0,
-               lf_bumps=None):
+               lf_bumps=None, sensor=None, camera=None):
     """The vertices V [V,3] of a clean mesh displaced at `level` x its mean edge length: float32 numpy [V,3].  lf_level
     (None: white noise only): plus the low-frequency field of RMS lf_level mean edge lengths, bumps of width lf_width mean
     edge lengths, lf_bumps of them (None: ceil(faces / 6)) - what FacetDenoiser.set_noise(step, level, lf_level) makes on
     a mesh bound with lf=(lf_width, lf_bumps).  direction: "random", "normal" (the area-weighted vertex normals) or a
     [V,3] array of unit rows, e.g. the viewing rays of utils.view_rays (finite, every norm within 1e-3 of 1): the white
-    noise goes along them.  The low-frequency bumps go along the clean vertex normals whatever the white direction."""
+    noise goes along them.  The low-frequency bumps go along the clean vertex normals whatever the white direction.
+    sensor = (power, quant) with camera = xyz (direction: the table of viewing rays from that camera; not with lf_level):
+    the depth-sensor model utils.sensor_model(V, camera, edge length, power, quant) - what a step makes on a mesh bound
+    with bind_clean(sensor=that model)."""
     import torch
     from . import ops
     from .utils import getAverageEdgeLength, areaWeightedVertexNormals, check_directions
@@ -44,6 +51,19 @@ def make_noisy(V, faces, level, seed=0, stream=0, step=0, direction="random", de
     elif direction not in ("random", "normal"):
         raise ValueError("direction must be 'random', 'normal' or a [V,3] array of unit rows")
     edge_len = getAverageEdgeLength(V, faces)[0]
+    if sensor is not None:
+        from .utils import check_sensor, sensor_model
+        sensor = check_sensor(sensor)
+        if rays is None or camera is None:
+            raise ValueError("sensor: the model works along viewing rays from a camera: direction must be the [V,3] table of "
+                             "rays and camera its position")
+        if lf_level is not None:
+            raise ValueError("sensor does not combine with lf_level: quantisation after bumps along the normals is not built")
+        model = sensor_model(V, camera, edge_len, *sensor)
+        out = ops.synth_noise_sensor(torch.as_tensor(V, device=device), rays, model.camera,
+                                     np.float32(level) * np.float32(edge_len), step, model.power, model.r_ref, model.q,
+                                     seed=seed, stream=stream)
+        return out.cpu().numpy()
     sigma = np.float32(level) * np.float32(edge_len)
     normals = None
     if (rays is None and direction == "normal") or lf_level is not None:
@@ -87,9 +107,27 @@ def main(argv=None):
                     "edge lengths, one or one per --levels entry (pair k = level k with lf level k)")
     ap.add_argument("--lf-width", type=float, default=3.0, help="bump width in mean edge lengths (default %(default)s)")
     ap.add_argument("--lf-bumps", type=int, default=None, help="bumps per mesh (default: faces / 6, rounded up)")
+    ap.add_argument("--sensor", default=None, metavar="POWER[:QUANT]",
+                    help="with --direction ray --camera: depth-sensor noise - sigma grows with (range / reference range)^POWER "
+                    "(0, 1 or 2), depth quantised in steps of QUANT mean edge lengths at the reference range (default 0: off)")
     ap.add_argument("--overwrite", action="store_true")
     args = ap.parse_args(argv)
     view = view_spec(ap, args)
+    sensor = None
+    if args.sensor is not None:
+        from .utils import parse_sensor
+        try:
+            sensor = parse_sensor(args.sensor)
+        except ValueError as e:
+            ap.error("--sensor POWER[:QUANT], e.g. 2:0.5 - %s (got %r)" % (e, args.sensor))
+        if args.view_dir is not None:
+            ap.error("--sensor needs a perspective view: --view-dir has no range, use --camera")
+        if args.direction != "ray":
+            ap.error("--sensor needs --direction ray (got --direction %s)" % args.direction)
+        if args.camera is None:
+            ap.error("--sensor needs --camera X,Y,Z (with --direction ray)")
+        if args.lf_levels is not None:
+            ap.error("--sensor does not combine with --lf-levels: quantisation after bumps along the normals is not built")
     if (args.direction == "ray") != bool(view):
         ap.error("--direction ray needs --view-dir or --camera, and the two go with --direction ray only")
     try:
@@ -124,7 +162,8 @@ def main(argv=None):
                 print("Skipping %s. File already exists." % os.path.basename(out))
                 continue
             write_mesh(make_noisy(V, faces, level, args.seed, 1 + i, k, direction, lf_level=lf_levels[k],
-                                  lf_width=args.lf_width, lf_bumps=args.lf_bumps), faces, out)
+                                  lf_width=args.lf_width, lf_bumps=args.lf_bumps, sensor=sensor,
+                                  camera=view.get("camera")), faces, out)
             written.append(out)
     return written
 

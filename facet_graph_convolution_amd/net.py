@@ -583,7 +583,8 @@ class FacetDenoiser:
     # ------------------------------------------------------------------------------------------
     # training from clean meshes (BUILD EXTENSION): per-step noise synthesis on the GPU
     # ------------------------------------------------------------------------------------------
-    def bind_clean(self, key, x, adjs, gt, verts, faces_rows, edge_len, seed=0, stream=0, direction="random", lf=None):
+    def bind_clean(self, key, x, adjs, gt, verts, faces_rows, edge_len, seed=0, stream=0, direction="random", lf=None,
+                   sensor=None):
         """Build extension: bind a CLEAN mesh whose input rows every step rebuilds from freshly displaced vertices
         (include/fgc.h: fgc_synth_noise, fgc_face_features_rows).  bind_cached(key, x, adjs, gt=gt) plus a synthesis
         state kept with the mesh: the clean vertices verts [V,3], faces_rows int [N0,3] (the faces in node order, -1 rows
@@ -597,15 +598,20 @@ class FacetDenoiser:
         a field of `bumps` Gaussian bumps (None: ceil(real faces / 6), the count of the reference's addLFGaussianNoise
         stub) of width width_rel mean edge lengths along the clean vertex normals (whatever the white direction, a table of
         rays included), switched on per step by
-        set_noise(step, level, lf_level).  Centres are uniform over the vertices, distances Euclidean."""
-        self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf), False,
+        set_noise(step, level, lf_level).  Centres are uniform over the vertices, distances Euclidean.
+        sensor = utils.sensor_model(...) (None: plain noise): the depth-sensor model (include/fgc.h: fgc_synth_noise_sensor) -
+        `direction` must be the table of viewing rays from the model's camera (refused otherwise, and together with lf=); a
+        level of set_noise is then the sigma at the model's reference range, growing with range^power, and a model with q > 0
+        quantises every range: noisy_vertices() returns the quantised vertices.  The model is fixed per bound mesh and part of
+        what two binds of one key are compared by."""
+        self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf, sensor), False,
                          lambda: self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt)))
         return self
 
     def _bind_synth(self, key, synth_args, points, bind):
         """What bind_clean and bind_clean_vertices (points=True) share: the refusals, the mesh cached under `key` (a training
         loop rebinds its meshes every iteration: a lookup, as in bind_cached), otherwise the synthesis state of synth_args =
-        (x, verts, faces_rows, edge_len, seed, stream, direction, lf) on the mesh bind() returns.  Returns (mesh, newly bound)."""
+        (x, verts, faces_rows, edge_len, seed, stream, direction, lf, sensor) on the mesh bind() returns.  Returns (mesh, newly bound)."""
         if self.comm is not None or (self._mesh is not None and self.sharded):
             raise NotImplementedError("noise synthesis runs on an unsharded network")
         if points:
@@ -623,6 +629,8 @@ class FacetDenoiser:
                 raise ValueError("mesh %r is bound with another seed / stream / direction" % (key,))
             if S["lf_key"] != self._lf_key(synth_args[7]):
                 raise ValueError("mesh %r is bound with another lf setting (%r)" % (key, S["lf_key"]))
+            if S["sensor_key"] != self._sensor_key(synth_args[8]):
+                raise ValueError("mesh %r is bound with another sensor model (%r)" % (key, S["sensor_key"]))
             self._mesh = M
             return M, False
         S = self._synth_state(*synth_args)
@@ -641,7 +649,19 @@ class FacetDenoiser:
         width_rel, bumps = lf
         return (float(width_rel), None if bumps is None else int(bumps))
 
-    def _synth_state(self, x, verts, faces_rows, edge_len, seed, stream, direction, lf=None):
+    @staticmethod
+    def _sensor_key(sensor):
+        """sensor = (power, r_ref, q, camera) of bind_clean / bind_clean_vertices (utils.sensor_model) as the value two binds
+        are compared by: the words the kernel reads and the camera in fp32."""
+        if sensor is None:
+            return None
+        try:
+            power, r_ref, q, camera = sensor
+        except (TypeError, ValueError):
+            raise ValueError("sensor: a model (power, r_ref, q, camera), as utils.sensor_model returns it") from None
+        return (tuple(int(w) for w in ops.sensor_words(power, r_ref, q)), tuple(float(t) for t in ops.sensor_camera(camera)))
+
+    def _synth_state(self, x, verts, faces_rows, edge_len, seed, stream, direction, lf=None, sensor=None):
         """The checked arguments of bind_clean / bind_clean_vertices as the synthesis state kept with the mesh."""
         rays = None
         if not isinstance(direction, str):
@@ -649,6 +669,13 @@ class FacetDenoiser:
         elif direction not in ("random", "normal"):
             raise ValueError("direction must be 'random', 'normal' or a [V,3] array of unit rows")
         lf_key = self._lf_key(lf)
+        sensor_key = self._sensor_key(sensor)
+        if sensor_key is not None:
+            if rays is None:
+                raise ValueError("sensor: the model works along viewing rays: direction must be the [V,3] table of rays "
+                                 "from its camera")
+            if lf_key is not None:
+                raise ValueError("sensor: quantisation after bumps along the normals (lf=) is not built; choose one")
         if lf_key is not None:
             if not 0 <= int(stream) < 1 << 31:
                 raise ValueError("lf: stream must lie below 2^31 (the top bit marks the bump counters)")
@@ -665,7 +692,8 @@ class FacetDenoiser:
         dev = self.device
         S = dict(v=torch.as_tensor(vx, device=dev), faces=torch.as_tensor(fr, device=dev), vn=None,
                  edge_len=float(edge_len), seed=int(seed), stream=int(stream),
-                 direction=direction_key(direction if rays is None else rays), direction_src=direction, lf_key=lf_key, lf=None)
+                 direction=direction_key(direction if rays is None else rays), direction_src=direction, lf_key=lf_key, lf=None,
+                 sensor_key=sensor_key, sensor=None)
         real = fr[fr[:, 0] >= 0]
         if (rays is None and direction == "normal") or lf_key is not None:
             from .utils import areaWeightedVertexNormals
@@ -681,6 +709,10 @@ class FacetDenoiser:
             # (the bumps always go along the clean vertex normals, whatever the white direction)
             S["lf"] = dict(vn=vn, K=K, width=width, area=area, ctl=torch.zeros(4, dtype=torch.int32, device=dev))
             need = self.L.fgc_synth_lf_scratch_floats(vx.shape[0], K)      # (its head: the same bounding boxes)
+        if sensor_key is not None:
+            words, cam = sensor_key
+            S["sensor"] = dict(ctl=torch.as_tensor(np.array(words, dtype=np.uint32).view(np.int32), device=dev),
+                               camera=(C.c_float * 3)(*cam))
         S["scratch"] = torch.zeros(max(need, 1), dtype=torch.float32, device=dev)
         return S
 
@@ -692,7 +724,8 @@ class FacetDenoiser:
     def _enqueue_synth(self):
         """Two launches: noise (+ per-workgroup bounding boxes), then the input rows (each workgroup reduces the boxes).
         Both read the step's noise words from device memory and return at once while they are zero.  A mesh bound with
-        lf=: three launches, the bump table and field + displacement of fgc_synth_noise_lf in the place of the first."""
+        lf=: three launches, the bump table and field + displacement of fgc_synth_noise_lf in the place of the first; with
+        sensor=: fgc_synth_noise_sensor in the place of the first."""
         M, L, st = self._mesh, self.L, self._st()
         B, S = M["B"], M["synth"]
         self._tag("fwd:synth")
@@ -702,6 +735,11 @@ class FacetDenoiser:
             _lib.check(L.fgc_synth_noise_lf(_p(S["v"]), _p(lf["vn"]), _p(S["vn"]), nv, _p(B["noise"]), _p(lf["ctl"]), lf["K"],
                                             S["seed"] & 0xFFFFFFFFFFFFFFFF, S["stream"] & 0xFFFFFFFF, _p(S["v_out"]),
                                             _p(sc), sc.numel(), st), "synth lf noise")
+        elif S["sensor"] is not None:
+            sn = S["sensor"]
+            _lib.check(L.fgc_synth_noise_sensor(_p(S["v"]), _p(S["vn"]), nv, _p(B["noise"]), _p(sn["ctl"]), sn["camera"],
+                                                S["seed"] & 0xFFFFFFFFFFFFFFFF, S["stream"] & 0xFFFFFFFF, _p(S["v_out"]),
+                                                _p(sc), sc.numel(), st), "synth sensor noise")
         else:
             _lib.check(L.fgc_synth_noise(_p(S["v"]), _p(S["vn"]), nv, _p(B["noise"]), S["seed"] & 0xFFFFFFFFFFFFFFFF,
                                          S["stream"] & 0xFFFFFFFF, _p(S["v_out"]), _p(sc), sc.numel(), st), "synth noise")
@@ -713,12 +751,12 @@ class FacetDenoiser:
         return self._require_synth()["v_out"]
 
     def bind_clean_vertices(self, key, x, adjs, verts, faces_rows, v_faces, edge_len, gt_normals=None, iters=VERTEX_ITERS,
-                            seed=0, stream=0, direction="random", lf=None, ray_update=False):
+                            seed=0, stream=0, direction="random", lf=None, ray_update=False, sensor=None):
         """Build extension: bind a CLEAN mesh for the point-set and double-loss steps on noise synthesised per step -
         bind_vertices plus bind_clean's synthesis state, kept with the mesh under `key`.  verts [V,3]: the RAW clean
         vertices (TrainingSet.addCleanMeshWithVertices' clean_vertices), which are also the ground-truth vertices;
         faces_rows int [N0,3]: the faces in node order (-1 rows = fake nodes), v_faces [V,K], edge_len, seed, stream,
-        direction, lf as in bind_clean; gt_normals: the clean face normals [N0,3] in node order, for the double loss.
+        direction, lf, sensor as in bind_clean; gt_normals: the clean face normals [N0,3] in node order, for the double loss.
         Every step then runs three launches in front (four with lf=: the two of fgc_synth_noise_lf in the place of the
         first): fgc_synth_noise, fgc_face_features_rows (the input rows) and fgc_point_sets_prepare, which normalises the displaced and the clean vertices by the diagonal of their union box
         and rotates both, straight into the buffers the vertex update and fgc_point_loss read - in the place of the two
@@ -739,7 +777,7 @@ class FacetDenoiser:
             self.bind_vertices(key, x, adjs, vn, faces_rows, v_faces, vn, iters=iters,
                                depth_dir=direction if ray_update else None)
             return self._mesh
-        M, fresh = self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf), True, bind)
+        M, fresh = self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf, sensor), True, bind)
         if bool(ray_update) != (M["verts"]["dirs"] is not None):      # (the direction itself: compared by _bind_synth)
             raise ValueError("mesh %r is bound %s ray_update" % (key, "without" if ray_update else "with"))
         if fresh:

@@ -934,6 +934,64 @@ def synth_noise(verts, sigma, step, seed=0, stream=0, normals=None, out=None, sc
     return out
 
 
+def sensor_words(power, r_ref, q):
+    """The four control words of the depth-sensor model (include/fgc.h: fgc_synth_noise_sensor) as uint32 numpy:
+    FGC_SYNTH_ON | power, float bits of r_ref, float bits of q, 0.  power None: four zeros, the model off (plain noise along
+    the rays).  Refused here, as the kernel switches them off: a power outside 0, 1, 2, an r_ref that is not a positive
+    normal finite float, a q that is neither 0 nor a positive normal finite float."""
+    if power is None:
+        return np.zeros(4, dtype=np.uint32)
+    if isinstance(power, (bool, np.bool_)) or int(power) != power or int(power) not in (0, 1, 2):
+        raise ValueError("sensor: power must be 0, 1 or 2 (got %r)" % (power,))
+    tiny = np.finfo(np.float32).tiny
+    with np.errstate(over="ignore"):
+        r_ref, q = np.float32(r_ref), np.float32(q)
+    if not (np.isfinite(r_ref) and r_ref >= tiny):
+        raise ValueError("sensor: the reference range must be finite and > 0 (got %r)" % (r_ref,))
+    if not (np.isfinite(q) and (q == 0 or q >= tiny)):
+        raise ValueError("sensor: the disparity step q must be finite and >= 0 (got %r)" % (q,))
+    bits = np.array([r_ref, abs(q)], dtype=np.float32).view(np.uint32)
+    return np.array([int(power) | _lib.SYNTH_ON, int(bits[0]), int(bits[1]), 0], dtype=np.uint32)
+
+
+def sensor_camera(camera):
+    c = np.asarray(camera, dtype=np.float64).reshape(-1)
+    if c.shape != (3,) or not np.isfinite(c).all() or not np.isfinite(c.astype(np.float32)).all():
+        raise ValueError("camera must be three finite numbers (got %r)" % (camera,))
+    return np.ascontiguousarray(c.astype(np.float32))
+
+
+def synth_noise_sensor(verts, rays, camera, sigma, step, power, r_ref, q, seed=0, stream=0, out=None, scratch=None, ctl=None,
+                       sensor_ctl=None):
+    """Build extension (include/fgc.h: fgc_synth_noise_sensor): synth_noise(verts, sigma, step, seed, stream, normals=rays)
+    under the depth-sensor model - sigma is the standard deviation at range r_ref from `camera` and grows with
+    (range / r_ref)^power, power 0, 1 or 2; q > 0 puts every range on the lattice 1 / (k q).  rays [V,3]: the unit viewing
+    rays (required).  ctl / sensor_ctl: the control words already on the device (int32 [3] / [4]) instead of (step, sigma) /
+    (power, r_ref, q); scratch as for synth_noise.  Returns the displaced vertices [V,3] (`out`)."""
+    if rays is None:
+        raise ValueError("the sensor model needs the table of viewing rays: rays is required")
+    _req_cuda(verts, rays, out, scratch, ctl, sensor_ctl)
+    verts = _f32c(verts.reshape(-1, 3))
+    nv = verts.shape[0]
+    rays = _f32c(rays.reshape(-1, 3))
+    if rays.shape[0] != nv:
+        raise ValueError("one ray per vertex")
+    cam = sensor_camera(camera)
+    if ctl is None:
+        ctl = torch.from_numpy(noise_words(step, sigma).view(np.int32)).to(verts.device)
+    if sensor_ctl is None:
+        sensor_ctl = torch.from_numpy(sensor_words(power, r_ref, q).view(np.int32)).to(verts.device)
+    if out is None:
+        out = torch.empty_like(verts)
+    need = _lib.lib().fgc_synth_scratch_floats(nv)
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=verts.device)
+    check(_lib.lib().fgc_synth_noise_sensor(ptr(verts), ptr(rays), nv, ptr(ctl), ptr(sensor_ctl), cam.ctypes.data,
+                                            int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, ptr(out), ptr(scratch),
+                                            scratch.numel(), stream_ptr()), "fgc_synth_noise_sensor")
+    return out
+
+
 def lf_words(amplitude, width):
     """The four control words of the low-frequency noise (include/fgc.h: fgc_synth_noise_lf) as uint32 numpy:
     FGC_SYNTH_ON | float bits of the amplitude, float bits of the width, 0, 0 - both ABSOLUTE, in mesh units.  amplitude

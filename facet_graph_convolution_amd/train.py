@@ -13,7 +13,7 @@ Training command (the reference's ``train(withVerts)``, train.py:1894-1921):
     python -m facet_graph_convolution_amd.train DUMP_DIR NETWORK_DIR [--num-iterations N] [--net-name NAME]
         [--with-vertices] [--double-loss] [--capture] [--seed S]
         [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal|ray] [--view-dir X,Y,Z | --camera X,Y,Z] [--ray-update]
-        [--lf-noise 0.3,0.2,0.1[:WIDTH[:BUMPS]]]
+        [--lf-noise 0.3,0.2,0.1[:WIDTH[:BUMPS]]] [--sensor POWER[:QUANT]]
 
 loads the pickles `preprocess` wrote and runs trainNet, trainAccuracyNet (--with-vertices) or trainDoubleLossNet
 (--with-vertices --double-loss).  --synth-noise (build extension) loads the CLEAN pickles of `preprocess --clean`
@@ -203,6 +203,36 @@ def _lf_inputs(levels, lf_levels, lf_width, lf_bumps):
     return lf, (float(lf_width), None if lf_bumps is None else int(lf_bumps))
 
 
+def _sensor_inputs(levels, sensor, noise_direction, lf):
+    """The checked depth-sensor setting of a trainer: None, or (power, quant) - resolved per mesh by _mesh_sensor."""
+    if sensor is None:
+        return None
+    from .utils import check_sensor
+    sensor = check_sensor(sensor)
+    if levels is None:
+        raise ValueError("sensor needs noise_levels (noise_levels=(0,) for the quantisation alone)")
+    if not (isinstance(noise_direction, dict) and "camera" in noise_direction):
+        raise ValueError("sensor needs a noise_direction of viewing rays from a camera, {'camera': xyz}: a view_dir view has "
+                         "no range, and 'random' / 'normal' noise no sensor")
+    if lf is not None:
+        raise ValueError("sensor does not combine with lf_levels: quantisation after bumps along the normals is not built")
+    return sensor
+
+
+def _mesh_sensor(sensor, direction, m):
+    """sensor = (power, quant) of a trainer as the model of mesh record m seen from the view's camera (utils.sensor_model):
+    the reference range is the camera's distance to the centre of the mesh's bounding box, so per mesh."""
+    from .utils import sensor_model
+    key = (id(m.verts), tuple(direction["camera"]), sensor)
+    hit = _SENSORS.get(key)
+    if hit is None or hit[0] is not m.verts:
+        hit = _SENSORS[key] = (m.verts, sensor_model(m.verts, direction["camera"], m.args[-1], *sensor))
+    return hit[1]
+
+
+_SENSORS = {}
+
+
 def _mesh_direction(direction, m):
     """The noise direction of mesh record m: a mode name or a [V,3] array as given, a view ({'camera': xyz} / {'view_dir':
     xyz}) as the viewing rays of the mesh's CLEAN vertices - one row per vertex, what makeNoisy --direction ray makes."""
@@ -224,7 +254,7 @@ _RAYS = {}
 
 def _bind(F, key, m, noise=None):
     """Bind mesh record m under `key` through F = net.trainer_form(form): plain, or - noise = (seed, stream, direction
-    [, lf = (width, bumps)[, ray_update]]) - clean for noise synthesis.  (A cached mesh returns at once; the bind methods
+    [, lf = (width, bumps)[, ray_update[, sensor = (power, quant)]]]) - clean for noise synthesis.  (A cached mesh returns at once; the bind methods
     reshape the [1, ...] arrays.)"""
     kw = {"gt_normals": m.gt_normals} if F.gt_normals else {}
     if noise is not None:
@@ -233,6 +263,8 @@ def _bind(F, key, m, noise=None):
             kw.update(lf=noise[3])
         if len(noise) > 4 and noise[4]:
             kw.update(ray_update=True)      # (the vertex trainers only: bind_clean_vertices)
+        if len(noise) > 5 and noise[5] is not None:
+            kw.update(sensor=_mesh_sensor(noise[5], noise[2], m))
     (F.bind if noise is None else F.bind_clean)(key, *m.args, **kw)
 
 
@@ -252,15 +284,17 @@ def _draw_step(rs, F, m, levels, counter, lf_levels=None):
     return samples, R, (counter, levels[k]) if lf_levels is None else (counter, levels[k], lf_levels[k])
 
 
-def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="random", lf=None, ray_update=False):
+def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="random", lf=None, ray_update=False,
+                     sensor=None):
     """The mean {total, points, normals} (entries a form does not have stay 0) of the loss alone over the validation mesh
     records, with rotation R and fresh rows from rs: one pass per mesh, or - levels given - per clean mesh and noise level
     with stream = 1 + mesh index and step = level index: the SAME noisy meshes at every call (and what makeNoisy writes for
     the same seed), so the validation curve is comparable along a run.  lf = (lf levels, (width, bumps)) of _lf_inputs:
-    level k goes with lf level k.  ray_update: the vertex update along the noise's rays, as in training."""
+    level k goes with lf level k.  ray_update: the vertex update along the noise's rays, as in training.  sensor = (power,
+    quant): the depth-sensor model, resolved per mesh as in training."""
     F, vsum = net.trainer_form(form), np.zeros(3)
     for vbm, m in enumerate(valid):
-        _bind(F, ("valid", vbm), m, None if levels is None else (seed, 1 + vbm, direction, lf and lf[1], ray_update))
+        _bind(F, ("valid", vbm), m, None if levels is None else (seed, 1 + vbm, direction, lf and lf[1], ray_update, sensor))
         for k, level in enumerate((None,) if levels is None else levels):
             F.set_samples(*_draw_samples(rs, F, m))
             net.set_rotation(R)
@@ -270,18 +304,18 @@ def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="ra
     return vsum / (len(valid) * (1 if levels is None else len(levels)))
 
 
-def synthValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", lf=None):
+def synthValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", lf=None, sensor=None):
     """Build extension: the mean loss over every clean validation mesh (records of _clean_meshes) at every noise level
     (_validation_loss).  R: the rotation; rs: the RandomState the loss rows are drawn from."""
-    return float(_validation_loss(net, "angular", valid, R, rs, noise_levels, seed, direction, lf)[0])
+    return float(_validation_loss(net, "angular", valid, R, rs, noise_levels, seed, direction, lf, sensor=sensor)[0])
 
 
 def synthVertexValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", double=False, lf=None,
-                              ray_update=False):
+                              ray_update=False, sensor=None):
     """Build extension: {total, points, normals} (double) or {points, 0, 0} - the mean loss over every clean validation mesh
     (records of _clean_vertex_meshes) at every noise level (_validation_loss).  R: rotation; rs draws the 500 + 500 rows."""
     return _validation_loss(net, "double" if double else "points", valid, R, rs, noise_levels, seed, direction, lf,
-                            ray_update)
+                            ray_update, sensor)
 
 
 def _resume(net, network_path, net_name):
@@ -299,7 +333,7 @@ def _resume(net, network_path, net_name):
 
 def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
              capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None, lf_width=3.0,
-             lf_bumps=None):
+             lf_bumps=None, sensor=None):
     """train.py:380-632.  trainSet / validSet: dataClasses.TrainingSet.  Returns (net, lossArray [iters/50, 2]).
 
     noise_levels (build extension; None = the reference's loop, untouched): trainSet / validSet hold CLEAN meshes
@@ -313,11 +347,17 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
     lf_levels (build extension; needs noise_levels, length 1 or that of noise_levels): low-frequency noise on top
     (FacetDenoiser.bind_clean(lf=(lf_width, lf_bumps)), set_noise(step, level, lf_level)): level index k pairs
     noise_levels[k] with lf_levels[k] - RMS displacements in mean edge lengths of bumps lf_width mean edge lengths wide,
-    lf_bumps per mesh (None: faces / 6).  The one draw that picks the level picks the pair."""
+    lf_bumps per mesh (None: faces / 6).  The one draw that picks the level picks the pair.
+
+    sensor = (power, quant) (build extension; needs noise_levels and noise_direction={'camera': xyz}; refused with a
+    view_dir view, any other direction and lf_levels): the depth-sensor model (utils.sensor_model, FacetDenoiser.bind_clean(
+    sensor=)), resolved per mesh - a level is the sigma at the camera's distance to the mesh's centre and grows with
+    range^power; quant > 0 is the depth step there in mean edge lengths.  Validation scores its fixed meshes with the same model."""
     form = "angular"
     levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
     lf = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
-    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1])
+    sensor = _sensor_inputs(levels, sensor, noise_direction, lf)
+    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1], False, sensor)
     net = FacetDenoiser(device, seed=seed)
     F = net.trainer_form(form)
     ckpt = os.path.join(network_path, net_name) if network_path else None
@@ -338,7 +378,7 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
             # train.py:588-617: every 100 iterations the loss alone on every validation mesh, with this iteration's
             # rotation and fresh random rows, BEFORE the training step; the previous row of the CSV gets the mean of
             # this and the last value
-            valid_loss = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf)[0]
+            valid_loss = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf, sensor=sensor)[0]
             log("Iteration %d, validation loss %g" % (it, valid_loss))
             row = min(it // evalStepNum, len(lossArray) - 1)
             lossArray[row, 1] = valid_loss
@@ -366,7 +406,7 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
 
 def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
                      capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None,
-                     lf_width=3.0, lf_bumps=None, ray_update=False):
+                     lf_width=3.0, lf_bumps=None, ray_update=False, sensor=None):
     """train.py:636-916: the multi-scale network trained through update_position_MS on the point-set loss fullLoss.
     trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT.  One iteration = a random mesh
     (meshes without ground-truth vertices are skipped), SAMP_NUM = 500 random rows of the vertices and of the
@@ -393,15 +433,16 @@ def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net"
     vertex update of every training and validation step is the ray-constrained one along those rays
     (update_position_MS(depth_dir=), FacetDenoiser.bind_clean_vertices(ray_update=True)): the network learns what
     `infer --with-vertices --camera / --view-dir` will ask of it.  False: the free update, as before.
+    sensor = (power, quant): the depth-sensor model, as in trainNet; ray_update composes with it unchanged.
 
     Returns (net, lossArray of the last block, per-iteration training losses [num_iterations])."""
     return _train_with_vertices("points", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
-                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update)
+                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update, sensor)
 
 
 def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
                        capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None,
-                       lf_width=3.0, lf_bumps=None, ray_update=False):
+                       lf_width=3.0, lf_bumps=None, ray_update=False, sensor=None):
     """train.py:919-1268: the multi-scale network trained on the point-set loss fullLoss PLUS the dense face-normal loss
     faceNormalsLoss of head 0 against the rotated ground-truth face normals (customLoss = pointsLoss + normalsLoss,
     unweighted, train.py:1100-1102).  trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT
@@ -416,25 +457,26 @@ def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="ne
     1, the previous row's validation entry set to the mean of its two neighbours), and the block is appended to
     `<net_name>.csv` at every save.
 
-    noise_levels / noise_direction / lf_levels / lf_width / lf_bumps / ray_update (build extension): as in
+    noise_levels / noise_direction / lf_levels / lf_width / lf_bumps / ray_update / sensor (build extension): as in
     trainAccuracyNet; the ground-truth normals are the clean ones.
 
     Returns (net, lossArray of the last block, per-iteration {total, points, normals} [num_iterations, 3])."""
     return _train_with_vertices("double", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
-                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update)
+                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update, sensor)
 
 
 def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
                          noise_levels=None, noise_direction="random", lf_levels=None, lf_width=3.0, lf_bumps=None,
-                         ray_update=False):
+                         ray_update=False, sensor=None):
     """The loop of trainAccuracyNet (form "points") and trainDoubleLossNet ("double")."""
     levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
     lf = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
+    sensor = _sensor_inputs(levels, sensor, noise_direction, lf)
     ray_update = bool(ray_update)
     if ray_update and (levels is None or isinstance(noise_direction, str)):
         raise ValueError("ray_update moves the vertices along the noise's rays: it needs noise_levels and a noise_direction "
                          "of rays (a view {'camera': xyz} / {'view_dir': xyz} or a [V,3] table)")
-    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1], ray_update)
+    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1], ray_update, sensor)
     net = FacetDenoiser(device, multi_scale=True, seed=seed)
     F = net.trainer_form(form)
     ckpt = os.path.join(network_path, net_name) if network_path else None
@@ -459,7 +501,7 @@ def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name,
         samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it, lf and lf[0])
         row = (it % block) // evalStepNum
         if valid and it % validStepNum == 0 and it >= first_valid:
-            vsum = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf, ray_update)
+            vsum = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf, ray_update, sensor)
             log(_VALID_LOG[F.outputs] % ((it,) + tuple(vsum[:F.outputs])))      # (the double loss with its points / normals split)
             lossArray[row, 1] = vsum[0]
             if row > 0:
@@ -821,8 +863,28 @@ def main(argv=None):
                     "edge lengths, one or one per --synth-noise level (level k pairs with lf level k); WIDTH = bump width "
                     "in mean edge lengths (default 3); BUMPS per mesh (default faces / 6).  E.g. --synth-noise 0,0.1,0.2 "
                     "--lf-noise 0.3,0.2,0.1:3")
+    ap.add_argument("--sensor", default=None, metavar="POWER[:QUANT]",
+                    help="with --synth-noise --noise-direction ray --camera: the noise of a triangulating depth sensor - sigma "
+                    "grows with (range / reference range)^POWER, POWER 0, 1 or 2; QUANT (default 0: off) is the depth step at "
+                    "the reference range in mean edge lengths, depth quantised in disparity.  The reference range is the "
+                    "camera's distance to each mesh's centre.  E.g. --sensor 2:0.5 (nobody has tuned these values)")
     args = ap.parse_args(argv)
     view = view_spec(ap, args)
+    sensor = None
+    if args.sensor is not None:
+        from .utils import parse_sensor
+        try:
+            sensor = parse_sensor(args.sensor)
+        except ValueError as e:
+            ap.error("--sensor POWER[:QUANT], e.g. 2:0.5 - %s (got %r)" % (e, args.sensor))
+        if args.view_dir is not None:
+            ap.error("--sensor needs a perspective view: --view-dir has no range, use --camera")
+        if args.noise_direction != "ray":
+            ap.error("--sensor needs --noise-direction ray (got --noise-direction %s)" % args.noise_direction)
+        if args.camera is None:
+            ap.error("--sensor needs --camera X,Y,Z (with --noise-direction ray)")
+        if args.lf_noise is not None:
+            ap.error("--sensor does not combine with --lf-noise: quantisation after bumps along the normals is not built")
     if (args.noise_direction == "ray") != bool(view):
         ap.error("--noise-direction ray needs --view-dir or --camera, and the two go with --noise-direction ray only")
     if view and args.synth_noise is None:
@@ -872,6 +934,8 @@ def main(argv=None):
     extra = dict(noise_levels=levels, noise_direction=view or args.noise_direction, **lf_extra) if levels is not None else {}
     if args.ray_update:
         extra["ray_update"] = True
+    if sensor is not None:
+        extra["sensor"] = sensor
     trainer(train_set, args.num_iterations, network_path=args.network_dir, net_name=args.net_name, seed=args.seed,
             capture=args.capture, validSet=valid_set, **extra)
     return trainer.__name__

@@ -1,4 +1,5 @@
 """Host-side helpers that keep the names of the reference's ``utils.py`` where a counterpart exists."""
+import collections
 import math
 
 import numpy as np
@@ -332,6 +333,70 @@ def view_rays(V, camera=None, view_dir=None):
     if not (n > 0).all():
         raise ValueError("vertex %d lies at the camera: it has no viewing ray" % int(np.argmin(n)))
     return (r / n).astype(np.float32)
+
+
+SensorModel = collections.namedtuple("SensorModel", "power r_ref q camera")
+
+
+def sensor_model(V, camera, edge_len, power=2, quant=0.0, ref_range=None):
+    """The depth-sensor noise model (build extension; include/fgc.h: fgc_synth_noise_sensor) of one clean mesh as
+    SensorModel(power, r_ref, q, camera) - what FacetDenoiser.bind_clean(sensor=), makeNoisy and the trainers hand to
+    ops.synth_noise_sensor, so that training, validation and the files cannot disagree.
+    camera: the sensor's position in the mesh's raw units (a perspective view: an orthographic one has no range).
+    power 0, 1, 2: sigma grows with (range / r_ref)^power; a noise level keeps its meaning, multiples of the mean edge length
+    edge_len, now AT THE REFERENCE RANGE.  quant = S >= 0: the depth step at the reference range in mean edge lengths; the step
+    at range r is r^2 q, so q = S edge_len / r_ref^2 (0: no quantisation).  ref_range (None: the distance from the camera to
+    the centre of V's bounding box; the centre in float64 from the fp32 extents, the distance rounded to fp32 once)."""
+    power, quant = check_sensor((power, quant))
+    if camera is None:
+        raise ValueError("sensor: the model needs a camera (a view_dir view has no range)")
+    c = np.asarray(camera, dtype=np.float64).reshape(-1)
+    if c.shape != (3,) or not np.isfinite(c).all():
+        raise ValueError("sensor: camera must be three finite numbers (got %r)" % (camera,))
+    if not (np.isfinite(edge_len) and edge_len > 0):
+        raise ValueError("sensor: edge_len must be a positive length")
+    if ref_range is None:
+        v = np.asarray(V, dtype=np.float32).reshape(-1, 3)
+        centre = (v.min(0).astype(np.float64) + v.max(0).astype(np.float64)) / 2.0
+        ref_range = np.sqrt(((centre - c) ** 2).sum())
+    r_ref = np.float32(ref_range)
+    if not (np.isfinite(r_ref) and r_ref >= np.finfo(np.float32).tiny):
+        raise ValueError("sensor: the reference range must be finite and > 0 (got %r; is the camera at the centre of the "
+                         "mesh's bounding box?)" % (float(ref_range),))
+    q = np.float32(float(quant) * float(edge_len) / float(r_ref) ** 2)
+    if not np.isfinite(q) or (quant > 0 and q < np.finfo(np.float32).tiny):
+        raise ValueError("sensor: quant %r gives a disparity step outside fp32 at reference range %g" % (quant, float(r_ref)))
+    return SensorModel(int(power), float(r_ref), float(q), tuple(float(np.float32(t)) for t in c))
+
+
+def parse_sensor(text):
+    """'POWER[:QUANT]' of --sensor as (power, quant); ValueError otherwise."""
+    parts = text.split(":")
+    if len(parts) not in (1, 2) or not all(parts):
+        raise ValueError("POWER[:QUANT]")
+    try:
+        power = int(parts[0])
+    except ValueError:
+        raise ValueError("POWER is 0, 1 or 2") from None
+    quant = float(parts[1]) if len(parts) == 2 else 0.0
+    if power not in (0, 1, 2):
+        raise ValueError("POWER is 0, 1 or 2")
+    if not (np.isfinite(quant) and quant >= 0):
+        raise ValueError("QUANT must be >= 0")
+    return power, quant
+
+
+def check_sensor(sensor):
+    """sensor=(power, quant) of the trainers and make_noisy as a checked (int, float) pair; ValueError names `sensor`."""
+    try:
+        power, quant = sensor
+    except (TypeError, ValueError):
+        raise ValueError("sensor: a pair (power, quant) (got %r)" % (sensor,)) from None
+    if isinstance(power, (bool, np.bool_)) or not isinstance(power, (int, np.integer)) or int(power) not in (0, 1, 2):
+        raise ValueError("sensor: power must be 0, 1 or 2 (got %r)" % (power,))
+    if not (np.isfinite(quant) and quant >= 0):
+        raise ValueError("sensor: quant must be finite and >= 0 (got %r)" % (quant,))
+    return int(power), float(quant)
 
 
 def parse_xyz(text):

@@ -71,7 +71,8 @@ extern "C" {
  * (+ _scratch_floats, _bwd_workspace_floats), the multi-scale vertex update along a per-vertex direction and its adjoint,
  * depth scans for the vertex networks; fgc_ray_cast (+ _workspace_bytes), rays against a triangle list: virtual depth
  * scans of a clean mesh; fgc_ray_tree_bytes / fgc_ray_tree_build / fgc_ray_cast_tree, the same cast through a bounding-box
- * tree: scans of large meshes. */
+ * tree: scans of large meshes; fgc_synth_noise_sensor, the noise of a triangulating depth sensor along the viewing rays:
+ * sigma grows with the range, depth is quantised in disparity. */
 #define FGC_ABI_VERSION 116
 
 const char* fgc_last_error(void);
@@ -989,6 +990,46 @@ size_t fgc_synth_lf_scratch_floats(int32_t nv, int32_t n_bumps);
 int fgc_synth_noise_lf(const float* v, const float* vnormals, const float* white_normals, int32_t nv, const uint32_t* ctl,
                        const uint32_t* lf_ctl, int32_t n_bumps, uint64_t seed, uint32_t stream_id, float* v_out,
                        float* scratch, size_t scratch_floats, void* stream);
+
+/* Depth-sensor noise (BUILD EXTENSION): fgc_synth_noise along a table of viewing rays, with the two properties of a
+ * triangulating sensor (structured light, stereo) - the error grows with the range, and the depth is quantised in
+ * disparity: the sensor reports r = 1 / (k q) for an integer k, so the depth step grows with r^2.  A perspective view only:
+ * a camera c and one unit ray per vertex, dirs [nv,3], taken as given (utils.view_rays makes normalize(v - c)).
+ * For clean vertex i, d_i = dirs[i], everything in fp32, one rounding per operation (no contraction):
+ *   w     = v_i - c
+ *   r_i   = sqrtf(fma(w_z, w_z, fma(w_y, w_y, w_x w_x)))
+ *   rho_i = r_i / r_ref                                    (IEEE division)
+ *   s_i   = sigma (power 0);  sigma * rho_i (power 1);  (sigma * rho_i) * rho_i (power 2)
+ *   len_i = s_i * z3_i        z3: the Gaussian fgc_synth_noise draws - the same Philox counter (i, step, stream_id), key
+ *                             and pair of words, so the same number
+ *   q = 0 (no quantisation):  v'_i = v_i + d_i * len_i, fgc_synth_noise's expression with s_i in the place of sigma: with
+ *     power 0 the output is BIT FOR BIT what fgc_synth_noise(v, dirs, ...) writes; sigma = 0 gives v' = v bit for bit.
+ *   q > 0:  rt = r_i + len_i; a sample with rt <= 0 (the noise carried it through the sensor) takes rt = r_i;
+ *           k = rintf(1 / (rt * q))  (two IEEE operations, ties to even), clamped to [1, 2^24];
+ *           r_q = 1 / (k * q);  len'_i = r_q - r_i;  v'_i = v_i + d_i * len'_i.
+ *     sigma = 0 with q > 0 quantises the clean range (terraces alone).
+ *   power is an integer (there is no powf); sigma is the standard deviation AT THE REFERENCE RANGE r_ref; q is in 1 / length:
+ *   the depth step at range r is r^2 q.  utils.sensor_model derives r_ref and q from a mesh, a camera and a step in mean
+ *   edge lengths.
+ * ctl: fgc_synth_noise's {step low, step high, sigma word}; ctl[2] = 0: off, nothing read or written.
+ * sensor_ctl (DEVICE, 4 x uint32, read by the kernel like ctl - a replayed hipGraph can change level, power and step without
+ *   a new capture): {FGC_SYNTH_ON | power, float bits of r_ref, float bits of q, 0}.  THIS BUILD'S CHOICE for words out of
+ *   range - sensor_ctl[0] without the on flag (0 included), power > 2, r_ref not a positive normal finite float, q neither
+ *   zero nor a positive normal finite float: the model is OFF and the launch writes the bits of
+ *   fgc_synth_noise(v, dirs, ...), plain noise along the rays; such words never give a non-finite vertex.  (The host cannot
+ *   refuse words it does not see; ops.sensor_words refuses the same values before they reach the device.)
+ * camera: a HOST pointer to three finite floats, read during the call and passed to the kernel BY VALUE: it is fixed per
+ *   bound mesh, and a captured launch keeps the values it was recorded with.
+ * scratch (device floats) >= fgc_synth_scratch_floats(nv): the per-workgroup bounding boxes of v_out, exactly as
+ *   fgc_synth_noise leaves them: fgc_face_features_rows(have_bbox = 1) and fgc_point_sets_prepare(have_bbox = 1) follow it
+ *   unchanged.
+ * One launch of fgc_synth_noise's shape (256 threads, one vertex per thread, grid-stride above 1024 workgroups), accurate
+ *   division and sqrtf, no atomics: the same bits eager and replayed.  Enqueue-only, nothing allocated.  A NULL among v,
+ *   dirs, ctl, sensor_ctl, camera, v_out, scratch, nv <= 0, v_out == v, a non-finite camera or a scratch below
+ *   fgc_synth_scratch_floats(nv): FGC_EINVAL, nothing launched. */
+int fgc_synth_noise_sensor(const float* v, const float* dirs, int32_t nv, const uint32_t* ctl, const uint32_t* sensor_ctl,
+                           const float* camera, uint64_t seed, uint32_t stream_id, float* v_out, float* scratch,
+                           size_t scratch_floats, void* stream);
 
 /* The two point sets of the point-set loss (fgc_point_loss) from displaced vertices: what the host does with
  * normalizePointSets (utils.py:2077-2104) and two fgc_rotate_rows, in ONE launch per step.

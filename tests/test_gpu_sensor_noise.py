@@ -1,0 +1,490 @@
+"""The depth-sensor noise model on the GPU (include/fgc.h: fgc_synth_noise_sensor; FacetDenoiser.bind_clean(sensor=...),
+bind_clean_vertices(sensor=...), the trainers and the two command lines) against the float64 oracle of its definition
+(tests/sensor_noise_cases.py), against fgc_synth_noise on the same table of rays, against the host feature routines, and
+against a second network fed host-made inputs."""
+import functools
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import sensor_noise_cases as sn  # noqa: E402
+import synth_cases as sc  # noqa: E402
+
+from facet_graph_convolution_amd import ops, utils
+from facet_graph_convolution_amd.dataClasses import TrainingSet
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+SEED = sn.SEED
+CLOUD_EDGE = 0.02          # the "mean edge length" of the point cloud: levels and quant are multiples of it
+
+
+def _bits(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float32)).view(np.uint32)
+
+
+def _dev(a):
+    return torch.as_tensor(np.ascontiguousarray(a), device=DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _input(tag):
+    """(V [n,3] float32, edge length, rays [n,3] float32) of a test input; "cloud": 262 144 + 300 random points in the unit
+    ball - 1 025 blocks' worth of vertices and a partial one, so the launch is capped at 1 024 workgroups and strides."""
+    if tag == "cloud":
+        rs = np.random.RandomState(11)
+        p = rs.normal(size=(262144 + 300, 3))
+        p *= (rs.uniform(size=(p.shape[0], 1)) ** (1.0 / 3.0)) / np.linalg.norm(p, axis=1, keepdims=True)
+        V, edge = p.astype(np.float32), CLOUD_EDGE
+    else:
+        V, F = sn.mesh(tag)
+        V, edge = np.ascontiguousarray(V, dtype=np.float32), float(utils.getAverageEdgeLength(V, F)[0])
+    return V, edge, utils.view_rays(V, camera=sn.CAMERA)
+
+
+def _model(tag, power, quant):
+    V, edge, _ = _input(tag)
+    return utils.sensor_model(V, sn.CAMERA, edge, power, quant)
+
+
+def _sigma(tag, level):
+    return np.float32(level) * np.float32(_input(tag)[1])
+
+
+def _sensor(tag, level, step, power, quant, stream=0, seed=SEED, **kw):
+    V, _, rays = _input(tag)
+    m = _model(tag, power, quant)
+    out = ops.synth_noise_sensor(_dev(V), _dev(rays), m.camera, _sigma(tag, level), step, m.power, m.r_ref, m.q, seed=seed,
+                                 stream=stream, **kw)
+    return out.cpu().numpy()
+
+
+def _plain(tag, level, step, stream=0):
+    V, _, rays = _input(tag)
+    return ops.synth_noise(_dev(V), _sigma(tag, level), step, seed=SEED, stream=stream, normals=_dev(rays)).cpu().numpy()
+
+
+def _steps(tag):
+    return sn.STEPS if tag != "cloud" else (7,)
+
+
+INPUTS = ["ico3", "flipped", "cloud"]
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 1. bit pin
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", INPUTS)
+def test_without_the_model_the_bits_are_those_of_plain_ray_noise(tag):
+    V = _input(tag)[0]
+    assert V.shape[0] == {"ico3": 642, "flipped": 480, "cloud": 262444}[tag]
+    for level in sn.LEVELS:
+        for step in _steps(tag):
+            want = _plain(tag, level, step)
+            assert not np.array_equal(_bits(want), _bits(V))
+            assert np.array_equal(_bits(_sensor(tag, level, step, 0, 0.0)), _bits(want)), (tag, level, step)
+    for power in sn.POWERS:
+        assert np.array_equal(_bits(_sensor(tag, 0.0, 3, power, 0.0)), _bits(V)), power
+
+
+@pytest.mark.parametrize("tag", ["ico3", "cloud"])
+def test_words_out_of_range_switch_the_model_off(tag):
+    """This build's choice (include/fgc.h): sensor words that are off or out of range give plain noise along the rays -
+    fgc_synth_noise's bits - never a non-finite vertex."""
+    V, _, rays = _input(tag)
+    Vd, rd = _dev(V), _dev(rays)
+    sigma = _sigma(tag, 0.3)
+    want = _plain(tag, 0.3, 7)
+    f = lambda x: int(np.array([x], dtype=np.float32).view(np.uint32)[0])  # noqa: E731
+    on = 0x80000000
+    good = ops.sensor_words(2, 2.8, 0.05).tolist()
+    bad = [[0, 0, 0, 0], [2, f(2.8), f(0.05), 0], [on | 3, f(2.8), f(0.05), 0], [on | 0x7FFFFFFF, f(2.8), 0, 0],
+           [on | 2, f(0.0), f(0.05), 0], [on | 2, f(-2.8), f(0.05), 0], [on | 2, f(np.inf), 0, 0], [on | 2, f(np.nan), 0, 0],
+           [on | 2, 1, f(0.05), 0], [on | 2, f(2.8), f(-0.05), 0], [on | 2, f(2.8), f(np.inf), 0], [on | 2, f(2.8), f(np.nan), 0],
+           [on | 2, f(2.8), 1, 0]]
+    for words in bad:
+        ctl = _dev(np.array(words, dtype=np.uint32).view(np.int32))
+        got = ops.synth_noise_sensor(Vd, rd, sn.CAMERA, sigma, 7, None, None, None, seed=SEED, sensor_ctl=ctl).cpu().numpy()
+        assert np.isfinite(got).all() and np.array_equal(_bits(got), _bits(want)), [hex(w) for w in words]
+    ctl = _dev(np.array(good, dtype=np.uint32).view(np.int32))
+    got = ops.synth_noise_sensor(Vd, rd, sn.CAMERA, sigma, 7, None, None, None, seed=SEED, sensor_ctl=ctl).cpu().numpy()
+    assert np.isfinite(got).all() and not np.array_equal(_bits(got), _bits(want))
+    assert np.array_equal(_bits(got), _bits(ops.synth_noise_sensor(Vd, rd, sn.CAMERA, sigma, 7, 2, 2.8, 0.05, seed=SEED).cpu().numpy()))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 2. the oracle, unquantised
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("tag", INPUTS)
+def test_unquantised_noise_matches_the_float64_oracle(tag):
+    V, _, rays = _input(tag)
+    worst = 0.0
+    for power in (1, 2):
+        m = _model(tag, power, 0.0)
+        for level in sn.LEVELS:
+            sigma = _sigma(tag, level)
+            bound = sn.position_bound(sigma, power, V, m.camera, m.r_ref)
+            for step in _steps(tag):
+                got = _sensor(tag, level, step, power, 0.0).astype(np.float64)
+                want = sn.oracle(V, rays, m.camera, sigma, step, SEED, 0, power, m.r_ref, 0.0)[0]
+                err = np.abs(got - want).max()
+                print("%s power %d level %.1f step %d: max |V' - oracle| = %.3e (bound %.3e, sigma %.3e)"
+                      % (tag, power, level, step, err, bound, sigma))
+                assert np.isfinite(got).all() and err <= bound, (tag, power, level, step, err, bound)
+                worst = max(worst, err / bound)
+    print("%s: worst error / bound = %.3f" % (tag, worst))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 3. the oracle, quantised
+# ---------------------------------------------------------------------------------------------------------------------
+def _check_quantised(V, rays, got, m, sigma, step, stream, what):
+    """The checks of a quantised output `got` of the model m at `sigma`; returns (vertices left out, worst error / bound)."""
+    want, k, x, through = sn.oracle(V, rays, m.camera, sigma, step, SEED, stream, m.power, m.r_ref, m.q)
+    r = sn.ranges(V, m.camera)
+    bound = sn.position_bound(sigma, m.power, V, m.camera, m.r_ref)
+    margin = sn.disparity_margin(bound, k.max(), r.min())
+    assert margin < 0.25, (what, margin)
+    robust = np.abs(np.abs(x - np.floor(x)) - 0.5) > margin
+    got = got.astype(np.float64)
+    assert np.isfinite(got).all(), what
+    y = 1.0 / (sn.ranges(got, m.camera) * m.q)
+    # every output lies on the lattice
+    off = np.abs(y - np.rint(y)).max()
+    assert off <= margin, (what, off, margin)
+    k_dev = np.rint(y)
+    assert np.array_equal(k_dev[robust], k[robust]), (what, int((k_dev[robust] != k[robust]).sum()))
+    r_q = 1.0 / (k * m.q)
+    err = np.abs(got - want).max(1)
+    ratio = (err / (bound + 2.0 ** -22 * r_q))[robust].max()
+    print("%s: %d of %d left out (margin %.2e), k %d ... %d, off the lattice %.2e, worst error / bound %.3f, %d through the sensor"
+          % (what, int((~robust).sum()), robust.size, margin, int(k.min()), int(k.max()), off, ratio, int(through.sum())))
+    assert ratio <= 1.0, (what, ratio)
+    return int((~robust).sum()), ratio, through
+
+
+@pytest.mark.parametrize("quant", sn.QUANTS)
+@pytest.mark.parametrize("tag", INPUTS)
+def test_quantised_noise_matches_the_float64_oracle(tag, quant):
+    V, _, rays = _input(tag)
+    for power in sn.POWERS if tag != "cloud" else (2,):
+        m = _model(tag, power, quant)
+        left, total = 0, 0
+        for level in sn.LEVELS:
+            for step in _steps(tag):
+                got = _sensor(tag, level, step, power, quant)
+                n, _, through = _check_quantised(V, rays, got, m, _sigma(tag, level), step, 0,
+                                                 "%s power %d quant %.1f level %.1f step %d" % (tag, power, quant, level, step))
+                assert not through.any()
+                left, total = left + n, total + V.shape[0]
+        assert left <= 0.01 * total, (tag, power, quant, left, total)      # a condition of the test, not a measurement
+    # level 0: the quantised clean ranges (terraces alone)
+    m = _model(tag, 2, quant)
+    got = _sensor(tag, 0.0, 3, 2, quant)
+    assert not np.array_equal(_bits(got), _bits(V))
+    n, _, _ = _check_quantised(V, rays, got, m, 0.0, 3, 0, "%s quant %.1f level 0" % (tag, quant))
+    assert n <= 0.01 * V.shape[0]
+    r, rq = sn.ranges(V, m.camera), sn.ranges(got, m.camera)
+    assert (np.abs(rq - r) <= 0.5 * r * rq * m.q * (1.0 + 1e-4)).all()   # within half a disparity step of the clean range
+
+
+def test_samples_carried_through_the_sensor_keep_their_clean_range():
+    """rt <= 0: a handful of points at range 0.01 from the camera with a sigma of 1 - about half of the draws carry the
+    sample through the sensor; those come back finite, on the lattice, at the k of their CLEAN range."""
+    n = 16
+    cam = np.array(sn.CAMERA, dtype=np.float32).astype(np.float64)
+    rs = np.random.RandomState(3)
+    d = rs.normal(size=(n, 3))
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    V = (cam + d * (0.01 * (1.0 + 0.002 * np.arange(n)))[:, None]).astype(np.float32)
+    rays = utils.view_rays(V, camera=sn.CAMERA)
+    m = utils.SensorModel(0, 0.01, float(np.float32(1.0 / (0.01 * 10.3))), tuple(float(t) for t in cam))
+    sigma = np.float32(1.0)
+    got = ops.synth_noise_sensor(_dev(V), _dev(rays), m.camera, sigma, 7, m.power, m.r_ref, m.q, seed=SEED).cpu().numpy()
+    n_out, _, through = _check_quantised(V, rays, got, m, sigma, 7, 0, "through the sensor")
+    assert n_out == 0 and 3 <= through.sum() <= n - 3
+    k_clean = np.rint(1.0 / (sn.ranges(V, m.camera) * m.q))
+    k_dev = np.rint(1.0 / (sn.ranges(got.astype(np.float64), m.camera) * m.q))
+    assert np.array_equal(k_dev[through], k_clean[through]) and (k_clean == 10).all()
+    assert (k_dev[~through] != 10).any()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 4. a property the oracle shares no code with
+# ---------------------------------------------------------------------------------------------------------------------
+def test_far_vertices_are_noisier_than_near_ones():
+    V, _, rays = _input("ico3")
+    m = _model("ico3", 2, 0.0)
+    rho = sn.ranges(V, m.camera) / m.r_ref
+    far, near = rho > 1, rho < 1
+    assert far.sum() > 100 and near.sum() > 100
+    along = np.concatenate([((_sensor("ico3", 0.3, step, 2, 0.0).astype(np.float64) - V) * rays).sum(1)[:, None]
+                            for step in sn.STEPS], axis=1)
+    rms = lambda a: float(np.sqrt((a * a).mean()))  # noqa: E731
+    flat = np.concatenate([((_sensor("ico3", 0.3, step, 0, 0.0).astype(np.float64) - V) * rays).sum(1)[:, None]
+                           for step in sn.STEPS], axis=1)
+    print("power 2: RMS along the ray far %.4e, near %.4e; power 0: far %.4e, near %.4e"
+          % (rms(along[far]), rms(along[near]), rms(flat[far]), rms(flat[near])))
+    assert rms(along[far]) > rms(along[near])
+    assert rms(along[far]) > rms(flat[far]) and rms(along[near]) < rms(flat[near])
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 5. the launches behind it
+# ---------------------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=None)
+def _clean_set(tag, vertices=False):
+    V, F = sn.mesh(tag)
+    ds = TrainingSet()
+    (ds.addCleanMeshWithVertices if vertices else ds.addCleanMesh)(V, F, seed=0)
+    return ds
+
+
+def _host_rows(ds, V):
+    """utils.face_features on the vertices V, in node order with zero fake rows: what bind_mesh would be fed."""
+    rows = ds.clean_faces_rows[0][0]
+    F = rows[np.asarray(ds.permutations[0])][:ds.num_faces[0]].astype(np.uint32)
+    nrm, ctr = utils.face_features(V, F)
+    per_face = np.concatenate([nrm.astype(np.float32), ctr.astype(np.float32)], axis=1)
+    return sc.rows_in_node_order(per_face, ds.permutations[0], ds.in_list[0].shape[1])
+
+
+@pytest.mark.parametrize("tag", ["ico3", "flipped"])
+def test_feature_rows_and_point_sets_read_the_boxes_the_launch_leaves(tag):
+    V, _, rays = _input(tag)
+    ds = _clean_set(tag)
+    rows = _dev(ds.clean_faces_rows[0][0])
+    for level, step, power, quant in ((0.3, 7, 2, 0.5), (0.1, 1, 1, 0.0), (0.0, 0, 2, 2.0)):
+        m = _model(tag, power, quant)
+        scratch = torch.full((6 * 1024,), float("nan"), dtype=torch.float32, device=DEV)
+        Vo = ops.synth_noise_sensor(_dev(V), _dev(rays), m.camera, _sigma(tag, level), step, m.power, m.r_ref, m.q, seed=SEED,
+                                    scratch=scratch)
+        Vn = Vo.cpu().numpy()
+        got = ops.face_features_rows(Vo, rows, scratch=scratch, have_bbox=True).cpu().numpy()
+        assert np.array_equal(_bits(got), _bits(_host_rows(ds, Vn))), (tag, level, step)
+        a, b = ops.point_sets_prepare(Vo, _dev(V), scratch=scratch, have_bbox=True)
+        wa, wb = utils.normalizePointSets(Vn, V)
+        assert np.array_equal(_bits(a.cpu().numpy()), _bits(wa)) and np.array_equal(_bits(b.cpu().numpy()), _bits(wb))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 6. network level
+# ---------------------------------------------------------------------------------------------------------------------
+def _rotation(seed=3):
+    return utils.rand_rotation_matrix(randnums=np.random.RandomState(seed).uniform(size=3)).astype(np.float32)
+
+
+def _expect_vertices(net, tag, model, step, level, stream=0):
+    V, _, rays = _input(tag)
+    want = ops.synth_noise_sensor(_dev(V), _dev(rays), model.camera, _sigma(tag, level), step, model.power, model.r_ref,
+                                  model.q, seed=SEED, stream=stream).cpu().numpy()
+    got = net.noisy_vertices().cpu().numpy()
+    assert np.array_equal(_bits(got), _bits(want)) and not np.array_equal(_bits(got), _bits(V))
+    return got
+
+
+def test_a_train_step_equals_a_step_on_host_made_features():
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    tag = "ico3"
+    ds = _clean_set(tag)
+    V, _, rays = _input(tag)
+    model = _model(tag, 2, 0.5)
+    net = FacetDenoiser(DEV, seed=0)
+    net.bind_clean("m", ds.in_list[0], ds.adj_list[0], ds.gt_list[0], ds.clean_vertices[0], ds.clean_faces_rows[0],
+                   ds.clean_edge_len[0], seed=SEED, direction=rays, sensor=model)
+    ref = FacetDenoiser(DEV, seed=0)
+    samp = np.random.RandomState(2).randint(ds.in_list[0].shape[1], size=4000)
+    Rm = _rotation()
+
+    def state(n):
+        torch.cuda.synchronize()
+        return n.buffers["loss"].clone(), n.buffers["nconv"].clone(), [g.clone() for g in n.params.grads]
+
+    seen = []
+    for capture, (step, level) in ((False, (7, 0.2)), (True, (7, 0.2)), (True, (8, 0.3)), (True, (1, 0.1)), (False, (1, 0.1))):
+        net.train_step(samp, Rm, capture=capture, noise=(step, level))
+        got = state(net)
+        Vn = _expect_vertices(net, tag, model, step, level)
+        seen.append(Vn)
+        ref.bind_mesh(_host_rows(ds, Vn), ds.adj_list[0], gt=ds.gt_list[0])
+        ref.train_step(samp, Rm)
+        want = state(ref)
+        what = "%s step %d level %.1f" % ("captured" if capture else "eager", step, level)
+        assert np.isfinite(got[0][0].item()) and got[0][0].item() > 0
+        assert torch.equal(got[0], want[0]), (what, got[0], want[0])
+        assert torch.equal(got[1], want[1]), what
+        assert len(got[2]) == len(want[2]) == 44 and all(torch.equal(p, q) for p, q in zip(got[2], want[2])), what
+        assert torch.equal(net.params.theta, ref.params.theta), what
+    assert np.array_equal(seen[0], seen[1]) and not np.array_equal(seen[1], seen[2]) and not np.array_equal(seen[2], seen[3])
+    assert net._mesh["captured"]
+
+
+def test_a_pointset_step_with_ray_update_equals_a_step_on_host_made_inputs():
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    tag = "ico3"
+    ds = _clean_set(tag, True)
+    V, _, rays = _input(tag)
+    model = _model(tag, 2, 0.5)
+    net = FacetDenoiser(DEV, multi_scale=True, seed=0)
+    net.bind_clean_vertices("m", ds.in_list[0], ds.adj_list[0], ds.clean_vertices[0], ds.clean_faces_rows[0],
+                            ds.v_faces_list[0], ds.clean_edge_len[0], seed=SEED, direction=rays, ray_update=True, sensor=model)
+    ref = FacetDenoiser(DEV, multi_scale=True, seed=0)
+    nv = V.shape[0]
+    rs = np.random.RandomState(2)
+    i0, i1 = rs.randint(nv, size=500), rs.randint(nv, size=500)
+    Rm = _rotation()
+
+    def state(n):
+        torch.cuda.synchronize()
+        S = n._mesh["verts"]
+        return S["loss"].clone(), S["traj"][-3 * nv:].clone(), [g.clone() for g in n.params.grads]
+
+    seen = []
+    for call, (capture, (step, level)) in enumerate(((False, (7, 0.2)), (True, (7, 0.2)), (True, (8, 0.3)), (True, (1, 0.1)))):
+        net.pointset_step(i0, i1, Rm, capture=capture, noise=(step, level))
+        got = state(net)
+        Vn = _expect_vertices(net, tag, model, step, level)
+        seen.append(Vn)
+        a, b = utils.normalizePointSets(Vn, V)
+        ref.bind_vertices(call, _host_rows(ds, Vn), ds.adj_list[0], a, ds.clean_faces_rows[0], ds.v_faces_list[0], b,
+                          depth_dir=rays)
+        ref.pointset_step(i0, i1, Rm)
+        want = state(ref)
+        what = "%s step %d level %.1f" % ("captured" if capture else "eager", step, level)
+        assert np.isfinite(got[0].cpu().numpy()).all() and got[0][0].item() > 0
+        assert torch.equal(got[0], want[0]), (what, got[0], want[0])
+        assert torch.equal(got[1], want[1]), what
+        assert len(got[2]) == len(want[2]) == 52 and all(torch.equal(p, q) for p, q in zip(got[2], want[2])), what
+        assert torch.equal(net.params.theta, ref.params.theta), what
+    assert not np.array_equal(seen[1], seen[2]) and not np.array_equal(seen[2], seen[3])
+    assert set(net._mesh["captured"]) == {"points"}
+
+
+@pytest.mark.parametrize("trainer", ["trainNet", "trainAccuracyNet", "trainDoubleLossNet"])
+def test_trainers_take_the_model(trainer):
+    """sensor=(power, quant) with a camera view: the last step's vertices are make_noisy's for the model of that mesh -
+    counter 2, the training stream 0 - and the validation pass ran on the same model (stream 1, step 0)."""
+    from facet_graph_convolution_amd import train as T
+    from facet_graph_convolution_amd.makeNoisy import make_noisy
+    vertices = trainer != "trainNet"
+    ds = _clean_set("ico3", vertices)
+    V, F = sn.mesh("ico3")
+    lines = []
+    kw = dict(ray_update=True) if vertices else {}
+    out = getattr(T, trainer)(ds, 3, seed=0, log=lines.append, validSet=ds, noise_levels=(0.2,), capture=True,
+                              noise_direction={"camera": sn.CAMERA}, sensor=(2, 0.5), **kw)
+    net = out[0]
+    torch.cuda.synchronize()
+    assert np.isfinite(np.asarray(out[1])).all() and any("validation loss" in s for s in lines)
+    cv = np.asarray(ds.clean_vertices[0], dtype=np.float32).reshape(-1, 3)
+    rays = utils.view_rays(cv, camera=sn.CAMERA)
+    want = make_noisy(cv, F, 0.2, seed=0, stream=0, step=2, direction=rays, sensor=(2, 0.5), camera=sn.CAMERA)
+    assert np.array_equal(_bits(net.noisy_vertices().cpu().numpy()), _bits(want))
+    assert not np.array_equal(_bits(want), _bits(make_noisy(cv, F, 0.2, seed=0, stream=0, step=2, direction=rays)))
+    S = net._mesh_cache[("valid", 0)]["synth"]
+    model = utils.sensor_model(cv, sn.CAMERA, ds.clean_edge_len[0], 2, 0.5)
+    assert S["sensor_key"][0] == tuple(int(w) for w in ops.sensor_words(model.power, model.r_ref, model.q)) and S["stream"] == 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 7. offline loop
+# ---------------------------------------------------------------------------------------------------------------------
+def test_offline_loop_validates_on_the_files_make_noisy_writes(tmp_path, capsys, monkeypatch):
+    from facet_graph_convolution_amd import train as T, preprocess, makeNoisy
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    V, F = sn.mesh("ico3")
+    clean, noisy, dump, path = (tmp_path / k for k in ("clean", "noisy", "dump", "net"))
+    clean.mkdir()
+    utils.write_mesh(V, F, str(clean / "ball.obj"))
+    view = ["--camera", ",".join(str(c) for c in sn.CAMERA), "--sensor", "2:0.5"]
+    written = makeNoisy.main([str(clean), str(noisy), "--seed", "3", "--direction", "ray"] + view)
+    assert sorted(os.listdir(noisy)) == ["ball_n1.obj", "ball_n2.obj", "ball_n3.obj"] and len(written) == 3
+    # the files are what make_noisy(sensor=) makes, and differ from plain ray noise
+    Vc = utils.load_mesh(str(clean), "ball.obj", 0, False)[0]
+    rays = utils.view_rays(Vc, camera=sn.CAMERA)
+    files = [utils.load_mesh(str(noisy), "ball_n%d.obj" % (k + 1), 0, False)[0] for k in range(3)]
+    for k, level in enumerate(makeNoisy.DEFAULT_LEVELS):
+        want = makeNoisy.make_noisy(Vc, F, level, 3, 1, k, rays, sensor=(2, 0.5), camera=sn.CAMERA)
+        assert np.abs(files[k] - want).max() <= 0.5e-6 + 2.0 ** -23 * np.abs(want).max()
+        assert np.abs(files[k] - makeNoisy.make_noisy(Vc, F, level, 3, 1, k, rays)).max() > 1e-3
+    preprocess.main([str(clean), str(dump), "--clean", "--valid", str(clean)])
+    seen = []
+    loss_only = FacetDenoiser._loss_only
+
+    def spy(self, form, rotate):      # (the validation passes are the trainers' only loss-only calls)
+        out = loss_only(self, form, rotate)
+        seen.append(self.noisy_vertices().cpu().numpy().copy())
+        return out
+    monkeypatch.setattr(FacetDenoiser, "_loss_only", spy)
+    capsys.readouterr()
+    assert T.main([str(dump), str(path), "--synth-noise", "0.1,0.2,0.3", "--num-iterations", "5", "--net-name", "sens", "--seed",
+                   "3", "--noise-direction", "ray"] + view) == "trainNet"
+    out = capsys.readouterr().out
+    assert "Iteration 0, validation loss" in out and "NAN" not in out
+    assert len(seen) == 3
+    for k in range(3):
+        err = np.abs(seen[k].astype(np.float64) - files[k]).max()
+        print("validation mesh %d against makeNoisy's file: max difference %.3e" % (k + 1, err))
+        assert err <= 0.5e-6 + 2.0 ** -23 * np.abs(files[k]).max()
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# 8. determinism and refusals
+# ---------------------------------------------------------------------------------------------------------------------
+def test_noise_is_deterministic_and_moves_with_step_and_stream():
+    a = _sensor("ico3", 0.2, 7, 2, 0.0, stream=2)
+    assert np.array_equal(_bits(a), _bits(_sensor("ico3", 0.2, 7, 2, 0.0, stream=2)))
+    for other in (_sensor("ico3", 0.2, 8, 2, 0.0, stream=2), _sensor("ico3", 0.2, 7, 2, 0.0, stream=3),
+                  _sensor("ico3", 0.2, 7, 2, 0.0, stream=2, seed=SEED + 1), _sensor("ico3", 0.2, 7 + (1 << 32), 2, 0.0, stream=2)):
+        assert (np.abs(other - a).max(1) > 0).mean() > 0.99
+    q = _sensor("ico3", 0.3, 7, 2, 0.5, stream=2)
+    assert np.array_equal(_bits(q), _bits(_sensor("ico3", 0.3, 7, 2, 0.5, stream=2)))
+    for other in (_sensor("ico3", 0.3, 8, 2, 0.5, stream=2), _sensor("ico3", 0.3, 7, 2, 0.5, stream=3)):
+        assert not np.array_equal(_bits(other), _bits(q))
+
+
+def test_refusals():
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    tag = "ico3"
+    ds = _clean_set(tag)
+    V, _, rays = _input(tag)
+    args = (ds.in_list[0], ds.adj_list[0], ds.gt_list[0], ds.clean_vertices[0], ds.clean_faces_rows[0], ds.clean_edge_len[0])
+    model, other = _model(tag, 2, 0.5), _model(tag, 1, 0.5)
+    net = FacetDenoiser(DEV, seed=0)
+    for direction in ("random", "normal"):
+        with pytest.raises(ValueError, match="sensor.*rays"):
+            net.bind_clean("a", *args, direction=direction, sensor=model)
+    with pytest.raises(ValueError, match="sensor.*lf"):
+        net.bind_clean("a", *args, direction=rays, lf=(3.0, None), sensor=model)
+    with pytest.raises(ValueError, match="sensor"):
+        net.bind_clean("a", *args, direction=rays, sensor=(3, 2.8, 0.0, sn.CAMERA))
+    with pytest.raises(ValueError, match="sensor"):
+        net.bind_clean("a", *args, direction=rays, sensor=(2, 0.0, 0.0, sn.CAMERA))
+    with pytest.raises(ValueError, match="sensor"):
+        net.bind_clean("a", *args, direction=rays, sensor=(2, 0.5))
+    assert "a" not in net._mesh_cache
+    net.bind_clean("m", *args, seed=SEED, direction=rays, sensor=model)
+    net.bind_clean("m", *args, seed=SEED, direction=rays, sensor=tuple(model))          # the same model: a lookup
+    with pytest.raises(ValueError, match="another sensor model"):
+        net.bind_clean("m", *args, seed=SEED, direction=rays, sensor=other)
+    with pytest.raises(ValueError, match="another sensor model"):
+        net.bind_clean("m", *args, seed=SEED, direction=rays)
+    with pytest.raises(ValueError, match="another sensor model"):
+        net.bind_clean("m", *args, seed=SEED, direction=rays, sensor=model._replace(camera=(2.5, 0.4, 1.3)))
+    net.bind_clean("p", *args, seed=SEED, direction=rays)
+    with pytest.raises(ValueError, match="another sensor model"):
+        net.bind_clean("p", *args, seed=SEED, direction=rays, sensor=model)
+    Vd, rd = _dev(V), _dev(rays)
+    with pytest.raises(ValueError, match="rays"):
+        ops.synth_noise_sensor(Vd, None, sn.CAMERA, 0.01, 0, 2, 2.8, 0.0)
+    with pytest.raises(ValueError, match="one ray per vertex"):
+        ops.synth_noise_sensor(Vd, rd[:-1], sn.CAMERA, 0.01, 0, 2, 2.8, 0.0)
+    with pytest.raises(ValueError, match="camera"):
+        ops.synth_noise_sensor(Vd, rd, (2.5, np.nan, 1.2), 0.01, 0, 2, 2.8, 0.0)
+    with pytest.raises(ValueError, match="sensor"):
+        ops.synth_noise_sensor(Vd, rd, sn.CAMERA, 0.01, 0, 3, 2.8, 0.0)

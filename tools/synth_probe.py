@@ -25,7 +25,14 @@ kernel - nv x K pairs x 8 VALU instructions over 256 CUs x 4 SIMDs, one wave64 i
 GHz - and beside the same with the exponential counted as four slots (11 per pair: an estimate, not a bound - the measured
 slope between two bump counts is faster than it); and, for the largest size, the captured point-set step
 and the captured trainNet step with the bumps against the same steps with white noise alone, alternating `rounds` times in
-this one process."""
+this one process.
+
+    python tools/synth_probe.py --sensor [--faces 20480 100000] [--steps 50] [--rounds 5] [--out FILE]
+
+The depth-sensor noise model (fgc_synth_noise_sensor): per mesh size the DEVICE time of the launch
+(power 0 without quantisation, power 2, power 2 with quant 0.5) beside fgc_synth_noise on the same table of rays, the forms
+alternating `rounds` times; and, for the largest size, the captured trainNet step and the captured point-set step
+(ray_update) with the model against the same steps with plain ray noise, two networks alternating in this one process."""
 import argparse
 import json
 import os
@@ -252,6 +259,86 @@ def lf(args):
     return res
 
 
+SENSOR_CAMERA = (2.5, 0.4, 1.2)
+
+
+def sensor(args):
+    """--sensor: fgc_synth_noise_sensor beside fgc_synth_noise on the same table of rays, and the captured steps with the
+    model (power 2, quant 0.5) and with plain ray noise."""
+    from facet_graph_convolution_amd import ops, _lib
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    from facet_graph_convolution_amd.dataClasses import TrainingSet
+    from facet_graph_convolution_amd.utils import rand_rotation_matrix, getAverageEdgeLength, view_rays, sensor_model
+    L = _lib.lib()
+    dev = "cuda:0"
+    res = []
+    for nf in args.faces:
+        V, F = _clean_mesh(nf)
+        nv, edge = V.shape[0], float(getAverageEdgeLength(V, F)[0])
+        rays = view_rays(V, camera=SENSOR_CAMERA)
+        Vd, rd = torch.as_tensor(V, device=dev), torch.as_tensor(rays, device=dev)
+        out_v = torch.empty_like(Vd)
+        scratch = torch.empty(6 * 1024, dtype=torch.float32, device=dev)
+        ctl = torch.from_numpy(ops.noise_words(3, 0.2 * edge).view(np.int32)).to(dev)
+        row = dict(faces=int(F.shape[0]), vertices=int(nv), noise_bytes=36 * nv, noise_floor_us=36 * nv / HBM_BYTES_PER_S * 1e6,
+                   kernel_device_us={})
+        calls = {"plain": lambda: ops.synth_noise(Vd, None, None, seed=1, normals=rd, out=out_v, scratch=scratch, ctl=ctl)}
+        for name, (power, quant) in (("power0", (0, 0.0)), ("power2", (2, 0.0)), ("power2_quant", (2, 0.5))):
+            m = sensor_model(V, SENSOR_CAMERA, edge, power, quant)
+            sctl = torch.from_numpy(ops.sensor_words(m.power, m.r_ref, m.q).view(np.int32)).to(dev)
+            calls[name] = lambda m=m, sctl=sctl: ops.synth_noise_sensor(Vd, rd, m.camera, None, None, None, None, None, seed=1,
+                                                                        out=out_v, scratch=scratch, ctl=ctl, sensor_ctl=sctl)
+        for r in range(args.rounds):      # (alternating: every form in every round)
+            for name, call in calls.items():
+                us = _device_us(L, call, args.steps)
+                row["kernel_device_us"].setdefault(name, []).append([t for k, t in us.items() if "synth_noise" in k][0])
+        if nf == max(args.faces):
+            rs = np.random.RandomState(0)
+            Rm = rand_rotation_matrix(randnums=rs.uniform(size=3))
+            model = sensor_model(V, SENSOR_CAMERA, edge, 2, 0.5)
+            ds = TrainingSet()
+            ds.addCleanMesh(V, F, seed=0)
+            samp = rs.randint(ds.in_list[0].shape[1], size=4000)
+            nets = {}
+            for k, kw in (("sensor", dict(sensor=model)), ("rays", {})):
+                nets[k] = FacetDenoiser(dev, seed=0)
+                nets[k].bind_clean(0, ds.in_list[0], ds.adj_list[0], ds.gt_list[0], ds.clean_vertices[0], ds.clean_faces_rows[0],
+                                   ds.clean_edge_len[0], direction=rays, **kw)
+                nets[k].set_samples(samp)
+                nets[k].set_rotation(Rm)
+            times = {"sensor": [], "rays": []}
+            for r in range(args.rounds):
+                for k, net in nets.items():
+                    net.set_noise(r + 1, 0.2)
+                    times[k].append(timed(lambda: net.forward_backward(rotate=True, capture=True), args.steps))
+            row["trainNet_captured_ms"] = times
+            row["trainNet_difference_us"] = (float(np.median(times["sensor"])) - float(np.median(times["rays"]))) * 1e3
+            del nets, ds
+            torch.cuda.empty_cache()
+            dv = TrainingSet()
+            dv.addCleanMeshWithVertices(V, F, seed=0)
+            i0, i1 = rs.randint(nv, size=500), rs.randint(nv, size=500)
+            nets = {}
+            for k, kw in (("sensor", dict(sensor=model)), ("rays", {})):
+                nets[k] = FacetDenoiser(dev, multi_scale=True, seed=0)
+                nets[k].bind_clean_vertices(0, dv.in_list[0], dv.adj_list[0], dv.clean_vertices[0], dv.clean_faces_rows[0],
+                                            dv.v_faces_list[0], dv.clean_edge_len[0], direction=rays, ray_update=True, **kw)
+                nets[k].set_point_samples(i0, i1)
+                nets[k].set_rotation(Rm)
+            times = {"sensor": [], "rays": []}
+            for r in range(args.rounds):
+                for k, net in nets.items():
+                    net.set_noise(r + 1, 0.2)
+                    times[k].append(timed(lambda: net.pointset_forward_backward(rotate=True, capture=True), args.steps))
+            row["pointset_captured_ms"] = times
+            row["pointset_difference_us"] = (float(np.median(times["sensor"])) - float(np.median(times["rays"]))) * 1e3
+            del nets, dv
+        print(json.dumps(row), flush=True)
+        res.append(row)
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--faces", type=int, nargs="+", default=[20480, 100000])
@@ -259,10 +346,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--points", action="store_true", help="the point sets of the vertex networks (fgc_point_sets_prepare)")
     ap.add_argument("--lf", action="store_true", help="the low-frequency noise (fgc_synth_noise_lf)")
+    ap.add_argument("--sensor", action="store_true", help="the depth-sensor noise model (fgc_synth_noise_sensor)")
     ap.add_argument("--out", default="")
     args = ap.parse_args()
-    if args.points or args.lf:
-        res = lf(args) if args.lf else points(args)
+    if args.points or args.lf or args.sensor:
+        res = sensor(args) if args.sensor else lf(args) if args.lf else points(args)
         if args.out:
             os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
             with open(args.out, "w") as fh:
