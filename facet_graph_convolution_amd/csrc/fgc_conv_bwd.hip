@@ -1842,6 +1842,18 @@ extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, v
                       "(cin=%d cout=%d max_deg=%d)", KMAX, cin, cout, d->max_deg);
         FGC_CHECK_ARG(!io->pool_dy || (io->pool_y && io->y && d->n % 4 == 0),
                       "fgc_conv_bwd: pool_dy needs pool_y, y and a row count that is a multiple of 4 (n=%d)", d->n);
+        // K2's parameters and form, decided before the first launch: a shape the bf16 data kernel does not serve (an in-degree
+        // above 24) is refused with nothing written - it used to be refused after the packing and the d-logits launch
+        const bool run_k2 = (stages & 4) && c.k1 != K1_NARROW && !(io->data_tile_list && io->n_data_tiles == 0);
+        CoreParams p2;
+        DataEpilogue ep2;
+        DataForm f2{};
+        if (run_k2) {
+            f2 = data_form(w, c, d, io, p2, ep2);
+            if (bf16)
+                FGC_CHECK_ARG(w8_bf16_supported(p2, io->max_in_deg), "fgc_conv_bwd: FGC_CONV_BF16: unsupported shape for the data "
+                              "gradient (cin=%d cout=%d max_in_deg=%d)", cin, cout, io->max_in_deg);
+        }
         if ((stages & 1) && (c.ds == DS_VEC || c.ds == DS_SCALAR)) {
             rc = launch_ds_db(w, c, d, io, st);
             if (rc) return rc;
@@ -1884,14 +1896,11 @@ extern "C" int fgc_conv_bwd(const fgc_conv_desc* d, const fgc_conv_bwd_io* io, v
             if (rc) return rc;   // dc partials: stage 8
         }
         // K2
-        if ((stages & 4) && !(io->data_tile_list && io->n_data_tiles == 0)) {
-            CoreParams p;
-            DataEpilogue ep;
-            const DataForm f = data_form(w, c, d, io, p, ep);
+        if (run_k2) {
+            const CoreParams& p = p2;
+            const DataEpilogue& ep = ep2;
+            const DataForm& f = f2;
             const size_t smem = conv_smem_bytes(w.g2, (size_t)TILE * 24 * 4);
-            if (bf16)
-                FGC_CHECK_ARG(w8_bf16_supported(p, io->max_in_deg), "fgc_conv_bwd: FGC_CONV_BF16: unsupported shape for the data "
-                              "gradient (cin=%d cout=%d max_in_deg=%d)", cin, cout, io->max_in_deg);
             if (f.kind == DATA_W8) {
                 rc = launch_data_w8(p, ep, smem, io->max_in_deg, st, bf16);
             } else if (f.vec4) {

@@ -384,6 +384,10 @@ extern "C" int fgc_conv_fwd(const fgc_conv_desc* d, float* ag, float* y, float* 
     FGC_CHECK_ARG(!bf16 || narrow || (conv_vec4_ok(d) && cin % 32 == 0 && (d->c1 == 0 || d->c0 % 32 == 0) && d->cout % 32 == 0),
                   "fgc_conv_fwd: FGC_CONV_BF16 needs widths that are multiples of 32 and 16-byte aligned tensors (c0=%d c1=%d "
                   "cout=%d)", d->c0, d->c1, d->cout);
+    // (refused before the first launch: it used to follow the packing and the logit table, which left ag overwritten)
+    if (bf16 && !narrow)
+        FGC_CHECK_ARG(w8_bf16_supported(p, d->max_deg), "fgc_conv_fwd: FGC_CONV_BF16: unsupported shape (cin=%d cout=%d "
+                      "max_deg=%d)", cin, d->cout, d->max_deg);
     if (!narrow && !(d->flags & FGC_CONV_PACKED)) {
         PackJob job;
         size_t total;
@@ -433,9 +437,6 @@ extern "C" int fgc_conv_fwd(const fgc_conv_desc* d, float* ag, float* y, float* 
 
     FwdEpilogue ep{d->b, d->bias_mask, d->act, d->alpha, y, y_pool};
     const size_t smem = conv_smem_bytes(g, 0);
-    if (bf16)
-        FGC_CHECK_ARG(w8_bf16_supported(p, d->max_deg), "fgc_conv_fwd: FGC_CONV_BF16: unsupported shape (cin=%d cout=%d "
-                      "max_deg=%d)", cin, d->cout, d->max_deg);
     if (f.kind == FWD_W8) return launch_fwd_w8(p, ep, smem, d->max_deg, st, bf16);
     if (f.vec4)
         return launch_kernel<conv_fwd_kernel<8, true>>(LaunchCfg{"conv_fwd_kernel<LPN, true>", "fgc_conv_fwd", st, core_grid(p), NTHREADS, smem}, p, ep);

@@ -48,28 +48,30 @@ def _graph(case, dev):
 class _Slices:
     """Device tensors at a byte offset from 16-byte alignment: slices of larger tensors filled with a sentinel (`fill`; NaN makes
     a value read from the surroundings show in whatever it is multiplied into, zero included).  padded: surroundings even at
-    offset 0.  (Shared with tests/test_gpu_mlp_forms.py.)"""
+    offset 0.  dtype: the element type (bf16 tensors of FGC_CONV_BF16 storage; PAD counts elements, the fill is rounded to the
+    type).  (Shared with tests/test_gpu_mlp_forms.py and tests/test_gpu_conv_forms_bf16.py.)"""
 
     def __init__(self, dev, fill=SENTINEL):
         self.dev, self.made, self.fill = dev, [], fill
 
-    def empty(self, shape, off_bytes=0, padded=False):
+    def empty(self, shape, off_bytes=0, padded=False, dtype=torch.float32):
         if not off_bytes and not padded:
-            return torch.empty(*shape, dtype=torch.float32, device=self.dev)
+            return torch.empty(*shape, dtype=dtype, device=self.dev)
         numel = int(np.prod(shape))
-        base = torch.empty(numel + 2 * PAD, dtype=torch.float32, device=self.dev)
+        base = torch.empty(numel + 2 * PAD, dtype=dtype, device=self.dev)
         base.fill_(self.fill)
-        start = PAD + off_bytes // 4
+        start = PAD + off_bytes // base.element_size()
         view = base[start:start + numel].view(*shape)
         assert view.data_ptr() % 16 == off_bytes % 16
         self.made.append((base, start, numel))
         return view
 
-    def copy(self, t, off_bytes=0, padded=False):
-        return self.empty(tuple(t.shape), off_bytes, padded).copy_(t)
+    def copy(self, t, off_bytes=0, padded=False, dtype=torch.float32):
+        return self.empty(tuple(t.shape), off_bytes, padded, dtype).copy_(t)
 
     def check(self):
-        untouched = (lambda t: bool(torch.isnan(t).all())) if self.fill != self.fill else (lambda t: bool((t == self.fill).all()))
+        same = lambda t: bool((t == torch.tensor(self.fill, dtype=t.dtype, device=t.device)).all())
+        untouched = (lambda t: bool(torch.isnan(t).all())) if self.fill != self.fill else same
         for base, start, numel in self.made:
             assert untouched(base[:start]) and untouched(base[start + numel:]), "the surroundings of an offset tensor were written"
 
