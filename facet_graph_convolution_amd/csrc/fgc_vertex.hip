@@ -10,15 +10,12 @@
 
 namespace fgc {
 
-__global__ __launch_bounds__(256) void vertex_update_kernel(const float* __restrict__ x, float* __restrict__ xo, int nv,
-                                                            const float* __restrict__ nrm, int nf,
-                                                            const int4* __restrict__ emap, int ne,
-                                                            const int* __restrict__ vemap, int max_edges,
-                                                            float lambda) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv) return;
-    const float xi0 = x[3 * (size_t)i], xi1 = x[3 * (size_t)i + 1], xi2 = x[3 * (size_t)i + 2];
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+// the edge-slot walk of vertex i at (xi0, xi1, xi2): per used slot, in slot order, add(u0, u1, u2) with u = n_f1 (n_f1 . d) +
+// n_f2 (n_f2 . d).  The one copy of this loop: both single-scale kernels accumulate through it.
+template <class Add>
+__device__ __forceinline__ void edge_walk(int i, float xi0, float xi1, float xi2, const float* __restrict__ x, int nv,
+                                          const float* __restrict__ nrm, int nf, const int4* __restrict__ emap, int ne,
+                                          const int* __restrict__ vemap, int max_edges, Add&& add) {
     const int* slots = vemap + (size_t)i * max_edges;
     for (int s = 0; s < max_edges; ++s) {
         const int e = slots[s];
@@ -42,10 +39,24 @@ __global__ __launch_bounds__(256) void vertex_update_kernel(const float* __restr
             u1 += n1 * dp;
             u2 += n2 * dp;
         }
+        add(u0, u1, u2);
+    }
+}
+
+__global__ __launch_bounds__(256) void vertex_update_kernel(const float* __restrict__ x, float* __restrict__ xo, int nv,
+                                                            const float* __restrict__ nrm, int nf,
+                                                            const int4* __restrict__ emap, int ne,
+                                                            const int* __restrict__ vemap, int max_edges,
+                                                            float lambda) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nv) return;
+    const float xi0 = x[3 * (size_t)i], xi1 = x[3 * (size_t)i + 1], xi2 = x[3 * (size_t)i + 2];
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+    edge_walk(i, xi0, xi1, xi2, x, nv, nrm, nf, emap, ne, vemap, max_edges, [&](float u0, float u1, float u2) {
         a0 += u0;
         a1 += u1;
         a2 += u2;
-    }
+    });
     xo[3 * (size_t)i] = xi0 + lambda * a0;
     xo[3 * (size_t)i + 1] = xi1 + lambda * a1;
     xo[3 * (size_t)i + 2] = xi2 + lambda * a2;
@@ -72,31 +83,8 @@ __global__ __launch_bounds__(256) void vertex_update_dir_kernel(const float* __r
     const float* dir = dirs + (size_t)i * dstride;
     const float e0 = dir[0], e1 = dir[1], e2 = dir[2];
     float acc = 0.f;
-    const int* slots = vemap + (size_t)i * max_edges;
-    for (int s = 0; s < max_edges; ++s) {
-        const int e = slots[s];
-        if (e < 0 || e >= ne) continue;           // unused slot, as in vertex_update_kernel
-        const int4 em = emap[e];
-        const int j = em.x == i ? em.y : em.x;    // the endpoint that is i itself contributes zero
-        if (j < 0 || j >= nv) continue;
-        const float d0 = x[3 * (size_t)j] - xi0, d1 = x[3 * (size_t)j + 1] - xi1, d2 = x[3 * (size_t)j + 2] - xi2;
-        float u0 = 0.f, u1 = 0.f, u2 = 0.f;
-        if (em.z >= 0 && em.z < nf) {
-            const float n0 = nrm[3 * (size_t)em.z], n1 = nrm[3 * (size_t)em.z + 1], n2 = nrm[3 * (size_t)em.z + 2];
-            const float dp = (d0 * n0 + d1 * n1) + d2 * n2;
-            u0 = n0 * dp;
-            u1 = n1 * dp;
-            u2 = n2 * dp;
-        }
-        if (em.w >= 0 && em.w < nf) {              // a boundary edge has f2 = -1
-            const float n0 = nrm[3 * (size_t)em.w], n1 = nrm[3 * (size_t)em.w + 1], n2 = nrm[3 * (size_t)em.w + 2];
-            const float dp = (d0 * n0 + d1 * n1) + d2 * n2;
-            u0 += n0 * dp;
-            u1 += n1 * dp;
-            u2 += n2 * dp;
-        }
-        acc += (u0 * e0 + u1 * e1) + u2 * e2;
-    }
+    edge_walk(i, xi0, xi1, xi2, x, nv, nrm, nf, emap, ne, vemap, max_edges,
+              [&](float u0, float u1, float u2) { acc += (u0 * e0 + u1 * e1) + u2 * e2; });
     const float ti = (first ? 0.f : t[i]) + lambda * acc;
     t[i] = ti;
     if (t_out) t_out[i] = ti;
@@ -163,15 +151,12 @@ __global__ __launch_bounds__(256) void pool4_avg_iz_kernel(const float* __restri
     y[idx] = (c0 + c1) / 2.0f;
 }
 
-// one Jacobi iteration at one scale: x_v += (1/#faces(v)) sum_k n (n . (c - x_v)) over the vertex' face slots
-__global__ __launch_bounds__(256) void vertex_update_ms_kernel(const float* __restrict__ x, float* __restrict__ xo,
-                                                               int nv, const int* __restrict__ vfaces, int k_v,
-                                                               int shift, const float* __restrict__ nrm,
-                                                               const float* __restrict__ fpos, int nnodes) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= nv) return;
-    const float x0 = x[3 * (size_t)v], x1 = x[3 * (size_t)v + 1], x2 = x[3 * (size_t)v + 2];
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+// the face-slot walk of vertex v at (x0, x1, x2), level `shift`: a = sum_k n (n . (c - x_v)) over the vertex' slots in slot
+// order; returns lam = 1 / #faces(v).  The one copy of this loop: both multi-scale kernels step through it.
+__device__ __forceinline__ float ms_walk(int v, float x0, float x1, float x2, const int* __restrict__ vfaces, int k_v,
+                                         int shift, const float* __restrict__ nrm, const float* __restrict__ fpos,
+                                         int nnodes, float& a0, float& a1, float& a2) {
+    a0 = a1 = a2 = 0.f;
     int numf = 0;
     for (int k = 0; k < k_v; ++k) {
         const int f = vfaces[(size_t)v * k_v + k];
@@ -188,7 +173,19 @@ __global__ __launch_bounds__(256) void vertex_update_ms_kernel(const float* __re
         a2 += w * n2;
     }
     // a vertex without faces keeps its position (the reference computes 0 * (1/0) = NaN there)
-    const float lm = numf > 0 ? 1.0f / (float)numf : 0.f;
+    return numf > 0 ? 1.0f / (float)numf : 0.f;
+}
+
+// one Jacobi iteration at one scale: x_v += (1/#faces(v)) sum_k n (n . (c - x_v)) over the vertex' face slots
+__global__ __launch_bounds__(256) void vertex_update_ms_kernel(const float* __restrict__ x, float* __restrict__ xo,
+                                                               int nv, const int* __restrict__ vfaces, int k_v,
+                                                               int shift, const float* __restrict__ nrm,
+                                                               const float* __restrict__ fpos, int nnodes) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= nv) return;
+    const float x0 = x[3 * (size_t)v], x1 = x[3 * (size_t)v + 1], x2 = x[3 * (size_t)v + 2];
+    float a0, a1, a2;
+    const float lm = ms_walk(v, x0, x1, x2, vfaces, k_v, shift, nrm, fpos, nnodes, a0, a1, a2);
     xo[3 * (size_t)v] = x0 + lm * a0;
     xo[3 * (size_t)v + 1] = x1 + lm * a1;
     xo[3 * (size_t)v + 2] = x2 + lm * a2;
@@ -359,23 +356,8 @@ __global__ __launch_bounds__(256) void vertex_update_ms_dir_kernel(const float* 
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= nv) return;
     const float p0 = x[3 * (size_t)v], p1 = x[3 * (size_t)v + 1], p2 = x[3 * (size_t)v + 2];   // the current iterate
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-    int numf = 0;
-    for (int k = 0; k < k_v; ++k) {
-        const int f = vfaces[(size_t)v * k_v + k];
-        if (f < 0) continue;                      // slot handling exactly as in vertex_update_ms_kernel
-        ++numf;
-        const int node = f >> shift;
-        if (node >= nnodes) continue;
-        const float n0 = nrm[3 * (size_t)node], n1 = nrm[3 * (size_t)node + 1], n2 = nrm[3 * (size_t)node + 2];
-        const float e0 = fpos[3 * (size_t)node] - p0, e1 = fpos[3 * (size_t)node + 1] - p1,
-                    e2 = fpos[3 * (size_t)node + 2] - p2;
-        const float w = (n0 * e0 + n1 * e1) + n2 * e2;
-        a0 += w * n0;
-        a1 += w * n1;
-        a2 += w * n2;
-    }
-    const float lm = numf > 0 ? 1.0f / (float)numf : 0.f;      // a vertex without faces: t stays where it is
+    float a0, a1, a2;      // (a vertex without faces: lm = 0, t stays where it is)
+    const float lm = ms_walk(v, p0, p1, p2, vfaces, k_v, shift, nrm, fpos, nnodes, a0, a1, a2);
     const float* dir = dirs + (size_t)v * dstride;
     const float d0 = dir[0], d1 = dir[1], d2 = dir[2];
     const float tv = t[v] + (((lm * a0) * d0 + (lm * a1) * d1) + (lm * a2) * d2);
@@ -435,67 +417,6 @@ extern "C" int fgc_pool4_avg_iz(const float* x, int32_t n, int32_t c, float* y, 
     FGC_LAUNCH("pool4_avg_iz_kernel", (hipStream_t)stream, pool4_avg_iz_kernel, dim3(cdiv(total, 256)), dim3(256), 0, x,
                n / 4, c, y);
     FGC_CHECK_LAUNCH("fgc_pool4_avg_iz");
-    return FGC_OK;
-}
-
-extern "C" int fgc_vertex_update_ms(const float* x, float* x_out, int32_t nv, const int32_t* faces, int32_t n0,
-                                    const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
-                                    const float* normals2, const int32_t* iters, float* dx_out, float* scratch,
-                                    size_t scratch_floats, void* stream) {
-    FGC_CHECK_ARG(x && x_out && faces && v_faces && normals0 && normals1 && normals2 && iters && scratch,
-                  "fgc_vertex_update_ms: null pointer");
-    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0, "fgc_vertex_update_ms: nv=%d n0=%d (multiple of 16) k_v=%d",
-                  nv, n0, k_v);
-    FGC_CHECK_ARG(x != x_out, "fgc_vertex_update_ms: x and x_out must be distinct");
-    const int n1 = n0 / 4, n2 = n0 / 16;
-    const size_t need = 3 * ((size_t)nv * 2 + n0 + n1 + n2);
-    FGC_CHECK_ARG(scratch_floats >= need, "fgc_vertex_update_ms: scratch too small (%zu < %zu floats)", scratch_floats, need);
-    hipStream_t st = (hipStream_t)stream;
-    float* xa = scratch;
-    float* xb = xa + 3 * (size_t)nv;
-    float* fp0 = xb + 3 * (size_t)nv;
-    float* fp1 = fp0 + 3 * (size_t)n0;
-    float* fp2 = fp1 + 3 * (size_t)n1;
-    const float* nrm[3] = {normals0, normals1, normals2};
-    float* fps[3] = {fp0, fp1, fp2};
-    const int nn[3] = {n0, n1, n2};
-    if (hipMemcpyAsync(xa, x, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        fgc::set_error("fgc_vertex_update_ms: copy failed");
-        return FGC_EHIP;
-    }
-    float* cur = xa;
-    float* nxt = xb;
-    for (int stage = 0; stage < 3; ++stage) {
-        const int scale = 2 - stage;                 // coarse to fine (train.py:1687)
-        FGC_CHECK_ARG(iters[stage] >= 0, "fgc_vertex_update_ms: negative iteration count");
-        float* start = nullptr;
-        if (dx_out) {   // remember where this stage started: dx = x_end - x_start (train.py:1763)
-            start = dx_out + (size_t)stage * nv * 3;
-            if (hipMemcpyAsync(start, cur, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-                fgc::set_error("fgc_vertex_update_ms: copy failed");
-                return FGC_EHIP;
-            }
-        }
-        for (int it = 0; it < iters[stage]; ++it) {
-            FGC_LAUNCH("face_centers_kernel", st, face_centers_kernel, dim3(cdiv(n0, 256)), dim3(256), 0, cur, nv, faces, n0, fp0);
-            if (scale >= 1)
-                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n1 * 3, 256)), dim3(256), 0, fp0, n1, 3, fp1);
-            if (scale >= 2)
-                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n2 * 3, 256)), dim3(256), 0, fp1, n2, 3, fp2);
-            FGC_LAUNCH("vertex_update_ms_kernel", st, vertex_update_ms_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, cur, nxt, nv,
-                       v_faces, k_v, 2 * scale, nrm[scale], fps[scale], nn[scale]);
-            float* t = cur;
-            cur = nxt;
-            nxt = t;
-        }
-        if (dx_out)
-            FGC_LAUNCH("sub3_kernel", st, sub3_kernel, dim3(cdiv(nv * 3, 256)), dim3(256), 0, cur, start, nv * 3, start);
-    }
-    if (hipMemcpyAsync(x_out, cur, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        fgc::set_error("fgc_vertex_update_ms: copy failed");
-        return FGC_EHIP;
-    }
-    FGC_CHECK_LAUNCH("fgc_vertex_update_ms");
     return FGC_OK;
 }
 
@@ -571,67 +492,33 @@ extern "C" int fgc_vertex_update_dir(const float* x, float* x_out, float* t_out,
     return FGC_OK;
 }
 
-// the trajectory form of fgc_vertex_update_ms: the same launches with the same arguments, every iteration writing its own
-// slot of traj (slot 0 = x, slot t + 1 = the output of iteration t) instead of a ping-pong buffer
-extern "C" int fgc_vertex_update_ms_traj(const float* x, int32_t nv, const int32_t* faces, int32_t n0,
-                                         const int32_t* v_faces, int32_t k_v, const float* normals0,
-                                         const float* normals1, const float* normals2, const int32_t* iters,
-                                         float* traj, size_t traj_floats, float* scratch, size_t scratch_floats,
-                                         void* stream) {
-    FGC_CHECK_ARG(x && faces && v_faces && normals0 && normals1 && normals2 && iters && traj && scratch,
-                  "fgc_vertex_update_ms_traj: null pointer");
-    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0,
-                  "fgc_vertex_update_ms_traj: nv=%d n0=%d (multiple of 16) k_v=%d", nv, n0, k_v);
-    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0, "fgc_vertex_update_ms_traj: negative iteration count");
+// ---------------------------------------------------------------------------------------------
+// the multi-scale update, free or along a per-vertex direction: host side
+// ---------------------------------------------------------------------------------------------
+// the three levels as the drivers index them by scale: normals, node centres (3 (n0 + n0/4 + n0/16) floats at `centres`,
+// inside the caller's scratch) and node counts
+struct MsLevels {
+    const float* nrm[3];
+    float* fps[3];
+    int nn[3];
+};
+
+static MsLevels ms_levels(const float* normals0, const float* normals1, const float* normals2, int n0, float* centres) {
     const int n1 = n0 / 4, n2 = n0 / 16;
-    const size_t T = (size_t)iters[0] + iters[1] + iters[2];
-    const size_t need_traj = (T + 1) * 3 * (size_t)nv;
-    FGC_CHECK_ARG(traj_floats >= need_traj, "fgc_vertex_update_ms_traj: traj too small (%zu < %zu floats)", traj_floats,
-                  need_traj);
-    const size_t need = 3 * ((size_t)n0 + n1 + n2);
-    FGC_CHECK_ARG(scratch_floats >= need, "fgc_vertex_update_ms_traj: scratch too small (%zu < %zu floats)", scratch_floats,
-                  need);
-    FGC_CHECK_ARG(x < traj || x >= traj + need_traj, "fgc_vertex_update_ms_traj: x must not lie in traj");
-    hipStream_t st = (hipStream_t)stream;
-    float* fp0 = scratch;
-    float* fp1 = fp0 + 3 * (size_t)n0;
-    float* fp2 = fp1 + 3 * (size_t)n1;
-    const float* nrm[3] = {normals0, normals1, normals2};
-    float* fps[3] = {fp0, fp1, fp2};
-    const int nn[3] = {n0, n1, n2};
-    if (hipMemcpyAsync(traj, x, (size_t)nv * 12, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        fgc::set_error("fgc_vertex_update_ms_traj: copy failed");
-        return FGC_EHIP;
-    }
-    size_t t = 0;
-    for (int stage = 0; stage < 3; ++stage) {
-        const int scale = 2 - stage;
-        for (int it = 0; it < iters[stage]; ++it, ++t) {
-            const float* cur = traj + t * 3 * (size_t)nv;
-            float* nxt = traj + (t + 1) * 3 * (size_t)nv;
-            FGC_LAUNCH("face_centers_kernel", st, face_centers_kernel, dim3(cdiv(n0, 256)), dim3(256), 0, cur, nv, faces, n0, fp0);
-            if (scale >= 1)
-                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n1 * 3, 256)), dim3(256), 0, fp0, n1, 3, fp1);
-            if (scale >= 2)
-                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n2 * 3, 256)), dim3(256), 0, fp1, n2, 3, fp2);
-            FGC_LAUNCH("vertex_update_ms_kernel", st, vertex_update_ms_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, cur, nxt, nv,
-                       v_faces, k_v, 2 * scale, nrm[scale], fps[scale], nn[scale]);
-        }
-    }
-    FGC_CHECK_LAUNCH("fgc_vertex_update_ms_traj");
-    return FGC_OK;
+    return {{normals0, normals1, normals2}, {centres, centres + 3 * (size_t)n0, centres + 3 * ((size_t)n0 + n1)}, {n0, n1, n2}};
 }
 
-extern "C" size_t fgc_vertex_update_ms_bwd_workspace_floats(int32_t nv, int32_t n0) {
-    if (nv <= 0 || n0 <= 0) return 0;
-    const size_t nodes = (size_t)n0 + n0 / 4 + n0 / 16;
-    return (size_t)nv * 7 + 6 * nodes;      // lam, two gradient buffers; centres and their gradients of the three levels
+// the node centres of levels 0 .. scale from the positions x: the barycentres, then one 4:1 pooling per coarser level.  The
+// one copy of this sequence: every iteration, forward and adjoint, gets its centres here.
+static void ms_centres(hipStream_t st, const float* x, int nv, const int32_t* faces, const MsLevels& L, int scale) {
+    FGC_LAUNCH("face_centers_kernel", st, face_centers_kernel, dim3(cdiv(L.nn[0], 256)), dim3(256), 0, x, nv, faces, L.nn[0],
+               L.fps[0]);
+    for (int l = 1; l <= scale; ++l)
+        FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(L.nn[l] * 3, 256)), dim3(256), 0, L.fps[l - 1],
+                   L.nn[l], 3, L.fps[l]);
 }
 
-// ---------------------------------------------------------------------------------------------
-// the multi-scale update along a per-vertex direction: host side
-// ---------------------------------------------------------------------------------------------
-static bool ms_dir_apart(const float* p, size_t n, const float* q, size_t m) {   // [p, p+n) and [q, q+m) do not meet
+static bool ms_apart(const float* p, size_t n, const float* q, size_t m) {   // [p, p+n) and [q, q+m) do not meet
     return p + n <= q || q + m <= p;
 }
 
@@ -641,142 +528,125 @@ extern "C" size_t fgc_vertex_update_ms_dir_scratch_floats(int32_t nv, int32_t n0
     return (size_t)nv * 7 + 3 * ((size_t)n0 + n0 / 4 + n0 / 16);
 }
 
-// one constrained iteration at `scale`: the centre launches of fgc_vertex_update_ms, then the projected vertex kernel
-static void ms_dir_iteration(hipStream_t st, const float* x0, const float* cur, float* nxt, float* t, int nv,
-                             const int32_t* faces, int n0, const int32_t* v_faces, int k_v, int scale,
-                             const float* const* nrm, float* const* fps, const int* nn, const float* dirs, int dstride) {
-    FGC_LAUNCH("face_centers_kernel", st, face_centers_kernel, dim3(cdiv(n0, 256)), dim3(256), 0, cur, nv, faces, n0, fps[0]);
-    if (scale >= 1)
-        FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(nn[1] * 3, 256)), dim3(256), 0, fps[0], nn[1], 3,
-                   fps[1]);
-    if (scale >= 2)
-        FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(nn[2] * 3, 256)), dim3(256), 0, fps[1], nn[2], 3,
-                   fps[2]);
-    FGC_LAUNCH("vertex_update_ms_dir_kernel", st, vertex_update_ms_dir_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, x0, cur,
-               nxt, t, nv, v_faces, k_v, 2 * scale, nrm[scale], fps[scale], nn[scale], dirs, dstride);
+// The four forward entry points in one body, so that they cannot drift apart: free (dirs == NULL) or along dirs, the plain
+// form (traj == NULL: ping-pong buffers in the scratch, the result copied to x_out, dx_out optional) or the trajectory form
+// (every iteration writes its own slot of traj; x_out and dx_out are NULL).  The first iteration of the plain form reads
+// the caller's x in place.  Scratch: two position buffers (plain form), t [nv] (along dirs), the centres of the three levels.
+// fn: the entry point's name, for the messages; the wrappers have checked dirs / x_out / traj, whichever is theirs.
+static int ms_fwd_impl(const char* fn, const float* x, float* x_out, int32_t nv, const int32_t* faces, int32_t n0,
+                       const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
+                       const float* normals2, const int32_t* iters, const float* dirs, int32_t n_dirs, float* traj,
+                       size_t traj_floats, float* t_out, float* dx_out, float* scratch, size_t scratch_floats, void* stream) {
+    FGC_CHECK_ARG(x && faces && v_faces && normals0 && normals1 && normals2 && iters && scratch, "%s: null pointer", fn);
+    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0, "%s: nv=%d n0=%d (multiple of 16) k_v=%d", fn, nv, n0, k_v);
+    FGC_CHECK_ARG(!dirs || n_dirs == 1 || n_dirs == nv, "%s: n_dirs=%d (1, or nv=%d)", fn, n_dirs, nv);
+    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0, "%s: negative iteration count", fn);
+    const size_t nx = 3 * (size_t)nv;
+    const size_t ncentres = 3 * ((size_t)n0 + n0 / 4 + n0 / 16);
+    float* out = traj ? traj : x_out;
+    const size_t nout = traj ? ((size_t)iters[0] + iters[1] + iters[2] + 1) * nx : nx;
+    FGC_CHECK_ARG(!traj || traj_floats >= nout, "%s: traj too small (%zu < %zu floats)", fn, traj_floats, nout);
+    const size_t need = ncentres + (dirs ? (size_t)nv : 0) + (traj ? 0 : 2 * nx);
+    FGC_CHECK_ARG(scratch_floats >= need, "%s: scratch too small (%zu < %zu floats)", fn, scratch_floats, need);
+    FGC_CHECK_ARG(ms_apart(x, nx, out, nout) && ms_apart(x, nx, scratch, need) && ms_apart(out, nout, scratch, need),
+                  "%s: x, %s and the scratch must be distinct", fn, traj ? "traj" : "x_out");
+    FGC_CHECK_ARG(!dx_out || (ms_apart(dx_out, 3 * nx, x, nx) && ms_apart(dx_out, 3 * nx, out, nout) &&
+                              ms_apart(dx_out, 3 * nx, scratch, need) && (!t_out || ms_apart(dx_out, 3 * nx, t_out, nv))),
+                  "%s: dx_out must be a buffer of its own", fn);
+    FGC_CHECK_ARG(!t_out || (ms_apart(t_out, nv, x, nx) && ms_apart(t_out, nv, out, nout) && ms_apart(t_out, nv, scratch, need)),
+                  "%s: t_out must be a buffer of its own", fn);
+    hipStream_t st = (hipStream_t)stream;
+    // the buffers that copies and the memset touch come first, in whole rows: they keep the scratch's alignment
+    float* xa = scratch;                              // (plain form only)
+    float* xb = xa + nx;
+    float* t = traj ? scratch : xb + nx;              // (along dirs only)
+    const MsLevels L = ms_levels(normals0, normals1, normals2, n0, dirs ? t + nv : t);
+    if (dirs && hipMemsetAsync(t, 0, (size_t)nv * 4, st) != hipSuccess) {
+        fgc::set_error("%s: memset failed", fn);
+        return FGC_EHIP;
+    }
+    if (traj && hipMemcpyAsync(traj, x, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+        fgc::set_error("%s: copy failed", fn);
+        return FGC_EHIP;
+    }
+    const float* cur = traj ? traj : x;      // x0 is the caller's x through all three stages
+    float* nxt = traj ? traj + nx : xa;
+    for (int stage = 0; stage < 3; ++stage) {
+        const int scale = 2 - stage;                 // coarse to fine (train.py:1687)
+        float* start = dx_out ? dx_out + (size_t)stage * nx : nullptr;
+        // remember where this stage started: dx = x_end - x_start (train.py:1763)
+        if (start && hipMemcpyAsync(start, cur, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+            fgc::set_error("%s: copy failed", fn);
+            return FGC_EHIP;
+        }
+        for (int it = 0; it < iters[stage]; ++it) {
+            ms_centres(st, cur, nv, faces, L, scale);
+            if (dirs)
+                FGC_LAUNCH("vertex_update_ms_dir_kernel", st, vertex_update_ms_dir_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, x,
+                           cur, nxt, t, nv, v_faces, k_v, 2 * scale, L.nrm[scale], L.fps[scale], L.nn[scale], dirs,
+                           n_dirs == 1 ? 0 : 3);
+            else
+                FGC_LAUNCH("vertex_update_ms_kernel", st, vertex_update_ms_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, cur, nxt,
+                           nv, v_faces, k_v, 2 * scale, L.nrm[scale], L.fps[scale], L.nn[scale]);
+            cur = nxt;
+            nxt = traj ? nxt + nx : (nxt == xa ? xb : xa);
+        }
+        if (start)
+            FGC_LAUNCH("sub3_kernel", st, sub3_kernel, dim3(cdiv(nv * 3, 256)), dim3(256), 0, cur, start, nv * 3, start);
+    }
+    if ((x_out && hipMemcpyAsync(x_out, cur, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) ||
+        (t_out && hipMemcpyAsync(t_out, t, (size_t)nv * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)) {
+        fgc::set_error("%s: copy failed", fn);
+        return FGC_EHIP;
+    }
+    FGC_CHECK_LAUNCH(fn);
+    return FGC_OK;
+}
+
+extern "C" int fgc_vertex_update_ms(const float* x, float* x_out, int32_t nv, const int32_t* faces, int32_t n0,
+                                    const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
+                                    const float* normals2, const int32_t* iters, float* dx_out, float* scratch,
+                                    size_t scratch_floats, void* stream) {
+    FGC_CHECK_ARG(x_out, "fgc_vertex_update_ms: null pointer");
+    return ms_fwd_impl("fgc_vertex_update_ms", x, x_out, nv, faces, n0, v_faces, k_v, normals0, normals1, normals2, iters,
+                       nullptr, 0, nullptr, 0, nullptr, dx_out, scratch, scratch_floats, stream);
+}
+
+// the trajectory form: the same launches with the same arguments, every iteration writing its own slot of traj (slot 0 = x,
+// slot t + 1 = the output of iteration t) instead of a ping-pong buffer
+extern "C" int fgc_vertex_update_ms_traj(const float* x, int32_t nv, const int32_t* faces, int32_t n0,
+                                         const int32_t* v_faces, int32_t k_v, const float* normals0,
+                                         const float* normals1, const float* normals2, const int32_t* iters,
+                                         float* traj, size_t traj_floats, float* scratch, size_t scratch_floats,
+                                         void* stream) {
+    FGC_CHECK_ARG(traj, "fgc_vertex_update_ms_traj: null pointer");
+    return ms_fwd_impl("fgc_vertex_update_ms_traj", x, nullptr, nv, faces, n0, v_faces, k_v, normals0, normals1, normals2,
+                       iters, nullptr, 0, traj, traj_floats, nullptr, nullptr, scratch, scratch_floats, stream);
 }
 
 extern "C" int fgc_vertex_update_ms_dir(const float* x, float* x_out, int32_t nv, const int32_t* faces, int32_t n0,
                                         const int32_t* v_faces, int32_t k_v, const float* normals0, const float* normals1,
                                         const float* normals2, const int32_t* iters, const float* dirs, int32_t n_dirs,
                                         float* t_out, float* dx_out, float* scratch, size_t scratch_floats, void* stream) {
-    FGC_CHECK_ARG(x && x_out && faces && v_faces && normals0 && normals1 && normals2 && iters && dirs && scratch,
-                  "fgc_vertex_update_ms_dir: null pointer");
-    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0,
-                  "fgc_vertex_update_ms_dir: nv=%d n0=%d (multiple of 16) k_v=%d", nv, n0, k_v);
-    FGC_CHECK_ARG(n_dirs == 1 || n_dirs == nv, "fgc_vertex_update_ms_dir: n_dirs=%d (1, or nv=%d)", n_dirs, nv);
-    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0, "fgc_vertex_update_ms_dir: negative iteration count");
-    const size_t need = fgc_vertex_update_ms_dir_scratch_floats(nv, n0);
-    FGC_CHECK_ARG(scratch_floats >= need, "fgc_vertex_update_ms_dir: scratch too small (%zu < %zu floats)", scratch_floats,
-                  need);
-    const size_t nx = 3 * (size_t)nv;
-    FGC_CHECK_ARG(ms_dir_apart(x, nx, x_out, nx) && ms_dir_apart(x, nx, scratch, need) &&
-                      ms_dir_apart(x_out, nx, scratch, need),
-                  "fgc_vertex_update_ms_dir: x, x_out and the scratch must be distinct");
-    FGC_CHECK_ARG(!dx_out || (ms_dir_apart(dx_out, 3 * nx, x, nx) && ms_dir_apart(dx_out, 3 * nx, x_out, nx) &&
-                              ms_dir_apart(dx_out, 3 * nx, scratch, need) &&
-                              (!t_out || ms_dir_apart(dx_out, 3 * nx, t_out, nv))),
-                  "fgc_vertex_update_ms_dir: dx_out must be a buffer of its own");
-    FGC_CHECK_ARG(!t_out || (ms_dir_apart(t_out, nv, x, nx) && ms_dir_apart(t_out, nv, x_out, nx) &&
-                             ms_dir_apart(t_out, nv, scratch, need)),
-                  "fgc_vertex_update_ms_dir: t_out must be a buffer of its own");
-    const int n1 = n0 / 4, n2 = n0 / 16;
-    hipStream_t st = (hipStream_t)stream;
-    float* t = scratch;
-    float* fp0 = t + nv;
-    float* fp1 = fp0 + 3 * (size_t)n0;
-    float* fp2 = fp1 + 3 * (size_t)n1;
-    float* xa = fp2 + 3 * (size_t)n2;
-    float* xb = xa + nx;
-    const float* nrm[3] = {normals0, normals1, normals2};
-    float* fps[3] = {fp0, fp1, fp2};
-    const int nn[3] = {n0, n1, n2};
-    if (hipMemsetAsync(t, 0, (size_t)nv * 4, st) != hipSuccess) {
-        fgc::set_error("fgc_vertex_update_ms_dir: memset failed");
-        return FGC_EHIP;
-    }
-    const float* cur = x;      // x0 is the caller's x through all three stages: the first iteration reads it in place
-    float* nxt = xa;
-    for (int stage = 0; stage < 3; ++stage) {
-        const int scale = 2 - stage;                 // coarse to fine
-        float* start = nullptr;
-        if (dx_out) {
-            start = dx_out + (size_t)stage * nx;
-            if (hipMemcpyAsync(start, cur, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-                fgc::set_error("fgc_vertex_update_ms_dir: copy failed");
-                return FGC_EHIP;
-            }
-        }
-        for (int it = 0; it < iters[stage]; ++it) {
-            ms_dir_iteration(st, x, cur, nxt, t, nv, faces, n0, v_faces, k_v, scale, nrm, fps, nn, dirs,
-                             n_dirs == 1 ? 0 : 3);
-            cur = nxt;
-            nxt = nxt == xa ? xb : xa;
-        }
-        if (dx_out)
-            FGC_LAUNCH("sub3_kernel", st, sub3_kernel, dim3(cdiv(nv * 3, 256)), dim3(256), 0, cur, start, nv * 3, start);
-    }
-    if (hipMemcpyAsync(x_out, cur, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-        (t_out && hipMemcpyAsync(t_out, t, (size_t)nv * 4, hipMemcpyDeviceToDevice, st) != hipSuccess)) {
-        fgc::set_error("fgc_vertex_update_ms_dir: copy failed");
-        return FGC_EHIP;
-    }
-    FGC_CHECK_LAUNCH("fgc_vertex_update_ms_dir");
-    return FGC_OK;
+    FGC_CHECK_ARG(x_out && dirs, "fgc_vertex_update_ms_dir: null pointer");
+    return ms_fwd_impl("fgc_vertex_update_ms_dir", x, x_out, nv, faces, n0, v_faces, k_v, normals0, normals1, normals2, iters,
+                       dirs, n_dirs, nullptr, 0, t_out, dx_out, scratch, scratch_floats, stream);
 }
 
-// the trajectory form: the same launches with the same arguments, every iteration writing its own slot of traj
 extern "C" int fgc_vertex_update_ms_dir_traj(const float* x, int32_t nv, const int32_t* faces, int32_t n0,
                                              const int32_t* v_faces, int32_t k_v, const float* normals0,
                                              const float* normals1, const float* normals2, const int32_t* iters,
                                              const float* dirs, int32_t n_dirs, float* traj, size_t traj_floats,
                                              float* t_out, float* scratch, size_t scratch_floats, void* stream) {
-    FGC_CHECK_ARG(x && faces && v_faces && normals0 && normals1 && normals2 && iters && dirs && traj && scratch,
-                  "fgc_vertex_update_ms_dir_traj: null pointer");
-    FGC_CHECK_ARG(nv > 0 && n0 > 0 && n0 % 16 == 0 && k_v > 0,
-                  "fgc_vertex_update_ms_dir_traj: nv=%d n0=%d (multiple of 16) k_v=%d", nv, n0, k_v);
-    FGC_CHECK_ARG(n_dirs == 1 || n_dirs == nv, "fgc_vertex_update_ms_dir_traj: n_dirs=%d (1, or nv=%d)", n_dirs, nv);
-    FGC_CHECK_ARG(iters[0] >= 0 && iters[1] >= 0 && iters[2] >= 0,
-                  "fgc_vertex_update_ms_dir_traj: negative iteration count");
-    const int n1 = n0 / 4, n2 = n0 / 16;
-    const size_t nx = 3 * (size_t)nv;
-    const size_t T = (size_t)iters[0] + iters[1] + iters[2];
-    const size_t need_traj = (T + 1) * nx;
-    FGC_CHECK_ARG(traj_floats >= need_traj, "fgc_vertex_update_ms_dir_traj: traj too small (%zu < %zu floats)", traj_floats,
-                  need_traj);
-    const size_t need = (size_t)nv + 3 * ((size_t)n0 + n1 + n2);
-    FGC_CHECK_ARG(scratch_floats >= need, "fgc_vertex_update_ms_dir_traj: scratch too small (%zu < %zu floats)",
-                  scratch_floats, need);
-    FGC_CHECK_ARG(ms_dir_apart(x, nx, traj, need_traj) && ms_dir_apart(x, nx, scratch, need) &&
-                      ms_dir_apart(traj, need_traj, scratch, need),
-                  "fgc_vertex_update_ms_dir_traj: x, traj and the scratch must be distinct");
-    FGC_CHECK_ARG(!t_out || (ms_dir_apart(t_out, nv, x, nx) && ms_dir_apart(t_out, nv, traj, need_traj) &&
-                             ms_dir_apart(t_out, nv, scratch, need)),
-                  "fgc_vertex_update_ms_dir_traj: t_out must be a buffer of its own");
-    hipStream_t st = (hipStream_t)stream;
-    float* t = scratch;
-    float* fp0 = t + nv;
-    float* fp1 = fp0 + 3 * (size_t)n0;
-    float* fp2 = fp1 + 3 * (size_t)n1;
-    const float* nrm[3] = {normals0, normals1, normals2};
-    float* fps[3] = {fp0, fp1, fp2};
-    const int nn[3] = {n0, n1, n2};
-    if (hipMemsetAsync(t, 0, (size_t)nv * 4, st) != hipSuccess ||
-        hipMemcpyAsync(traj, x, nx * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        fgc::set_error("fgc_vertex_update_ms_dir_traj: copy failed");
-        return FGC_EHIP;
-    }
-    size_t k = 0;
-    for (int stage = 0; stage < 3; ++stage)
-        for (int it = 0; it < iters[stage]; ++it, ++k)
-            ms_dir_iteration(st, x, traj + k * nx, traj + (k + 1) * nx, t, nv, faces, n0, v_faces, k_v, 2 - stage, nrm, fps,
-                             nn, dirs, n_dirs == 1 ? 0 : 3);
-    if (t_out && hipMemcpyAsync(t_out, t, (size_t)nv * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
-        fgc::set_error("fgc_vertex_update_ms_dir_traj: copy failed");
-        return FGC_EHIP;
-    }
-    FGC_CHECK_LAUNCH("fgc_vertex_update_ms_dir_traj");
-    return FGC_OK;
+    FGC_CHECK_ARG(traj && dirs, "fgc_vertex_update_ms_dir_traj: null pointer");
+    return ms_fwd_impl("fgc_vertex_update_ms_dir_traj", x, nullptr, nv, faces, n0, v_faces, k_v, normals0, normals1,
+                       normals2, iters, dirs, n_dirs, traj, traj_floats, t_out, nullptr, scratch, scratch_floats, stream);
+}
+
+extern "C" size_t fgc_vertex_update_ms_bwd_workspace_floats(int32_t nv, int32_t n0) {
+    if (nv <= 0 || n0 <= 0) return 0;
+    const size_t nodes = (size_t)n0 + n0 / 4 + n0 / 16;
+    return (size_t)nv * 7 + 6 * nodes;      // lam, two gradient buffers; centres and their gradients of the three levels
 }
 
 extern "C" size_t fgc_vertex_update_ms_dir_bwd_workspace_floats(int32_t nv, int32_t n0) {
@@ -806,26 +676,18 @@ static int ms_bwd_impl(const char* fn, const float* traj, size_t traj_floats, in
     const size_t need_traj = ((size_t)iters[0] + iters[1] + iters[2] + 1) * 3 * (size_t)nv;
     FGC_CHECK_ARG(traj_floats >= need_traj, "%s: traj too small (%zu < %zu floats)", fn, traj_floats, need_traj);
     FGC_CHECK_ARG(g_out != g_x, "%s: g_out and g_x must be distinct", fn);
-    const int n1 = n0 / 4, n2 = n0 / 16;
     const int dstride = n_dirs == 1 ? 0 : 3;
     hipStream_t st = (hipStream_t)stream;
     float* lam = workspace;
     float* ga = lam + nv;
     float* gb = ga + 3 * (size_t)nv;
     float* gp = gb + 3 * (size_t)nv;                      // (along dirs only)
-    float* fp0 = dirs ? gp + 3 * (size_t)nv : gp;
-    float* fp1 = fp0 + 3 * (size_t)n0;
-    float* fp2 = fp1 + 3 * (size_t)n1;
-    float* gc0 = fp2 + 3 * (size_t)n2;
-    float* gc1 = gc0 + 3 * (size_t)n0;
-    float* gc2 = gc1 + 3 * (size_t)n1;
-    const float* nrm[3] = {normals0, normals1, normals2};
+    const MsLevels L = ms_levels(normals0, normals1, normals2, n0, dirs ? gp + 3 * (size_t)nv : gp);
+    float* gc0 = L.fps[2] + 3 * (size_t)L.nn[2];          // the centres' gradients, laid out like the centres behind them
+    float* gcs[3] = {gc0, gc0 + 3 * (size_t)L.nn[0], gc0 + 3 * ((size_t)L.nn[0] + L.nn[1])};
     float* gns[3] = {g_n0, g_n1, g_n2};
-    float* fps[3] = {fp0, fp1, fp2};
-    float* gcs[3] = {gc0, gc1, gc2};
-    const int nn[3] = {n0, n1, n2};
     for (int s = 0; s < 3; ++s)
-        if (hipMemsetAsync(gns[s], 0, (size_t)nn[s] * 12, st) != hipSuccess) {
+        if (hipMemsetAsync(gns[s], 0, (size_t)L.nn[s] * 12, st) != hipSuccess) {
             fgc::set_error("%s: memset failed", fn);
             return FGC_EHIP;
         }
@@ -838,32 +700,27 @@ static int ms_bwd_impl(const char* fn, const float* traj, size_t traj_floats, in
     float* cur = ga;     // dL/d x_{t+1}
     float* nxt = gb;
     for (int stage = 2; stage >= 0; --stage) {
-        const int scale = 2 - stage;
+        const int scale = 2 - stage, nn = L.nn[scale];
         for (int it = 0; it < iters[stage]; ++it) {
             --t;
             const float* xt = traj + t * 3 * (size_t)nv;
             // the centres the forward iteration read, recomputed by the forward's own kernels from x_t
-            FGC_LAUNCH("face_centers_kernel", st, face_centers_kernel, dim3(cdiv(n0, 256)), dim3(256), 0, xt, nv, faces, n0, fp0);
-            if (scale >= 1)
-                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n1 * 3, 256)), dim3(256), 0, fp0, n1, 3, fp1);
-            if (scale >= 2)
-                FGC_LAUNCH("pool4_avg_iz_kernel", st, pool4_avg_iz_kernel, dim3(cdiv(n2 * 3, 256)), dim3(256), 0, fp1, n2, 3, fp2);
+            ms_centres(st, xt, nv, faces, L, scale);
             if (dirs)
                 FGC_LAUNCH("project_rows_kernel", st, project_rows_kernel, dim3(cdiv(nv, 256)), dim3(256), 0, cur, nv, dirs,
                            dstride, gp);
-            FGC_LAUNCH("vertex_ms_bwd_node_kernel", st, vertex_ms_bwd_node_kernel, dim3(cdiv(nn[scale], 256)), dim3(256), 0,
-                       dirs ? gp : cur, xt, lam, slot_ptr, slot_vert, 2 * scale, nn[scale], nrm[scale], fps[scale], gcs[scale],
+            FGC_LAUNCH("vertex_ms_bwd_node_kernel", st, vertex_ms_bwd_node_kernel, dim3(cdiv(nn, 256)), dim3(256), 0,
+                       dirs ? gp : cur, xt, lam, slot_ptr, slot_vert, 2 * scale, nn, L.nrm[scale], L.fps[scale], gcs[scale],
                        gns[scale]);
             for (int l = scale; l >= 1; --l)
-                FGC_LAUNCH("pool4_avg_iz_bwd_kernel", st, pool4_avg_iz_bwd_kernel, dim3(cdiv(nn[l], 256)), dim3(256), 0,
-                           fps[l - 1], nn[l], gcs[l], gcs[l - 1]);
+                FGC_LAUNCH("pool4_avg_iz_bwd_kernel", st, pool4_avg_iz_bwd_kernel, dim3(cdiv(L.nn[l], 256)), dim3(256), 0,
+                           L.fps[l - 1], L.nn[l], gcs[l], gcs[l - 1]);
             if (dirs)
                 FGC_LAUNCH("vertex_ms_dir_bwd_vertex_kernel", st, vertex_ms_dir_bwd_vertex_kernel, dim3(cdiv(nv, 256)),
-                           dim3(256), 0, cur, gp, nv, lam, v_faces, k_v, 2 * scale, nrm[scale], nn[scale], inc_ptr, inc_face, gc0,
-                           nxt);
+                           dim3(256), 0, cur, gp, nv, lam, v_faces, k_v, 2 * scale, L.nrm[scale], nn, inc_ptr, inc_face, gc0, nxt);
             else
                 FGC_LAUNCH("vertex_ms_bwd_vertex_kernel", st, vertex_ms_bwd_vertex_kernel, dim3(cdiv(nv, 256)), dim3(256), 0,
-                           cur, nv, lam, v_faces, k_v, 2 * scale, nrm[scale], nn[scale], inc_ptr, inc_face, gc0, nxt);
+                           cur, nv, lam, v_faces, k_v, 2 * scale, L.nrm[scale], nn, inc_ptr, inc_face, gc0, nxt);
             float* tmp = cur;
             cur = nxt;
             nxt = tmp;

@@ -1604,13 +1604,12 @@ class FacetDenoiser:
     def _attach_rays(self, V, depth_dir, n0):
         """The ray table of the constrained vertex update and its buffers into the vertex state V."""
         nv = V["x"].shape[0]
-        if isinstance(depth_dir, torch.Tensor):
-            depth_dir = depth_dir.detach().cpu().numpy()
-        d = np.array(depth_dir, dtype=np.float32, order="C").reshape(-1, 3)
-        if d.shape[0] not in (1, nv) or not np.isfinite(d).all():
+        rows = ops.ray_rows(depth_dir, nv, self.device, "depth_dir").detach().clone()      # (the state's own copy)
+        d = rows.cpu().numpy()
+        if not np.isfinite(d).all():
             raise ValueError("depth_dir: finite rows, one or one per vertex (%d), got %d" % (nv, d.shape[0]))
         f = dict(dtype=torch.float32, device=self.device)
-        V["dirs"], V["dirs_key"] = torch.as_tensor(d, device=self.device), direction_key(d)
+        V["dirs"], V["dirs_key"] = rows, direction_key(d)
         V["dirs_r"] = torch.empty_like(V["dirs"])
         V["dir_scratch"] = torch.empty(self.L.fgc_vertex_update_ms_dir_scratch_floats(nv, n0), **f)
         V["dir_bwd_ws"] = torch.empty(self.L.fgc_vertex_update_ms_dir_bwd_workspace_floats(nv, n0), **f)
@@ -1664,6 +1663,35 @@ class FacetDenoiser:
         B, names = self._mesh["B"], ("nconv", "nconv1", "nconv2") if double else ("nconv", "y1", "y2")
         return tuple(B[k] for k in names), tuple(B["g_" + k] for k in names)
 
+    def _vertex_fwd(self, x, heads, rotate):
+        """The multi-scale vertex update of x with its trajectory into V["traj"]: the free one, or - the bound mesh has rays
+        (_step_rays) - the one along them."""
+        M, L, st = self._mesh, self.L, self._st()
+        V, rays = M["verts"], self._step_rays(rotate)
+        fn, what, sc, ray_args, t_out = L.fgc_vertex_update_ms_traj, "vertex update", V["centres"], (), ()
+        if rays is not None:
+            # along rays: the rays turn with the vertices (fgc_point_sets_prepare scales uniformly: they stay valid there)
+            if rotate:
+                _lib.check(L.fgc_rotate_rows(_p(V["dirs"]), _p(rays), rays.shape[0], 1, _p(M["B"]["R"]), st), "rotate rays")
+            fn, what, sc = L.fgc_vertex_update_ms_dir_traj, "vertex update along rays", V["dir_scratch"]
+            ray_args, t_out = (_p(rays), rays.shape[0]), (None,)
+        _lib.check(fn(_p(x), V["x"].shape[0], _p(V["faces"]), M["ns"][0], _p(V["v_faces"]), V["v_faces"].shape[1],
+                      *(_p(h) for h in heads), (C.c_int32 * 3)(*V["iters"]), *ray_args, _p(V["traj"]), V["traj"].numel(),
+                      *t_out, _p(sc), sc.numel(), st), what)
+
+    def _vertex_bwd(self, heads, g_heads, rotate):
+        """The adjoint of _vertex_fwd: V["g_p"] = dL/d refined vertices into V["g_x"] and the heads' gradients."""
+        M, L, st = self._mesh, self.L, self._st()
+        V, rays = M["verts"], self._step_rays(rotate)      # (rotated by the forward)
+        fn, what, ws, ray_args = L.fgc_vertex_update_ms_bwd, "vertex update bwd", V["bwd_ws"], ()
+        if rays is not None:
+            fn, what, ws = L.fgc_vertex_update_ms_dir_bwd, "vertex update along rays bwd", V["dir_bwd_ws"]
+            ray_args = (_p(rays), rays.shape[0])
+        _lib.check(fn(_p(V["traj"]), V["traj"].numel(), V["x"].shape[0], _p(V["faces"]), M["ns"][0], _p(V["v_faces"]),
+                      V["v_faces"].shape[1], *(_p(h) for h in heads), (C.c_int32 * 3)(*V["iters"]), *ray_args,
+                      *(_p(t) for t in V["tables"]), _p(V["g_p"]), _p(V["g_x"]), *(_p(g) for g in g_heads), _p(ws),
+                      ws.numel(), st), what)
+
     def _pointset_forward(self, rotate, want_grad, double=False):
         """Network (normalizeTensor on head 0 only, train.py:767-773), the rotated vertices moved by update_position_MS
         with its trajectory, fullLoss (and its gradient on the moved vertices).  double: trainDoubleLossNet's form
@@ -1694,22 +1722,7 @@ class FacetDenoiser:
             _lib.check(L.fgc_rotate_rows(_p(gt), _p(V["gtr"]), gt.shape[0], 1, _p(B["R"]), st), "rotate gt vertices")
             x, gt = V["xr"], V["gtr"]
         self._tag("pts:vertex_fwd")
-        it = (C.c_int32 * 3)(*V["iters"])
-        rays = self._step_rays(rotate)
-        if rays is not None:
-            # along rays: the rays turn with the vertices (fgc_point_sets_prepare scales uniformly: they stay valid there)
-            if rotate:
-                _lib.check(L.fgc_rotate_rows(_p(V["dirs"]), _p(rays), rays.shape[0], 1, _p(B["R"]), st), "rotate rays")
-            sc = V["dir_scratch"]
-            _lib.check(L.fgc_vertex_update_ms_dir_traj(_p(x), nv, _p(V["faces"]), n0, _p(V["v_faces"]),
-                                                       V["v_faces"].shape[1], _p(heads[0]), _p(heads[1]), _p(heads[2]), it,
-                                                       _p(rays), rays.shape[0], _p(V["traj"]), V["traj"].numel(), None,
-                                                       _p(sc), sc.numel(), st), "vertex update along rays")
-        else:
-            _lib.check(L.fgc_vertex_update_ms_traj(_p(x), nv, _p(V["faces"]), n0, _p(V["v_faces"]), V["v_faces"].shape[1],
-                                                   _p(heads[0]), _p(heads[1]), _p(heads[2]), it, _p(V["traj"]),
-                                                   V["traj"].numel(), _p(V["centres"]), V["centres"].numel(), st),
-                       "vertex update")
+        self._vertex_fwd(x, heads, rotate)
         self._tag("pts:loss")
         T = sum(V["iters"])
         refined = C.c_void_p(V["traj"].data_ptr() + T * nv * 12)
@@ -1730,29 +1743,11 @@ class FacetDenoiser:
         self._pointset_forward(rotate, True, double)
         M, L, st = self._mesh, self.L, self._st()
         B, V = M["B"], M["verts"]
-        n0, nv = M["ns"][0], V["x"].shape[0]
+        n0 = M["ns"][0]
         self._tag("pts:vertex_bwd")
-        it = (C.c_int32 * 3)(*V["iters"])
-        sp, sv, ip, fi = V["tables"]
-        wsv = V["bwd_ws"]
         # dL/d normals: head 0 into g_nconv (then through normalizeTensor), the raw coarse heads straight into g_y1 / g_y2
         # (double: the normalised coarse heads into g_nconv1 / g_nconv2, then through their own normalizeTensor)
-        heads, g_heads = self._vertex_heads(double)
-        rays = self._step_rays(rotate)      # (rotated by the forward)
-        if rays is not None:
-            wsv = V["dir_bwd_ws"]
-            _lib.check(L.fgc_vertex_update_ms_dir_bwd(_p(V["traj"]), V["traj"].numel(), nv, _p(V["faces"]), n0,
-                                                      _p(V["v_faces"]), V["v_faces"].shape[1], _p(heads[0]), _p(heads[1]),
-                                                      _p(heads[2]), it, _p(rays), rays.shape[0], _p(sp), _p(sv), _p(ip),
-                                                      _p(fi), _p(V["g_p"]), _p(V["g_x"]), _p(g_heads[0]), _p(g_heads[1]),
-                                                      _p(g_heads[2]), _p(wsv), wsv.numel(), st),
-                       "vertex update along rays bwd")
-        else:
-            _lib.check(L.fgc_vertex_update_ms_bwd(_p(V["traj"]), V["traj"].numel(), nv, _p(V["faces"]), n0, _p(V["v_faces"]),
-                                                  V["v_faces"].shape[1], _p(heads[0]), _p(heads[1]), _p(heads[2]), it,
-                                                  _p(sp), _p(sv), _p(ip), _p(fi), _p(V["g_p"]), _p(V["g_x"]),
-                                                  _p(g_heads[0]), _p(g_heads[1]), _p(g_heads[2]), _p(wsv), wsv.numel(), st),
-                       "vertex update bwd")
+        self._vertex_bwd(*self._vertex_heads(double), rotate)
         if double:
             self._tag("dl:bwd")      # (added to what the vertex adjoint has just written)
             sc = V["dl_scratch"]

@@ -570,23 +570,7 @@ def face_centers(x, faces):
 def vertex_update_ms(x, normals, faces, v_faces, iters=(80, 20, 20)):
     """update_position_MS (train.py:1668-1798), coarsening_steps = 2.  x [V,3]; normals = [n0 [N0,3], n1 [N0/4,3],
     n2 [N0/16,3]]; faces int [N0,3] (-1 rows = fake nodes); v_faces int [V,K].  Returns (x_out [V,3], dx [3,V,3])."""
-    _req_cuda(x, faces, v_faces, *normals)
-    x = _f32c(x)
-    n0, n1, n2 = (_f32c(t.reshape(-1, 3)) for t in normals)
-    faces = faces.to(torch.int32).contiguous()
-    v_faces = v_faces.to(torch.int32).contiguous()
-    nv, N0 = x.shape[0], faces.shape[0]
-    if n0.shape[0] != N0 or n1.shape[0] * 4 != N0 or n2.shape[0] * 16 != N0:
-        raise ValueError("normals must have N0, N0/4 and N0/16 rows (N0 = %d)" % N0)
-    out = torch.empty_like(x)
-    dx = torch.empty(3, nv, 3, dtype=torch.float32, device=x.device)
-    nscr = 3 * (2 * nv + N0 + N0 // 4 + N0 // 16)
-    scr = torch.empty(nscr, dtype=torch.float32, device=x.device)
-    it = (C.c_int32 * 3)(*[int(i) for i in iters])
-    check(_lib.lib().fgc_vertex_update_ms(ptr(x), ptr(out), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0),
-                                          ptr(n1), ptr(n2), it, ptr(dx), ptr(scr), nscr, stream_ptr()),
-          "fgc_vertex_update_ms")
-    return out, dx
+    return _ms_forward(x, normals, faces, v_faces, iters)
 
 
 def pack_cells(ijk):
@@ -724,30 +708,67 @@ def _ms_args(x, normals, faces, v_faces):
     return x, (n0, n1, n2), faces, v_faces
 
 
-def vertex_update_ms_traj(x, normals, faces, v_faces, iters=(80, 20, 20)):
-    """vertex_update_ms keeping every iterate: traj [T+1, V, 3] (traj[0] = x, traj[-1] = vertex_update_ms's x_out, bit
-    for bit; include/fgc.h: fgc_vertex_update_ms_traj)."""
+def ray_rows(dirs, nv, device, name="dirs"):
+    """Rows of rays ([V,3] or [1,3]; tensor or array-like) as the contiguous fp32 rows on `device` that the *_dir entry
+    points read: one row, or one per vertex.  name: what the caller calls them, for the message."""
+    if not isinstance(dirs, torch.Tensor):
+        dirs = torch.from_numpy(np.ascontiguousarray(np.asarray(dirs, dtype=np.float32)))
+    dirs = _f32c(dirs.to(device).reshape(-1, 3))
+    if dirs.shape[0] not in (1, nv):
+        raise ValueError("%s has %d rows: one row, or one per vertex (%d)" % (name, dirs.shape[0], nv))
+    return dirs
+
+
+def _given(dirs):
+    if dirs is None:      # (None selects the free form in the two helpers below: not through a *_dir function)
+        raise ValueError("dirs is None: the free update is vertex_update_ms")
+    return dirs
+
+
+def _ms_forward(x, normals, faces, v_faces, iters, dirs=None, traj=False, return_t=False):
+    """The four forward entry points of the multi-scale update: free (dirs None) or along dirs, the plain form -> (x_out,
+    dx) or, traj, the trajectory form -> traj [T+1, V, 3]; return_t (along dirs): t [V] appended."""
     x, (n0, n1, n2), faces, v_faces = _ms_args(x, normals, faces, v_faces)
     nv, N0 = x.shape[0], faces.shape[0]
-    T = sum(int(i) for i in iters)
-    traj = torch.empty(T + 1, nv, 3, dtype=torch.float32, device=x.device)
-    nscr = 3 * (N0 + N0 // 4 + N0 // 16)
-    scr = torch.empty(nscr, dtype=torch.float32, device=x.device)
+    L = _lib.lib()
+    f32 = dict(dtype=torch.float32, device=x.device)
     it = (C.c_int32 * 3)(*[int(i) for i in iters])
-    check(_lib.lib().fgc_vertex_update_ms_traj(ptr(x), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0),
-                                               ptr(n1), ptr(n2), it, ptr(traj), traj.numel(), ptr(scr), nscr,
-                                               stream_ptr()), "fgc_vertex_update_ms_traj")
-    return traj
+    mesh = (nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0), ptr(n1), ptr(n2), it)
+    nscr = 3 * (N0 + N0 // 4 + N0 // 16) + (0 if traj else 6 * nv)
+    rays = t_arg = ()
+    t = None
+    if dirs is not None:
+        dirs = ray_rows(dirs, nv, x.device)
+        t = torch.empty(nv, **f32) if return_t else None
+        rays, t_arg = (ptr(dirs), dirs.shape[0]), (ptr(t),)
+        nscr = L.fgc_vertex_update_ms_dir_scratch_floats(nv, N0)
+    scr = torch.empty(nscr, **f32)
+    tail = (ptr(scr), scr.numel(), stream_ptr())
+    if traj:
+        res = (torch.empty(sum(int(i) for i in iters) + 1, nv, 3, **f32),)
+        args = (ptr(x),) + mesh + rays + (ptr(res[0]), res[0].numel()) + t_arg + tail
+    else:
+        res = (torch.empty_like(x), torch.empty(3, nv, 3, **f32))
+        args = (ptr(x), ptr(res[0])) + mesh + rays + t_arg + (ptr(res[1]),) + tail
+    name = "fgc_vertex_update_ms" + ("_dir" if dirs is not None else "") + ("_traj" if traj else "")
+    check(getattr(L, name)(*args), name)
+    if return_t:
+        res += (t,)
+    return res[0] if len(res) == 1 else res
 
 
-def vertex_update_ms_bwd(traj, normals, faces, v_faces, g_out, iters=(80, 20, 20), tables=None):
-    """Adjoint of vertex_update_ms (include/fgc.h: fgc_vertex_update_ms_bwd): given the trajectory of
-    vertex_update_ms_traj and g_out = dL/dx_out [V,3], returns (dL/dx [V,3], [dL/dn0, dL/dn1, dL/dn2]).  tables: the
-    device tensors of vertex_ms_tables (built here when None)."""
+def _ms_backward(traj, normals, faces, v_faces, g_out, iters, tables, dirs=None):
+    """The two adjoint entry points of the multi-scale update, free (dirs None) or along dirs: (dL/dx [V,3], [dL/dn0,
+    dL/dn1, dL/dn2])."""
+    form = "_dir" if dirs is not None else ""
     nv = traj.shape[1]
     if traj.dtype != torch.float32 or not traj.is_contiguous():
-        raise ValueError("traj must be the contiguous float32 [T+1, V, 3] of vertex_update_ms_traj")
+        raise ValueError("traj must be the contiguous float32 [T+1, V, 3] of vertex_update_ms%s_traj" % form)
     _, (n0, n1, n2), faces, v_faces = _ms_args(traj[0], normals, faces, v_faces)
+    rays = ()
+    if dirs is not None:
+        dirs = ray_rows(dirs, nv, traj.device)
+        rays = (ptr(dirs), dirs.shape[0])
     _req_cuda(g_out)
     g_out = _f32c(g_out.reshape(nv, 3))
     N0 = faces.shape[0]
@@ -757,26 +778,27 @@ def vertex_update_ms_bwd(traj, normals, faces, v_faces, g_out, iters=(80, 20, 20
     sp, sv, ip, fi = tables
     g_x = torch.empty(nv, 3, dtype=torch.float32, device=traj.device)
     g_n = [torch.empty_like(t) for t in (n0, n1, n2)]
-    nws = _lib.lib().fgc_vertex_update_ms_bwd_workspace_floats(nv, N0)
-    ws = _workspace(nws * 4, traj.device, "vms_bwd")
+    L = _lib.lib()
+    name = "fgc_vertex_update_ms%s_bwd" % form
+    ws = _workspace(getattr(L, name + "_workspace_floats")(nv, N0) * 4, traj.device, "vms%s_bwd" % form)
     it = (C.c_int32 * 3)(*[int(i) for i in iters])
-    check(_lib.lib().fgc_vertex_update_ms_bwd(ptr(traj), traj.numel(), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0),
-                                              ptr(n1), ptr(n2), it, ptr(sp), ptr(sv), ptr(ip), ptr(fi), ptr(g_out),
-                                              ptr(g_x), ptr(g_n[0]), ptr(g_n[1]), ptr(g_n[2]), ptr(ws), ws.numel() // 4,
-                                              stream_ptr()), "fgc_vertex_update_ms_bwd")
+    check(getattr(L, name)(ptr(traj), traj.numel(), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0), ptr(n1),
+                           ptr(n2), it, *rays, ptr(sp), ptr(sv), ptr(ip), ptr(fi), ptr(g_out), ptr(g_x), ptr(g_n[0]),
+                           ptr(g_n[1]), ptr(g_n[2]), ptr(ws), ws.numel() // 4, stream_ptr()), name)
     return g_x, g_n
 
 
-def _ms_dirs(dirs, nv, device):
-    """dirs ([V,3] or [1,3]; tensor or array-like) as the contiguous fp32 device rows of the *_ms_dir entry points."""
-    if not isinstance(dirs, torch.Tensor):
-        dirs = torch.from_numpy(np.ascontiguousarray(np.asarray(dirs, dtype=np.float32)))
-    dirs = dirs.to(device)
-    _req_cuda(dirs)
-    dirs = _f32c(dirs.reshape(-1, 3))
-    if dirs.shape[0] not in (1, nv):
-        raise ValueError("dirs has %d rows: one row, or one per vertex (%d)" % (dirs.shape[0], nv))
-    return dirs
+def vertex_update_ms_traj(x, normals, faces, v_faces, iters=(80, 20, 20)):
+    """vertex_update_ms keeping every iterate: traj [T+1, V, 3] (traj[0] = x, traj[-1] = vertex_update_ms's x_out, bit
+    for bit; include/fgc.h: fgc_vertex_update_ms_traj)."""
+    return _ms_forward(x, normals, faces, v_faces, iters, traj=True)
+
+
+def vertex_update_ms_bwd(traj, normals, faces, v_faces, g_out, iters=(80, 20, 20), tables=None):
+    """Adjoint of vertex_update_ms (include/fgc.h: fgc_vertex_update_ms_bwd): given the trajectory of
+    vertex_update_ms_traj and g_out = dL/dx_out [V,3], returns (dL/dx [V,3], [dL/dn0, dL/dn1, dL/dn2]).  tables: the
+    device tensors of vertex_ms_tables (built here when None)."""
+    return _ms_backward(traj, normals, faces, v_faces, g_out, iters, tables)
 
 
 def vertex_update_ms_dir(x, normals, faces, v_faces, dirs, iters=(80, 20, 20), return_t=False):
@@ -784,65 +806,20 @@ def vertex_update_ms_dir(x, normals, faces, v_faces, dirs, iters=(80, 20, 20), r
     given; rows longer than 1 can diverge) - a build extension, include/fgc.h: fgc_vertex_update_ms_dir.  Returns
     (x_out [V,3], dx [3,V,3]); return_t: (x_out, dx, t [V]), t the signed step along the direction, x_out = fma(t, dirs,
     x)."""
-    x, (n0, n1, n2), faces, v_faces = _ms_args(x, normals, faces, v_faces)
-    nv, N0 = x.shape[0], faces.shape[0]
-    dirs = _ms_dirs(dirs, nv, x.device)
-    L = _lib.lib()
-    out = torch.empty_like(x)
-    dx = torch.empty(3, nv, 3, dtype=torch.float32, device=x.device)
-    t = torch.empty(nv, dtype=torch.float32, device=x.device) if return_t else None
-    scr = torch.empty(L.fgc_vertex_update_ms_dir_scratch_floats(nv, N0), dtype=torch.float32, device=x.device)
-    it = (C.c_int32 * 3)(*[int(i) for i in iters])
-    check(L.fgc_vertex_update_ms_dir(ptr(x), ptr(out), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0), ptr(n1),
-                                     ptr(n2), it, ptr(dirs), dirs.shape[0], ptr(t), ptr(dx), ptr(scr), scr.numel(),
-                                     stream_ptr()), "fgc_vertex_update_ms_dir")
-    return (out, dx, t) if return_t else (out, dx)
+    return _ms_forward(x, normals, faces, v_faces, iters, _given(dirs), return_t=return_t)
 
 
 def vertex_update_ms_dir_traj(x, normals, faces, v_faces, dirs, iters=(80, 20, 20), return_t=False):
     """vertex_update_ms_dir keeping every iterate: traj [T+1, V, 3] (traj[0] = x, traj[-1] = vertex_update_ms_dir's x_out,
     bit for bit; include/fgc.h: fgc_vertex_update_ms_dir_traj); return_t: (traj, t [V])."""
-    x, (n0, n1, n2), faces, v_faces = _ms_args(x, normals, faces, v_faces)
-    nv, N0 = x.shape[0], faces.shape[0]
-    dirs = _ms_dirs(dirs, nv, x.device)
-    L = _lib.lib()
-    T = sum(int(i) for i in iters)
-    traj = torch.empty(T + 1, nv, 3, dtype=torch.float32, device=x.device)
-    t = torch.empty(nv, dtype=torch.float32, device=x.device) if return_t else None
-    scr = torch.empty(L.fgc_vertex_update_ms_dir_scratch_floats(nv, N0), dtype=torch.float32, device=x.device)
-    it = (C.c_int32 * 3)(*[int(i) for i in iters])
-    check(L.fgc_vertex_update_ms_dir_traj(ptr(x), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1], ptr(n0), ptr(n1),
-                                          ptr(n2), it, ptr(dirs), dirs.shape[0], ptr(traj), traj.numel(), ptr(t), ptr(scr),
-                                          scr.numel(), stream_ptr()), "fgc_vertex_update_ms_dir_traj")
-    return (traj, t) if return_t else traj
+    return _ms_forward(x, normals, faces, v_faces, iters, _given(dirs), traj=True, return_t=return_t)
 
 
 def vertex_update_ms_dir_bwd(traj, normals, faces, v_faces, dirs, g_out, iters=(80, 20, 20), tables=None):
     """Adjoint of vertex_update_ms_dir (include/fgc.h: fgc_vertex_update_ms_dir_bwd): given the trajectory of
     vertex_update_ms_dir_traj and g_out = dL/dx_out [V,3], returns (dL/dx [V,3], [dL/dn0, dL/dn1, dL/dn2]); no gradient
     with respect to dirs.  tables: the device tensors of vertex_ms_tables (built here when None)."""
-    nv = traj.shape[1]
-    if traj.dtype != torch.float32 or not traj.is_contiguous():
-        raise ValueError("traj must be the contiguous float32 [T+1, V, 3] of vertex_update_ms_dir_traj")
-    _, (n0, n1, n2), faces, v_faces = _ms_args(traj[0], normals, faces, v_faces)
-    dirs = _ms_dirs(dirs, nv, traj.device)
-    _req_cuda(g_out)
-    g_out = _f32c(g_out.reshape(nv, 3))
-    N0 = faces.shape[0]
-    if tables is None:
-        tables = [torch.as_tensor(t, device=traj.device)
-                  for t in vertex_ms_tables(faces.cpu().numpy(), v_faces.cpu().numpy(), nv)]
-    sp, sv, ip, fi = tables
-    g_x = torch.empty(nv, 3, dtype=torch.float32, device=traj.device)
-    g_n = [torch.empty_like(t) for t in (n0, n1, n2)]
-    L = _lib.lib()
-    ws = _workspace(L.fgc_vertex_update_ms_dir_bwd_workspace_floats(nv, N0) * 4, traj.device, "vms_dir_bwd")
-    it = (C.c_int32 * 3)(*[int(i) for i in iters])
-    check(L.fgc_vertex_update_ms_dir_bwd(ptr(traj), traj.numel(), nv, ptr(faces), N0, ptr(v_faces), v_faces.shape[1],
-                                         ptr(n0), ptr(n1), ptr(n2), it, ptr(dirs), dirs.shape[0], ptr(sp), ptr(sv), ptr(ip),
-                                         ptr(fi), ptr(g_out), ptr(g_x), ptr(g_n[0]), ptr(g_n[1]), ptr(g_n[2]), ptr(ws),
-                                         ws.numel() // 4, stream_ptr()), "fgc_vertex_update_ms_dir_bwd")
-    return g_x, g_n
+    return _ms_backward(traj, normals, faces, v_faces, g_out, iters, tables, _given(dirs))
 
 
 def point_loss(p0, p1, sample_ind0, sample_ind1, threshold=5000.0, want_grad=True):

@@ -557,11 +557,7 @@ def depth_update(V, normals, e_map, v_e_map, depth_dir, iters):
     """What the single-scale drivers (inferNetOld, bilateral.denoise_mesh) run in the place of update_position2 when they are
     given viewing rays: update_position_with_depth on device tensors V [V,3], normals [F,3], e_map [1,E,4], v_e_map
     [1,V,slots] and depth_dir [V,3] / [1,3] (array-like or tensor).  Returns the positions [V,3]."""
-    if not isinstance(depth_dir, torch.Tensor):
-        depth_dir = torch.from_numpy(np.ascontiguousarray(np.asarray(depth_dir, dtype=np.float32)))
-    d = depth_dir.to(V.device).reshape(-1, 3)
-    if d.shape[0] not in (1, V.shape[0]):
-        raise ValueError("depth_dir has %d rows: one row, or one per vertex (%d)" % (d.shape[0], V.shape[0]))
+    d = ops.ray_rows(depth_dir, V.shape[0], V.device, "depth_dir")
     return update_position_with_depth(V.unsqueeze(0), normals.unsqueeze(0), e_map, v_e_map, d, iter_num=iters)[0][0]
 
 
@@ -576,10 +572,11 @@ def updateFacesCenter(vertices, faces, coarsening_steps):
 
 
 class _UpdatePositionMSFn(torch.autograd.Function):
+    """The multi-scale update with its adjoint, free (dirs None) or along the rays `dirs` (no gradient with respect to them)."""
     @staticmethod
-    def forward(ctx, x, n0, n1, n2, faces, v_faces, iters, tables):
-        traj = ops.vertex_update_ms_traj(x, [n0, n1, n2], faces, v_faces, iters)
-        ctx.save_for_backward(traj, n0, n1, n2, faces, v_faces)
+    def forward(ctx, x, n0, n1, n2, faces, v_faces, dirs, iters, tables):
+        traj = ops._ms_forward(x, [n0, n1, n2], faces, v_faces, iters, dirs, traj=True)
+        ctx.save_for_backward(traj, n0, n1, n2, faces, v_faces, dirs)
         ctx.iters, ctx.tables = iters, tables
         ctx.set_materialize_grads(False)      # (unused outputs: None, not zero tensors)
         T0, T1 = iters[0], iters[0] + iters[1]
@@ -589,43 +586,11 @@ class _UpdatePositionMSFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_out, g_dx0, g_dx1, g_dx2):
-        traj, n0, n1, n2, faces, v_faces = ctx.saved_tensors
-        it = ctx.iters
-        if g_out is None or any(g is not None for g in (g_dx0, g_dx1, g_dx2)):
-            raise NotImplementedError("update_position_MS differentiates its positions, not the stage displacements")
-        g_x, g_n = ops.vertex_update_ms_bwd(traj, [n0, n1, n2], faces, v_faces, g_out, it, tables=ctx.tables)
-        return g_x, g_n[0], g_n[1], g_n[2], None, None, None, None
-
-
-class _UpdatePositionMSDirFn(torch.autograd.Function):
-    """_UpdatePositionMSFn along the rays `dirs` (no gradient with respect to them)."""
-    @staticmethod
-    def forward(ctx, x, n0, n1, n2, faces, v_faces, dirs, iters, tables):
-        traj = ops.vertex_update_ms_dir_traj(x, [n0, n1, n2], faces, v_faces, dirs, iters)
-        ctx.save_for_backward(traj, n0, n1, n2, faces, v_faces, dirs)
-        ctx.iters, ctx.tables = iters, tables
-        ctx.set_materialize_grads(False)
-        T0, T1 = iters[0], iters[0] + iters[1]
-        return traj[-1].clone(), traj[T0] - traj[0], traj[T1] - traj[T0], traj[-1] - traj[T1]
-
-    @staticmethod
-    def backward(ctx, g_out, g_dx0, g_dx1, g_dx2):
         traj, n0, n1, n2, faces, v_faces, dirs = ctx.saved_tensors
         if g_out is None or any(g is not None for g in (g_dx0, g_dx1, g_dx2)):
             raise NotImplementedError("update_position_MS differentiates its positions, not the stage displacements")
-        g_x, g_n = ops.vertex_update_ms_dir_bwd(traj, [n0, n1, n2], faces, v_faces, dirs, g_out, ctx.iters,
-                                                tables=ctx.tables)
+        g_x, g_n = ops._ms_backward(traj, [n0, n1, n2], faces, v_faces, g_out, ctx.iters, ctx.tables, dirs)
         return g_x, g_n[0], g_n[1], g_n[2], None, None, None, None, None
-
-
-def _depth_rows(depth_dir, nv, device):
-    """depth_dir ([V,3] or [1,3]; array-like or tensor) as fp32 device rows, one row or one per vertex."""
-    if not isinstance(depth_dir, torch.Tensor):
-        depth_dir = torch.from_numpy(np.ascontiguousarray(np.asarray(depth_dir, dtype=np.float32)))
-    d = depth_dir.to(device=device, dtype=torch.float32).reshape(-1, 3).contiguous()
-    if d.shape[0] not in (1, nv):
-        raise ValueError("depth_dir has %d rows: one row, or one per vertex (%d)" % (d.shape[0], nv))
-    return d
 
 
 def update_position_MS(x, face_normals_list, faces, v_faces0, coarsening_steps, iter_num_list=[80, 20, 20], tables=None,
@@ -644,26 +609,15 @@ def update_position_MS(x, face_normals_list, faces, v_faces0, coarsening_steps, 
     diverge."""
     if coarsening_steps != 2 or len(face_normals_list) != 3:
         raise NotImplementedError("three levels pooled 4:1, as the network has them (settings.py:31-32)")
-    if depth_dir is not None:
-        xr = x.reshape(-1, 3)
-        nv = xr.shape[0]
-        d = _depth_rows(depth_dir, nv, xr.device)
-        ns = [t.reshape(-1, 3) for t in face_normals_list]
-        it = tuple(int(i) for i in iter_num_list)
-        if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in face_normals_list)):
-            out, d0, d1, d2 = _UpdatePositionMSDirFn.apply(xr, *ns, faces.reshape(-1, 3), v_faces0.reshape(nv, -1), d, it,
-                                                           tables)
-            return out.unsqueeze(0), [d0, d1, d2]
-        out, dx = ops.vertex_update_ms_dir(xr, ns, faces.reshape(-1, 3), v_faces0.reshape(nv, -1), d, it)
-        return out.unsqueeze(0), [dx[0], dx[1], dx[2]]
+    xr = x.reshape(-1, 3)
+    nv = xr.shape[0]
+    d = None if depth_dir is None else ops.ray_rows(depth_dir, nv, xr.device, "depth_dir")
+    ns = [t.reshape(-1, 3) for t in face_normals_list]
+    faces, vf, it = faces.reshape(-1, 3), v_faces0.reshape(nv, -1), tuple(int(i) for i in iter_num_list)
     if torch.is_grad_enabled() and (x.requires_grad or any(t.requires_grad for t in face_normals_list)):
-        nv = x.reshape(-1, 3).shape[0]
-        out, d0, d1, d2 = _UpdatePositionMSFn.apply(x.reshape(-1, 3), *[t.reshape(-1, 3) for t in face_normals_list],
-                                                     faces.reshape(-1, 3), v_faces0.reshape(nv, -1),
-                                                     tuple(int(i) for i in iter_num_list), tables)
+        out, d0, d1, d2 = _UpdatePositionMSFn.apply(xr, *ns, faces, vf, d, it, tables)
         return out.unsqueeze(0), [d0, d1, d2]
-    out, dx = ops.vertex_update_ms(x.reshape(-1, 3), [t.reshape(-1, 3) for t in face_normals_list], faces.reshape(-1, 3),
-                                   v_faces0.reshape(x.reshape(-1, 3).shape[0], -1), iter_num_list)
+    out, dx = ops._ms_forward(xr, ns, faces, vf, it, d)
     return out.unsqueeze(0), [dx[0], dx[1], dx[2]]
 
 
@@ -690,9 +644,7 @@ def inferNet(inputMesh, net_or_checkpoint, device="cuda", depth_dir=None):
     dev = net.device
     c = lambda t: t.cpu().numpy()
     n_patches = len(inputMesh.in_list)
-    rays = None
-    if depth_dir is not None:
-        rays = _depth_rows(depth_dir, inputMesh.vNum, dev)
+    rays = None if depth_dir is None else ops.ray_rows(depth_dir, inputMesh.vNum, dev, "depth_dir")
     if n_patches > 1:
         # train.py:255-330: the vertex positions of the patches are averaged over the patches that hold a vertex, the
         # normals of a face are those of the last patch that holds it, and (as in the reference) the three position
@@ -715,13 +667,10 @@ def inferNet(inputMesh, net_or_checkpoint, device="cuda", depth_dir=None):
         xp = torch.as_tensor(inputMesh.v_list[i][0], dtype=torch.float32, device=dev)
         faces = torch.as_tensor(np.asarray(inputMesh.faces_list[i][0]).astype(np.int32), device=dev)
         vf = torch.as_tensor(np.asarray(inputMesh.v_faces_list[i][0]).astype(np.int32), device=dev)
-        if rays is None:
-            pts, dx = ops.vertex_update_ms(xp, [n0, n1, n2], faces, vf, (80, 20, 20))
-        else:
-            d = rays
-            if len(inputMesh.vOldInd_list[i]) and rays.shape[0] > 1:      # a patch: the rows of its own vertices
-                d = rays[torch.as_tensor(np.asarray(inputMesh.vOldInd_list[i]).astype(np.int64), device=dev)]
-            pts, dx = ops.vertex_update_ms_dir(xp, [n0, n1, n2], faces, vf, d, (80, 20, 20))
+        d = rays
+        if rays is not None and len(inputMesh.vOldInd_list[i]) and rays.shape[0] > 1:      # a patch: the rows of its own vertices
+            d = rays[torch.as_tensor(np.asarray(inputMesh.vOldInd_list[i]).astype(np.int64), device=dev)]
+        pts, dx = ops._ms_forward(xp, [n0, n1, n2], faces, vf, (80, 20, 20), d)
         pts_mid = pts - dx[2]                                        # train.py:249-250
         pts_coarse = pts_mid - dx[1]
         perm = torch.as_tensor(np.asarray(inputMesh.permutations[i]).astype(np.int64), device=dev)

@@ -202,6 +202,19 @@ def test_ragged_sizes(name):
             assert (vf[-1] < 0).all()
             assert np.array_equal(_bits(_np(out)[-1]), _bits(V[-1])) and _np(t)[-1] == 0
             assert np.array_equal(_bits(_np(g_x)[-1]), _bits(g_out[-1]))
+    # the free forms run through the same driver: the same inputs, bit for bit among themselves and from run to run
+    args = args[:4]
+    out, dx = ops.vertex_update_ms(*args, its)
+    traj = ops.vertex_update_ms_traj(*args, its)
+    T0, T1 = its[0], its[0] + its[1]
+    assert traj.shape[0] == sum(its) + 1 and torch.equal(traj[0], args[0]) and torch.equal(traj[-1], out)
+    assert torch.equal(dx[0], traj[T0] - traj[0]) and torch.equal(dx[1], traj[T1] - traj[T0])
+    assert torch.equal(dx[2], traj[-1] - traj[T1]) and np.abs(_np(out) - V).max() > 1e-3
+    out2, dx2 = ops.vertex_update_ms(*args, its)
+    assert torch.equal(out, out2) and torch.equal(dx, dx2) and torch.equal(ops.vertex_update_ms_traj(*args, its), traj)
+    if name == "t257":      # the isolated vertex again: its position bits, and g_out's row through the free adjoint
+        g_x, _ = ops.vertex_update_ms_bwd(traj, *args[1:], _dev(g_out), its)
+        assert np.array_equal(_bits(_np(out)[-1]), _bits(V[-1])) and np.array_equal(_bits(_np(g_x)[-1]), _bits(g_out[-1]))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
