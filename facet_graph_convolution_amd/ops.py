@@ -546,6 +546,43 @@ def ray_cast_tree(tree, origins, dirs, t_min=0.0, want_bary=False, sort_rays=Tru
     return (t, face, bary) if want_bary else (t, face)
 
 
+CP_EXHAUSTIVE = 1  # FGC_CP_EXHAUSTIVE of include/fgc.h
+
+
+def closest_point_tree(tree, points, want_bary=False, sort_points=True, exhaustive=False):
+    """The closest point of the mesh of a RayTree to every row of points [Q,3] (include/fgc.h: fgc_closest_point_tree; a
+    build extension) on GPU tensors.  Returns (dist [Q] fp32 = sqrt(dist2) in IEEE, face [Q] int32, the original face
+    index) - a mesh without a face that takes part gives (+inf, -1) - and with want_bary also bary [Q,2] = (u, v), the
+    point being (1 - u - v) a + u b + v c.  sort_points: query in the (stable) Morton order of the points and scatter the
+    results back - neighbours in a wave then walk the same nodes.  exhaustive: no culling, every point against every
+    record (points x faces pairs).  Neither changes one bit of the result."""
+    if not isinstance(tree, RayTree):
+        raise TypeError("closest_point_tree needs the RayTree that ray_tree returns (got %s)" % type(tree).__name__)
+    _req_cuda(tree.tree, points)
+    points = _f32c(points.reshape(-1, 3))
+    nq = points.shape[0]
+    if nq == 0:
+        raise ValueError("closest_point_tree needs at least one point")
+    perm = None
+    if sort_points and nq > 1:
+        perm = torch.sort(_morton30(points), stable=True).indices
+        points = points[perm].contiguous()
+    dev = points.device
+    d2 = torch.empty(nq, dtype=torch.float32, device=dev)
+    face = torch.empty(nq, dtype=torch.int32, device=dev)
+    bary = torch.empty(nq, 2, dtype=torch.float32, device=dev) if want_bary else None
+    check(_lib.lib().fgc_closest_point_tree(ptr(tree.tree), tree.tree.numel(), tree.nf, ptr(points), nq,
+                                            CP_EXHAUSTIVE if exhaustive else 0, ptr(d2), ptr(face), ptr(bary), stream_ptr()),
+          "fgc_closest_point_tree")
+    if perm is not None:
+        d2 = torch.empty_like(d2).index_copy_(0, perm, d2)
+        face = torch.empty_like(face).index_copy_(0, perm, face)
+        if want_bary:
+            bary = torch.empty_like(bary).index_copy_(0, perm, bary)
+    dist = torch.sqrt(d2)
+    return (dist, face, bary) if want_bary else (dist, face)
+
+
 def pool4_avg_iz(x):
     """custom_binary_tree_pooling(x, steps=2, 'avg_ignore_zeros') (model.py:792-814) on [n, c] rows."""
     _req_cuda(x)

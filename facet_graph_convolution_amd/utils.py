@@ -767,6 +767,78 @@ def mesh_distances(V0, V1):
     return out
 
 
+def closest_points(P, V, faces, accel=None):
+    """The closest point of the mesh (V, faces) to every row of P (ops.closest_point_tree, include/fgc.h:
+    fgc_closest_point_tree), numpy in and out: (dist float32 [Q], face int32 [Q], point float64 [Q,3]).  accel: a handle of
+    utils.ray_tree built of these very arrays, so that several point sets share a build; None builds one for this call.
+    The point is rebuilt in float64 from the kernel's (u, v) and the vertices: (1 - u - v) a + u b + v c.  A mesh without a
+    face that takes part gives (inf, -1, nan)."""
+    from . import ops
+    V32 = np.array(V, dtype=np.float32).reshape(-1, 3)
+    F = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    if accel is None:
+        accel = ray_tree(V32, F)
+    elif not isinstance(accel, ops.RayTree):
+        raise ValueError("accel must be None or a handle of utils.ray_tree (got %r)" % (accel,))
+    if (accel.nv, accel.nf) != (V32.shape[0], F.shape[0]):
+        raise ValueError("the tree was built of a mesh of %d vertices and %d faces, this one has %d and %d"
+                         % (accel.nv, accel.nf, V32.shape[0], F.shape[0]))
+    dist, face, bary = (x.cpu().numpy() for x in ops.closest_point_tree(accel, _put(P, np.float32), want_bary=True))
+    T = V32.astype(np.float64)[F[np.maximum(face, 0)].clip(0, V32.shape[0] - 1)]
+    u, v = bary[:, :1].astype(np.float64), bary[:, 1:].astype(np.float64)
+    point = (1.0 - u - v) * T[:, 0] + u * T[:, 1] + v * T[:, 2]
+    point[face < 0] = np.nan
+    return dist, face, point
+
+
+class SurfaceTree:
+    """What surface_tree returns: the float32 shift, the shifted vertices, the faces and the tree built of them."""
+
+    def __init__(self, shift, V, faces, tree):
+        self.shift, self.V, self.faces, self.tree = shift, V, faces, tree
+
+
+def surface_tree(V, faces, shift=None):
+    """A mesh prepared as the SURFACE of surface_distances: translated by `shift` (float32 [1,3]; None: its own float32
+    corner) and put under a bounding-box tree on the current GPU.  Pass it as accel= so that several meshes scored against
+    one ground truth share its build."""
+    V = np.asarray(V).reshape(-1, 3)
+    shift = V.min(0).astype(np.float32)[None] if shift is None else np.asarray(shift, dtype=np.float32).reshape(1, 3)
+    Vt = (V - shift).astype(np.float32)
+    F = np.asarray(faces).astype(np.int64).reshape(-1, 3)
+    return SurfaceTree(shift, Vt, F, ray_tree(Vt, F))
+
+
+def surface_distances(V0, V1, F1, F0=None, accel=None):
+    """Distances between a mesh and a SURFACE: the counterpart of mesh_distances, which measures to the nearest vertex.
+    Normalised like it - float32 corner translation, division by the bounding-box diagonal of V0 u V1 - with the division
+    applied to the distances (a distance scales with the coordinates, so this is the same number up to rounding, and the
+    tree of the surface does not depend on V0); the translation takes the coordinates' magnitude out of the fp32 error.
+      ev_max, ev_mean, ev_rms   max / mean / root mean square over the vertices V0 of the distance to the surface (V1, F1):
+                                E_v of the denoising papers,
+      comp_max, comp_mean       (with F0) max / mean over the vertices V1 of the distance to the surface (V0, F0),
+      hausdorff                 (with F0) max(ev_max, comp_max);
+    without F0 the last three are nan.  V0 and V1 need not have the same number of vertices.  accel: surface_tree(V1, F1),
+    to share the build of one surface among several V0 (the translation is then that surface's own corner instead of the
+    corner of V0 u V1).  Returns a dict of float32 values.  The distances are ops.closest_point_tree's."""
+    V0, V1 = np.asarray(V0).reshape(-1, 3), np.asarray(V1).reshape(-1, 3)
+    lo = np.minimum(V0.min(0), V1.min(0))
+    hi = np.maximum(V0.max(0), V1.max(0))
+    diag = math.sqrt(sum(math.pow(float(h) - float(l), 2) for l, h in zip(lo, hi)))
+    if accel is None:
+        accel = surface_tree(V1, F1, lo.astype(np.float32)[None])
+    elif not isinstance(accel, SurfaceTree):
+        raise ValueError("accel must be None or a handle of utils.surface_tree (got %r)" % (accel,))
+    A = (V0 - accel.shift).astype(np.float32)
+    ev = closest_points(A, accel.V, accel.faces, accel.tree)[0].astype(np.float64) / diag
+    out = {"ev_max": ev.max(), "ev_mean": ev.mean(), "ev_rms": math.sqrt(float((ev * ev).mean())),
+           "comp_max": np.nan, "comp_mean": np.nan, "hausdorff": np.nan}
+    if F0 is not None:
+        comp = closest_points(accel.V, A, F0)[0].astype(np.float64) / diag
+        out.update(comp_max=comp.max(), comp_mean=comp.mean(), hausdorff=max(ev.max(), comp.max()))
+    return {k: np.float32(v) for k, v in out.items()}
+
+
 def angularDiffVec(n0, n1):
     """utils.py:1218-1239: per-row angle in degrees between n0 and n1, arccos(0.999999 * <normalize(n0), normalize(n1)>)
     with the reference's double normalisation (1e-8 in the norm); fake nodes (rows of n1 with every |entry| <= 1e-3)

@@ -72,7 +72,8 @@ extern "C" {
  * depth scans for the vertex networks; fgc_ray_cast (+ _workspace_bytes), rays against a triangle list: virtual depth
  * scans of a clean mesh; fgc_ray_tree_bytes / fgc_ray_tree_build / fgc_ray_cast_tree, the same cast through a bounding-box
  * tree: scans of large meshes; fgc_synth_noise_sensor, the noise of a triangulating depth sensor along the viewing rays:
- * sigma grows with the range, depth is quantised in disparity. */
+ * sigma grows with the range, depth is quantised in disparity; fgc_closest_point_tree, the closest point on a mesh through
+ * the same tree: distances to a surface. */
 #define FGC_ABI_VERSION 116
 
 const char* fgc_last_error(void);
@@ -1160,6 +1161,69 @@ int fgc_ray_tree_build(const float* verts, int32_t nv, const int32_t* faces, int
 int fgc_ray_cast_tree(const void* tree, size_t tree_bytes, int32_t nf, const float* origins, int32_t n_origins,
                       const float* dirs, int32_t nq, float t_min, float* t_out, int32_t* face_out, float* bary_out,
                       void* stream);
+
+/* Closest point on the mesh of a tree, for every point q in [0, nq): the walk of fgc_ray_cast_tree with a distance bound in
+ * place of the slab test.  tree, tree_bytes, nf: those of fgc_ray_tree_build, untouched (any order of the records).
+ *
+ * THE PAIR.  Record (a, e1, e2), point q, x . y = fma(x_z, y_z, fma(x_y, y_y, x_x y_x)); fp32 throughout, IEEE divisions, no
+ *   contraction: every fused operation is one of the fma written here, va, vb, vc are two products and one subtraction.
+ *   The region walk of Ericson, Real-Time Collision Detection 5.1.5; the FIRST region that applies wins:
+ *     ap = q - a;  d1 = e1 . ap, d2 = e2 . ap                     d1 <= 0 and d2 <= 0                 -> (u, v) = (0, 0)
+ *     bp = ap - e1; d3 = e1 . bp, d4 = e2 . bp                    d3 >= 0 and d4 <= d3                -> (1, 0)
+ *     vc = d1 d4 - d3 d2                                          vc <= 0, d1 >= 0, d3 <= 0           -> (d1 / (d1 - d3), 0)
+ *     cp = ap - e2; d5 = e1 . cp, d6 = e2 . cp                    d6 >= 0 and d5 <= d6                -> (0, 1)
+ *     vb = d5 d2 - d1 d6                                          vb <= 0, d2 >= 0, d6 <= 0           -> (0, d2 / (d2 - d6))
+ *     va = d3 d6 - d5 d4;  w = (d4 - d3) / ((d4 - d3) + (d5 - d6))
+ *                                                                 va <= 0, d4 - d3 >= 0, d5 - d6 >= 0 -> (1 - w, w)
+ *     otherwise  den = 1 / ((va + vb) + vc), u = vb den, v = vc den, then clamped by comparisons that leave a NaN alone:
+ *                u < 0 -> 0, u > 1 -> 1, v < 0 -> 0, v > 1 - u -> 1 - u
+ *     r_x = fma(-v, e2_x, fma(-u, e1_x, ap_x)) (y, z alike);  dist2 = r . r;  the closest point is a + u e1 + v e2.
+ *   The clamp of the last region is this build's addition to Ericson: in exact arithmetic it does nothing; in fp32 it keeps
+ *   (u, v) inside u >= 0, v >= 0, u + v <= 1 + 2^-24 whatever cancellation did to va, vb, vc on a sliver, so the point lies
+ *   on the triangle in EVERY region, which the culling bound below needs.  A record with e1 = e2 = 0 (all six +-0) takes no
+ *   part: a triangle collapsed to a point, which is how the tree stores an invalid row and the padding (a wave-uniform
+ *   test: records come through scalar loads).  A NaN dist2 never wins, every comparison with it being false: a collinear
+ *   triangle that reaches the last line with 0 x inf, a non-finite coordinate of the record (it is multiplied into r in
+ *   every region, 0 x inf included) or of q.  A dist2 that overflowed to +inf does not win either.
+ * RESULT.  Per point the smallest (dist2 bits, face_of) in full key order over ALL records that take part: dist2_out [nq],
+ *   face_out [nq] the ORIGINAL face index, bary_out [nq,2] = (u, v) of the winner (may be NULL).  No winner: (+inf, -1, (0, 0)).
+ * THE INVARIANT.  flags = 0 returns, for every point, bit for bit what FGC_CP_EXHAUSTIVE returns (no culling: every point
+ *   tests every record, nq x nf pairs - the brute force, through the same kernel with every bound taken as 0).  Hence the
+ *   result of a point is a function of the mesh and that point alone: not of the order of the records or of the points, the
+ *   neighbours in the wave, the launch geometry, eager or replayed.
+ * THE BOUND of a lane's point against a box (lo, hi): per axis g = max(lo - q, q - hi, 0) taken by comparisons that keep a
+ *   NaN, g' = max(g - 2^-18 max(|lo|, |hi|, |q|), 0); s = g'_x^2 + g'_y^2 + g'_z^2 summed in that order;
+ *   lb = max(s - (s 2^-21 + 2^-125), 0).  The lane takes part in the box iff lb <= best dist2 and lb < inf, non-strict: an
+ *   equal dist2 on a lower face index inside a box at exactly best is still found.  A box is skipped only if lb > best.
+ *   Why lb never exceeds the COMPUTED dist2 of a record in the box.  The box holds the original vertices a, b, c exactly
+ *   (min / max), so on every axis |a|, |b|, |c| <= B = max(|lo|, |hi|) and, with M = max(B, |q|): |e1|, |e2| <= 2B(1 + 2^-24),
+ *   each within 2^-24 2B of b - a, c - a.  (u, v) lies in the triangle of the parameter plane up to 2^-24 (every region,
+ *   thanks to the clamp), so p = a + u e1 + v e2 taken exactly lies within 2^-24 4B(1 + ..) of the real triangle, which is
+ *   inside the box: |q - p| >= g - 2^-22 B(1 + ..), g taken exactly; the computed g adds 2^-24 2M.  The computed r is
+ *   q - p up to three roundings (the subtraction, two fma) of intermediates no larger than |q| + |a| + |e1| + |e2| <= 6M(1 + ..):
+ *   18 x 2^-24 M.  Together below 25 x 2^-24 M per axis - absolute, in units of the coordinates, NOT relative to the distance:
+ *   a point near the surface has g ~ 0 and the full error.  The slack 2^-18 M is 64 x 2^-24 M.  So g' <= |computed r| on
+ *   every axis; the three squares and two sums of s round up by at most (1 + 2^-24)^3, r . r rounds down by at most as
+ *   much, and 2^-21 (and 2^-125 for a sum that underflowed) is more than both: lb <= dist2.  Over-visiting a few boxes
+ *   costs nothing measurable; losing the winner is a wrong answer.  An empty box (+inf, -inf) gives inf - inf, a NaN, which
+ *   no comparison admits; so does a point with a NaN.  Records the tree keeps out of every box (a non-finite vertex) have a
+ *   NaN dist2 and win nothing under FGC_CP_EXHAUSTIVE either.
+ * THE WALK is fgc_ray_cast_tree's: one wave of 64 points per workgroup, a wave-uniform stack of (node, ballot) entries in
+ *   LDS, boxes and records through scalar loads; a lane takes part in a node only while its own bound allows, with the best
+ *   it has at that moment.  The children of a node are visited NEAREST-FIRST by the wave's smallest lb over the lanes that
+ *   take part, among equal lb (a point near the surface lies inside several boxes: lb = 0) by the smallest squared distance
+ *   to the middle of the box, then by index; the farthest is pushed first.  Before the search the wave walks the tree once
+ *   greedily - every lane follows only its own nearest child by that order, down to one leaf - so that each lane starts
+ *   the search with a finite best of its own neighbourhood.  By the invariant, the order and the first walk change the
+ *   time and not one bit (the first walk only tests pairs the search may test again).  A lane beyond nq holds the last
+ *   point and stores nothing.  NO LOOP ENDS ON DEVICE DATA: a walk pushes each node at most once, so each of the two pops at most (number of
+ *   nodes) times, a host-side count; the stack holds at most 7 entries per level + 1; every popped id is bounded before
+ *   it addresses anything.  One launch, no atomics, no workspace, enqueue-only, capturable.
+ * A NULL among tree, points, dist2_out, face_out; nf or nq <= 0; nf > FGC_RAY_CAST_MAX_FACES; flag bits other than
+ *   FGC_CP_EXHAUSTIVE; a tree that is misaligned or below fgc_ray_tree_bytes(nf): FGC_EINVAL, nothing launched. */
+#define FGC_CP_EXHAUSTIVE 1u
+int fgc_closest_point_tree(const void* tree, size_t tree_bytes, int32_t nf, const float* points, int32_t nq, uint32_t flags,
+                           float* dist2_out, int32_t* face_out, float* bary_out, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Checkpoint files (CPU; HOST pointers)
