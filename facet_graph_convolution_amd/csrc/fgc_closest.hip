@@ -4,16 +4,15 @@
 // box is skipped only if a lower bound that never exceeds the COMPUTED dist2 of a record inside it is > the lane's best: the
 // tree returns bit for bit what FGC_CP_EXHAUSTIVE returns (include/fgc.h and DESIGN.md 8e.2 have the argument).
 //
-// cp_kernel   one wave of 64 points per workgroup, one point per lane, the walk of rt_cast_kernel: a stack of (node, ballot of
-//             the lanes whose bound let them in) in the wave's LDS, popped into SGPRs, boxes and records through scalar loads.
-//             A lane takes part in a child only while lower bound <= its best dist2.  The children of a node are visited
+// cp_kernel   one wave of 64 points per workgroup, one point per lane, the walk of rt_cast_kernel (fgc_treewalk.h).  A lane
+//             takes part in a child only while lower bound <= its best dist2.  The children of a node are visited
 //             nearest-first by the wave's smallest (bound, distance to the middle of the box) over the lanes that take part
 //             (the farthest is pushed first), after one greedy walk that gives every lane a finite best: a good bound early.
 //             The order and the greedy walk change the time and, by the invariant above, not one bit.
-// No loop ends on device data: each of the two walks pops at most `nodes` times (a host-side count; a walk pushes each node
-// at most once), the stack holds at most 7 entries per level + 1, and every popped id is bounded before it addresses anything.
+// The stack, the bounded pop, the node and leaf loads and the push are the steps of fgc_treewalk.h, which argues why a walk
+// ends and stays in bounds; what is here is the point's: cp_lower, the greedy mask, the wave's order, the skip, cp_pair.
 #include "fgc_closest.h"
-#include "fgc_raytree.h"
+#include "fgc_treewalk.h"
 
 #pragma clang fp contract(off)
 
@@ -67,9 +66,7 @@ __global__ __launch_bounds__(64) void cp_kernel(const f32x4* __restrict__ rec, c
                                                 const float* __restrict__ points, int nq, int all,
                                                 float* __restrict__ dist2_out, int* __restrict__ face_out,
                                                 float* __restrict__ bary_out, unsigned* __restrict__ count_out) {
-    __shared__ unsigned st_id[RT_STACK];                    // (L << 28) | k
-    __shared__ unsigned long long st_mask[RT_STACK];        // the lanes whose bound let them into that node
-    __shared__ float ent[RT_FAN][64];                       // a node's lower bounds, one row per child
+    __shared__ RtWave W;
     const int lane = threadIdx.x;
     const int i = blockIdx.x * 64 + lane;
     const bool live = i < nq;
@@ -91,25 +88,13 @@ __global__ __launch_bounds__(64) void cp_kernel(const f32x4* __restrict__ rec, c
 #pragma unroll 1
     for (int pass = all ? 1 : 0; pass < 2; ++pass) {
         const bool greedy = pass == 0;
-        int sp = 1;
-        st_id[0] = (unsigned)depth << 28;
-        st_mask[0] = __ballot(live);
+        int sp = rt_start(W, depth, live);
         for (unsigned it = 0; it < nodes && sp > 0; ++it) {
-            --sp;
-            const unsigned long long mask_v = st_mask[sp];
-            const unsigned id = __builtin_amdgcn_readfirstlane(st_id[sp]);
-            const unsigned long long mask = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(mask_v >> 32)) << 32) |
-                                            __builtin_amdgcn_readfirstlane((unsigned)mask_v);
-            const int L = (int)(id >> 28), k = (int)(id & 0x0FFFFFFFu);
-            if (L < 1 || L > depth || k >= S.n[L]) continue;          // the wave's own ids; bounded all the same
-            const f32x4* nb = boxes + (size_t)(S.noff[L] + (unsigned)k) * RT_NODE_F4;      // wave-uniform: scalar loads
-            f32x4 b4[RT_NODE_F4];
-#pragma unroll
-            for (int x = 0; x < RT_NODE_F4; ++x) b4[x] = nb[x];
+            int L, k;
+            bool active;
+            if (!rt_pop(W, sp, S, depth, L, k, active)) continue;
             float bx[RT_FAN * 6];
-#pragma unroll
-            for (int x = 0; x < RT_NODE_F4; ++x) bx[4 * x] = b4[x].x, bx[4 * x + 1] = b4[x].y, bx[4 * x + 2] = b4[x].z, bx[4 * x + 3] = b4[x].w;
-            const bool active = (mask >> lane) & 1ull;
+            rt_node(boxes, S, L, k, bx);
             const int nchild = S.n[L - 1];          // the boxes of the level below (the leaves for L = 1)
             if (COUNT && active) n_boxes += RT_FAN;
             if (COUNT) ++w_nodes;
@@ -130,7 +115,7 @@ __global__ __launch_bounds__(64) void cp_kernel(const f32x4* __restrict__ rec, c
 #pragma unroll
             for (int c = 0; c < RT_FAN; ++c) {
                 const float lb = (greedy && c != mine) ? __builtin_nanf("") : lbv[c];
-                ent[c][lane] = lb;
+                W.ent[c][lane] = lb;
                 const bool in = lb <= best && lb < __builtin_inff();
                 key[c] = cp_wave_min(in ? __float_as_uint(lb) : 0xFFFFFFFFu);
                 key2[c] = cp_wave_min(in && __float_as_uint(lb) == key[c] ? __float_as_uint(cen[c]) : 0xFFFFFFFFu);
@@ -152,13 +137,8 @@ __global__ __launch_bounds__(64) void cp_kernel(const f32x4* __restrict__ rec, c
                     const int c = (int)((ord >> (4 * r)) & 7u);
                     const int child = RT_FAN * k + c;
                     if (child >= nchild) continue;
-                    const float lb = ent[c][lane];
-                    const unsigned long long m = __ballot(lb <= best && lb < __builtin_inff());
-                    if (m != 0 && sp < RT_STACK) {
-                        st_id[sp] = ((unsigned)(L - 1) << 28) | (unsigned)child;
-                        st_mask[sp] = m;
-                        ++sp;
-                    }
+                    const float lb = W.ent[c][lane];
+                    rt_push(W, sp, L, child, __ballot(lb <= best && lb < __builtin_inff()));
                 }
             } else {
 #pragma unroll 1
@@ -166,18 +146,13 @@ __global__ __launch_bounds__(64) void cp_kernel(const f32x4* __restrict__ rec, c
                     const int c = (int)((ord >> (4 * r)) & 7u);
                     const int leaf = RT_FAN * k + c;
                     if (leaf >= nchild || leaf >= S.nleaf) continue;
-                    const float lb = ent[c][lane];
+                    const float lb = W.ent[c][lane];
                     const bool meet = lb <= best && lb < __builtin_inff();          // best as it is NOW: earlier leaves have shrunk it
                     if (__ballot(meet) == 0) continue;
                     if (COUNT) ++w_leaves;
-                    const f32x4* rb = rec + 3 * (size_t)RC_CHUNK * leaf;      // wave-uniform: scalar loads
-                    const int* fb = face_of + (size_t)RC_CHUNK * leaf;
                     f32x4 rr[3 * RC_CHUNK];
                     int fid[RC_CHUNK];
-#pragma unroll
-                    for (int x = 0; x < 3 * RC_CHUNK; ++x) rr[x] = rb[x];
-#pragma unroll
-                    for (int x = 0; x < RC_CHUNK; ++x) fid[x] = fb[x];
+                    rt_leaf(rec, face_of, leaf, rr, fid);
 #pragma unroll
                     for (int x = 0; x < RC_CHUNK; ++x) {
                         const f32x4 e1 = rr[3 * x + 1], e2 = rr[3 * x + 2];
@@ -213,22 +188,10 @@ static int cp_query(const char* what, const void* tree, size_t tree_bytes, int32
     FGC_CHECK_ARG(nf > 0 && nq > 0, "%s: nf=%d nq=%d (both > 0)", what, nf, nq);
     FGC_CHECK_ARG(nf <= FGC_RAY_CAST_MAX_FACES, "%s: nf=%d (at most %d)", what, nf, FGC_RAY_CAST_MAX_FACES);
     FGC_CHECK_ARG((flags & ~FGC_CP_EXHAUSTIVE) == 0, "%s: unknown flags 0x%x", what, flags);
-    FGC_CHECK_ARG((uintptr_t)tree % 16 == 0, "%s: tree needs 16-byte alignment", what);
-    const RtLayout T = rt_layout(nf);
-    FGC_CHECK_ARG(tree_bytes >= T.total, "%s: tree too small (%zu < %zu bytes)", what, tree_bytes, T.total);
-    hipStream_t st = (hipStream_t)stream;
-    const char* base = (const char*)tree;
-    const int all = (int)(flags & FGC_CP_EXHAUSTIVE);
-#ifdef FGC_CP_COUNT
-    if (count_out)
-        FGC_LAUNCH("cp_kernel", st, cp_kernel<true>, dim3(cdiv(nq, 64)), dim3(64), 0, (const f32x4*)base,
-                   (const int*)(base + T.face_of), (const f32x4*)(base + T.boxes), T.s, T.nodes, points, nq, all, dist2_out,
-                   face_out, bary_out, count_out);
-    else
-#endif
-        FGC_LAUNCH("cp_kernel", st, cp_kernel<false>, dim3(cdiv(nq, 64)), dim3(64), 0, (const f32x4*)base,
-                   (const int*)(base + T.face_of), (const f32x4*)(base + T.boxes), T.s, T.nodes, points, nq, all, dist2_out,
-                   face_out, bary_out, (unsigned*)nullptr);
+    RtView T;
+    if (int rc = rt_view(what, tree, tree_bytes, nf, T)) return rc;
+    FGC_LAUNCH("cp_kernel", (hipStream_t)stream, RT_COUNT_KERNEL(cp_kernel, count_out), dim3(cdiv(nq, 64)), dim3(64), 0, T.rec,
+               T.face_of, T.boxes, T.s, T.nodes, points, nq, (int)(flags & FGC_CP_EXHAUSTIVE), dist2_out, face_out, bary_out, count_out);
     FGC_CHECK_LAUNCH(what);
     return FGC_OK;
 }

@@ -1,6 +1,6 @@
-// The per-pair arithmetic of the ray casts (include/fgc.h: fgc_ray_cast, fgc_ray_cast_tree): ONE definition, shared by the
-// brute-force kernels (fgc_raycast.hip) and the tree kernels (fgc_raytree.hip), so that a pair tested by either gives the
-// same bits.  Contraction is off, every FMA is written out.
+// What the ray casts share (include/fgc.h: fgc_ray_cast, fgc_ray_cast_tree): ONE definition each of a face's record, a lane's
+// ray and the per-pair arithmetic, for the brute-force kernels (fgc_raycast.hip) and the tree kernels (fgc_raytree.hip), so
+// that a pair tested by either gives the same bits.  Contraction is off, every FMA is written out.
 #pragma once
 #include "fgc_common.h"
 
@@ -30,6 +30,34 @@ __device__ __forceinline__ bool rc_uvt(const float (&o)[3], const float (&d)[3],
     v = rc_dot(d[0], d[1], d[2], qx, qy, qz) / det;
     t = rc_dot(e2.x, e2.y, e2.z, qx, qy, qz) / det;
     return v >= 0.f && u + v <= 1.f && t > t_min && t < __builtin_inff();
+}
+
+// Face f as a record: (a, 0), (e1 = b - a, 0), (e2 = c - a, 0), and its three vertices in v.  An f outside [0, nf) (the
+// padding) or a row with a vertex id outside [0, nv) gives the zero record (det = 0: it can never hit) and false; nothing is
+// loaded through an id that was not bounded.  v is written only where true is returned.  A caller that does not read v
+// pays nothing: the values are the loads the record needs anyway.
+__device__ __forceinline__ bool rc_record(const float* __restrict__ verts, int nv, const int* __restrict__ faces, int nf, int f,
+                                          f32x4& r0, f32x4& r1, f32x4& r2, float (&v)[3][3]) {
+    r0 = r1 = r2 = f32x4{0.f, 0.f, 0.f, 0.f};
+    if ((unsigned)f >= (unsigned)nf) return false;
+    const int id[3] = {faces[3 * (size_t)f], faces[3 * (size_t)f + 1], faces[3 * (size_t)f + 2]};
+    if (!((unsigned)id[0] < (unsigned)nv && (unsigned)id[1] < (unsigned)nv && (unsigned)id[2] < (unsigned)nv)) return false;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k][0] = verts[3 * (size_t)id[k]], v[k][1] = verts[3 * (size_t)id[k] + 1], v[k][2] = verts[3 * (size_t)id[k] + 2];
+    r0 = f32x4{v[0][0], v[0][1], v[0][2], 0.f};
+    r1 = f32x4{v[1][0] - v[0][0], v[1][1] - v[0][1], v[1][2] - v[0][2], 0.f};
+    r2 = f32x4{v[2][0] - v[0][0], v[2][1] - v[0][1], v[2][2] - v[0][2], 0.f};
+    return true;
+}
+
+// Ray q of a cast with one origin row or one per ray.  A dead lane's ray is o = d = 0: det = 0, never a hit.
+__device__ __forceinline__ void rc_load_ray(const float* __restrict__ origins, int n_origins, const float* __restrict__ dirs,
+                                            int q, bool live, float (&o)[3], float (&d)[3]) {
+    o[0] = o[1] = o[2] = d[0] = d[1] = d[2] = 0.f;
+    if (!live) return;
+    const size_t oo = n_origins == 1 ? 0 : 3 * (size_t)q;
+    o[0] = origins[oo], o[1] = origins[oo + 1], o[2] = origins[oo + 2];
+    d[0] = dirs[3 * (size_t)q], d[1] = dirs[3 * (size_t)q + 1], d[2] = dirs[3 * (size_t)q + 2];
 }
 
 }  // namespace fgc

@@ -3,9 +3,8 @@
 // utils.depth_image); run once per mesh at preparation time, never per training step.
 //
 // Three launches:
-//   rc_gather_kernel  one thread per record: triangle f as three float4 (a, e1 = b - a, e2 = c - a); a row with a vertex id
-//                     outside [0, nv) and the padding behind nf become zero records (det = 0: they can never hit).  The
-//                     same launch sets every ray's key to (+inf, -1).
+//   rc_gather_kernel  one thread per record: rc_record of triangle f (zero records for a bad row and the padding behind nf).
+//                     The same launch sets every ray's key to (+inf, -1).
 //   rc_cast_kernel    64 rays per workgroup, one per lane and the same in all four waves (bl_filter_kernel's shape); the
 //                     records are wave-uniform: chunks of RC_CHUNK come through scalar loads and reach the VALU from SGPRs,
 //                     the waves take the chunks of the workgroup's slab in turn.  Each lane keeps its smallest (t, face),
@@ -64,21 +63,10 @@ __global__ __launch_bounds__(256) void rc_gather_kernel(const float* __restrict_
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j < nq) keys[j] = RC_MISS;
     if (j >= nrec) return;
-    f32x4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = r0, r2 = r0;
-    if (j < nf) {
-        const int a = faces[3 * (size_t)j], b = faces[3 * (size_t)j + 1], c = faces[3 * (size_t)j + 2];
-        if ((unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv) {
-            const float* pa = verts + 3 * (size_t)a;
-            const float* pb = verts + 3 * (size_t)b;
-            const float* pc = verts + 3 * (size_t)c;
-            r0 = f32x4{pa[0], pa[1], pa[2], 0.f};
-            r1 = f32x4{pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2], 0.f};
-            r2 = f32x4{pc[0] - pa[0], pc[1] - pa[1], pc[2] - pa[2], 0.f};
-        }
-    }
-    rec[3 * (size_t)j] = r0;
-    rec[3 * (size_t)j + 1] = r1;
-    rec[3 * (size_t)j + 2] = r2;
+    f32x4 r0, r1, r2;
+    float v[3][3];
+    rc_record(verts, nv, faces, nf, j, r0, r1, r2, v);
+    rec[3 * (size_t)j] = r0, rec[3 * (size_t)j + 1] = r1, rec[3 * (size_t)j + 2] = r2;
 }
 
 // grid (ceil(nq / 64), slabs)
@@ -92,12 +80,8 @@ __global__ __launch_bounds__(RC_THREADS) void rc_cast_kernel(const f32x4* __rest
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int q = blockIdx.x * RC_Q + lane;
     const bool live = q < nq;
-    float o[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f};      // (a dead lane's ray has d = 0: det = 0, never a hit)
-    if (live) {
-        const size_t oo = n_origins == 1 ? 0 : 3 * (size_t)q;
-        o[0] = origins[oo], o[1] = origins[oo + 1], o[2] = origins[oo + 2];
-        d[0] = dirs[3 * (size_t)q], d[1] = dirs[3 * (size_t)q + 1], d[2] = dirs[3 * (size_t)q + 2];
-    }
+    float o[3], d[3];
+    rc_load_ray(origins, n_origins, dirs, q, live, o, d);
     float best_t = __builtin_inff();
     int best_f = -1;
     // records [j0, j1) of this slab, whole chunks (nrec and per_slab are multiples of RC_CHUNK); faces in rising order, so

@@ -1,5 +1,5 @@
 // The layout of the bounding-box tree (include/fgc.h: fgc_ray_tree_build), shared by its builder and the ray walk
-// (fgc_raytree.hip) and by the closest-point walk (fgc_closest.hip): the constants of the format and where each part of the
+// (fgc_raytree.hip) and by the closest-point walk (fgc_closest.hip): the constants of the format, where each part of the
 // buffer starts.  Nothing here decides a byte of what is built; fgc_raytree.hip describes the format.
 #pragma once
 #include "fgc_raycast.h"

@@ -5,7 +5,7 @@
 //
 // The tree is implicit: a caller-given order of the triangles, cut into chunks of RC_CHUNK records (the leaves), and above
 // them levels of fan-out 8.  Nothing in the buffer is a pointer or an index that addresses memory:
-//   records   nrec x 3 float4, record j = (a, 0), (e1, 0), (e2, 0) of face order[j] (what rc_gather_kernel makes of it)
+//   records   nrec x 3 float4, record j = (a, 0), (e1, 0), (e2, 0) of face order[j] (rc_record of fgc_raycast.h)
 //   face_of   nrec x int32, order[j] (-1 behind nf)
 //   nodes     node (L, k), L = 1 .. depth, k < n[L]: the boxes of its 8 children, 8 x (lo.xyz, hi.xyz) = 48 dwords, three
 //             16-dword scalar loads like a chunk of records.  The children of (1, k) are the leaves 8k .. 8k + 7, those of
@@ -15,16 +15,15 @@
 // rt_leaf_kernel   one thread per leaf box (padding included): its four records, their face ids, and the exact min / max over
 //                  the ORIGINAL vertices of its valid, finite faces.
 // rt_level_kernel  one launch per level above, one thread per box: the union of its 8 children (min / max: exact).
-// rt_cast_kernel   one wave of 64 rays per workgroup, one ray per lane.  The walk is the wave's: a stack of (node, ballot of
-//                  the lanes that met it) in the wave's LDS row, popped into SGPRs, so node boxes and records come through
-//                  scalar loads and no memory access diverges.  A lane takes part in a node only if ITS ray met that node and
-//                  every node above it, tests a leaf's records only if its ray meets the leaf's box within [t_min, best_t]
-//                  at that moment, and keeps the smallest (t, face_of) in full key order.  Children go in index order, so
-//                  the leaves a lane tests, and in which order, are what its own ray would visit walking alone: the result
-//                  of a ray does not depend on its neighbours, the launch or the order of the rays.
-// No loop ends on device data: the walk pops at most `nodes` times (a host-side count; each node is pushed at most once),
-// the stack holds at most 7 entries per level + 1, and every popped id is bounded before it addresses anything.
-#include "fgc_raytree.h"          // the layout: RtShape, rt_layout, the RT_ constants
+// rt_cast_kernel   one wave of 64 rays per workgroup, one ray per lane, the walk the wave's (fgc_treewalk.h).  A lane takes
+//                  part in a node only if ITS ray met that node and every node above it, tests a leaf's records only if
+//                  its ray meets the leaf's box within [t_min, best_t] at that moment, and keeps the smallest (t, face_of)
+//                  in full key order.  Children go in index order, so the leaves a lane tests, and in which order, are what
+//                  its own ray would visit walking alone: the result of a ray does not depend on its neighbours, the launch
+//                  or the order of the rays.
+// The stack, the bounded pop, the node and leaf loads and the push are the steps of fgc_treewalk.h, which argues why a walk
+// ends and stays in bounds; what is here is the ray's: the slab test, `entry <= best_t`, index order, rc_uvt.
+#include "fgc_treewalk.h"         // the walk's steps, and through fgc_raytree.h the layout: RtShape, rt_layout, the RT_ constants
 
 #pragma clang fp contract(off)
 
@@ -48,28 +47,16 @@ __global__ __launch_bounds__(256) void rt_leaf_kernel(const float* __restrict__ 
         for (int k = 0; k < RC_CHUNK; ++k) {
             const int j = RC_CHUNK * i + k;
             const int f = j < nf ? order[j] : -1;
-            f32x4 r0 = {0.f, 0.f, 0.f, 0.f}, r1 = r0, r2 = r0;
-            if ((unsigned)f < (unsigned)nf) {
-                const int a = faces[3 * (size_t)f], b = faces[3 * (size_t)f + 1], c = faces[3 * (size_t)f + 2];
-                if ((unsigned)a < (unsigned)nv && (unsigned)b < (unsigned)nv && (unsigned)c < (unsigned)nv) {
-                    const float* pa = verts + 3 * (size_t)a;
-                    const float* pb = verts + 3 * (size_t)b;
-                    const float* pc = verts + 3 * (size_t)c;
-                    r0 = f32x4{pa[0], pa[1], pa[2], 0.f};
-                    r1 = f32x4{pb[0] - pa[0], pb[1] - pa[1], pb[2] - pa[2], 0.f};
-                    r2 = f32x4{pc[0] - pa[0], pc[1] - pa[1], pc[2] - pa[2], 0.f};
-                    if (rt_finite3(pa) && rt_finite3(pb) && rt_finite3(pc)) {
+            f32x4 r0, r1, r2;
+            float v[3][3];
+            if (rc_record(verts, nv, faces, nf, f, r0, r1, r2, v) && rt_finite3(v[0]) && rt_finite3(v[1]) && rt_finite3(v[2])) {
 #pragma unroll
-                        for (int x = 0; x < 3; ++x) {
-                            lo[x] = fminf(lo[x], fminf(pa[x], fminf(pb[x], pc[x])));
-                            hi[x] = fmaxf(hi[x], fmaxf(pa[x], fmaxf(pb[x], pc[x])));
-                        }
-                    }
+                for (int x = 0; x < 3; ++x) {
+                    lo[x] = fminf(lo[x], fminf(v[0][x], fminf(v[1][x], v[2][x])));
+                    hi[x] = fmaxf(hi[x], fmaxf(v[0][x], fmaxf(v[1][x], v[2][x])));
                 }
             }
-            rec[3 * (size_t)j] = r0;
-            rec[3 * (size_t)j + 1] = r1;
-            rec[3 * (size_t)j + 2] = r2;
+            rec[3 * (size_t)j] = r0, rec[3 * (size_t)j + 1] = r1, rec[3 * (size_t)j + 2] = r2;
             face_of[j] = f;
         }
     }
@@ -125,18 +112,12 @@ __global__ __launch_bounds__(64) void rt_cast_kernel(const f32x4* __restrict__ r
                                                      const float* __restrict__ dirs, int nq, float t_min,
                                                      float* __restrict__ t_out, int* __restrict__ face_out,
                                                      float* __restrict__ bary_out, unsigned* __restrict__ count_out) {
-    __shared__ unsigned st_id[RT_STACK];                    // (L << 28) | k
-    __shared__ unsigned long long st_mask[RT_STACK];        // the lanes whose ray met that node
-    __shared__ float ent[RT_FAN][64];                       // a leaf node's entry values, one row per child
+    __shared__ RtWave W;
     const int lane = threadIdx.x;
     const int q = blockIdx.x * 64 + lane;
     const bool live = q < nq;
-    float o[3] = {0.f, 0.f, 0.f}, d[3] = {0.f, 0.f, 0.f};
-    if (live) {
-        const size_t oo = n_origins == 1 ? 0 : 3 * (size_t)q;
-        o[0] = origins[oo], o[1] = origins[oo + 1], o[2] = origins[oo + 2];
-        d[0] = dirs[3 * (size_t)q], d[1] = dirs[3 * (size_t)q + 1], d[2] = dirs[3 * (size_t)q + 2];
-    }
+    float o[3], d[3];
+    rc_load_ray(origins, n_origins, dirs, q, live, o, d);
     const float inv[3] = {1.f / d[0], 1.f / d[1], 1.f / d[2]};
     const bool neg[3] = {inv[0] < 0.f, inv[1] < 0.f, inv[2] < 0.f};
     float best_t = __builtin_inff(), best_u = 0.f, best_v = 0.f;
@@ -144,25 +125,13 @@ __global__ __launch_bounds__(64) void rt_cast_kernel(const f32x4* __restrict__ r
     unsigned n_pairs = 0, n_boxes = 0;
     const int depth = min(max(S.depth, 1), RT_MAX_LEVELS);
 
-    int sp = 1;
-    st_id[0] = (unsigned)depth << 28;
-    st_mask[0] = __ballot(live);          // a dead lane takes part in no ballot
+    int sp = rt_start(W, depth, live);
     for (unsigned it = 0; it < nodes && sp > 0; ++it) {
-        --sp;
-        const unsigned long long mask_v = st_mask[sp];
-        const unsigned id = __builtin_amdgcn_readfirstlane(st_id[sp]);
-        const unsigned long long mask = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(mask_v >> 32)) << 32) |
-                                        __builtin_amdgcn_readfirstlane((unsigned)mask_v);
-        const int L = (int)(id >> 28), k = (int)(id & 0x0FFFFFFFu);
-        if (L < 1 || L > depth || k >= S.n[L]) continue;          // the wave's own ids; bounded all the same
-        const f32x4* nb = boxes + (size_t)(S.noff[L] + (unsigned)k) * RT_NODE_F4;      // wave-uniform: scalar loads
-        f32x4 b4[RT_NODE_F4];
-#pragma unroll
-        for (int x = 0; x < RT_NODE_F4; ++x) b4[x] = nb[x];
+        int L, k;
+        bool active;
+        if (!rt_pop(W, sp, S, depth, L, k, active)) continue;
         float bx[RT_FAN * 6];
-#pragma unroll
-        for (int x = 0; x < RT_NODE_F4; ++x) bx[4 * x] = b4[x].x, bx[4 * x + 1] = b4[x].y, bx[4 * x + 2] = b4[x].z, bx[4 * x + 3] = b4[x].w;
-        const bool active = (mask >> lane) & 1ull;
+        rt_node(boxes, S, L, k, bx);
         float en[RT_FAN];
 #pragma unroll
         for (int c = 0; c < RT_FAN; ++c) en[c] = active ? rt_entry(o, inv, neg, bx + 6 * c, bx + 6 * c + 3, t_min) : __builtin_nanf("");
@@ -170,31 +139,19 @@ __global__ __launch_bounds__(64) void rt_cast_kernel(const f32x4* __restrict__ r
         if (L > 1) {
             // push in falling order: child 0 is popped first
 #pragma unroll
-            for (int c = RT_FAN - 1; c >= 0; --c) {
-                const unsigned long long m = __ballot(en[c] <= best_t);
-                if (m != 0 && sp < RT_STACK) {
-                    st_id[sp] = ((unsigned)(L - 1) << 28) | (unsigned)(RT_FAN * k + c);
-                    st_mask[sp] = m;
-                    ++sp;
-                }
-            }
+            for (int c = RT_FAN - 1; c >= 0; --c) rt_push(W, sp, L, RT_FAN * k + c, __ballot(en[c] <= best_t));
         } else {
 #pragma unroll
-            for (int c = 0; c < RT_FAN; ++c) ent[c][lane] = en[c];
+            for (int c = 0; c < RT_FAN; ++c) W.ent[c][lane] = en[c];
 #pragma unroll 1
             for (int c = 0; c < RT_FAN; ++c) {
                 const int leaf = RT_FAN * k + c;
                 if (leaf >= S.nleaf) break;
-                const bool meet = ent[c][lane] <= best_t;          // best_t as it is NOW: earlier leaves have shrunk it
+                const bool meet = W.ent[c][lane] <= best_t;          // best_t as it is NOW: earlier leaves have shrunk it
                 if (__ballot(meet) == 0) continue;
-                const f32x4* rb = rec + 3 * (size_t)RC_CHUNK * leaf;      // wave-uniform: scalar loads
-                const int* fb = face_of + (size_t)RC_CHUNK * leaf;
                 f32x4 r[3 * RC_CHUNK];
                 int fid[RC_CHUNK];
-#pragma unroll
-                for (int x = 0; x < 3 * RC_CHUNK; ++x) r[x] = rb[x];
-#pragma unroll
-                for (int x = 0; x < RC_CHUNK; ++x) fid[x] = fb[x];
+                rt_leaf(rec, face_of, leaf, r, fid);
                 if (meet) {
                     if (COUNT) n_pairs += RC_CHUNK;
 #pragma unroll
@@ -223,21 +180,10 @@ static int rt_cast(const char* what, const void* tree, size_t tree_bytes, int32_
     FGC_CHECK_ARG(nf <= FGC_RAY_CAST_MAX_FACES, "%s: nf=%d (at most %d)", what, nf, FGC_RAY_CAST_MAX_FACES);
     FGC_CHECK_ARG(n_origins == 1 || n_origins == nq, "%s: n_origins=%d (1 or nq=%d)", what, n_origins, nq);
     FGC_CHECK_ARG(t_min >= 0.f && t_min < __builtin_inff(), "%s: t_min=%g (>= 0 and finite)", what, (double)t_min);
-    FGC_CHECK_ARG((uintptr_t)tree % 16 == 0, "%s: tree needs 16-byte alignment", what);
-    const RtLayout T = rt_layout(nf);
-    FGC_CHECK_ARG(tree_bytes >= T.total, "%s: tree too small (%zu < %zu bytes)", what, tree_bytes, T.total);
-    hipStream_t st = (hipStream_t)stream;
-    const char* base = (const char*)tree;
-#ifdef FGC_RT_COUNT
-    if (count_out)
-        FGC_LAUNCH("rt_cast_kernel", st, rt_cast_kernel<true>, dim3(cdiv(nq, 64)), dim3(64), 0, (const f32x4*)base,
-                   (const int*)(base + T.face_of), (const f32x4*)(base + T.boxes), T.s, T.nodes, origins, n_origins, dirs, nq,
-                   t_min, t_out, face_out, bary_out, count_out);
-    else
-#endif
-        FGC_LAUNCH("rt_cast_kernel", st, rt_cast_kernel<false>, dim3(cdiv(nq, 64)), dim3(64), 0, (const f32x4*)base,
-                   (const int*)(base + T.face_of), (const f32x4*)(base + T.boxes), T.s, T.nodes, origins, n_origins, dirs, nq,
-                   t_min, t_out, face_out, bary_out, (unsigned*)nullptr);
+    RtView T;
+    if (int rc = rt_view(what, tree, tree_bytes, nf, T)) return rc;
+    FGC_LAUNCH("rt_cast_kernel", (hipStream_t)stream, RT_COUNT_KERNEL(rt_cast_kernel, count_out), dim3(cdiv(nq, 64)), dim3(64), 0,
+               T.rec, T.face_of, T.boxes, T.s, T.nodes, origins, n_origins, dirs, nq, t_min, t_out, face_out, bary_out, count_out);
     FGC_CHECK_LAUNCH(what);
     return FGC_OK;
 }
@@ -256,16 +202,14 @@ extern "C" int fgc_ray_tree_build(const float* verts, int32_t nv, const int32_t*
     FGC_CHECK_ARG(verts && faces && order && tree, "fgc_ray_tree_build: null pointer");
     FGC_CHECK_ARG(nv > 0 && nf > 0, "fgc_ray_tree_build: nv=%d nf=%d (both > 0)", nv, nf);
     FGC_CHECK_ARG(nf <= FGC_RAY_CAST_MAX_FACES, "fgc_ray_tree_build: nf=%d (at most %d)", nf, FGC_RAY_CAST_MAX_FACES);
-    FGC_CHECK_ARG((uintptr_t)tree % 16 == 0, "fgc_ray_tree_build: tree needs 16-byte alignment");
-    const RtLayout T = rt_layout(nf);
-    FGC_CHECK_ARG(tree_bytes >= T.total, "fgc_ray_tree_build: tree too small (%zu < %zu bytes)", tree_bytes, T.total);
+    RtView T;
+    if (int rc = rt_view("fgc_ray_tree_build", tree, tree_bytes, nf, T)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    char* base = (char*)tree;
-    float* boxes = (float*)(base + T.boxes);
-    auto level = [&](int L) { return boxes + (size_t)T.s.noff[L + 1] * RT_FAN * 6; };      // the boxes of level L: the nodes of L + 1
+    // the one place that writes a tree; the boxes of level L: the nodes of L + 1
+    auto level = [&](int L) { return (float*)T.boxes + (size_t)T.s.noff[L + 1] * RT_FAN * 6; };
     const int nbox0 = RT_FAN * T.s.n[1];
     FGC_LAUNCH("rt_leaf_kernel", st, rt_leaf_kernel, dim3(cdiv(nbox0, 256)), dim3(256), 0, verts, nv, faces, nf, order, T.s.nleaf,
-               nbox0, (f32x4*)base, (int*)(base + T.face_of), level(0));
+               nbox0, (f32x4*)T.rec, (int*)T.face_of, level(0));
     for (int L = 1; L < T.s.depth; ++L) {
         const int nbox = RT_FAN * T.s.n[L + 1];
         FGC_LAUNCH("rt_level_kernel", st, rt_level_kernel, dim3(cdiv(nbox, 256)), dim3(256), 0, (const float*)level(L - 1),

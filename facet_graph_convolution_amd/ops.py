@@ -509,6 +509,25 @@ def ray_tree(verts, faces, order=None):
     return RayTree(tree, nf, nv)
 
 
+def _tree_query(key, inputs, want_bary, call):
+    """What ray_cast_tree and closest_point_tree share.  key: the [Q,3] rows in whose (stable) Morton order the queries are
+    made, None for the order given; inputs: the per-query tensors; Q is the row count of the LAST of them, and only the
+    inputs with Q rows are permuted (one origin for all rays, a single row, stays as it is); call(inputs, outputs) makes the
+    C call.  Returns [value [Q] fp32, face [Q] int32, bary [Q,2] fp32 or None], scattered back."""
+    nq = inputs[-1].shape[0]
+    perm = None
+    if key is not None and nq > 1:
+        perm = torch.sort(_morton30(key), stable=True).indices
+        inputs = [x[perm].contiguous() if x.shape[0] == nq else x for x in inputs]
+    dev = inputs[-1].device
+    out = [torch.empty(nq, dtype=torch.float32, device=dev), torch.empty(nq, dtype=torch.int32, device=dev),
+           torch.empty(nq, 2, dtype=torch.float32, device=dev) if want_bary else None]
+    call(inputs, out)
+    if perm is not None:
+        out = [None if x is None else torch.empty_like(x).index_copy_(0, perm, x) for x in out]
+    return out
+
+
 def ray_cast_tree(tree, origins, dirs, t_min=0.0, want_bary=False, sort_rays=True):
     """ray_cast through a RayTree (include/fgc.h: fgc_ray_cast_tree): the same arguments and the same returns, the mesh
     being the one the tree was built of.  sort_rays: cast the rays in the (stable) Morton order of their unit directions
@@ -525,24 +544,12 @@ def ray_cast_tree(tree, origins, dirs, t_min=0.0, want_bary=False, sort_rays=Tru
         raise ValueError("t_min must be finite and >= 0 (got %r)" % (t_min,))
     if nq == 0:
         raise ValueError("ray_cast_tree needs at least one ray")
-    perm = None
+    key = None
     if sort_rays and nq > 1:
         key = dirs / dirs.norm(dim=1, keepdim=True) if origins.shape[0] == 1 else origins
-        perm = torch.sort(_morton30(key), stable=True).indices
-        dirs = dirs[perm].contiguous()
-        if origins.shape[0] != 1:
-            origins = origins[perm].contiguous()
-    dev = dirs.device
-    t = torch.empty(nq, dtype=torch.float32, device=dev)
-    face = torch.empty(nq, dtype=torch.int32, device=dev)
-    bary = torch.empty(nq, 2, dtype=torch.float32, device=dev) if want_bary else None
-    check(_lib.lib().fgc_ray_cast_tree(ptr(tree.tree), tree.tree.numel(), tree.nf, ptr(origins), origins.shape[0], ptr(dirs),
-                                       nq, float(t_min), ptr(t), ptr(face), ptr(bary), stream_ptr()), "fgc_ray_cast_tree")
-    if perm is not None:
-        t = torch.empty_like(t).index_copy_(0, perm, t)
-        face = torch.empty_like(face).index_copy_(0, perm, face)
-        if want_bary:
-            bary = torch.empty_like(bary).index_copy_(0, perm, bary)
+    t, face, bary = _tree_query(key, [origins, dirs], want_bary, lambda inp, out: check(_lib.lib().fgc_ray_cast_tree(
+        ptr(tree.tree), tree.tree.numel(), tree.nf, ptr(inp[0]), inp[0].shape[0], ptr(inp[1]), nq, float(t_min), ptr(out[0]),
+        ptr(out[1]), ptr(out[2]), stream_ptr()), "fgc_ray_cast_tree"))
     return (t, face, bary) if want_bary else (t, face)
 
 
@@ -563,22 +570,10 @@ def closest_point_tree(tree, points, want_bary=False, sort_points=True, exhausti
     nq = points.shape[0]
     if nq == 0:
         raise ValueError("closest_point_tree needs at least one point")
-    perm = None
-    if sort_points and nq > 1:
-        perm = torch.sort(_morton30(points), stable=True).indices
-        points = points[perm].contiguous()
-    dev = points.device
-    d2 = torch.empty(nq, dtype=torch.float32, device=dev)
-    face = torch.empty(nq, dtype=torch.int32, device=dev)
-    bary = torch.empty(nq, 2, dtype=torch.float32, device=dev) if want_bary else None
-    check(_lib.lib().fgc_closest_point_tree(ptr(tree.tree), tree.tree.numel(), tree.nf, ptr(points), nq,
-                                            CP_EXHAUSTIVE if exhaustive else 0, ptr(d2), ptr(face), ptr(bary), stream_ptr()),
-          "fgc_closest_point_tree")
-    if perm is not None:
-        d2 = torch.empty_like(d2).index_copy_(0, perm, d2)
-        face = torch.empty_like(face).index_copy_(0, perm, face)
-        if want_bary:
-            bary = torch.empty_like(bary).index_copy_(0, perm, bary)
+    d2, face, bary = _tree_query(points if sort_points else None, [points], want_bary, lambda inp, out: check(
+        _lib.lib().fgc_closest_point_tree(ptr(tree.tree), tree.tree.numel(), tree.nf, ptr(inp[0]), nq,
+                                          CP_EXHAUSTIVE if exhaustive else 0, ptr(out[0]), ptr(out[1]), ptr(out[2]), stream_ptr()),
+        "fgc_closest_point_tree"))
     dist = torch.sqrt(d2)
     return (dist, face, bary) if want_bary else (dist, face)
 

@@ -476,6 +476,21 @@ def ray_tree(V, faces):
                         _put(np.asarray(faces).astype(np.int64).reshape(-1, 3), np.int32))
 
 
+def _tree_for(accel, V, faces, build):
+    """The tree a call with accel= goes through: one built for this call if `build`, else accel itself if it is a handle of
+    ray_tree - which must have been built of a mesh of these sizes - else None: the caller says what it accepts."""
+    from . import ops
+    if build:
+        return ray_tree(V, faces)
+    if not isinstance(accel, ops.RayTree):
+        return None
+    nv, nf = np.asarray(V).reshape(-1, 3).shape[0], np.asarray(faces).reshape(-1, 3).shape[0]
+    if (accel.nv, accel.nf) != (nv, nf):
+        raise ValueError("the tree was built of a mesh of %d vertices and %d faces, this one has %d and %d"
+                         % (accel.nv, accel.nf, nv, nf))
+    return accel
+
+
 def _ray_cast_host(V, faces, origins, dirs, t_min=0.0, accel="none"):
     """ops.ray_cast on host arrays: (t float32 [Q], face int32 [Q]).  accel: "none" - rays x faces, brute force; "tree" -
     build a bounding-box tree for this call and cast through it (ops.ray_cast_tree); a handle of utils.ray_tree - cast
@@ -485,15 +500,10 @@ def _ray_cast_host(V, faces, origins, dirs, t_min=0.0, accel="none"):
         t, face = ops.ray_cast(_put(V, np.float32), _put(np.asarray(faces).astype(np.int64), np.int32),
                                _put(origins, np.float32), _put(dirs, np.float32), t_min)
         return t.cpu().numpy(), face.cpu().numpy()
-    if isinstance(accel, str) and accel == "tree":
-        accel = ray_tree(V, faces)
-    elif not isinstance(accel, ops.RayTree):
+    tree = _tree_for(accel, V, faces, isinstance(accel, str) and accel == "tree")
+    if tree is None:
         raise ValueError('accel must be "none", "tree" or a handle of utils.ray_tree (got %r)' % (accel,))
-    nv, nf = np.asarray(V).reshape(-1, 3).shape[0], np.asarray(faces).reshape(-1, 3).shape[0]
-    if (accel.nv, accel.nf) != (nv, nf):
-        raise ValueError("the tree was built of a mesh of %d vertices and %d faces, this one has %d and %d"
-                         % (accel.nv, accel.nf, nv, nf))
-    t, face = ops.ray_cast_tree(accel, _put(origins, np.float32), _put(dirs, np.float32), t_min)
+    t, face = ops.ray_cast_tree(tree, _put(origins, np.float32), _put(dirs, np.float32), t_min)
     return t.cpu().numpy(), face.cpu().numpy()
 
 
@@ -776,14 +786,10 @@ def closest_points(P, V, faces, accel=None):
     from . import ops
     V32 = np.array(V, dtype=np.float32).reshape(-1, 3)
     F = np.asarray(faces).astype(np.int64).reshape(-1, 3)
-    if accel is None:
-        accel = ray_tree(V32, F)
-    elif not isinstance(accel, ops.RayTree):
+    tree = _tree_for(accel, V32, F, accel is None)
+    if tree is None:
         raise ValueError("accel must be None or a handle of utils.ray_tree (got %r)" % (accel,))
-    if (accel.nv, accel.nf) != (V32.shape[0], F.shape[0]):
-        raise ValueError("the tree was built of a mesh of %d vertices and %d faces, this one has %d and %d"
-                         % (accel.nv, accel.nf, V32.shape[0], F.shape[0]))
-    dist, face, bary = (x.cpu().numpy() for x in ops.closest_point_tree(accel, _put(P, np.float32), want_bary=True))
+    dist, face, bary = (x.cpu().numpy() for x in ops.closest_point_tree(tree, _put(P, np.float32), want_bary=True))
     T = V32.astype(np.float64)[F[np.maximum(face, 0)].clip(0, V32.shape[0] - 1)]
     u, v = bary[:, :1].astype(np.float64), bary[:, 1:].astype(np.float64)
     point = (1.0 - u - v) * T[:, 0] + u * T[:, 1] + v * T[:, 2]
