@@ -104,15 +104,87 @@ FGC_HD bool sensor_words_valid(uint32_t w0, float r_ref, float q) {
     return on && ref_ok && q_ok;
 }
 
-// ---- what the noise launches share (fgc_synth.hip, fgc_synth_lf.hip): launch shape and the workgroup's bounding box ----
+// ---- what the noise launches share (fgc_synth.hip, fgc_synth_lf.hip): launch shape, control words, the per-vertex white
+// step and the workgroup's bounding box - one copy of each ----
 constexpr int SY_THREADS = 256;
 constexpr int SY_MAX_BLOCKS = 1024;      // vertex blocks of a launch = bounding-box partials the feature kernel re-reduces
 
 static inline int synth_blocks(int nv) { return std::min(cdiv(nv, SY_THREADS), SY_MAX_BLOCKS); }
 
+// The Philox key of a launch, by value: seed -> (lo, hi) and the stream id.
+struct NoiseKey {
+    uint32_t seed_lo, seed_hi, stream_id;
+};
+
+static inline NoiseKey noise_key(uint64_t seed, uint32_t stream_id) {
+    return NoiseKey{(uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), stream_id};
+}
+
+// What every noise entry point checks, under the entry point's name `who`: no null pointer (`pointers`: all of its own are
+// set; null_note: what it adds to that message), nv > 0, an output of its own, a scratch of `need` floats.
+static inline int check_noise_args(const char* who, bool pointers, const char* null_note, int nv, const float* v,
+                                   const float* v_out, size_t scratch_floats, size_t need) {
+    FGC_CHECK_ARG(pointers, "%s: null pointer%s", who, null_note);
+    FGC_CHECK_ARG(nv > 0, "%s: nv=%d (> 0)", who, nv);
+    FGC_CHECK_ARG(v_out != v, "%s: v_out and v must be distinct (the clean vertices are kept)", who);
+    FGC_CHECK_ARG(scratch_floats >= need, "%s: scratch too small (%zu < %zu floats)", who, scratch_floats, need);
+    return FGC_OK;
+}
+
+// ctl (device) of every noise launch: {step low, step high, sigma word}; sigma word 0 = off (the launch reads and writes
+// nothing more), otherwise bit 31 is the on flag and the low 31 bits are the float bits of sigma >= 0.
+struct NoiseCtl {
+    bool on;      // (uniform over the launch: `if (!c.on) return;` is no divergence)
+    float sigma;
+    uint32_t step_lo, step_hi;
+};
+
+FGC_HD NoiseCtl load_noise_ctl(const uint32_t* __restrict__ ctl) {
+    const uint32_t word = ctl[2];
+    return NoiseCtl{word != 0, __uint_as_float(word & 0x7FFFFFFFu), ctl[0], ctl[1]};
+}
+
+// The white step of vertex i: q = v[i] displaced by synth_displace along dir[i] (dir == nullptr: a random direction).
+FGC_HD void synth_white_vertex(const float* __restrict__ v, const float* __restrict__ dir, int i, const NoiseCtl& c,
+                               const NoiseKey& key, float q[3]) {
+    const size_t o = 3 * (size_t)i;
+    const float p[3] = {v[o], v[o + 1], v[o + 2]};
+    float nrm[3] = {0.f, 0.f, 0.f};
+    if (dir) {
+        nrm[0] = dir[o];
+        nrm[1] = dir[o + 1];
+        nrm[2] = dir[o + 2];
+    }
+    synth_displace((uint32_t)i, c.step_lo, c.step_hi, key.stream_id, key.seed_lo, key.seed_hi, c.sigma, p, dir != nullptr, nrm,
+                   q);
+}
+
+// A thread's share of a bounding box: empty, grown point by point, reduced over the workgroup.
+struct Box3 {
+    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+
+    FGC_HD void add(const float lo[3], const float hi[3]) {
+#pragma unroll
+        for (int t = 0; t < 3; ++t) {
+            mn[t] = fminf(mn[t], lo[t]);
+            mx[t] = fmaxf(mx[t], hi[t]);
+        }
+    }
+};
+
+// v_out[i] = q, folded into the thread's box.
+FGC_HD void store_vertex(float* __restrict__ v_out, int i, const float q[3], Box3& box) {
+    const size_t o = 3 * (size_t)i;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) v_out[o + t] = q[t];
+    box.add(q, q);
+}
+
 // min over mn[0..2] / max over mx[0..2] of the workgroup's threads; the result in every thread.  min / max are exact:
 // the order of the reduction is free.
-__device__ __forceinline__ void block_minmax(float mn[3], float mx[3], float (*red)[6]) {
+FGC_HD void block_minmax(Box3& box, float (*red)[6]) {
+    float* mn = box.mn;
+    float* mx = box.mx;
 #pragma unroll
     for (int t = 0; t < 3; ++t)
 #pragma unroll
@@ -140,12 +212,36 @@ __device__ __forceinline__ void block_minmax(float mn[3], float mx[3], float (*r
     }
 }
 
-__device__ __forceinline__ void store_box(float* __restrict__ dst, const float mn[3], const float mx[3]) {
+// The epilogue of a launch that made vertices: the workgroup's box into partials[6 * blockIdx.x ..] = {min xyz, max xyz}.
+FGC_HD void store_block_box(Box3& box, float (*red)[6], float* __restrict__ partials) {
+    block_minmax(box, red);
+    if (threadIdx.x == 0) {
+        float* dst = partials + 6 * (size_t)blockIdx.x;
 #pragma unroll
-    for (int t = 0; t < 3; ++t) {      // (constant indices: the arrays stay in registers)
-        dst[t] = mn[t];
-        dst[3 + t] = mx[t];
+        for (int t = 0; t < 3; ++t) {      // (constant indices: the arrays stay in registers)
+            dst[t] = box.mn[t];
+            dst[3 + t] = box.mx[t];
+        }
     }
+}
+
+// The bounding-box diagonal the input rows and the point sets are divided by: every workgroup reduces the n_partials boxes
+// of a noise launch (at most SY_MAX_BLOCKS x 24 bytes, from the L2) - with gt_box, six floats, the union with that box - and
+// takes the diagonal in double from the fp32 extents, then rounds it to fp32 (what numpy's float32 / python float divides
+// by: utils.py:1271-1280, utils.normalizePointSets).  Contraction is off in the files that call it.
+FGC_HD float box_diagonal(const float* __restrict__ partials, int n_partials, const float* __restrict__ gt_box,
+                          float (*red)[6]) {
+    Box3 box;
+    for (int j = threadIdx.x; j < n_partials; j += SY_THREADS) box.add(partials + 6 * j, partials + 6 * j + 3);
+    if (gt_box && threadIdx.x == 0) box.add(gt_box, gt_box + 3);
+    block_minmax(box, red);
+    double diag2 = 0.0;
+#pragma unroll
+    for (int t = 0; t < 3; ++t) {
+        const double e = (double)(box.mx[t] - box.mn[t]);
+        diag2 += e * e;
+    }
+    return (float)sqrt(diag2);
 }
 
 }  // namespace fgc

@@ -17,94 +17,61 @@
 
 namespace fgc {
 
-// One thread per vertex (grid-stride above SY_MAX_BLOCKS workgroups): v_out = v + direction * sigma z3, and the
-// workgroup's bounding box of v_out into partials[6 * blockIdx.x ..] = {min xyz, max xyz}.
-// ctl (device): {step low, step high, sigma word}; sigma word 0 = off (nothing is read or written), otherwise bit 31 is
-// the on flag and the low 31 bits are the float bits of sigma >= 0.  vn == nullptr: random direction.
-__global__ __launch_bounds__(SY_THREADS) void synth_noise_kernel(const float* __restrict__ v, const float* __restrict__ vn,
-                                                                 int nv, const uint32_t* __restrict__ ctl, uint32_t seed_lo,
-                                                                 uint32_t seed_hi, uint32_t stream_id,
-                                                                 float* __restrict__ v_out, float* __restrict__ partials) {
-    __shared__ float red[SY_THREADS / 64][6];
-    const uint32_t word = ctl[2];
-    if (word == 0) return;      // (uniform over the launch)
-    const float sigma = __uint_as_float(word & 0x7FFFFFFFu);
-    const uint32_t step_lo = ctl[0], step_hi = ctl[1];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = blockIdx.x * SY_THREADS + threadIdx.x; i < nv; i += gridDim.x * SY_THREADS) {
-        const size_t o = 3 * (size_t)i;
-        const float p[3] = {v[o], v[o + 1], v[o + 2]};
-        float nrm[3] = {0.f, 0.f, 0.f};
-        if (vn) {
-            nrm[0] = vn[o];
-            nrm[1] = vn[o + 1];
-            nrm[2] = vn[o + 2];
-        }
-        float q[3];
-        synth_displace((uint32_t)i, step_lo, step_hi, stream_id, seed_lo, seed_hi, sigma, p, vn != nullptr, nrm, q);
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            v_out[o + t] = q[t];
-            mn[t] = fminf(mn[t], q[t]);
-            mx[t] = fmaxf(mx[t], q[t]);
-        }
-    }
-    block_minmax(mn, mx, red);
-    if (threadIdx.x == 0) store_box(partials + 6 * (size_t)blockIdx.x, mn, mx);
-}
+// What the depth-sensor instantiation of synth_noise_kernel takes on top.  ctl (device): {FGC_SYNTH_ON | power, float bits of
+// r_ref, float bits of q, 0}; words that are off or out of range (sensor_words_valid) give plain noise along the rays, the
+// bits of the white instantiation.  The camera comes by value: it is fixed per bound mesh, and a captured launch keeps it.
+struct SensorArgs {
+    const uint32_t* ctl;
+    float cam[3];
+};
 
-// synth_noise_kernel's launch for the depth-sensor model (fgc_synth.h: synth_displace_sensor): the same vertex sets per
-// workgroup, so the same bounding-box partials layout.  sensor_ctl (device): {FGC_SYNTH_ON | power, float bits of r_ref,
-// float bits of q, 0}; words that are off or out of range (sensor_words_valid) give plain noise along dirs, the bits of
-// synth_noise_kernel(vn = dirs).  The camera comes by value: it is fixed per bound mesh, and a captured launch keeps it.
-__global__ __launch_bounds__(SY_THREADS) void synth_noise_sensor_kernel(const float* __restrict__ v,
-                                                                        const float* __restrict__ dirs, int nv,
-                                                                        const uint32_t* __restrict__ ctl,
-                                                                        const uint32_t* __restrict__ sensor_ctl, float cx,
-                                                                        float cy, float cz, uint32_t seed_lo, uint32_t seed_hi,
-                                                                        uint32_t stream_id, float* __restrict__ v_out,
-                                                                        float* __restrict__ partials) {
+// One thread per vertex (grid-stride above SY_MAX_BLOCKS workgroups): v_out = v + direction * length, and the workgroup's
+// bounding box of v_out into partials[6 * blockIdx.x ..].  White (fgc_synth_noise): length sigma z3 along dir, or - dir ==
+// nullptr - along a random direction.  SENSOR (fgc_synth_noise_sensor; fgc_synth.h: synth_displace_sensor): the model's
+// length along the viewing rays dir; the same vertex sets per workgroup, so the same partials.
+template <bool SENSOR>
+__global__ __launch_bounds__(SY_THREADS) void synth_noise_kernel(const float* __restrict__ v, const float* __restrict__ dir,
+                                                                 int nv, const uint32_t* __restrict__ ctl, SensorArgs sensor,
+                                                                 NoiseKey key, float* __restrict__ v_out,
+                                                                 float* __restrict__ partials) {
     __shared__ float red[SY_THREADS / 64][6];
-    const uint32_t word = ctl[2];
-    if (word == 0) return;      // (uniform over the launch)
-    const float sigma = __uint_as_float(word & 0x7FFFFFFFu);
-    const uint32_t step_lo = ctl[0], step_hi = ctl[1];
-    const uint32_t w0 = sensor_ctl[0];
-    float r_ref = __uint_as_float(sensor_ctl[1]), q = __uint_as_float(sensor_ctl[2]);
-    uint32_t power = w0 & 0x7FFFFFFFu;
-    if (!sensor_words_valid(w0, r_ref, q)) {
-        power = 0;
-        r_ref = 1.0f;
-        q = 0.0f;
-    }
-    const float cam[3] = {cx, cy, cz};
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = blockIdx.x * SY_THREADS + threadIdx.x; i < nv; i += gridDim.x * SY_THREADS) {
-        const size_t o = 3 * (size_t)i;
-        const float p[3] = {v[o], v[o + 1], v[o + 2]};
-        const float d[3] = {dirs[o], dirs[o + 1], dirs[o + 2]};
-        float out[3];
-        synth_displace_sensor((uint32_t)i, step_lo, step_hi, stream_id, seed_lo, seed_hi, sigma, power, r_ref, q, cam, p, d,
-                              out);
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            v_out[o + t] = out[t];
-            mn[t] = fminf(mn[t], out[t]);
-            mx[t] = fmaxf(mx[t], out[t]);
+    const NoiseCtl c = load_noise_ctl(ctl);
+    if (!c.on) return;
+    uint32_t power = 0;
+    float r_ref = 1.0f, qs = 0.0f;
+    if (SENSOR) {
+        const uint32_t w0 = sensor.ctl[0];
+        const float r = __uint_as_float(sensor.ctl[1]), q = __uint_as_float(sensor.ctl[2]);
+        if (sensor_words_valid(w0, r, q)) {
+            power = w0 & 0x7FFFFFFFu;
+            r_ref = r;
+            qs = q;
         }
     }
-    block_minmax(mn, mx, red);
-    if (threadIdx.x == 0) store_box(partials + 6 * (size_t)blockIdx.x, mn, mx);
+    Box3 box;
+    for (int i = blockIdx.x * SY_THREADS + threadIdx.x; i < nv; i += gridDim.x * SY_THREADS) {
+        float q[3];
+        if (SENSOR) {
+            const size_t o = 3 * (size_t)i;
+            const float p[3] = {v[o], v[o + 1], v[o + 2]};
+            const float d[3] = {dir[o], dir[o + 1], dir[o + 2]};
+            synth_displace_sensor((uint32_t)i, c.step_lo, c.step_hi, key.stream_id, key.seed_lo, key.seed_hi, c.sigma, power,
+                                  r_ref, qs, sensor.cam, p, d, q);
+        } else {
+            synth_white_vertex(v, dir, i, c, key, q);
+        }
+        store_vertex(v_out, i, q, box);
+    }
+    store_block_box(box, red, partials);
 }
 
 // The raw generator, for the known-answer test: out[4 i ..] = Philox4x32-10 of counter (first + i, step, stream_id).
 __global__ __launch_bounds__(SY_THREADS) void philox_words_kernel(uint32_t first, int n, uint32_t step_lo, uint32_t step_hi,
-                                                                  uint32_t seed_lo, uint32_t seed_hi, uint32_t stream_id,
-                                                                  uint32_t* __restrict__ out) {
+                                                                  NoiseKey key, uint32_t* __restrict__ out) {
     const int i = blockIdx.x * SY_THREADS + threadIdx.x;
     if (i >= n) return;
-    uint32_t c[4] = {first + (uint32_t)i, step_lo, step_hi, stream_id};
-    philox4x32_10(c, seed_lo, seed_hi);
+    uint32_t c[4] = {first + (uint32_t)i, step_lo, step_hi, key.stream_id};
+    philox4x32_10(c, key.seed_lo, key.seed_hi);
     *reinterpret_cast<u32x4*>(out + 4 * (size_t)i) = u32x4{c[0], c[1], c[2], c[3]};
 }
 
@@ -114,16 +81,12 @@ __global__ __launch_bounds__(SY_THREADS) void synth_bbox_kernel(const float* __r
                                                                 float* __restrict__ partials) {
     __shared__ float red[SY_THREADS / 64][6];
     if (ctl && ctl[2] == 0) return;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int i = blockIdx.x * SY_THREADS + threadIdx.x; i < nv; i += gridDim.x * SY_THREADS)
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            const float q = v[3 * (size_t)i + t];
-            mn[t] = fminf(mn[t], q);
-            mx[t] = fmaxf(mx[t], q);
-        }
-    block_minmax(mn, mx, red);
-    if (threadIdx.x == 0) store_box(partials + 6 * (size_t)blockIdx.x, mn, mx);
+    Box3 box;
+    for (int i = blockIdx.x * SY_THREADS + threadIdx.x; i < nv; i += gridDim.x * SY_THREADS) {
+        const float* q = v + 3 * (size_t)i;
+        box.add(q, q);
+    }
+    store_block_box(box, red, partials);
 }
 
 // One thread per node row: x[i] = [unit normal | barycentre / bounding-box diagonal] of face faces_rows[i] on the
@@ -137,22 +100,7 @@ __global__ __launch_bounds__(SY_THREADS) void face_features_rows_kernel(const fl
                                                                         float* __restrict__ x) {
     __shared__ float red[SY_THREADS / 64][6];
     if (ctl && ctl[2] == 0) return;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int j = threadIdx.x; j < n_partials; j += SY_THREADS)
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            mn[t] = fminf(mn[t], partials[6 * j + t]);
-            mx[t] = fmaxf(mx[t], partials[6 * j + 3 + t]);
-        }
-    block_minmax(mn, mx, red);
-    // the diagonal in double from the fp32 extents, then rounded to fp32 (utils.py:1271-1280 through numpy)
-    double diag2 = 0.0;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const double e = (double)(mx[t] - mn[t]);
-        diag2 += e * e;
-    }
-    const float diag = (float)sqrt(diag2);
+    const float diag = box_diagonal(partials, n_partials, nullptr, red);
     const int i = blockIdx.x * SY_THREADS + threadIdx.x;
     if (i >= n) return;
     const int a = faces[3 * (size_t)i], b = faces[3 * (size_t)i + 1], c = faces[3 * (size_t)i + 2];
@@ -208,28 +156,7 @@ __global__ __launch_bounds__(SY_THREADS) void point_sets_prepare_kernel(const fl
                                                                         const float* __restrict__ Rd,
                                                                         float* __restrict__ v_out, float* __restrict__ gt_out) {
     __shared__ float red[SY_THREADS / 64][6];
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
-    for (int j = threadIdx.x; j < n_partials; j += SY_THREADS)
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            mn[t] = fminf(mn[t], partials[6 * j + t]);
-            mx[t] = fmaxf(mx[t], partials[6 * j + 3 + t]);
-        }
-    if (threadIdx.x == 0)
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            mn[t] = fminf(mn[t], gt_box[t]);
-            mx[t] = fmaxf(mx[t], gt_box[3 + t]);
-        }
-    block_minmax(mn, mx, red);
-    // the diagonal in double from the fp32 extents, then rounded to fp32 (what numpy's float32 / python float divides by)
-    double diag2 = 0.0;
-#pragma unroll
-    for (int t = 0; t < 3; ++t) {
-        const double e = (double)(mx[t] - mn[t]);
-        diag2 += e * e;
-    }
-    const float diag = (float)sqrt(diag2);
+    const float diag = box_diagonal(partials, n_partials, gt_box, red);
     const int64_t i = (int64_t)blockIdx.x * SY_THREADS + threadIdx.x;
     if (i >= (int64_t)nv + ngt) return;
     const bool first = i < nv;
@@ -260,14 +187,12 @@ extern "C" size_t fgc_synth_scratch_floats(int32_t nv) {
 
 extern "C" int fgc_synth_noise(const float* v, const float* vnormals, int32_t nv, const uint32_t* ctl, uint64_t seed,
                                uint32_t stream_id, float* v_out, float* scratch, size_t scratch_floats, void* stream) {
-    FGC_CHECK_ARG(v && ctl && v_out && scratch, "fgc_synth_noise: null pointer");
-    FGC_CHECK_ARG(nv > 0, "fgc_synth_noise: nv=%d (> 0)", nv);
-    FGC_CHECK_ARG(v_out != v, "fgc_synth_noise: v_out and v must be distinct (the clean vertices are kept)");
-    const size_t need = fgc_synth_scratch_floats(nv);
-    FGC_CHECK_ARG(scratch_floats >= need, "fgc_synth_noise: scratch too small (%zu < %zu floats)", scratch_floats, need);
+    if (int rc = check_noise_args("fgc_synth_noise", v && ctl && v_out && scratch, "", nv, v, v_out, scratch_floats,
+                                  fgc_synth_scratch_floats(nv)))
+        return rc;
     hipStream_t st = (hipStream_t)stream;
-    FGC_LAUNCH("synth_noise_kernel", st, synth_noise_kernel, dim3(synth_blocks(nv)), dim3(SY_THREADS), 0, v, vnormals, nv,
-               ctl, (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32), stream_id, v_out, scratch);
+    FGC_LAUNCH("synth_noise_kernel", st, synth_noise_kernel<false>, dim3(synth_blocks(nv)), dim3(SY_THREADS), 0, v, vnormals,
+               nv, ctl, SensorArgs{}, noise_key(seed, stream_id), v_out, scratch);
     FGC_CHECK_LAUNCH("fgc_synth_noise");
     return FGC_OK;
 }
@@ -275,19 +200,15 @@ extern "C" int fgc_synth_noise(const float* v, const float* vnormals, int32_t nv
 extern "C" int fgc_synth_noise_sensor(const float* v, const float* dirs, int32_t nv, const uint32_t* ctl,
                                       const uint32_t* sensor_ctl, const float* camera, uint64_t seed, uint32_t stream_id,
                                       float* v_out, float* scratch, size_t scratch_floats, void* stream) {
-    FGC_CHECK_ARG(v && dirs && ctl && sensor_ctl && camera && v_out && scratch,
-                  "fgc_synth_noise_sensor: null pointer (the model needs the table of rays and the camera)");
-    FGC_CHECK_ARG(nv > 0, "fgc_synth_noise_sensor: nv=%d (> 0)", nv);
-    FGC_CHECK_ARG(v_out != v, "fgc_synth_noise_sensor: v_out and v must be distinct (the clean vertices are kept)");
+    if (int rc = check_noise_args("fgc_synth_noise_sensor", v && dirs && ctl && sensor_ctl && camera && v_out && scratch,
+                                  " (the model needs the table of rays and the camera)", nv, v, v_out, scratch_floats,
+                                  fgc_synth_scratch_floats(nv)))
+        return rc;
     FGC_CHECK_ARG(std::isfinite(camera[0]) && std::isfinite(camera[1]) && std::isfinite(camera[2]),
                   "fgc_synth_noise_sensor: the camera must be three finite numbers");
-    const size_t need = fgc_synth_scratch_floats(nv);
-    FGC_CHECK_ARG(scratch_floats >= need, "fgc_synth_noise_sensor: scratch too small (%zu < %zu floats)", scratch_floats,
-                  need);
     hipStream_t st = (hipStream_t)stream;
-    FGC_LAUNCH("synth_noise_sensor_kernel", st, synth_noise_sensor_kernel, dim3(synth_blocks(nv)), dim3(SY_THREADS), 0, v,
-               dirs, nv, ctl, sensor_ctl, camera[0], camera[1], camera[2], (uint32_t)(seed & 0xFFFFFFFFu),
-               (uint32_t)(seed >> 32), stream_id, v_out, scratch);
+    FGC_LAUNCH("synth_noise_sensor_kernel", st, synth_noise_kernel<true>, dim3(synth_blocks(nv)), dim3(SY_THREADS), 0, v, dirs,
+               nv, ctl, SensorArgs{sensor_ctl, {camera[0], camera[1], camera[2]}}, noise_key(seed, stream_id), v_out, scratch);
     FGC_CHECK_LAUNCH("fgc_synth_noise_sensor");
     return FGC_OK;
 }
@@ -298,8 +219,7 @@ extern "C" int fgc_philox_words(uint32_t first, int32_t n, uint64_t step, uint64
     FGC_CHECK_ARG(((uintptr_t)out & 15) == 0, "fgc_philox_words: out must be 16-byte aligned");
     hipStream_t st = (hipStream_t)stream;
     FGC_LAUNCH("philox_words_kernel", st, philox_words_kernel, dim3(cdiv(n, SY_THREADS)), dim3(SY_THREADS), 0, first, n,
-               (uint32_t)(step & 0xFFFFFFFFu), (uint32_t)(step >> 32), (uint32_t)(seed & 0xFFFFFFFFu), (uint32_t)(seed >> 32),
-               stream_id, out);
+               (uint32_t)(step & 0xFFFFFFFFu), (uint32_t)(step >> 32), noise_key(seed, stream_id), out);
     FGC_CHECK_LAUNCH("fgc_philox_words");
     return FGC_OK;
 }

@@ -47,17 +47,17 @@ static LfLayout lf_layout(int nv, int n_bumps) {
 __global__ __launch_bounds__(SY_THREADS) void lf_table_kernel(const float* __restrict__ v, int nv,
                                                               const uint32_t* __restrict__ ctl,
                                                               const uint32_t* __restrict__ lf_ctl, int n_bumps,
-                                                              uint32_t seed_lo, uint32_t seed_hi, uint32_t stream_id,
-                                                              f32x4* __restrict__ table, int* __restrict__ counters,
-                                                              int n_counters) {
+                                                              NoiseKey key, f32x4* __restrict__ table,
+                                                              int* __restrict__ counters, int n_counters) {
+    const NoiseCtl c0 = load_noise_ctl(ctl);
     const uint32_t word = lf_ctl[0];
-    if (ctl[2] == 0 || word == 0) return;      // (uniform over the launch)
+    if (!c0.on || word == 0) return;      // (uniform over the launch)
     const int k = blockIdx.x * SY_THREADS + threadIdx.x;
     if (k < n_counters) counters[k] = 0;
     if (k >= n_bumps) return;
     const float A = __uint_as_float(word & 0x7FFFFFFFu);
-    uint32_t c[4] = {(uint32_t)k, ctl[0], ctl[1], stream_id | 0x80000000u};
-    philox4x32_10(c, seed_lo, seed_hi);
+    uint32_t c[4] = {(uint32_t)k, c0.step_lo, c0.step_hi, key.stream_id | 0x80000000u};
+    philox4x32_10(c, key.seed_lo, key.seed_hi);
     const size_t o = 3 * (size_t)mulhi32(c[0], (uint32_t)nv);      // (< nv: in bounds)
     float z, unused;
     box_muller(c[2], c[3], &z, &unused);
@@ -76,44 +76,30 @@ __global__ __launch_bounds__(SY_THREADS) void lf_field_kernel(const float* __res
                                                               const float* __restrict__ wn, int nv,
                                                               const uint32_t* __restrict__ ctl,
                                                               const uint32_t* __restrict__ lf_ctl, int n_bumps,
-                                                              int per_slice, uint32_t seed_lo, uint32_t seed_hi,
-                                                              uint32_t stream_id, const float* __restrict__ table,
-                                                              float* part, int* counters, float* __restrict__ v_out,
-                                                              float* __restrict__ partials) {
+                                                              int per_slice, NoiseKey key,
+                                                              const float* __restrict__ table, float* part, int* counters,
+                                                              float* __restrict__ v_out, float* __restrict__ partials) {
     __shared__ float red[SY_THREADS / 64][6];
     __shared__ int arrived;
-    const uint32_t word = ctl[2];
-    if (word == 0) return;      // (uniform over the launch)
+    const NoiseCtl c = load_noise_ctl(ctl);
+    if (!c.on) return;
     const bool lf_on = lf_ctl[0] != 0;
     const int slices = lf_on ? (int)gridDim.y : 1;
     if ((int)blockIdx.y >= slices) return;      // bumps off: the launch is fgc_synth_noise's
-    const float sigma = __uint_as_float(word & 0x7FFFFFFFu);
-    const uint32_t step_lo = ctl[0], step_hi = ctl[1];
     const float w = __uint_as_float(lf_ctl[1]);
     const float scale = -1.44269504088896341f / (2.0f * w * w);
     const int stride = gridDim.x * SY_THREADS;
     const int j0 = blockIdx.y * per_slice, j1 = lf_on ? min(n_bumps, j0 + per_slice) : j0;
-    float mn[3] = {INFINITY, INFINITY, INFINITY}, mx[3] = {-INFINITY, -INFINITY, -INFINITY};
+    Box3 box;
 
-    // the epilogue of vertex i with the field value s: white draw, bump displacement, v_out, box
+    // the epilogue of vertex i with the field value s: white step, bump displacement, v_out, box
     auto finish = [&](int i, float s) {
-        const size_t o = 3 * (size_t)i;
-        const float p[3] = {v[o], v[o + 1], v[o + 2]};
-        float nrm[3] = {0.f, 0.f, 0.f};
-        if (wn) {
-            nrm[0] = wn[o];
-            nrm[1] = wn[o + 1];
-            nrm[2] = wn[o + 2];
-        }
         float q[3];
-        synth_displace((uint32_t)i, step_lo, step_hi, stream_id, seed_lo, seed_hi, sigma, p, wn != nullptr, nrm, q);
+        synth_white_vertex(v, wn, i, c, key, q);
+        if (lf_on)      // (off: the white vertex bit for bit, a -0.0 included)
 #pragma unroll
-        for (int t = 0; t < 3; ++t) {
-            if (lf_on) q[t] = q[t] + vn[o + t] * s;      // (off: the white vertex bit for bit, a -0.0 included)
-            v_out[o + t] = q[t];
-            mn[t] = fminf(mn[t], q[t]);
-            mx[t] = fmaxf(mx[t], q[t]);
-        }
+            for (int t = 0; t < 3; ++t) q[t] = q[t] + vn[3 * (size_t)i + t] * s;
+        store_vertex(v_out, i, q, box);
     };
 
     // (the loop is uniform and the lanes past nv predicated: the table addresses stay provably wave-uniform)
@@ -157,8 +143,7 @@ __global__ __launch_bounds__(SY_THREADS) void lf_field_kernel(const float* __res
             finish(i, s);
         }
     }
-    block_minmax(mn, mx, red);
-    if (threadIdx.x == 0) store_box(partials + 6 * (size_t)blockIdx.x, mn, mx);
+    store_block_box(box, red, partials);
 }
 
 }  // namespace fgc
@@ -173,27 +158,25 @@ extern "C" size_t fgc_synth_lf_scratch_floats(int32_t nv, int32_t n_bumps) {
 extern "C" int fgc_synth_noise_lf(const float* v, const float* vnormals, const float* white_normals, int32_t nv,
                                   const uint32_t* ctl, const uint32_t* lf_ctl, int32_t n_bumps, uint64_t seed,
                                   uint32_t stream_id, float* v_out, float* scratch, size_t scratch_floats, void* stream) {
-    FGC_CHECK_ARG(v && vnormals && ctl && lf_ctl && v_out && scratch,
-                  "fgc_synth_noise_lf: null pointer (the bumps need the vertex normals)");
-    FGC_CHECK_ARG(nv > 0, "fgc_synth_noise_lf: nv=%d (> 0)", nv);
+    if (int rc = check_noise_args("fgc_synth_noise_lf", v && vnormals && ctl && lf_ctl && v_out && scratch,
+                                  " (the bumps need the vertex normals)", nv, v, v_out, scratch_floats,
+                                  fgc_synth_lf_scratch_floats(nv, n_bumps)))      // (0 for a count the next line refuses)
+        return rc;
     FGC_CHECK_ARG(n_bumps >= 1 && n_bumps <= FGC_SYNTH_LF_MAX_BUMPS, "fgc_synth_noise_lf: n_bumps=%d (1 ... %d)", n_bumps,
                   FGC_SYNTH_LF_MAX_BUMPS);
     FGC_CHECK_ARG(stream_id < 0x80000000u, "fgc_synth_noise_lf: stream_id=%u (below 2^31: the top bit marks the bump counters)",
                   stream_id);
-    FGC_CHECK_ARG(v_out != v, "fgc_synth_noise_lf: v_out and v must be distinct (the clean vertices are kept)");
     FGC_CHECK_ARG(((uintptr_t)scratch & 15) == 0, "fgc_synth_noise_lf: scratch must be 16-byte aligned");
     const LfLayout lay = lf_layout(nv, n_bumps);
-    FGC_CHECK_ARG(scratch_floats >= lay.total, "fgc_synth_noise_lf: scratch too small (%zu < %zu floats)", scratch_floats,
-                  lay.total);
     hipStream_t st = (hipStream_t)stream;
-    const uint32_t seed_lo = (uint32_t)(seed & 0xFFFFFFFFu), seed_hi = (uint32_t)(seed >> 32);
+    const NoiseKey key = noise_key(seed, stream_id);
     const int nblk = synth_blocks(nv);
     float* table = scratch + lay.table;
     int* counters = reinterpret_cast<int*>(scratch + lay.counters);
     FGC_LAUNCH("lf_table_kernel", st, lf_table_kernel, dim3(cdiv(std::max(n_bumps, nblk), SY_THREADS)), dim3(SY_THREADS), 0, v,
-               nv, ctl, lf_ctl, n_bumps, seed_lo, seed_hi, stream_id, reinterpret_cast<f32x4*>(table), counters, nblk);
+               nv, ctl, lf_ctl, n_bumps, key, reinterpret_cast<f32x4*>(table), counters, nblk);
     FGC_LAUNCH("lf_field_kernel", st, lf_field_kernel, dim3(nblk, lay.slices), dim3(SY_THREADS), 0, v, vnormals,
-               white_normals, nv, ctl, lf_ctl, n_bumps, lay.per_slice, seed_lo, seed_hi, stream_id, (const float*)table,
+               white_normals, nv, ctl, lf_ctl, n_bumps, lay.per_slice, key, (const float*)table,
                scratch + lay.part, counters, v_out, scratch);
     FGC_CHECK_LAUNCH("fgc_synth_noise_lf");
     return FGC_OK;

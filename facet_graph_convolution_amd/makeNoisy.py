@@ -42,42 +42,31 @@ def make_noisy(V, faces, level, seed=0, stream=0, step=0, direction="random", de
     the depth-sensor model utils.sensor_model(V, camera, edge length, power, quant) - what a step makes on a mesh bound
     with bind_clean(sensor=that model)."""
     import torch
-    from . import ops
-    from .utils import getAverageEdgeLength, areaWeightedVertexNormals, check_directions
+    from . import _lib, ops, synth
+    from .utils import getAverageEdgeLength
     V = np.ascontiguousarray(np.asarray(V, dtype=np.float32))
-    rays = None
-    if not isinstance(direction, str):
-        rays = torch.as_tensor(check_directions(direction, V.reshape(-1, 3).shape[0]), device=device)
-    elif direction not in ("random", "normal"):
-        raise ValueError("direction must be 'random', 'normal' or a [V,3] array of unit rows")
     edge_len = getAverageEdgeLength(V, faces)[0]
     if sensor is not None:
         from .utils import check_sensor, sensor_model
         sensor = check_sensor(sensor)
-        if rays is None or camera is None:
+        if isinstance(direction, str) or camera is None:
             raise ValueError("sensor: the model works along viewing rays from a camera: direction must be the [V,3] table of "
                              "rays and camera its position")
         if lf_level is not None:
             raise ValueError("sensor does not combine with lf_level: quantisation after bumps along the normals is not built")
-        model = sensor_model(V, camera, edge_len, *sensor)
-        out = ops.synth_noise_sensor(torch.as_tensor(V, device=device), rays, model.camera,
-                                     np.float32(level) * np.float32(edge_len), step, model.power, model.r_ref, model.q,
-                                     seed=seed, stream=stream)
-        return out.cpu().numpy()
-    sigma = np.float32(level) * np.float32(edge_len)
-    normals = None
-    if (rays is None and direction == "normal") or lf_level is not None:
-        normals = torch.as_tensor(areaWeightedVertexNormals(V, faces).astype(np.float32), device=device)
-    Vd = torch.as_tensor(V, device=device)
-    if lf_level is None:
-        out = ops.synth_noise(Vd, sigma, step, seed=seed, stream=stream, normals=normals if rays is None else rays)
-    else:
-        if not (np.isfinite(lf_level) and lf_level >= 0):
-            raise ValueError("lf_level must be finite and >= 0 (got %r)" % (lf_level,))
-        K, width, area = ops.lf_plan(V, faces, edge_len, lf_width, lf_bumps)
-        out = ops.synth_noise_lf(Vd, normals, sigma, step, ops.lf_amplitude(lf_level, edge_len, width, K, area), width, K,
-                                 seed=seed, stream=stream,
-                                 white_normals=rays if rays is not None else normals if direction == "normal" else None)
+        sensor = sensor_model(V, camera, edge_len, *sensor)
+    if lf_level is not None and not (np.isfinite(lf_level) and lf_level >= 0):
+        raise ValueError("lf_level must be finite and >= 0 (got %r)" % (lf_level,))
+    # the spec, plan and launch of a training step (synth.py): one copy of which table and which entry point
+    spec = synth.NoiseSpec(seed, stream, direction, None if lf_level is None else (lf_width, lf_bumps), sensor)
+    plan = synth.NoisePlan(spec, V, faces, edge_len, device)
+    Vd = torch.as_tensor(V.reshape(-1, 3), device=device)
+    ops._req_cuda(Vd)      # (a missing kernel is an error: no CPU fallback)
+    out = torch.empty_like(Vd)
+    scratch = torch.empty(max(plan.scratch_floats, 1), dtype=torch.float32, device=device)
+    ctl = torch.from_numpy(plan.noise_words(step, level)).to(device)
+    lf_ctl = None if plan.lf is None else torch.from_numpy(plan.lf_words(lf_level)).to(device)
+    synth.enqueue(plan, Vd, out, scratch, ctl, lf_ctl, _lib.stream_ptr())
     return out.cpu().numpy()
 
 
@@ -101,7 +90,7 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--direction", choices=("random", "normal", "ray"), default="random",
                     help="ray: along the viewing rays of --view-dir / --camera, built from the clean vertices")
-    from .utils import view_options, view_spec, view_rays
+    from .utils import view_options, noise_view_spec, view_rays
     view_options(ap)
     ap.add_argument("--lf-levels", default=None, help="low-frequency noise on top: comma-separated RMS levels in mean "
                     "edge lengths, one or one per --levels entry (pair k = level k with lf level k)")
@@ -112,24 +101,7 @@ def main(argv=None):
                     "(0, 1 or 2), depth quantised in steps of QUANT mean edge lengths at the reference range (default 0: off)")
     ap.add_argument("--overwrite", action="store_true")
     args = ap.parse_args(argv)
-    view = view_spec(ap, args)
-    sensor = None
-    if args.sensor is not None:
-        from .utils import parse_sensor
-        try:
-            sensor = parse_sensor(args.sensor)
-        except ValueError as e:
-            ap.error("--sensor POWER[:QUANT], e.g. 2:0.5 - %s (got %r)" % (e, args.sensor))
-        if args.view_dir is not None:
-            ap.error("--sensor needs a perspective view: --view-dir has no range, use --camera")
-        if args.direction != "ray":
-            ap.error("--sensor needs --direction ray (got --direction %s)" % args.direction)
-        if args.camera is None:
-            ap.error("--sensor needs --camera X,Y,Z (with --direction ray)")
-        if args.lf_levels is not None:
-            ap.error("--sensor does not combine with --lf-levels: quantisation after bumps along the normals is not built")
-    if (args.direction == "ray") != bool(view):
-        ap.error("--direction ray needs --view-dir or --camera, and the two go with --direction ray only")
+    view, sensor = noise_view_spec(ap, args, "--direction", "--lf-levels")
     try:
         levels = [float(t) for t in args.levels.split(",")]
     except ValueError:

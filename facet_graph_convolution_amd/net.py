@@ -26,10 +26,11 @@ import types
 import numpy as np
 import torch
 
-from . import _lib, ops, require_graph_replay_safe, schedule, shard
+from . import _lib, ops, require_graph_replay_safe, schedule, shard, synth
 from ._lib import ConvDesc, ConvBwdIO, AG_LD, DL_LD, FGC_M
 from .graph import FacetGraph, as_graph
-from .utils import check_directions, direction_key
+from .synth import NoiseSpec, SynthState
+from .utils import direction_key
 
 LRELU_ALPHA = 0.1      # model.py:846
 STD_W, STD_B = 0.05, 0.01  # model.py:17-18
@@ -604,14 +605,15 @@ class FacetDenoiser:
         level of set_noise is then the sigma at the model's reference range, growing with range^power, and a model with q > 0
         quantises every range: noisy_vertices() returns the quantised vertices.  The model is fixed per bound mesh and part of
         what two binds of one key are compared by."""
-        self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf, sensor), False,
+        self._bind_synth(key, NoiseSpec(seed, stream, direction, lf, sensor), (x, verts, faces_rows, edge_len), False,
                          lambda: self._cached(key, lambda: self.bind_mesh(x, adjs, gt=gt)))
         return self
 
-    def _bind_synth(self, key, synth_args, points, bind):
+    def _bind_synth(self, key, spec, mesh_args, points, bind):
         """What bind_clean and bind_clean_vertices (points=True) share: the refusals, the mesh cached under `key` (a training
-        loop rebinds its meshes every iteration: a lookup, as in bind_cached), otherwise the synthesis state of synth_args =
-        (x, verts, faces_rows, edge_len, seed, stream, direction, lf, sensor) on the mesh bind() returns.  Returns (mesh, newly bound)."""
+        loop rebinds its meshes every iteration: a lookup, as in bind_cached), otherwise the synthesis state (synth.py:
+        SynthState) of the NoiseSpec `spec` and mesh_args = (x, verts, faces_rows, edge_len) on the mesh bind() returns.
+        Returns (mesh, newly bound)."""
         if self.comm is not None or (self._mesh is not None and self.sharded):
             raise NotImplementedError("noise synthesis runs on an unsharded network")
         if points:
@@ -620,20 +622,10 @@ class FacetDenoiser:
         if M is not None and (M["mode"].clean or (points and M["mode"].verts)):
             if points and not M["mode"].synth_points:
                 raise ValueError("mesh %r is bound under this key without synthesised point sets" % (key,))
-            S = M["synth"]
-            d = synth_args[6]
-            # (a training loop rebinds every step: the very table this mesh was bound with, read-only, needs no digest)
-            same = (isinstance(d, np.ndarray) and d is S["direction_src"] and not d.flags.writeable) or \
-                S["direction"] == direction_key(d)
-            if (S["seed"], S["stream"]) != (int(synth_args[4]), int(synth_args[5])) or not same:
-                raise ValueError("mesh %r is bound with another seed / stream / direction" % (key,))
-            if S["lf_key"] != self._lf_key(synth_args[7]):
-                raise ValueError("mesh %r is bound with another lf setting (%r)" % (key, S["lf_key"]))
-            if S["sensor_key"] != self._sensor_key(synth_args[8]):
-                raise ValueError("mesh %r is bound with another sensor model (%r)" % (key, S["sensor_key"]))
+            M["synth"].same_setting(spec, key)
             self._mesh = M
             return M, False
-        S = self._synth_state(*synth_args)
+        S = SynthState(spec, *mesh_args, self.device)
         M = bind()
         M["synth"] = S
         M["mode"].clean = True
@@ -641,114 +633,31 @@ class FacetDenoiser:
         M["captured"].clear()
         return M, True
 
-    @staticmethod
-    def _lf_key(lf):
-        """lf = (width_rel, bumps) of bind_clean / bind_clean_vertices as the value two binds are compared by."""
-        if lf is None:
-            return None
-        width_rel, bumps = lf
-        return (float(width_rel), None if bumps is None else int(bumps))
-
-    @staticmethod
-    def _sensor_key(sensor):
-        """sensor = (power, r_ref, q, camera) of bind_clean / bind_clean_vertices (utils.sensor_model) as the value two binds
-        are compared by: the words the kernel reads and the camera in fp32."""
-        if sensor is None:
-            return None
-        try:
-            power, r_ref, q, camera = sensor
-        except (TypeError, ValueError):
-            raise ValueError("sensor: a model (power, r_ref, q, camera), as utils.sensor_model returns it") from None
-        return (tuple(int(w) for w in ops.sensor_words(power, r_ref, q)), tuple(float(t) for t in ops.sensor_camera(camera)))
-
-    def _synth_state(self, x, verts, faces_rows, edge_len, seed, stream, direction, lf=None, sensor=None):
-        """The checked arguments of bind_clean / bind_clean_vertices as the synthesis state kept with the mesh."""
-        rays = None
-        if not isinstance(direction, str):
-            rays = check_directions(direction, np.asarray(verts).reshape(-1, 3).shape[0])
-        elif direction not in ("random", "normal"):
-            raise ValueError("direction must be 'random', 'normal' or a [V,3] array of unit rows")
-        lf_key = self._lf_key(lf)
-        sensor_key = self._sensor_key(sensor)
-        if sensor_key is not None:
-            if rays is None:
-                raise ValueError("sensor: the model works along viewing rays: direction must be the [V,3] table of rays "
-                                 "from its camera")
-            if lf_key is not None:
-                raise ValueError("sensor: quantisation after bumps along the normals (lf=) is not built; choose one")
-        if lf_key is not None:
-            if not 0 <= int(stream) < 1 << 31:
-                raise ValueError("lf: stream must lie below 2^31 (the top bit marks the bump counters)")
-        vx = np.ascontiguousarray(np.asarray(verts, dtype=np.float32).reshape(-1, 3))
-        fr = np.ascontiguousarray(np.asarray(faces_rows).reshape(-1, 3).astype(np.int32))
-        xa = np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)
-        n0 = xa.size // xa.shape[-1]
-        if fr.shape[0] != n0:
-            raise ValueError("faces_rows has %d rows, the graph %d nodes" % (fr.shape[0], n0))
-        if fr.max() >= vx.shape[0]:
-            raise ValueError("faces_rows names vertex %d of %d" % (fr.max(), vx.shape[0]))
-        if not (np.isfinite(edge_len) and edge_len > 0):
-            raise ValueError("edge_len must be a positive length")
-        dev = self.device
-        S = dict(v=torch.as_tensor(vx, device=dev), faces=torch.as_tensor(fr, device=dev), vn=None,
-                 edge_len=float(edge_len), seed=int(seed), stream=int(stream),
-                 direction=direction_key(direction if rays is None else rays), direction_src=direction, lf_key=lf_key, lf=None,
-                 sensor_key=sensor_key, sensor=None)
-        real = fr[fr[:, 0] >= 0]
-        if (rays is None and direction == "normal") or lf_key is not None:
-            from .utils import areaWeightedVertexNormals
-            vn = torch.as_tensor(areaWeightedVertexNormals(vx, real).astype(np.float32), device=dev)
-            if rays is None and direction == "normal":
-                S["vn"] = vn
-        if rays is not None:
-            S["vn"] = torch.as_tensor(rays, device=dev)      # (where the vertex normals land: the kernel reads rows as given)
-        S["v_out"] = S["v"].clone()
-        need = self.L.fgc_synth_scratch_floats(vx.shape[0])
-        if lf_key is not None:
-            K, width, area = ops.lf_plan(vx, real, edge_len, *lf_key)
-            # (the bumps always go along the clean vertex normals, whatever the white direction)
-            S["lf"] = dict(vn=vn, K=K, width=width, area=area, ctl=torch.zeros(4, dtype=torch.int32, device=dev))
-            need = self.L.fgc_synth_lf_scratch_floats(vx.shape[0], K)      # (its head: the same bounding boxes)
-        if sensor_key is not None:
-            words, cam = sensor_key
-            S["sensor"] = dict(ctl=torch.as_tensor(np.array(words, dtype=np.uint32).view(np.int32), device=dev),
-                               camera=(C.c_float * 3)(*cam))
-        S["scratch"] = torch.zeros(max(need, 1), dtype=torch.float32, device=dev)
-        return S
-
     def _require_synth(self):
         if self._mesh is None or not self._mesh["mode"].clean:
             raise RuntimeError("bind_clean(...) or bind_clean_vertices(...) is required for noise synthesis")
         return self._mesh["synth"]
 
+    def _enqueue_rows(self, M, ctl, have_bbox, what):
+        """fgc_face_features_rows of the mesh's displaced vertices into its input rows (ctl None: whatever the noise words)."""
+        S = M["synth"]
+        _lib.check(self.L.fgc_face_features_rows(_p(S.v_out), S.plan.nv, _p(S.faces), M["ns"][0], _p(ctl), have_bbox,
+                                                 _p(M["B"]["x"]), _p(S.scratch), S.scratch.numel(), self._st()), what)
+
     def _enqueue_synth(self):
         """Two launches: noise (+ per-workgroup bounding boxes), then the input rows (each workgroup reduces the boxes).
         Both read the step's noise words from device memory and return at once while they are zero.  A mesh bound with
         lf=: three launches, the bump table and field + displacement of fgc_synth_noise_lf in the place of the first; with
-        sensor=: fgc_synth_noise_sensor in the place of the first."""
-        M, L, st = self._mesh, self.L, self._st()
-        B, S = M["B"], M["synth"]
+        sensor=: fgc_synth_noise_sensor in the place of the first (synth.enqueue: the plan's entry point)."""
+        M = self._mesh
+        S, noise = M["synth"], M["B"]["noise"]
         self._tag("fwd:synth")
-        nv, sc = S["v"].shape[0], S["scratch"]
-        if S["lf"] is not None:
-            lf = S["lf"]
-            _lib.check(L.fgc_synth_noise_lf(_p(S["v"]), _p(lf["vn"]), _p(S["vn"]), nv, _p(B["noise"]), _p(lf["ctl"]), lf["K"],
-                                            S["seed"] & 0xFFFFFFFFFFFFFFFF, S["stream"] & 0xFFFFFFFF, _p(S["v_out"]),
-                                            _p(sc), sc.numel(), st), "synth lf noise")
-        elif S["sensor"] is not None:
-            sn = S["sensor"]
-            _lib.check(L.fgc_synth_noise_sensor(_p(S["v"]), _p(S["vn"]), nv, _p(B["noise"]), _p(sn["ctl"]), sn["camera"],
-                                                S["seed"] & 0xFFFFFFFFFFFFFFFF, S["stream"] & 0xFFFFFFFF, _p(S["v_out"]),
-                                                _p(sc), sc.numel(), st), "synth sensor noise")
-        else:
-            _lib.check(L.fgc_synth_noise(_p(S["v"]), _p(S["vn"]), nv, _p(B["noise"]), S["seed"] & 0xFFFFFFFFFFFFFFFF,
-                                         S["stream"] & 0xFFFFFFFF, _p(S["v_out"]), _p(sc), sc.numel(), st), "synth noise")
-        _lib.check(L.fgc_face_features_rows(_p(S["v_out"]), nv, _p(S["faces"]), M["ns"][0], _p(B["noise"]), 1, _p(B["x"]),
-                                            _p(sc), sc.numel(), st), "synth features")
+        synth.enqueue(S.plan, S.v, S.v_out, S.scratch, noise, S.lf_ctl, self._st())
+        self._enqueue_rows(M, noise, 1, "synth features")
 
     def noisy_vertices(self):
         """The displaced vertices [V,3] of the last step that synthesised noise (device tensor, overwritten by the next)."""
-        return self._require_synth()["v_out"]
+        return self._require_synth().v_out
 
     def bind_clean_vertices(self, key, x, adjs, verts, faces_rows, v_faces, edge_len, gt_normals=None, iters=VERTEX_ITERS,
                             seed=0, stream=0, direction="random", lf=None, ray_update=False, sensor=None):
@@ -777,16 +686,15 @@ class FacetDenoiser:
             self.bind_vertices(key, x, adjs, vn, faces_rows, v_faces, vn, iters=iters,
                                depth_dir=direction if ray_update else None)
             return self._mesh
-        M, fresh = self._bind_synth(key, (x, verts, faces_rows, edge_len, seed, stream, direction, lf, sensor), True, bind)
-        if bool(ray_update) != (M["verts"]["dirs"] is not None):      # (the direction itself: compared by _bind_synth)
+        spec = NoiseSpec(seed, stream, direction, lf, sensor, bool(ray_update))
+        M, fresh = self._bind_synth(key, spec, (x, verts, faces_rows, edge_len), True, bind)
+        if spec.ray_update != (M["verts"]["dirs"] is not None):      # (the direction itself: compared by _bind_synth)
             raise ValueError("mesh %r is bound %s ray_update" % (key, "without" if ray_update else "with"))
         if fresh:
             S = M["synth"]
-            nv, sc = S["v"].shape[0], S["scratch"]
-            S["gt_box"] = torch.cat([S["v"].min(0).values, S["v"].max(0).values])
+            S.gt_box = torch.cat([S.v.min(0).values, S.v.max(0).values])
             # the boxes of the clean vertices (and the clean input rows once more): what a step without noise words runs on
-            _lib.check(self.L.fgc_face_features_rows(_p(S["v_out"]), nv, _p(S["faces"]), M["ns"][0], None, 0,
-                                                     _p(M["B"]["x"]), _p(sc), sc.numel(), self._st()), "clean features")
+            self._enqueue_rows(M, None, 0, "clean features")
             M["mode"].synth_points = True
         self._attach_gt_normals(M, gt_normals)
         return self
@@ -1306,20 +1214,17 @@ class FacetDenoiser:
         count and the clean mesh's area.  The bump words live in a buffer of their own, beside the packed step inputs: a
         packed row carries the white words only, and the last set_noise holds for the bumps."""
         S = self._require_synth()
-        lf = S["lf"]
         if lf_level is not None:
-            if lf is None:
+            if S.plan.lf is None:
                 raise ValueError("lf_level needs a mesh bound with lf=(width, bumps)")
             if level is None:
                 raise ValueError("lf_level needs a level (0 for bumps alone): level None switches the synthesis off")
             if not (np.isfinite(lf_level) and lf_level >= 0):
                 raise ValueError("lf_level must be finite and >= 0 (got %r)" % (lf_level,))
         self._own_step_inputs()
-        words = ops.noise_words(step, None if level is None else np.float32(level) * np.float32(S["edge_len"]))
-        self._upload(self._mesh["B"]["noise"], words.view(np.int32))
-        if lf is not None:
-            amp = None if lf_level is None else ops.lf_amplitude(lf_level, S["edge_len"], lf["width"], lf["K"], lf["area"])
-            self._upload(lf["ctl"], ops.lf_words(amp, lf["width"]).view(np.int32))
+        self._upload(self._mesh["B"]["noise"], S.plan.noise_words(step, level))
+        if S.plan.lf is not None:
+            self._upload(S.lf_ctl, S.plan.lf_words(lf_level))
 
     def set_samples(self, sample_ind):
         """Indices of the rows the loss is evaluated on (train.py:561), any of the N0 padded rows."""
@@ -1711,8 +1616,8 @@ class FacetDenoiser:
             # box, rotated - one launch behind the two of _enqueue_synth, whose boxes it reads
             self._tag("pts:prepare")
             S = M["synth"]
-            sc = S["scratch"]
-            _lib.check(L.fgc_point_sets_prepare(_p(S["v_out"]), nv, _p(S["v"]), nv, _p(S["gt_box"]),
+            sc = S.scratch
+            _lib.check(L.fgc_point_sets_prepare(_p(S.v_out), nv, _p(S.v), nv, _p(S.gt_box),
                                                 _p(B["R"]) if rotate else None, 1, _p(V["xr"]), _p(V["gtr"]), _p(sc),
                                                 sc.numel(), st), "point sets")
             x, gt = V["xr"], V["gtr"]

@@ -917,6 +917,25 @@ def noise_words(step, sigma):
     return np.array([step & 0xFFFFFFFF, step >> 32, bits | _lib.SYNTH_ON], dtype=np.uint32)
 
 
+def _synth_prologue(verts, tables, row, step, sigma, ctl, out, scratch, scratch_floats):
+    """What the three noise calls share: verts as contiguous float32 [V,3]; the per-vertex tables (None stays None) the same
+    and refused unless each has V rows ("one <row> per vertex"); the control words of (step, sigma) on the device unless ctl
+    is given; the output; a scratch of scratch_floats(V) floats unless one is given.
+    Returns (verts, V, tables, ctl, out, scratch)."""
+    verts = _f32c(verts.reshape(-1, 3))
+    nv = verts.shape[0]
+    tables = [None if t is None else _f32c(t.reshape(-1, 3)) for t in tables]
+    if any(t is not None and t.shape[0] != nv for t in tables):
+        raise ValueError("one %s per vertex" % row)
+    if ctl is None:
+        ctl = torch.from_numpy(noise_words(step, sigma).view(np.int32)).to(verts.device)
+    if out is None:
+        out = torch.empty_like(verts)
+    if scratch is None:
+        scratch = torch.empty(max(scratch_floats(nv), 1), dtype=torch.float32, device=verts.device)
+    return verts, nv, tables, ctl, out, scratch
+
+
 def synth_noise(verts, sigma, step, seed=0, stream=0, normals=None, out=None, scratch=None, ctl=None):
     """Build extension (include/fgc.h: fgc_synth_noise): the vertices verts [V,3] displaced by Philox4x32-10 Gaussian noise
     of standard deviation sigma - along a random direction, or along `normals` [V,3] (unit vertex normals) - for the
@@ -924,19 +943,8 @@ def synth_noise(verts, sigma, step, seed=0, stream=0, normals=None, out=None, sc
     ctl: the control words already on the device (int32 [3]) instead of (step, sigma); scratch: float32, at least
     fgc_synth_scratch_floats(V) - it receives the bounding-box partials face_features_rows(have_bbox=True) reads."""
     _req_cuda(verts, normals, out, scratch, ctl)
-    verts = _f32c(verts.reshape(-1, 3))
-    nv = verts.shape[0]
-    if normals is not None:
-        normals = _f32c(normals.reshape(-1, 3))
-        if normals.shape[0] != nv:
-            raise ValueError("one normal per vertex")
-    if ctl is None:
-        ctl = torch.from_numpy(noise_words(step, sigma).view(np.int32)).to(verts.device)
-    if out is None:
-        out = torch.empty_like(verts)
-    need = _lib.lib().fgc_synth_scratch_floats(nv)
-    if scratch is None:
-        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=verts.device)
+    verts, nv, (normals,), ctl, out, scratch = _synth_prologue(verts, (normals,), "normal", step, sigma, ctl, out, scratch,
+                                                               _lib.lib().fgc_synth_scratch_floats)
     check(_lib.lib().fgc_synth_noise(ptr(verts), ptr(normals), nv, ptr(ctl), int(seed) & 0xFFFFFFFFFFFFFFFF,
                                      int(stream) & 0xFFFFFFFF, ptr(out), ptr(scratch), scratch.numel(), stream_ptr()),
           "fgc_synth_noise")
@@ -980,21 +988,11 @@ def synth_noise_sensor(verts, rays, camera, sigma, step, power, r_ref, q, seed=0
     if rays is None:
         raise ValueError("the sensor model needs the table of viewing rays: rays is required")
     _req_cuda(verts, rays, out, scratch, ctl, sensor_ctl)
-    verts = _f32c(verts.reshape(-1, 3))
-    nv = verts.shape[0]
-    rays = _f32c(rays.reshape(-1, 3))
-    if rays.shape[0] != nv:
-        raise ValueError("one ray per vertex")
+    verts, nv, (rays,), ctl, out, scratch = _synth_prologue(verts, (rays,), "ray", step, sigma, ctl, out, scratch,
+                                                            _lib.lib().fgc_synth_scratch_floats)
     cam = sensor_camera(camera)
-    if ctl is None:
-        ctl = torch.from_numpy(noise_words(step, sigma).view(np.int32)).to(verts.device)
     if sensor_ctl is None:
         sensor_ctl = torch.from_numpy(sensor_words(power, r_ref, q).view(np.int32)).to(verts.device)
-    if out is None:
-        out = torch.empty_like(verts)
-    need = _lib.lib().fgc_synth_scratch_floats(nv)
-    if scratch is None:
-        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=verts.device)
     check(_lib.lib().fgc_synth_noise_sensor(ptr(verts), ptr(rays), nv, ptr(ctl), ptr(sensor_ctl), cam.ctypes.data,
                                             int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, ptr(out), ptr(scratch),
                                             scratch.numel(), stream_ptr()), "fgc_synth_noise_sensor")
@@ -1052,23 +1050,12 @@ def synth_noise_lf(verts, normals, sigma, step, amplitude, width, bumps, seed=0,
     if normals is None:
         raise ValueError("the bumps go along the vertex normals: normals is required")
     _req_cuda(verts, normals, white_normals, out, scratch, ctl, lf_ctl)
-    verts = _f32c(verts.reshape(-1, 3))
-    nv = verts.shape[0]
-    normals = _f32c(normals.reshape(-1, 3))
-    if white_normals is not None:
-        white_normals = _f32c(white_normals.reshape(-1, 3))
-    if normals.shape[0] != nv or (white_normals is not None and white_normals.shape[0] != nv):
-        raise ValueError("one normal per vertex")
     bumps = int(bumps)      # (the library refuses a count outside 1 ... FGC_SYNTH_LF_MAX_BUMPS and a stream >= 2^31)
-    if ctl is None:
-        ctl = torch.from_numpy(noise_words(step, sigma).view(np.int32)).to(verts.device)
+    verts, nv, (normals, white_normals), ctl, out, scratch = _synth_prologue(
+        verts, (normals, white_normals), "normal", step, sigma, ctl, out, scratch,
+        lambda nv: _lib.lib().fgc_synth_lf_scratch_floats(nv, bumps))
     if lf_ctl is None:
         lf_ctl = torch.from_numpy(lf_words(amplitude, width).view(np.int32)).to(verts.device)
-    if out is None:
-        out = torch.empty_like(verts)
-    need = _lib.lib().fgc_synth_lf_scratch_floats(nv, bumps)
-    if scratch is None:
-        scratch = torch.empty(max(need, 1), dtype=torch.float32, device=verts.device)
     check(_lib.lib().fgc_synth_noise_lf(ptr(verts), ptr(normals), ptr(white_normals), nv, ptr(ctl), ptr(lf_ctl), bumps,
                                         int(seed) & 0xFFFFFFFFFFFFFFFF, int(stream) & 0xFFFFFFFF, ptr(out), ptr(scratch),
                                         scratch.numel(), stream_ptr()), "fgc_synth_noise_lf")

@@ -32,6 +32,7 @@ from . import ops, tfckpt
 from .makeNoisy import pair_lf_levels
 from .net import FacetDenoiser, COST_SAMPLES, POINT_SAMPLES, POINT_LOSS_THRESHOLD
 from .settings import SAVEITER, NUM_ITERATIONS
+from .synth import NoiseSpec
 from .utils import rand_rotation_matrix
 
 
@@ -189,10 +190,10 @@ def _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction):
 
 
 def _lf_inputs(levels, lf_levels, lf_width, lf_bumps):
-    """The checked low-frequency setting of a trainer: None, or (one lf level per noise level, (width, bumps)) - level
-    index k pairs levels[k] with lf_levels[k]; a single lf level goes with every noise level."""
+    """The checked low-frequency setting of a trainer: (None, None), or (one lf level per noise level, (width, bumps)) -
+    level index k pairs levels[k] with lf_levels[k]; a single lf level goes with every noise level."""
     if lf_levels is None:
-        return None
+        return None, None
     if levels is None:
         raise ValueError("lf_levels needs noise_levels (noise_levels=(0,) for bumps alone)")
     lf = pair_lf_levels(lf_levels, len(levels))
@@ -252,19 +253,24 @@ def _mesh_direction(direction, m):
 _RAYS = {}
 
 
+def _run_noise(levels, seed, direction, lf_shape, ray_update, sensor):
+    """The per-run part of a trainer's noise setting as a NoiseSpec (None: a plain run): stream 0, direction as given - a
+    view is resolved per mesh - lf_shape = (width, bumps) of _lf_inputs, sensor = (power, quant) of _sensor_inputs."""
+    if levels is None:
+        return None
+    return NoiseSpec(seed, 0, direction, lf_shape, sensor, bool(ray_update))
+
+
 def _bind(F, key, m, noise=None):
-    """Bind mesh record m under `key` through F = net.trainer_form(form): plain, or - noise = (seed, stream, direction
-    [, lf = (width, bumps)[, ray_update[, sensor = (power, quant)]]]) - clean for noise synthesis.  (A cached mesh returns at once; the bind methods
-    reshape the [1, ...] arrays.)"""
+    """Bind mesh record m under `key` through F = net.trainer_form(form): plain, or - noise: the run's NoiseSpec with the
+    stream to bind under - clean for noise synthesis, direction and sensor filled per mesh.  (A cached mesh returns at once;
+    the bind methods reshape the [1, ...] arrays.)"""
     kw = {"gt_normals": m.gt_normals} if F.gt_normals else {}
     if noise is not None:
-        kw.update(seed=noise[0], stream=noise[1], direction=_mesh_direction(noise[2], m))
-        if len(noise) > 3 and noise[3] is not None:
-            kw.update(lf=noise[3])
-        if len(noise) > 4 and noise[4]:
-            kw.update(ray_update=True)      # (the vertex trainers only: bind_clean_vertices)
-        if len(noise) > 5 and noise[5] is not None:
-            kw.update(sensor=_mesh_sensor(noise[5], noise[2], m))
+        spec = noise._replace(direction=_mesh_direction(noise.direction, m),
+                              sensor=None if noise.sensor is None else _mesh_sensor(noise.sensor, noise.direction, m))
+        # (the settings a run does not use stay out: bind_clean has no ray_update)
+        kw.update({k: v for k, v in spec._asdict().items() if k in ("seed", "stream", "direction") or v})
     (F.bind if noise is None else F.bind_clean)(key, *m.args, **kw)
 
 
@@ -284,24 +290,32 @@ def _draw_step(rs, F, m, levels, counter, lf_levels=None):
     return samples, R, (counter, levels[k]) if lf_levels is None else (counter, levels[k], lf_levels[k])
 
 
-def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="random", lf=None, ray_update=False,
-                     sensor=None):
+def _validate(net, form, valid, R, rs, levels=None, noise=None, lf_levels=None):
     """The mean {total, points, normals} (entries a form does not have stay 0) of the loss alone over the validation mesh
     records, with rotation R and fresh rows from rs: one pass per mesh, or - levels given - per clean mesh and noise level
     with stream = 1 + mesh index and step = level index: the SAME noisy meshes at every call (and what makeNoisy writes for
-    the same seed), so the validation curve is comparable along a run.  lf = (lf levels, (width, bumps)) of _lf_inputs:
-    level k goes with lf level k.  ray_update: the vertex update along the noise's rays, as in training.  sensor = (power,
-    quant): the depth-sensor model, resolved per mesh as in training."""
+    the same seed), so the validation curve is comparable along a run.  noise: the run's NoiseSpec (_run_noise), bound as
+    in training but for the stream; lf_levels: level k goes with lf level k."""
     F, vsum = net.trainer_form(form), np.zeros(3)
     for vbm, m in enumerate(valid):
-        _bind(F, ("valid", vbm), m, None if levels is None else (seed, 1 + vbm, direction, lf and lf[1], ray_update, sensor))
+        _bind(F, ("valid", vbm), m, None if levels is None else noise._replace(stream=1 + vbm))
         for k, level in enumerate((None,) if levels is None else levels):
             F.set_samples(*_draw_samples(rs, F, m))
             net.set_rotation(R)
             if level is not None:
-                net.set_noise(k, level, *((lf[0][k],) if lf else ()))
+                net.set_noise(k, level, *((lf_levels[k],) if lf_levels else ()))
             vsum[:F.outputs] += F.loss(rotate=True)[:F.outputs].cpu().numpy()
     return vsum / (len(valid) * (1 if levels is None else len(levels)))
+
+
+def _validation_loss(net, form, valid, R, rs, levels=None, seed=0, direction="random", lf=None, ray_update=False,
+                     sensor=None):
+    """_validate with the noise setting as loose arguments: lf = (lf levels, (width, bumps)) of _lf_inputs; ray_update: the
+    vertex update along the noise's rays, as in training; sensor = (power, quant): the depth-sensor model, resolved per
+    mesh as in training."""
+    lf_levels, lf_shape = lf or (None, None)
+    return _validate(net, form, valid, R, rs, levels, _run_noise(levels, seed, direction, lf_shape, ray_update, sensor),
+                     lf_levels)
 
 
 def synthValidationLoss(net, valid, noise_levels, R, rs, seed=0, direction="random", lf=None, sensor=None):
@@ -355,9 +369,9 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
     range^power; quant > 0 is the depth step there in mean edge lengths.  Validation scores its fixed meshes with the same model."""
     form = "angular"
     levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
-    lf = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
-    sensor = _sensor_inputs(levels, sensor, noise_direction, lf)
-    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1], False, sensor)
+    lf_levels, lf_shape = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
+    sensor = _sensor_inputs(levels, sensor, noise_direction, lf_levels)
+    train_noise = _run_noise(levels, seed, noise_direction, lf_shape, False, sensor)
     net = FacetDenoiser(device, seed=seed)
     F = net.trainer_form(form)
     ckpt = os.path.join(network_path, net_name) if network_path else None
@@ -373,12 +387,12 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
         if b != bound:       # the reference feeds a new patch through feed_dict; here every mesh stays bound in HBM
             _bind(F, b, meshes[b], train_noise)
             bound = b
-        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it, lf and lf[0])
+        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it, lf_levels)
         if valid and it % (evalStepNum * 2) == 0:
             # train.py:588-617: every 100 iterations the loss alone on every validation mesh, with this iteration's
             # rotation and fresh random rows, BEFORE the training step; the previous row of the CSV gets the mean of
             # this and the last value
-            valid_loss = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf, sensor=sensor)[0]
+            valid_loss = _validate(net, form, valid, R_it, rs, levels, train_noise, lf_levels)[0]
             log("Iteration %d, validation loss %g" % (it, valid_loss))
             row = min(it // evalStepNum, len(lossArray) - 1)
             lossArray[row, 1] = valid_loss
@@ -470,13 +484,13 @@ def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name,
                          ray_update=False, sensor=None):
     """The loop of trainAccuracyNet (form "points") and trainDoubleLossNet ("double")."""
     levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
-    lf = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
-    sensor = _sensor_inputs(levels, sensor, noise_direction, lf)
+    lf_levels, lf_shape = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
+    sensor = _sensor_inputs(levels, sensor, noise_direction, lf_levels)
     ray_update = bool(ray_update)
     if ray_update and (levels is None or isinstance(noise_direction, str)):
         raise ValueError("ray_update moves the vertices along the noise's rays: it needs noise_levels and a noise_direction "
                          "of rays (a view {'camera': xyz} / {'view_dir': xyz} or a [V,3] table)")
-    train_noise = None if levels is None else (seed, 0, noise_direction, lf and lf[1], ray_update, sensor)
+    train_noise = _run_noise(levels, seed, noise_direction, lf_shape, ray_update, sensor)
     net = FacetDenoiser(device, multi_scale=True, seed=seed)
     F = net.trainer_form(form)
     ckpt = os.path.join(network_path, net_name) if network_path else None
@@ -498,10 +512,10 @@ def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name,
 
     for it in range(num_iterations):
         b = rs.randint(len(meshes))
-        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it, lf and lf[0])
+        samp_it, R_it, noise_it = _draw_step(rs, F, meshes[b], levels, start + it, lf_levels)
         row = (it % block) // evalStepNum
         if valid and it % validStepNum == 0 and it >= first_valid:
-            vsum = _validation_loss(net, form, valid, R_it, rs, levels, seed, noise_direction, lf, ray_update, sensor)
+            vsum = _validate(net, form, valid, R_it, rs, levels, train_noise, lf_levels)
             log(_VALID_LOG[F.outputs] % ((it,) + tuple(vsum[:F.outputs])))      # (the double loss with its points / normals split)
             lossArray[row, 1] = vsum[0]
             if row > 0:
@@ -802,7 +816,7 @@ def main(argv=None):
     ap.add_argument("--noise-direction", choices=("random", "normal", "ray"), default="random",
                     help="with --synth-noise: displace along a random direction, along the vertex normal, or (ray) along the "
                     "viewing rays of --view-dir / --camera, built from each mesh's clean vertices (depth scans)")
-    from .utils import view_options, view_spec
+    from .utils import view_options, noise_view_spec
     view_options(ap)
     ap.add_argument("--ray-update", action="store_true",
                     help="with --with-vertices --noise-direction ray: the vertex update of every step moves the vertices along "
@@ -818,24 +832,7 @@ def main(argv=None):
                     "the reference range in mean edge lengths, depth quantised in disparity.  The reference range is the "
                     "camera's distance to each mesh's centre.  E.g. --sensor 2:0.5 (nobody has tuned these values)")
     args = ap.parse_args(argv)
-    view = view_spec(ap, args)
-    sensor = None
-    if args.sensor is not None:
-        from .utils import parse_sensor
-        try:
-            sensor = parse_sensor(args.sensor)
-        except ValueError as e:
-            ap.error("--sensor POWER[:QUANT], e.g. 2:0.5 - %s (got %r)" % (e, args.sensor))
-        if args.view_dir is not None:
-            ap.error("--sensor needs a perspective view: --view-dir has no range, use --camera")
-        if args.noise_direction != "ray":
-            ap.error("--sensor needs --noise-direction ray (got --noise-direction %s)" % args.noise_direction)
-        if args.camera is None:
-            ap.error("--sensor needs --camera X,Y,Z (with --noise-direction ray)")
-        if args.lf_noise is not None:
-            ap.error("--sensor does not combine with --lf-noise: quantisation after bumps along the normals is not built")
-    if (args.noise_direction == "ray") != bool(view):
-        ap.error("--noise-direction ray needs --view-dir or --camera, and the two go with --noise-direction ray only")
+    view, sensor = noise_view_spec(ap, args, "--noise-direction", "--lf-noise")
     if view and args.synth_noise is None:
         ap.error("--noise-direction ray needs --synth-noise")
     if args.double_loss and not args.with_vertices:

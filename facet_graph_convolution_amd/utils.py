@@ -431,6 +431,32 @@ def view_spec(ap, args):
     return out
 
 
+def noise_view_spec(ap, args, direction_opt, lf_opt):
+    """view_spec for the two programs that make noise along the view (train, makeNoisy), with their --sensor: the refusals of
+    a --sensor that has no camera to range from and of a ray direction without a view (or a view without it).  direction_opt
+    / lf_opt: the names of the program's direction and low-frequency options (their values: args.<name>).
+    Returns (view, sensor = (power, quant) | None)."""
+    view = view_spec(ap, args)
+    attr = lambda opt: getattr(args, opt[2:].replace("-", "_"))  # noqa: E731
+    sensor = None
+    if args.sensor is not None:
+        try:
+            sensor = parse_sensor(args.sensor)
+        except ValueError as e:
+            ap.error("--sensor POWER[:QUANT], e.g. 2:0.5 - %s (got %r)" % (e, args.sensor))
+        if args.view_dir is not None:
+            ap.error("--sensor needs a perspective view: --view-dir has no range, use --camera")
+        if attr(direction_opt) != "ray":
+            ap.error("--sensor needs %s ray (got %s %s)" % (direction_opt, direction_opt, attr(direction_opt)))
+        if args.camera is None:
+            ap.error("--sensor needs --camera X,Y,Z (with %s ray)" % direction_opt)
+        if attr(lf_opt) is not None:
+            ap.error("--sensor does not combine with %s: quantisation after bumps along the normals is not built" % lf_opt)
+    if (attr(direction_opt) == "ray") != bool(view):
+        ap.error("%s ray needs --view-dir or --camera, and the two go with %s ray only" % (direction_opt, direction_opt))
+    return view, sensor
+
+
 def check_directions(direction, nv):
     """A [V,3] table of unit noise directions (rays) as a contiguous float32 copy (the caller's may be read-only): nv rows,
     finite, every row norm within 1e-3 of 1; ValueError otherwise."""

@@ -121,7 +121,7 @@ def test_direction_tables_are_checked():
     from facet_graph_convolution_amd import makeNoisy
     from facet_graph_convolution_amd import train as T
     from facet_graph_convolution_amd.meshgen import icosphere
-    from facet_graph_convolution_amd.net import FacetDenoiser
+    from facet_graph_convolution_amd.synth import NoiseSpec, SynthState
     V, F = icosphere(1)
     V = V.astype(np.float32)
     rays = utils.view_rays(V, camera=(0, 0, 5))
@@ -132,7 +132,6 @@ def test_direction_tables_are_checked():
     assert utils.check_directions(rays, V.shape[0]).tobytes() == rays.tobytes()
     near = rays * np.float32(1.0005)
     utils.check_directions(near, V.shape[0])           # within 1e-3 of 1
-    state = FacetDenoiser._synth_state
     x = np.zeros((1, F.shape[0], 6), dtype=np.float32)
     for d, msg in bad:
         with pytest.raises(ValueError, match=msg):
@@ -140,7 +139,7 @@ def test_direction_tables_are_checked():
         with pytest.raises(ValueError, match=msg):
             makeNoisy.make_noisy(V, F, 0.1, direction=d)
         with pytest.raises(ValueError, match=msg):
-            state(None, x, V, F, 0.1, 0, 0, d)
+            SynthState(NoiseSpec(0, 0, d), x, V, F, 0.1, "cpu")      # (what bind_clean builds: refused before any device work)
     with pytest.raises(ValueError, match="direction must be"):
         makeNoisy.make_noisy(V, F, 0.1, direction="sideways")
     # the key two binds are compared by: hashable, equal for equal rows, different otherwise

@@ -406,7 +406,7 @@ def test_trainer_with_ray_update_moves_vertices_along_the_view(double):
         Vs, S = n._mesh["verts"], n._mesh["synth"]
         noisy, refined = n.noisy_vertices(), Vs["traj"].reshape(121, -1, 3)[-1]
         # (the step reads the noisy vertices over the diagonal of the union box: xr; the clean mesh's x and y survive the noise)
-        assert torch.equal(noisy[:, :2], S["v"][:, :2]) and not torch.equal(noisy[:, 2], S["v"][:, 2])
+        assert torch.equal(noisy[:, :2], S.v[:, :2]) and not torch.equal(noisy[:, 2], S.v[:, 2])
         scale = (noisy[:, :2] / Vs["xr"][:, :2])[Vs["xr"][:, :2].abs() > 1e-3]
         assert (scale.max() - scale.min()).item() < 1e-5 * scale.max().item()
         shared.append(torch.equal(refined[:, :2], Vs["xr"][:, :2]))

@@ -388,7 +388,7 @@ def test_trainers_take_the_model(trainer):
     assert not np.array_equal(_bits(want), _bits(make_noisy(cv, F, 0.2, seed=0, stream=0, step=2, direction=rays)))
     S = net._mesh_cache[("valid", 0)]["synth"]
     model = utils.sensor_model(cv, sn.CAMERA, ds.clean_edge_len[0], 2, 0.5)
-    assert S["sensor_key"][0] == tuple(int(w) for w in ops.sensor_words(model.power, model.r_ref, model.q)) and S["stream"] == 1
+    assert S.key.sensor[0] == tuple(int(w) for w in ops.sensor_words(model.power, model.r_ref, model.q)) and S.key.stream == 1
 
 
 # ---------------------------------------------------------------------------------------------------------------------

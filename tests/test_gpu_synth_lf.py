@@ -296,7 +296,7 @@ def _rotation(seed=3):
 def test_a_network_bound_with_lf_and_no_lf_level_is_the_white_network(tag, direction):
     net, ds = _bound_net(tag, direction=direction)
     white, _ = _bound_net(tag, lf_arg=None, direction=direction)
-    assert net._mesh["synth"]["lf"]["K"] == -(-ds.num_faces[0] // 6) and white._mesh["synth"]["lf"] is None
+    assert net._mesh["synth"].plan.lf.K == -(-ds.num_faces[0] // 6) and white._mesh["synth"].plan.lf is None
     for step, level in ((7, 0.2), (8, 0.0)):
         for n in (net, white):
             n.set_noise(step, level)
