@@ -14,7 +14,8 @@ namespace fgc {
 // non-finite coordinate) is returned as it is: every comparison with it is false, so it never wins.
 // In the last region (u, v) is clamped to u in [0, 1], v in [0, 1 - u] by comparisons that leave a NaN alone: whatever the
 // rounding of va, vb, vc did, the point a + u e1 + v e2 lies on the triangle, which is what the culling bound rests on.
-__device__ __forceinline__ float cp_pair(const float (&q)[3], f32x4 a, f32x4 e1, f32x4 e2, float& u, float& v) {
+// cp_pair_r also hands out r (what the surface loss differentiates); cp_pair is the same arithmetic without it.
+__device__ __forceinline__ float cp_pair_r(const float (&q)[3], f32x4 a, f32x4 e1, f32x4 e2, float& u, float& v, float (&r)[3]) {
     const float apx = q[0] - a.x, apy = q[1] - a.y, apz = q[2] - a.z;
     const float d1 = rc_dot(e1.x, e1.y, e1.z, apx, apy, apz), d2 = rc_dot(e2.x, e2.y, e2.z, apx, apy, apz);
     const float bpx = apx - e1.x, bpy = apy - e1.y, bpz = apz - e1.z;
@@ -48,7 +49,12 @@ __device__ __forceinline__ float cp_pair(const float (&q)[3], f32x4 a, f32x4 e1,
     const float rx = __builtin_fmaf(-v, e2.x, __builtin_fmaf(-u, e1.x, apx));
     const float ry = __builtin_fmaf(-v, e2.y, __builtin_fmaf(-u, e1.y, apy));
     const float rz = __builtin_fmaf(-v, e2.z, __builtin_fmaf(-u, e1.z, apz));
+    r[0] = rx, r[1] = ry, r[2] = rz;
     return rc_dot(rx, ry, rz, rx, ry, rz);
+}
+__device__ __forceinline__ float cp_pair(const float (&q)[3], f32x4 a, f32x4 e1, f32x4 e2, float& u, float& v) {
+    float r[3];
+    return cp_pair_r(q, a, e1, e2, u, v, r);
 }
 
 }  // namespace fgc

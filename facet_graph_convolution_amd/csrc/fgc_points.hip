@@ -4,7 +4,7 @@
 // a term (its P0 row, its masked distance, its gradient on that row) and one single-workgroup launch sums the loss and
 // reduces the terms that share a P0 row: a term is summed by the first term of its row, in term order.  No atomics: the
 // loss and the gradient are the same bits from run to run and under hipGraph replay.
-#include "fgc_common.h"
+#include "fgc_points.h"
 
 extern "C" int fgc_nn_query(const float* q, int32_t nq, const float* p, int32_t np, const int32_t* q_cell,
                             const int32_t* p_cell, float* dist, int32_t* idx, void* workspace, size_t workspace_bytes,
@@ -64,17 +64,19 @@ __global__ __launch_bounds__(256) void point_loss_terms_kernel(const float* __re
                            (p0[3 * (size_t)r + 2] - p1[3 * (size_t)m + 2]) * w, keep ? d : 0.f);
 }
 
-// one workgroup: loss = 1000 (sum of the first ns0 values / ns0 + sum of the rest / ns1), both sums in a fixed tree order;
-// gradient rows written by the first term of each row (g must be zero on entry)
+// one workgroup: loss = 1000 (sum of the first nt0 values / n0 + sum of the other nt1 / n1), both sums in a fixed tree order;
+// gradient rows written by the first term of each row (g must be zero on entry).  fgc_point_loss has one term per sample
+// (nt = n); fgc_surface_loss three per completeness sample, the value on the first of them.
 __global__ __launch_bounds__(PL_THREADS) void point_loss_finish_kernel(const int* __restrict__ rows,
-                                                                       const float4* __restrict__ terms, int ns0, int ns1,
-                                                                       float* __restrict__ loss, float* __restrict__ g) {
+                                                                       const float4* __restrict__ terms, int nt0, int nt1,
+                                                                       int n0, int n1, float* __restrict__ loss,
+                                                                       float* __restrict__ g) {
     __shared__ float s0[PL_THREADS], s1[PL_THREADS];
     const int tid = threadIdx.x;
-    const int nt = ns0 + ns1;
+    const int nt = nt0 + nt1;
     float a0 = 0.f, a1 = 0.f;
     for (int t = tid; t < nt; t += PL_THREADS) {
-        if (t < ns0)
+        if (t < nt0)
             a0 += terms[t].w;
         else
             a1 += terms[t].w;
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(PL_THREADS) void point_loss_finish_kernel(const int
         }
         __syncthreads();
     }
-    if (tid == 0) loss[0] = 1000.0f * (s0[0] / (float)ns0 + s1[0] / (float)ns1);
+    if (tid == 0) loss[0] = 1000.0f * (s0[0] / (float)n0 + s1[0] / (float)n1);
     if (!g) return;
     for (int t = tid; t < nt; t += PL_THREADS) {
         const int r = rows[t];
@@ -109,6 +111,16 @@ __global__ __launch_bounds__(PL_THREADS) void point_loss_finish_kernel(const int
         g[3 * (size_t)r + 1] = gy;
         g[3 * (size_t)r + 2] = gz;
     }
+}
+
+void point_gather(const float* p, int np, const int* ind, int n, float* q, hipStream_t st) {
+    FGC_LAUNCH("point_gather_kernel", st, point_gather_kernel, dim3(cdiv(n, 256)), dim3(256), 0, p, np, ind, n, q);
+}
+
+void point_loss_finish(const int* rows, const float4* terms, int nt0, int nt1, int n0, int n1, float* loss, float* g,
+                       hipStream_t st) {
+    FGC_LAUNCH("point_loss_finish_kernel", st, point_loss_finish_kernel, dim3(1), dim3(PL_THREADS), 0, rows, terms, nt0, nt1,
+               n0, n1, loss, g);
 }
 
 }  // namespace fgc
@@ -169,8 +181,8 @@ extern "C" int fgc_point_loss(const float* p0, int32_t np0, const float* p1, int
     int* rows = (int*)(ws + L.rows);
     float4* terms = (float4*)(ws + L.terms);
     const size_t nnb = L.q0 - L.nn;
-    FGC_LAUNCH("point_gather_kernel", st, point_gather_kernel, dim3(cdiv(ns0, 256)), dim3(256), 0, p0, np0, i0, ns0, q0);
-    FGC_LAUNCH("point_gather_kernel", st, point_gather_kernel, dim3(cdiv(ns1, 256)), dim3(256), 0, p1, np1, i1, ns1, q1);
+    point_gather(p0, np0, i0, ns0, q0, st);
+    point_gather(p1, np1, i1, ns1, q1, st);
     int rc = fgc_nn_query(q0, ns0, p1, np1, nullptr, nullptr, d0, x0, ws + L.nn, nnb, stream);
     if (rc != FGC_OK) return rc;
     rc = fgc_nn_query(q1, ns1, p0, np0, nullptr, nullptr, d1, x1, ws + L.nn, nnb, stream);
@@ -181,8 +193,7 @@ extern "C" int fgc_point_loss(const float* p0, int32_t np0, const float* p1, int
         fgc::set_error("fgc_point_loss: memset failed");
         return FGC_EHIP;
     }
-    FGC_LAUNCH("point_loss_finish_kernel", st, point_loss_finish_kernel, dim3(1), dim3(PL_THREADS), 0, rows, terms, ns0, ns1,
-               loss, g_p0);
+    point_loss_finish(rows, terms, ns0, ns1, ns0, ns1, loss, g_p0, st);
     FGC_CHECK_LAUNCH("fgc_point_loss");
     return FGC_OK;
 }

@@ -2,7 +2,7 @@
 // triangle it meets, brute force over rays x triangles.  What a virtual depth scan is made of (utils.visible_vertices,
 // utils.depth_image); run once per mesh at preparation time, never per training step.
 //
-// Three launches:
+// Three launches (the layout, the slab split and rc_gather_kernel live in fgc_slabs.h, shared with fgc_surface.hip):
 //   rc_gather_kernel  one thread per record: rc_record of triangle f (zero records for a bad row and the padding behind nf).
 //                     The same launch sets every ray's key to (+inf, -1).
 //   rc_cast_kernel    64 rays per workgroup, one per lane and the same in all four waves (bl_filter_kernel's shape); the
@@ -26,48 +26,11 @@
 //
 // Contraction is off, every FMA is written out.  Device data is never trusted for addressing: vertex ids are checked
 // before a load, the face of a key before the record is read.
-#include "fgc_raycast.h"
+#include "fgc_slabs.h"
 
 #pragma clang fp contract(off)
 
 namespace fgc {
-
-constexpr int RC_THREADS = 256;
-constexpr int RC_WAVES = RC_THREADS / 64;
-constexpr int RC_Q = 64;               // rays per workgroup: one per lane, the same in every wave
-constexpr int RC_TARGET_WGS = 2048;    // workgroups that fill the device: 256 CUs x 8 of 256 threads
-constexpr int RC_MIN_SLAB = 1024;      // records a slab has at least (a slab costs one atomic per ray)
-constexpr unsigned long long RC_MISS = 0x7F800000FFFFFFFFull;      // (+inf, face -1)
-
-struct RcLayout {
-    int nrec;            // records: nf rounded up to whole chunks
-    int slabs, per_slab;
-    size_t keys, total;
-};
-
-// the slab split depends on (nf, nq) alone
-static RcLayout rc_layout(int nf, int nq) {
-    RcLayout l;
-    l.nrec = cdiv(nf, RC_CHUNK) * RC_CHUNK;
-    const int slabs = std::min(cdiv(RC_TARGET_WGS, cdiv(nq, RC_Q)), std::max(1, nf / RC_MIN_SLAB));
-    l.per_slab = cdiv(cdiv(nf, slabs), RC_CHUNK * RC_WAVES) * (RC_CHUNK * RC_WAVES);
-    l.slabs = cdiv(nf, l.per_slab);
-    l.keys = align_up((size_t)l.nrec * 3 * sizeof(f32x4), 16);
-    l.total = l.keys + align_up((size_t)nq * sizeof(unsigned long long), 16);
-    return l;
-}
-
-__global__ __launch_bounds__(256) void rc_gather_kernel(const float* __restrict__ verts, int nv, const int* __restrict__ faces,
-                                                        int nf, int nrec, f32x4* __restrict__ rec,
-                                                        unsigned long long* __restrict__ keys, int nq) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < nq) keys[j] = RC_MISS;
-    if (j >= nrec) return;
-    f32x4 r0, r1, r2;
-    float v[3][3];
-    rc_record(verts, nv, faces, nf, j, r0, r1, r2, v);
-    rec[3 * (size_t)j] = r0, rec[3 * (size_t)j + 1] = r1, rec[3 * (size_t)j + 2] = r2;
-}
 
 // grid (ceil(nq / 64), slabs)
 __global__ __launch_bounds__(RC_THREADS) void rc_cast_kernel(const f32x4* __restrict__ rec, int nrec, int per_slab,

@@ -282,6 +282,48 @@ class TrainingSet(PreprocessedData):
         self.faces = np.asarray(faces)
         self.normals = utils.computeFacesNormals(V_noisy, self.faces)
 
+    def addMeshWithVerticesAndGTMesh(self, V_noisy, faces, V_gt, F_gt, seed=None, parents=None):
+        """Build extension: a noisy mesh with a ground-truth MESH of any topology, for trainAccuracyNet - its vertex and face
+        counts need not be the noisy mesh's, and nothing pairs its facets with the noisy ones.  Arrays
+        addMeshWithVerticesAndGTMesh(V_noisy, faces, V_gt, F_gt) or the file form (inputFilePath, filename, gtFilePath,
+        gtfilename), each OBJ read with its OWN faces.  Everything addMeshWithVertices(V_noisy, faces) does, with v_list and
+        gtv_list normalised together (utils.normalizePointSets(V_noisy, V_gt)) and the ground-truth faces in gtf_list
+        (int32 [1, Fgt, 3], one entry per mesh of the set; [1, 0, 3] for a mesh added without).  NO gt_list entry: there
+        are no face normals of another topology, so trainNet and the double loss do not take such a set.  Patch mode (more
+        faces than maxSize) is refused."""
+        if isinstance(V_noisy, str):
+            in_path, in_name, gt_path, gt_name = V_noisy, faces, V_gt, F_gt
+            V_noisy, _, _, faces, _ = utils.load_mesh(in_path, in_name, 0, False)
+            V_gt, _, _, F_gt, _ = utils.load_mesh(gt_path, gt_name, 0, False)
+            seed = parents = None
+        V_noisy = np.ascontiguousarray(np.asarray(V_noisy, dtype=np.float32)).reshape(-1, 3)
+        V_gt = np.ascontiguousarray(np.asarray(V_gt, dtype=np.float32)).reshape(-1, 3)
+        faces, F_gt = np.asarray(faces), np.asarray(F_gt)
+        if faces.shape[0] > self.maxSize:
+            raise NotImplementedError("addMeshWithVerticesAndGTMesh keeps a mesh whole: %d faces > maxSize %d (patch mode)"
+                                      % (faces.shape[0], self.maxSize))
+        if F_gt.ndim != 2 or F_gt.shape[1] != 3 or F_gt.shape[0] == 0 or V_gt.shape[0] == 0:
+            raise ValueError("the ground-truth mesh needs vertices [Vgt,3] and faces [Fgt,3], got %r and %r"
+                             % (V_gt.shape, F_gt.shape))
+        if F_gt.min() < 0 or F_gt.max() >= V_gt.shape[0]:
+            raise ValueError("the ground-truth faces index %d vertices, ids run from %d to %d"
+                             % (V_gt.shape[0], F_gt.min(), F_gt.max()))
+        first = len(self.in_list)
+        self.fNum, self.vNum = faces.shape[0], V_noisy.shape[0]
+        PreprocessedData.addMeshWithVertices(self, V_noisy, faces, seed=seed, parents=parents)
+        Vn, GTn = utils.normalizePointSets(V_noisy, V_gt)
+        self.v_list[-1] = Vn[np.newaxis]        # (addMeshWithVertices normalised the noisy mesh by its own box)
+        gtv, gtf = (self.__dict__.setdefault(k, []) for k in ("gtv_list", "gtf_list"))
+        if len(gtv) != first:
+            raise ValueError("the set holds %d meshes and %d ground-truth vertex sets: a mesh was added without one"
+                             % (first, len(gtv)))
+        gtf.extend(np.zeros((1, 0, 3), dtype=np.int32) for _ in range(first - len(gtf)))
+        gtv.append(GTn[np.newaxis])
+        gtf.append(np.ascontiguousarray(F_gt.astype(np.int32))[np.newaxis])
+        self.vertices = V_noisy[np.newaxis]
+        self.faces = faces
+        self.normals = utils.computeFacesNormals(V_noisy, faces)
+
 
 class InferenceMesh(PreprocessedData):
     """dataClasses.py:510-531."""

@@ -20,6 +20,7 @@ Design (MI355X-first, nothing traced or compiled at run time):
 """
 import collections
 import ctypes as C
+import hashlib
 import os
 import types
 
@@ -660,7 +661,8 @@ class FacetDenoiser:
         return self._require_synth().v_out
 
     def bind_clean_vertices(self, key, x, adjs, verts, faces_rows, v_faces, edge_len, gt_normals=None, iters=VERTEX_ITERS,
-                            seed=0, stream=0, direction="random", lf=None, ray_update=False, sensor=None):
+                            seed=0, stream=0, direction="random", lf=None, ray_update=False, sensor=None,
+                            surface_loss=False):
         """Build extension: bind a CLEAN mesh for the point-set and double-loss steps on noise synthesised per step -
         bind_vertices plus bind_clean's synthesis state, kept with the mesh under `key`.  verts [V,3]: the RAW clean
         vertices (TrainingSet.addCleanMeshWithVertices' clean_vertices), which are also the ground-truth vertices;
@@ -674,7 +676,9 @@ class FacetDenoiser:
         synthesising step left; right after binding these are the clean ones.
         ray_update: the vertex update of every step is the ray-constrained one (bind_vertices(depth_dir=)) along the table
         of rays the noise goes along - `direction`, built from the clean vertices - so the network is trained on what a depth
-        scan asks of it; refused unless `direction` is such a table."""
+        scan asks of it; refused unless `direction` is such a table.
+        surface_loss: the clean mesh's own faces_rows are the ground-truth faces (bind_vertices(gt_faces=)): the steps
+        measure to surfaces.  With or without for good."""
         if ray_update and isinstance(direction, str):
             raise ValueError("ray_update moves the vertices along the noise's rays: direction must be a [V,3] table of rays")
 
@@ -684,12 +688,15 @@ class FacetDenoiser:
             vx = np.asarray(verts, dtype=np.float32).reshape(-1, 3)
             vn = normalizePointSets(vx, vx)[0]
             self.bind_vertices(key, x, adjs, vn, faces_rows, v_faces, vn, iters=iters,
-                               depth_dir=direction if ray_update else None)
+                               depth_dir=direction if ray_update else None,
+                               gt_faces=np.asarray(faces_rows).reshape(-1, 3).astype(np.int32) if surface_loss else None)
             return self._mesh
         spec = NoiseSpec(seed, stream, direction, lf, sensor, bool(ray_update))
         M, fresh = self._bind_synth(key, spec, (x, verts, faces_rows, edge_len), True, bind)
         if spec.ray_update != (M["verts"]["dirs"] is not None):      # (the direction itself: compared by _bind_synth)
             raise ValueError("mesh %r is bound %s ray_update" % (key, "without" if ray_update else "with"))
+        if bool(surface_loss) != (M["verts"]["gt_faces"] is not None):
+            raise ValueError("mesh %r is bound %s surface_loss" % (key, "without" if surface_loss else "with"))
         if fresh:
             S = M["synth"]
             S.gt_box = torch.cat([S.v.min(0).values, S.v.max(0).values])
@@ -1447,7 +1454,7 @@ class FacetDenoiser:
     # point-set training (trainAccuracyNet, train.py:636-916): network -> update_position_MS -> fullLoss
     # ------------------------------------------------------------------------------------------
     def bind_vertices(self, key, x, adjs, verts, faces, v_faces, gt_verts, iters=VERTEX_ITERS, gt_normals=None,
-                      depth_dir=None):
+                      depth_dir=None, gt_faces=None):
         """Bind a mesh for the point-set step: its graph (bind_cached under `key`) together with its vertex data - the
         normalised vertices [V,3], the faces in node order [N0,3] (-1 rows = fake nodes), v_faces [V,K], the
         ground-truth vertices [Vgt,3] and the two inverse tables of the vertex-update adjoint (ops.vertex_ms_tables) -
@@ -1456,8 +1463,16 @@ class FacetDenoiser:
         depth_dir (build extension): [V,3] or [1,3] viewing rays (utils.view_rays; used as given, rows longer than 1 can
         diverge), kept with the cached vertex state - the steps then run the ray-constrained update and its adjoint
         (include/fgc.h: fgc_vertex_update_ms_dir_traj / _bwd), with the rays rotated like the vertices.  A key is bound
-        with its rays or without for good: a later bind that differs is refused."""
+        with its rays or without for good: a later bind that differs is refused.
+        gt_faces (build extension): int [Fgt,3], the faces of the ground-truth mesh on gt_verts, of any topology, kept
+        with the cached vertex state - the steps then measure to SURFACES (include/fgc.h: fgc_surface_loss on the refined
+        mesh and the ground-truth mesh) in the place of fgc_point_loss.  With or without for good, like the rays."""
         self._require_vertex_network()
+        if gt_faces is not None:
+            gt_faces = np.asarray(gt_faces.cpu() if isinstance(gt_faces, torch.Tensor) else gt_faces)
+            if gt_faces.ndim < 2 or gt_faces.shape[-1] != 3 or gt_faces.size == 0 or gt_faces.dtype.kind not in "iu":
+                raise ValueError("gt_faces: an int [Fgt,3] table, got %s %r" % (gt_faces.dtype, gt_faces.shape))
+            gt_faces = np.ascontiguousarray(gt_faces.reshape(-1, 3).astype(np.int32))
         if depth_dir is not None:      # (before anything is bound under the key)
             shape = tuple(depth_dir.shape) if hasattr(depth_dir, "shape") else np.shape(depth_dir)
             nv = np.asarray(verts).reshape(-1, 3).shape[0]
@@ -1493,8 +1508,13 @@ class FacetDenoiser:
             V["bwd_ws"] = torch.empty(self.L.fgc_vertex_update_ms_bwd_workspace_floats(nv, n0), **f)
             V["i0"], V["i1"] = (torch.zeros(POINT_SAMPLES, dtype=torch.int32, device=dev) for _ in range(2))
             V["loss"] = torch.zeros(1, **f)
-            V["loss_ws"] = torch.empty(self.L.fgc_point_loss_workspace_bytes(nv, gv.shape[0], POINT_SAMPLES, POINT_SAMPLES)
-                                       + 256, dtype=torch.uint8, device=dev)
+            V["gt_faces"] = None if gt_faces is None else torch.as_tensor(gt_faces, device=dev)
+            V["gt_faces_key"] = self._faces_key(gt_faces)
+            V["loss_ws"] = torch.empty((self.L.fgc_point_loss_workspace_bytes(nv, gv.shape[0], POINT_SAMPLES, POINT_SAMPLES)
+                                        if gt_faces is None else
+                                        self.L.fgc_surface_loss_workspace_bytes(n0, gt_faces.shape[0], POINT_SAMPLES,
+                                                                                POINT_SAMPLES)) + 256,
+                                       dtype=torch.uint8, device=dev)
             V["threshold"] = POINT_LOSS_THRESHOLD
             V["dirs"] = None
             if depth_dir is not None:
@@ -1503,8 +1523,15 @@ class FacetDenoiser:
             M["mode"].verts = True
         elif not self._same_rays(M["verts"], depth_dir):
             raise ValueError("mesh %r is bound with other rays, or without (depth_dir)" % (key,))
+        elif M["verts"]["gt_faces_key"] != self._faces_key(gt_faces):
+            raise ValueError("mesh %r is bound with other ground-truth faces, or without (gt_faces)" % (key,))
         self._attach_gt_normals(M, gt_normals)
         return self
+
+    @staticmethod
+    def _faces_key(gt_faces):
+        """What two binds compare the ground-truth faces by (None: without): the digest of the int32 rows."""
+        return None if gt_faces is None else hashlib.sha1(gt_faces.tobytes()).hexdigest()
 
     def _attach_rays(self, V, depth_dir, n0):
         """The ray table of the constrained vertex update and its buffers into the vertex state V."""
@@ -1634,9 +1661,14 @@ class FacetDenoiser:
         ws = V["loss_ws"]
         out = V["dl_out"] if double else None
         loss = C.c_void_p(out.data_ptr() + 4) if double else _p(V["loss"])
-        _lib.check(L.fgc_point_loss(refined, nv, _p(gt), gt.shape[0], _p(V["i0"]), V["i0"].numel(), _p(V["i1"]),
-                                    V["i1"].numel(), V["threshold"], loss, _p(V["g_p"]) if want_grad else None,
-                                    _p(ws), ws.numel(), st), "point loss")
+        samples = (_p(V["i0"]), V["i0"].numel(), _p(V["i1"]), V["i1"].numel(), V["threshold"], loss,
+                   _p(V["g_p"]) if want_grad else None, _p(ws), ws.numel(), st)
+        if V["gt_faces"] is None:
+            _lib.check(L.fgc_point_loss(refined, nv, _p(gt), gt.shape[0], *samples), "point loss")
+        else:      # to surfaces: the refined mesh on the bound faces, the ground-truth mesh on its own
+            gf = V["gt_faces"]
+            _lib.check(L.fgc_surface_loss(refined, nv, _p(V["faces"]), n0, _p(gt), gt.shape[0], _p(gf), gf.shape[0], *samples),
+                       "surface loss")
         if double:
             self._tag("dl:loss")
             sc = V["dl_scratch"]

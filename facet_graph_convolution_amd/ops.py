@@ -578,6 +578,29 @@ def closest_point_tree(tree, points, want_bary=False, sort_points=True, exhausti
     return (dist, face, bary) if want_bary else (dist, face)
 
 
+def closest_point(verts, faces, points, want_bary=False):
+    """closest_point_tree without a tree (include/fgc.h: fgc_closest_point; a build extension), over all points x faces
+    pairs: verts [V,3] fp32, faces int [F,3] (a row with an id outside [0, V) takes no part), points [Q,3].  The same
+    returns, bit for bit what closest_point_tree gives on a tree of the same mesh.  For a mesh that changes with every
+    call and a few hundred points; anything larger wants the tree."""
+    _req_cuda(verts, faces, points)
+    verts, points = _f32c(verts.reshape(-1, 3)), _f32c(points.reshape(-1, 3))
+    faces = faces.to(torch.int32).reshape(-1, 3).contiguous()
+    nv, nf, nq = verts.shape[0], faces.shape[0], points.shape[0]
+    L = _lib.lib()
+    nbytes = L.fgc_closest_point_workspace_bytes(nf, nq)
+    if nbytes == 0 or nv == 0:
+        raise ValueError("closest_point needs at least one vertex, one face and one point (got %d, %d, %d)" % (nv, nf, nq))
+    d2 = torch.empty(nq, dtype=torch.float32, device=verts.device)
+    face = torch.empty(nq, dtype=torch.int32, device=verts.device)
+    bary = torch.empty(nq, 2, dtype=torch.float32, device=verts.device) if want_bary else None
+    ws = _workspace(nbytes, verts.device, "closest_point")
+    check(L.fgc_closest_point(ptr(verts), nv, ptr(faces), nf, ptr(points), nq, ptr(d2), ptr(face), ptr(bary), ptr(ws),
+                              ws.numel(), stream_ptr()), "fgc_closest_point")
+    dist = torch.sqrt(d2)
+    return (dist, face, bary) if want_bary else (dist, face)
+
+
 def pool4_avg_iz(x):
     """custom_binary_tree_pooling(x, steps=2, 'avg_ignore_zeros') (model.py:792-814) on [n, c] rows."""
     _req_cuda(x)
@@ -868,6 +891,33 @@ def point_loss(p0, p1, sample_ind0, sample_ind1, threshold=5000.0, want_grad=Tru
     check(_lib.lib().fgc_point_loss(ptr(p0), p0.shape[0], ptr(p1), p1.shape[0], ptr(i0), i0.numel(), ptr(i1), i1.numel(),
                                     float(threshold), ptr(loss), ptr(g), ptr(ws), ws.numel(), stream_ptr()),
           "fgc_point_loss")
+    return loss, g
+
+
+POINT_LOSS_MAX_TERMS = 16384  # FGC_POINT_LOSS_MAX_SAMPLES of include/fgc.h
+
+
+def surface_loss(p0, faces0, p1, faces1, sample_ind0, sample_ind1, threshold=5000.0, want_grad=True):
+    """The two-sided point-to-surface loss (include/fgc.h: fgc_surface_loss; a build extension) of the mesh (p0 [n0,3],
+    faces0 int [F0,3], -1 rows allowed) against the mesh (p1 [n1,3], faces1 int [F1,3]) on the sampled rows of p0 and p1:
+    (loss [1], dloss/dp0 [n0,3] or None).  fullLoss's scale; the two meshes need share nothing."""
+    _req_cuda(p0, faces0, p1, faces1, sample_ind0, sample_ind1)
+    p0, p1 = _f32c(p0.reshape(-1, 3)), _f32c(p1.reshape(-1, 3))
+    f0 = faces0.to(torch.int32).reshape(-1, 3).contiguous()
+    f1 = faces1.to(torch.int32).reshape(-1, 3).contiguous()
+    i0 = sample_ind0.to(torch.int32).reshape(-1).contiguous()
+    i1 = sample_ind1.to(torch.int32).reshape(-1).contiguous()
+    L = _lib.lib()
+    nbytes = L.fgc_surface_loss_workspace_bytes(f0.shape[0], f1.shape[0], i0.numel(), i1.numel())
+    if nbytes == 0 or p0.shape[0] == 0 or p1.shape[0] == 0:
+        raise ValueError("surface_loss needs vertices, faces and samples on both sides, and at most %d terms "
+                         "(got %d + 3 x %d samples)" % (POINT_LOSS_MAX_TERMS, i0.numel(), i1.numel()))
+    loss = torch.empty(1, dtype=torch.float32, device=p0.device)
+    g = torch.empty_like(p0) if want_grad else None
+    ws = _workspace(nbytes, p0.device, "surface_loss")
+    check(L.fgc_surface_loss(ptr(p0), p0.shape[0], ptr(f0), f0.shape[0], ptr(p1), p1.shape[0], ptr(f1), f1.shape[0], ptr(i0),
+                             i0.numel(), ptr(i1), i1.numel(), float(threshold), ptr(loss), ptr(g), ptr(ws), ws.numel(),
+                             stream_ptr()), "fgc_surface_loss")
     return loss, g
 
 

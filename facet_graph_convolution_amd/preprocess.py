@@ -8,7 +8,9 @@ natively (adjacency, coarsening, padding) `redundancy` times (each pass draws a 
 uses this as data augmentation, settings.py:24) and pickled as `trainingSet.pkl` / `validSet.pkl`.  With --with-vertices
 (the reference's INCLUDE_VERTICES) every mesh also keeps its vertices, faces in node order, vertex-face slots and
 ground-truth vertices (addMeshWithVerticesAndGT) for trainAccuracyNet, pickled as `trainingSetWithVertices.pkl` /
-`validSetWithVertices.pkl`.
+`validSetWithVertices.pkl`.  With --gt-surface on top (a build extension) every ground-truth OBJ is read with its OWN faces
+(addMeshWithVerticesAndGTMesh): a pair may differ in vertex and face count, nothing pairs their facets; the same two file
+names, for `train --with-vertices` with or without `--surface-loss`.
 
 Build extension - training from clean meshes, the noise synthesised per step on the GPU (train --synth-noise):
 
@@ -35,7 +37,10 @@ def gt_filename(noisy_name):
 
 
 def pickleData(training_dir, gt_dir, dump_dir, valid_dir=None, redundancy=1, gt_name=getGTFilename, log=print,
-               withVerts=False):
+               withVerts=False, gtSurface=False):
+    if gtSurface and not withVerts:
+        raise ValueError("gtSurface (a ground-truth mesh of its own topology) needs withVerts: only the vertex networks "
+                         "train without face correspondence")
     os.makedirs(dump_dir, exist_ok=True)
     out = {}
     names = ("trainingSetWithVertices.pkl", "validSetWithVertices.pkl") if withVerts else ("trainingSet.pkl", "validSet.pkl")
@@ -48,7 +53,9 @@ def pickleData(training_dir, gt_dir, dump_dir, valid_dir=None, redundancy=1, gt_
                 continue
             log("Adding %s (%i)" % (f, ds.mesh_count))
             for _ in range(rep):
-                if withVerts:
+                if gtSurface:
+                    ds.addMeshWithVerticesAndGTMesh(folder, f, gt_dir, gt_name(f))
+                elif withVerts:
                     ds.addMeshWithVerticesAndGT(folder, f, gt_dir, gt_name(f))
                 else:
                     ds.addMeshWithGT(folder, f, gt_dir, gt_name(f))
@@ -98,7 +105,12 @@ def main(argv=None):
                     help="keep the vertex data trainAccuracyNet needs (with --clean: trainingSetCleanWithVertices.pkl)")
     ap.add_argument("--clean", action="store_true",
                     help="build extension: CLEAN_DIR DUMP_DIR - clean meshes for training on synthesised noise")
+    ap.add_argument("--gt-surface", action="store_true",
+                    help="build extension, with --with-vertices: read every ground-truth OBJ with its own faces - a ground "
+                         "truth of another topology (train --surface-loss)")
     args = ap.parse_args(argv)
+    if args.gt_surface and (args.clean or not args.with_vertices):
+        ap.error("--gt-surface needs --with-vertices and does not go with --clean (a clean mesh is its own ground truth)")
     if args.clean:
         if args.dump_dir is not None:
             ap.error("--clean takes two folders: CLEAN_DIR DUMP_DIR (a clean mesh is its own ground truth)")
@@ -109,7 +121,8 @@ def main(argv=None):
         if args.dump_dir is None:
             ap.error("three folders are needed: TRAINING_DIR GT_DIR DUMP_DIR (or CLEAN_DIR DUMP_DIR --clean)")
         dump = args.dump_dir
-        pickleData(args.training_dir, args.gt_dir, dump, args.valid, args.redundancy, withVerts=args.with_vertices)
+        pickleData(args.training_dir, args.gt_dir, dump, args.valid, args.redundancy, withVerts=args.with_vertices,
+                   gtSurface=args.gt_surface)
     print("Preprocessing complete. Dump files saved to " + dump)
 
 

@@ -13,7 +13,7 @@ Training command (the reference's ``train(withVerts)``, train.py:1894-1921):
     python -m facet_graph_convolution_amd.train DUMP_DIR NETWORK_DIR [--num-iterations N] [--net-name NAME]
         [--with-vertices] [--double-loss] [--capture] [--seed S]
         [--synth-noise 0.1,0.2,0.3] [--noise-direction random|normal|ray] [--view-dir X,Y,Z | --camera X,Y,Z] [--ray-update]
-        [--lf-noise 0.3,0.2,0.1[:WIDTH[:BUMPS]]] [--sensor POWER[:QUANT]]
+        [--lf-noise 0.3,0.2,0.1[:WIDTH[:BUMPS]]] [--sensor POWER[:QUANT]] [--surface-loss]
 
 loads the pickles `preprocess` wrote and runs trainNet, trainAccuracyNet (--with-vertices) or trainDoubleLossNet
 (--with-vertices --double-loss).  --synth-noise (build extension) loads the CLEAN pickles of `preprocess --clean`
@@ -81,6 +81,33 @@ def fullLoss(P0, P1, sample_ind0, sample_ind1, threshold=POINT_LOSS_THRESHOLD):
     return _FullLossFn.apply(P0.reshape(-1, 3), P1.reshape(-1, 3).detach(), i0, i1, float(threshold))
 
 
+class _SurfaceLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p0, faces0, p1, faces1, i0, i1, threshold):
+        loss, g = ops.surface_loss(p0, faces0, p1, faces1, i0, i1, threshold, want_grad=True)
+        ctx.save_for_backward(g)
+        return loss[0]
+
+    @staticmethod
+    def backward(ctx, dloss):
+        g, = ctx.saved_tensors
+        return g * dloss, None, None, None, None, None, None
+
+
+def surfaceLoss(P0, faces0, P1, faces1, sample_ind0, sample_ind1, threshold=POINT_LOSS_THRESHOLD):
+    """fullLoss with distances to a SURFACE (a build extension; include/fgc.h: fgc_surface_loss): 1000 (mean distance of
+    the sampled rows of P0 to the mesh (P1, faces1) + mean distance of the sampled rows of P1 to the mesh (P0, faces0)),
+    distances above `threshold` counted as 0.  P0 [1,n0,3] / [n0,3] (differentiable, through the sampled rows and through
+    the vertices of the faces the P1 samples land on), faces0 int [F0,3] (-1 rows allowed); P1, faces1 the ground-truth
+    mesh, of any topology.  The gradient is 0 at distance 0."""
+    dev = P0.device
+
+    def ints(a):
+        return torch.as_tensor(np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a), dtype=torch.int32).to(dev)
+    return _SurfaceLossFn.apply(P0.reshape(-1, 3), ints(faces0).reshape(-1, 3), P1.reshape(-1, 3).detach(),
+                                ints(faces1).reshape(-1, 3), ints(sample_ind0), ints(sample_ind1), float(threshold))
+
+
 def save_checkpoint(path, net, iteration):
     """saver.save(sess, path, global_step=iteration) (train.py:551-552,626): weights + Adam moments + step as the
     TensorFlow bundle `<path>-<iteration>.index/.data-00000-of-00001` plus the `checkpoint` state file (tfckpt.py).
@@ -118,7 +145,7 @@ DEFAULT_NOISE_LEVELS = (0.1, 0.2, 0.3)      # --synth-noise without a value: a c
 # One mesh of a trainer's input: `args` follow the key in the bind call, `gt_normals` go with them (a keyword) for the
 # double loss only, rows = the number of rows each sample set of a step is drawn from: (N0,), or (V, Vgt).
 # verts: the raw clean vertices of a clean mesh, what the viewing rays of a depth-scan noise direction are built from.
-_Mesh = collections.namedtuple("_Mesh", "args gt_normals rows verts", defaults=(None,))
+_Mesh = collections.namedtuple("_Mesh", "args gt_normals rows verts bind_kw", defaults=(None, None))
 _VALID_LOG = {1: "Iteration %d, validation loss %g", 3: "Iteration %d, validation loss = %g (points %g, normals %g)"}
 
 
@@ -141,37 +168,50 @@ def _clean_meshes(ds, what):
             for i in range(len(ds.in_list))]
 
 
-def _vertex_meshes(ds, double):
+def _vertex_meshes(ds, double, surface_loss=False):
     """The meshes of a TrainingSet that have ground-truth vertices: bind_vertices(key, features, adjacency, vertices,
-    faces, v_faces, gt vertices[, gt_normals=gt normals])."""
-    gtv, gtn = getattr(ds, "gtv_list", []), getattr(ds, "gt_list", [])
+    faces, v_faces, gt vertices[, gt_normals=gt normals][, gt_faces=gt faces]).  surface_loss: the ground-truth faces are
+    the set's own (gtf_list, addMeshWithVerticesAndGTMesh) where it has them, otherwise - a paired set of one topology - the
+    mesh's faces_list rows."""
+    gtv, gtn, gtf = getattr(ds, "gtv_list", []), getattr(ds, "gt_list", []), getattr(ds, "gtf_list", [])
     out = []
     for i in range(len(ds.in_list)):
         if i >= len(gtv) or _rows(gtv[i]) == 0:
             continue        # train.py:792-796 draws again when a mesh has no ground-truth vertices
         if double and (i >= len(gtn) or _rows(gtn[i]) == 0):
             raise ValueError("mesh %d has no ground-truth face normals (gt_list) for the double loss" % i)
+        kw = None
+        if surface_loss:
+            own = i < len(gtf) and _rows(gtf[i]) > 0
+            if not own and _rows(gtv[i]) != _rows(ds.v_list[i]):
+                raise ValueError("mesh %d has %d ground-truth vertices for %d vertices and no ground-truth faces (gtf_list: "
+                                 "addMeshWithVerticesAndGTMesh, preprocess --gt-surface)"
+                                 % (i, _rows(gtv[i]), _rows(ds.v_list[i])))
+            kw = {"gt_faces": np.asarray(gtf[i] if own else ds.faces_list[i]).reshape(-1, 3).astype(np.int32)}
         out.append(_Mesh((ds.in_list[i], ds.adj_list[i], ds.v_list[i], ds.faces_list[i], ds.v_faces_list[i], gtv[i]),
-                         gtn[i] if double else None, (_rows(ds.v_list[i]), _rows(gtv[i]))))
+                         gtn[i] if double else None, (_rows(ds.v_list[i]), _rows(gtv[i])), None, kw))
     return out
 
 
-def _clean_vertex_meshes(ds, what):
+def _clean_vertex_meshes(ds, what, surface_loss=False):
     """The meshes of a clean vertex TrainingSet (addCleanMeshWithVertices): bind_clean_vertices(key, x, adjs, raw clean
-    vertices, faces_rows, v_faces, edge_len[, gt_normals=clean normals]); the clean vertices are the ground truth too."""
+    vertices, faces_rows, v_faces, edge_len[, gt_normals=clean normals][, surface_loss=True]); the clean vertices are the
+    ground truth too, and - surface_loss - the clean faces the ground-truth faces."""
     n = len(getattr(ds, "in_list", ()))
     if not (hasattr(ds, "is_clean") and ds.is_clean() and len(ds.v_faces_list) == n and len(ds.gt_list) == n):
         raise ValueError("noise_levels needs a %s of clean meshes with their vertex data (TrainingSet."
                          "addCleanMeshWithVertices, preprocess --clean --with-vertices)" % what)
     return [_Mesh((ds.in_list[i], ds.adj_list[i], ds.clean_vertices[i], ds.clean_faces_rows[i], ds.v_faces_list[i],
-                   ds.clean_edge_len[i]), ds.gt_list[i], (_rows(ds.clean_vertices[i]),) * 2, ds.clean_vertices[i])
+                   ds.clean_edge_len[i]), ds.gt_list[i], (_rows(ds.clean_vertices[i]),) * 2, ds.clean_vertices[i],
+                  {"surface_loss": True} if surface_loss else None)
             for i in range(n)]
 
 
-def _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction):
-    """The checked noise levels (None: the plain mode) and the training and validation meshes of a trainer."""
+def _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction, surface_loss=False):
+    """The checked noise levels (None: the plain mode) and the training and validation meshes of a trainer.  surface_loss
+    (the vertex trainers): the mesh records carry the ground-truth faces to bind."""
     if noise_levels is None:
-        plain = _meshes if form == "angular" else lambda ds: _vertex_meshes(ds, form == "double")
+        plain = _meshes if form == "angular" else lambda ds: _vertex_meshes(ds, form == "double", surface_loss)
         sets = [plain(ds) if ds is not None else [] for ds in (trainSet, validSet)]
         if form != "angular" and not sets[0]:
             raise ValueError("no training mesh has ground-truth vertices (addMeshWithVerticesAndGT)")
@@ -185,7 +225,7 @@ def _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction):
     elif isinstance(noise_direction, str) and noise_direction not in ("random", "normal"):
         raise ValueError("noise_direction must be 'random' or 'normal', a [V,3] array of unit rows or a view "
                          "({'camera': xyz} / {'view_dir': xyz})")
-    clean = _clean_meshes if form == "angular" else _clean_vertex_meshes
+    clean = _clean_meshes if form == "angular" else lambda ds, what: _clean_vertex_meshes(ds, what, surface_loss)
     return levels, clean(trainSet, "training set"), clean(validSet, "validation set") if validSet is not None else []
 
 
@@ -266,6 +306,7 @@ def _bind(F, key, m, noise=None):
     stream to bind under - clean for noise synthesis, direction and sensor filled per mesh.  (A cached mesh returns at once;
     the bind methods reshape the [1, ...] arrays.)"""
     kw = {"gt_normals": m.gt_normals} if F.gt_normals else {}
+    kw.update(m.bind_kw or {})      # (the surface loss: the ground-truth faces, or the clean mesh's own)
     if noise is not None:
         spec = noise._replace(direction=_mesh_direction(noise.direction, m),
                               sensor=None if noise.sensor is None else _mesh_sensor(noise.sensor, noise.direction, m))
@@ -420,7 +461,7 @@ def trainNet(trainSet, num_iterations, network_path=None, net_name="net", device
 
 def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
                      capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None,
-                     lf_width=3.0, lf_bumps=None, ray_update=False, sensor=None):
+                     lf_width=3.0, lf_bumps=None, ray_update=False, sensor=None, surface_loss=False):
     """train.py:636-916: the multi-scale network trained through update_position_MS on the point-set loss fullLoss.
     trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT.  One iteration = a random mesh
     (meshes without ground-truth vertices are skipped), SAMP_NUM = 500 random rows of the vertices and of the
@@ -449,14 +490,23 @@ def trainAccuracyNet(trainSet, num_iterations, network_path=None, net_name="net"
     `infer --with-vertices --camera / --view-dir` will ask of it.  False: the free update, as before.
     sensor = (power, quant): the depth-sensor model, as in trainNet; ray_update composes with it unchanged.
 
+    surface_loss (build extension; False = fullLoss as above, the same launches): the loss of every training and
+    validation step is surfaceLoss, distances to SURFACES on both sides (include/fgc.h: fgc_surface_loss) - the refined
+    mesh on its own faces against the ground-truth mesh on ITS faces: the set's gtf_list where it has one
+    (TrainingSet.addMeshWithVerticesAndGTMesh: a ground truth of any topology), otherwise the mesh's own faces (a paired
+    set of one topology), the clean faces with noise_levels.  The same scale as fullLoss, so curves compare; a vertex of a
+    sparser ground truth no longer pulls the refined vertices sideways.  A gtf_list set also trains with
+    surface_loss=False: fullLoss against ground-truth vertices of another count.
+
     Returns (net, lossArray of the last block, per-iteration training losses [num_iterations])."""
     return _train_with_vertices("points", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
-                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update, sensor)
+                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update, sensor,
+                                surface_loss)
 
 
 def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="net", device="cuda", seed=0, log=print,
                        capture=False, validSet=None, noise_levels=None, noise_direction="random", lf_levels=None,
-                       lf_width=3.0, lf_bumps=None, ray_update=False, sensor=None):
+                       lf_width=3.0, lf_bumps=None, ray_update=False, sensor=None, surface_loss=False):
     """train.py:919-1268: the multi-scale network trained on the point-set loss fullLoss PLUS the dense face-normal loss
     faceNormalsLoss of head 0 against the rotated ground-truth face normals (customLoss = pointsLoss + normalsLoss,
     unweighted, train.py:1100-1102).  trainSet / validSet: dataClasses.TrainingSet filled by addMeshWithVerticesAndGT
@@ -472,18 +522,25 @@ def trainDoubleLossNet(trainSet, num_iterations, network_path=None, net_name="ne
     `<net_name>.csv` at every save.
 
     noise_levels / noise_direction / lf_levels / lf_width / lf_bumps / ray_update / sensor (build extension): as in
-    trainAccuracyNet; the ground-truth normals are the clean ones.
+    trainAccuracyNet; the ground-truth normals are the clean ones.  surface_loss: the points part is surfaceLoss, as in
+    trainAccuracyNet; the normals part still needs ground-truth normals of the mesh's own topology (gt_list), so a set made by
+    addMeshWithVerticesAndGTMesh is refused here.
 
     Returns (net, lossArray of the last block, per-iteration {total, points, normals} [num_iterations, 3])."""
     return _train_with_vertices("double", trainSet, num_iterations, network_path, net_name, device, seed, log, capture,
-                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update, sensor)
+                                validSet, noise_levels, noise_direction, lf_levels, lf_width, lf_bumps, ray_update, sensor,
+                                surface_loss)
 
 
 def _train_with_vertices(form, trainSet, num_iterations, network_path, net_name, device, seed, log, capture, validSet,
                          noise_levels=None, noise_direction="random", lf_levels=None, lf_width=3.0, lf_bumps=None,
-                         ray_update=False, sensor=None):
+                         ray_update=False, sensor=None, surface_loss=False):
     """The loop of trainAccuracyNet (form "points") and trainDoubleLossNet ("double")."""
-    levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction)
+    surface_loss = bool(surface_loss)
+    levels, meshes, valid = _trainer_inputs(form, trainSet, validSet, noise_levels, noise_direction, surface_loss)
+    # (said without the lower-case word the numeric log lines carry: readers of the log parse those by it)
+    log("Point sets are scored by %s" % ("surfaceLoss: vertices to surfaces, both sides" if surface_loss
+                                         else "fullLoss: vertices to nearest vertices"))
     lf_levels, lf_shape = _lf_inputs(levels, lf_levels, lf_width, lf_bumps)
     sensor = _sensor_inputs(levels, sensor, noise_direction, lf_levels)
     ray_update = bool(ray_update)
@@ -821,6 +878,9 @@ def main(argv=None):
     ap.add_argument("--ray-update", action="store_true",
                     help="with --with-vertices --noise-direction ray: the vertex update of every step moves the vertices along "
                     "the same viewing rays only (what `infer --with-vertices --view-dir / --camera` runs)")
+    ap.add_argument("--surface-loss", action="store_true",
+                    help="build extension, with --with-vertices: measure to SURFACES in the point loss - the ground-truth mesh "
+                    "of `preprocess --gt-surface` (any topology), else the mesh's own faces; with --synth-noise the clean faces")
     ap.add_argument("--lf-noise", default=None, metavar="LEVELS[:WIDTH[:BUMPS]]",
                     help="with --synth-noise: low-frequency noise on top - LEVELS = comma-separated RMS displacements in mean "
                     "edge lengths, one or one per --synth-noise level (level k pairs with lf level k); WIDTH = bump width "
@@ -840,6 +900,8 @@ def main(argv=None):
     if args.ray_update and not (view and args.with_vertices):
         ap.error("--ray-update constrains the multi-scale vertex update to the noise's rays: it needs --with-vertices and "
                  "--noise-direction ray with --view-dir or --camera")
+    if args.surface_loss and not args.with_vertices:
+        ap.error("--surface-loss is the point loss of the vertex networks: it needs --with-vertices")
     if args.num_iterations < 0:
         ap.error("--num-iterations must be >= 0")
     levels = None
@@ -882,6 +944,8 @@ def main(argv=None):
         extra["ray_update"] = True
     if sensor is not None:
         extra["sensor"] = sensor
+    if args.surface_loss:
+        extra["surface_loss"] = True
     trainer(train_set, args.num_iterations, network_path=args.network_dir, net_name=args.net_name, seed=args.seed,
             capture=args.capture, validSet=valid_set, **extra)
     return trainer.__name__

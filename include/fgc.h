@@ -73,7 +73,9 @@ extern "C" {
  * scans of a clean mesh; fgc_ray_tree_bytes / fgc_ray_tree_build / fgc_ray_cast_tree, the same cast through a bounding-box
  * tree: scans of large meshes; fgc_synth_noise_sensor, the noise of a triangulating depth sensor along the viewing rays:
  * sigma grows with the range, depth is quantised in disparity; fgc_closest_point_tree, the closest point on a mesh through
- * the same tree: distances to a surface. */
+ * the same tree: distances to a surface; fgc_closest_point (+ _workspace_bytes), the closest point without a tree, and
+ * fgc_surface_loss (+ _workspace_bytes), the point-to-surface loss and its gradient: the vertex networks trained against a
+ * ground-truth mesh of any topology. */
 #define FGC_ABI_VERSION 116
 
 const char* fgc_last_error(void);
@@ -1224,6 +1226,53 @@ int fgc_ray_cast_tree(const void* tree, size_t tree_bytes, int32_t nf, const flo
 #define FGC_CP_EXHAUSTIVE 1u
 int fgc_closest_point_tree(const void* tree, size_t tree_bytes, int32_t nf, const float* points, int32_t nq, uint32_t flags,
                            float* dist2_out, int32_t* face_out, float* bary_out, void* stream);
+
+/* The same query without a tree, over all nq x nf pairs: what fgc_ray_cast is to fgc_ray_cast_tree.  For a mesh that moves
+ * every step (fgc_surface_loss), where a build per step costs more than a thousand points save.
+ *   verts [nv,3], faces [nf,3], points [nq,3]; dist2_out [nq], face_out [nq], bary_out [nq,2] (may be NULL) as above.
+ *   Records are fgc_ray_cast's: a row with a vertex id outside [0, nv) is a zero record and takes no part, which covers the
+ *   -1 rows of a node-ordered face table.  THE PAIR is the one function above; the winner is the smallest
+ *   (dist2 bits, face) in full key order; a NaN and +inf never win; no winner: (+inf, -1, (0, 0)).
+ * THE CONTRACT.  Every output is bit for bit what fgc_closest_point_tree returns on a tree of the same mesh (any order):
+ *   the same records, the same per-pair function, an exact minimum - each workgroup's result goes into a 64-bit integer
+ *   atomic min on (float bits of dist2) << 32 | face, and dist2 >= 0 orders like its bits - so the result does not depend on
+ *   how the launch splits points and faces, and is the same bits eager or replayed.  No floating-point atomics.
+ * workspace (device, 16-byte aligned) >= fgc_closest_point_workspace_bytes(nf, nq) (0 for arguments out of range):
+ *   fgc_ray_cast's layout, the records and one 64-bit key per point.
+ * Three launches, enqueue-only, capturable, nothing allocated: the records (and the keys' initial value); points x faces
+ *   (64 points per workgroup, the records wave-uniform through scalar loads, the faces split into slabs over blockIdx.y
+ *   where the points alone do not fill the device, one atomic per point and slab); keys -> outputs, (u, v) evaluated again
+ *   on the winner, whose index is bounded by nf before it addresses anything.  Every loop bound is a host-side count.
+ * A NULL among verts, faces, points, dist2_out, face_out, workspace; nv, nf or nq <= 0; nf > FGC_RAY_CAST_MAX_FACES; a
+ *   workspace that is misaligned or too small: FGC_EINVAL, nothing launched. */
+size_t fgc_closest_point_workspace_bytes(int32_t nf, int32_t nq);
+int fgc_closest_point(const float* verts, int32_t nv, const int32_t* faces, int32_t nf, const float* points, int32_t nq,
+                      float* dist2_out, int32_t* face_out, float* bary_out, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
+/* Two-sided point-to-surface loss, shaped like fgc_point_loss, and its gradient: the ground truth may be a mesh of any
+ * topology.  p0 [np0,3] refined vertices with faces0 [nf0,3] (-1 rows allowed: a node-ordered table), p1 [np1,3] and
+ * faces1 [nf1,3] the ground-truth mesh, i0 [ns0] rows of p0 and i1 [ns1] rows of p1 (repeats allowed):
+ *   precision_t = distance of p0[i0_t] to the surface (p1, faces1), completeness_t = distance of p1[i1_t] to the surface
+ *   (p0, faces0), each d = sqrtf(dist2) of the winner of fgc_closest_point;
+ *   loss[0] = 1000 (mean(d <= threshold ? d : 0 over precision) + mean(the same over completeness)): fgc_point_loss's scale.
+ * g_p0 (may be NULL) [np0,3] receives dL/dp0 (dL/dloss = 1), with r = q - closest point as THE PAIR forms it and (u, v) of
+ *   the winner held fixed: a kept precision term adds (1000/ns0) r / d to row i0_t; a kept completeness term adds
+ *   -(1000/ns1) w_k r / d to the three rows faces0[f][k] of its winning face, w = (1 - u - v, u, v).  Holding (u, v) fixed is
+ *   exact wherever the distance is differentiable: the closest point minimises over the triangle, so the derivative
+ *   through (u, v) vanishes.  At d = 0 a term's gradient is 0; a masked term's gradient is 0.  Terms that share a row are
+ *   summed in term order by the row's first term - precision terms first, then completeness terms in the order (t, k) - by
+ *   fgc_point_loss's reduction: no atomics on floats, the same bits from run to run and under hipGraph replay.
+ * A sample index out of range, or a sample with no winner, makes the loss NaN and adds no gradient.
+ * ns0 + 3 ns1 <= FGC_POINT_LOSS_MAX_SAMPLES.  workspace (device, 256-byte aligned) >=
+ *   fgc_surface_loss_workspace_bytes(nf0, nf1, ns0, ns1) (0 for arguments out of range).  Enqueue-only, capturable: two
+ *   gathers, two scans of two launches, the terms, a memset of g_p0, the reduction.  A NULL among the pointers other than
+ *   g_p0; a count <= 0; too many samples or faces; a workspace that is misaligned or too small: FGC_EINVAL, nothing
+ *   launched. */
+size_t fgc_surface_loss_workspace_bytes(int32_t nf0, int32_t nf1, int32_t ns0, int32_t ns1);
+int fgc_surface_loss(const float* p0, int32_t np0, const int32_t* faces0, int32_t nf0, const float* p1, int32_t np1,
+                     const int32_t* faces1, int32_t nf1, const int32_t* i0, int32_t ns0, const int32_t* i1, int32_t ns1,
+                     float threshold, float* loss, float* g_p0, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Checkpoint files (CPU; HOST pointers)

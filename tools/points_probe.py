@@ -1,7 +1,7 @@
 """Cost of the point-set training step (trainAccuracyNet) on the MI355X.
 
     python tools/points_probe.py [--faces 20000 100000] [--steps 20] [--out FILE] [--only all|network|vertex_fwd|vertex_bwd|loss]
-        [--double-loss]
+        [--double-loss] [--surface-loss]
 
 Per mesh size (a noisy torus): ms per point-set step eager and replayed from its hipGraph, the graph's node count
 (launches per step), the multi-scale angular-loss step on the same mesh for comparison, and the parts of the step timed
@@ -9,7 +9,10 @@ alone with device events: network forward + backward, vertex update forward with
 --only runs one part in a loop (for a `rocprofv3 --kernel-trace --stats` run of its own).  --double-loss: the mesh is bound
 with its ground-truth face normals, and the double-loss step (trainDoubleLossNet) is timed next to the point-set step,
 eager and replayed, with the dense face-normal loss alone (forward + accumulating backward) as one more part; --only then
-also takes `double` (the whole double-loss step) and `dense_loss`."""
+also takes `double` (the whole double-loss step) and `dense_loss`.  --surface-loss (nothing else is timed then): the mesh is
+bound twice, without and with its own faces as ground-truth faces (bind_vertices(gt_faces=)), and per mesh size the two
+losses alone (ops.point_loss, ops.surface_loss on the bound vertices) and the two captured point-set steps are timed in
+alternating rounds in one process; the step without the faces issues the launches of a build without the surface loss."""
 import argparse
 import json
 import os
@@ -34,6 +37,50 @@ def timed(fn, steps, warmup=3):
     return a.elapsed_time(b) / steps
 
 
+def surface_rows(args):
+    """--surface-loss: fullLoss against the surface loss, alone and inside the captured step, in alternating rounds."""
+    from facet_graph_convolution_amd import ops
+    from facet_graph_convolution_amd.net import FacetDenoiser
+    from facet_graph_convolution_amd.dataClasses import TrainingSet
+    from facet_graph_convolution_amd.meshgen import torus, add_noise
+    from facet_graph_convolution_amd.utils import rand_rotation_matrix
+    res = []
+    for nf in args.faces:
+        n = int(round((nf / 2) ** 0.5))
+        V, F = torus(n, n)
+        ds = TrainingSet()
+        ds.addMeshWithVerticesAndGT(add_noise(V, F, seed=1), F, V, seed=0)
+        v, faces, vf, gtv = ds.v_list[0][0], ds.faces_list[0][0], ds.v_faces_list[0][0], ds.gtv_list[0][0]
+        rs = np.random.RandomState(0)
+        Rm = rand_rotation_matrix(randnums=rs.uniform(size=3))
+        i0, i1 = rs.randint(len(v), size=500), rs.randint(len(gtv), size=500)
+        nets = {}
+        for name, extra in (("points", {}), ("surface", {"gt_faces": faces.astype(np.int32)})):
+            net = nets[name] = FacetDenoiser("cuda:0", multi_scale=True, seed=0)
+            net.bind_vertices(0, ds.in_list[0], ds.adj_list[0], v, faces, vf, gtv, **extra)
+            net.set_point_samples(i0, i1)
+            net.set_rotation(Rm)
+        Vb = nets["surface"]._mesh["verts"]
+        steps = {k: (lambda net=net: net.pointset_forward_backward(rotate=True, capture=True)) for k, net in nets.items()}
+        losses = {"points": lambda: ops.point_loss(Vb["x"], Vb["gt"], Vb["i0"], Vb["i1"]),
+                  "surface": lambda: ops.surface_loss(Vb["x"], Vb["faces"], Vb["gt"], Vb["gt_faces"], Vb["i0"], Vb["i1"])}
+        row = dict(faces=int(F.shape[0]), nodes=int(ds.in_list[0].shape[1]), vertices=int(len(v)), rounds=args.rounds,
+                   step_loss={k: float(fn().item()) for k, fn in steps.items()})
+        for what, fns in (("loss_ms", losses), ("step_replay_ms", steps)):
+            row[what] = {k: [] for k in fns}
+            for _ in range(args.rounds):
+                for k, fn in fns.items():
+                    row[what][k].append(timed(fn, args.steps))
+            row[what + "_median"] = {k: float(np.median(t)) for k, t in row[what].items()}
+        row["step_replay_ms_surface_minus_points"] = (row["step_replay_ms_median"]["surface"] -
+                                                      row["step_replay_ms_median"]["points"])
+        print(json.dumps(row), flush=True)
+        res.append(row)
+        del nets, steps, losses, Vb
+        torch.cuda.empty_cache()
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--faces", type=int, nargs="+", default=[20000, 100000])
@@ -41,7 +88,16 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--only", default="all")
     ap.add_argument("--double-loss", action="store_true")
+    ap.add_argument("--surface-loss", action="store_true")
+    ap.add_argument("--rounds", type=int, default=5, help="--surface-loss: alternating rounds of --steps calls each")
     args = ap.parse_args()
+    if args.surface_loss:
+        res = surface_rows(args)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as fh:
+                json.dump(res, fh, indent=1)
+        return
     from facet_graph_convolution_amd import ops
     from facet_graph_convolution_amd.net import FacetDenoiser
     from facet_graph_convolution_amd.schedule import _graph_node_count

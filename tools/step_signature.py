@@ -5,7 +5,8 @@ Per configuration and mesh, as JSON: the profile table {tag/kernel: launches} of
 configurations (2 simulated shards) the request trace of both schedules of shard 0 as [kind, key or None, item kinds]
 and the segment_nodes of a segment capture; SHA-256 digests of params.grad, the loss tensor and nconv after the step.
 points_rays / double_rays: the points / double step bound with viewing rays (depth_dir), once with a per-vertex table and
-once with one [1,3] row, with the digest of the vertex trajectory.  vertex_ops: no step - the digests of every output of the
+once with one [1,3] row, with the digest of the vertex trajectory.  points_surface: the points step bound with the mesh's own
+faces as ground-truth faces (gt_faces: the surface loss in the place of fullLoss).  vertex_ops: no step - the digests of every output of the
 eight vertex-update ops (free and along rays, [V,3] and [1,3] rays) on the ico3 fixtures and the ragged tori of the tests,
 and their launch table - to hold a refactor of csrc/fgc_vertex.hip and its callers against its parent.
 The backward pass has a fixed order and no float atomics: two commits with the same library build must print the same
@@ -35,6 +36,7 @@ CONFIGS = {
     "double": ("double", "f32", True, 0, None, ("ico3",)),
     "points_rays": ("points", "f32", True, 0, None, ("ico3_table", "ico3_row")),
     "double_rays": ("double", "f32", True, 0, None, ("ico3_table", "ico3_row")),
+    "points_surface": ("points", "f32", True, 0, None, ("ico3_surface",)),
     "vertex_ops": None,
     "shard2_f32": ("angular", "f32", False, 2, None, BOTH),
     "shard2_bf16": ("angular", "bf16", False, 2, None, BOTH),
@@ -67,7 +69,9 @@ def _unsharded(form, dtype, multi_scale, tag):
     else:
         p, z = np.load(os.path.join(GOLDEN, "points_ico3.npz")), np.load(os.path.join(GOLDEN, "double_ico3.npz"))
         rays = {}
-        if tag != "ico3":      # ico3_table: the camera's rays, one per vertex; ico3_row: one view direction
+        if tag == "ico3_surface":
+            rays = {"gt_faces": p["faces"].astype(np.int32)}
+        elif tag != "ico3":      # ico3_table: the camera's rays, one per vertex; ico3_row: one view direction
             import depth_ms_cases as mc
             from facet_graph_convolution_amd import utils
             view = {"camera": mc.CAMERA} if tag == "ico3_table" else {"view_dir": mc.VIEW_DIR}
